@@ -4,11 +4,19 @@
 encode -> [prefix | audio | suffix[1:]] -> prefill -> KV-cached greedy decode (generate_audio_response,
 ref:inference.py:95-137), random-init weights of the true shapes, inputs resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]          # N>1: launched by torch.distributed.run
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]   # N>1: launched by torch.distributed.run
 
 Prints ONE JSON line (rank 0).  value = generated tokens/s of the whole job (all ranks, all pipeline
-stages inside the timed region); audio_sec_per_s_encoder_alone = throughput of the encoder stage run on its own on the same
-batch (HIP events), audio_sec_per_s_in_pipeline = audio seconds per second of the timed steps; latency_b1 = the reference's
+stages inside the timed region); ms_per_step = wall time of one timed step; audio_sec_per_s_encoder_alone = throughput of the encoder stage run on its own on the same
+batch (HIP events), audio_sec_per_s_in_pipeline = audio seconds per second of the timed steps.  A plain run stops there: set-up,
+W warm-up steps, the K timed steps, those two encoder passes and the line.  `--full` adds everything else below: the KD training leg,
+the one-batch-alone step, roofline probes, the side legs (batch 1, stop-length mix, dev-clean mix, long-form, Whisper) and the CPU
+baseline.  `--dump-outputs DIR` writes what the last timed step returned (rank 0): DIR/generated_ids.npy, the (B, max_new_tokens)
+greedy ids as float32, and DIR/audio_embeds_sample.npy, a fixed seeded sample of the encoder's output rows of that step (float32).
+The same arguments give the same inputs.  Two runs with the same arguments have written identical files; runs that differed only in
+--steps / --warmup wrote encoder rows that differ by bf16 rounding in some utterances, and greedy rows that part at a near tie, so
+compare dumps with a tolerance.
+latency_b1 = the reference's
 one-utterance-per-call pattern against the batch-1 HBM ceiling; stage_ms = per-batch wall times inside the timed steps (two batches take turns on the GPU).  roofline = the decode kernel with the largest share of the step (split attention over the KV cache at
 the default batch of 1024, the gate/up weight-streaming GEMM below ~128) against the HBM peak; roofline_other = the other.
 cpu_baseline = the CPU oracle (oracle/*.py, a port of the reference's HF path) on a bounded sample.
@@ -643,20 +651,23 @@ def dry_rank(args, rank, world) -> None:
         red.close()
     if os.environ.get("SL_BENCH_DRY_FAIL_RANK") == str(rank):
         sys.exit(7)
-    # SL_BENCH_DRY_KD_HUNG=1: the KD leg of every rank blocks for ever (a collective that never completes) behind the same bounded
+    # SL_BENCH_DRY_KD_HUNG=1 with --full: the KD leg of every rank blocks for ever (a collective that never completes) behind the same bounded
     # helper and exit path the real run uses: the line still comes out, with kd_step.error, and every rank exits EXIT_KD_HUNG
     kd_rec, hung = {"comm": comm}, False
-    if os.environ.get("SL_BENCH_DRY_KD_HUNG") == "1":
+    if args.full and os.environ.get("SL_BENCH_DRY_KD_HUNG") == "1":
         import threading
         kd_rec, hung = run_bounded(lambda: threading.Event().wait(), 1.0, True)
         kd_rec["comm"] = comm
     if rank == 0:
         print("a stray stdout line from a rank", flush=True)
-        print(json.dumps({"metric": "dry run of the launcher (no GPU work)", "value": 0.0, "unit": "tokens/s",
-                          "n_gpus": int(os.environ.get("SL_BENCH_DRY_REPORT_GPUS", world)), "steps": done, "warmup": args.warmup,
-                          "ms_per_step": float(tt.item()) * 1e3 / max(1, done), "dry_run": True,
-                          "per_rank": [{"rank": int(r_[0]), "utterances": int(r_[1]), "audio_sec": r_[2], "tokens": int(r_[3]), "elapsed_s": r_[4]} for r_ in per_rank],
-                          "collective_backend": (dist.get_backend() if world > 1 else None), "kd_step": kd_rec}), file=RESULT_OUT, flush=True)
+        rec = {"metric": "dry run of the launcher (no GPU work)", "value": 0.0, "unit": "tokens/s",
+               "n_gpus": int(os.environ.get("SL_BENCH_DRY_REPORT_GPUS", world)), "steps": done, "warmup": args.warmup,
+               "ms_per_step": float(tt.item()) * 1e3 / max(1, done), "dry_run": True, "full": args.full,
+               "per_rank": [{"rank": int(r_[0]), "utterances": int(r_[1]), "audio_sec": r_[2], "tokens": int(r_[3]), "elapsed_s": r_[4]} for r_ in per_rank],
+               "collective_backend": (dist.get_backend() if world > 1 else None)}
+        if args.full:       # as in the real run, the KD leg (and with it kd_step) belongs to --full
+            rec["kd_step"] = kd_rec
+        print(json.dumps(rec), file=RESULT_OUT, flush=True)
     leave_process(hung, dist if world > 1 else None)
 
 
@@ -684,6 +695,9 @@ def main():
                     "rank per optimizer step, the line's \"scaling\": \"weak\"), strong = the reference's grad_accum_interval 16 dealt to the ranks")
     ap.add_argument("--kd-local-accum", type=int, default=2, help="single-GPU KD probe: windows of this many samples per optimizer step, the per-rank "
                     "regime of an 8-rank run (grad_accum_interval 16 / 8); 0 = skip")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: KD leg, one-batch-alone step, roofline probes, "
+                    "side legs and CPU baseline (the --kd-* / --no-* options above shape those)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -744,7 +758,7 @@ def main():
     S_long = prefix.shape[1] + 15 + (harch.num_frames(max(LONGFORM_SEC) * 16000) - 8) // 4 + 1 + suffix.shape[1] - 1
     long_ctx = ((S_long + new + 63) // 64) * 64
     rope_ctx = mix_ctx if args.no_extra_legs else max(mix_ctx, long_ctx)
-    keep_sd = dict(llm_sd) if (rank == 0 and not args.no_cpu_baseline) else None
+    keep_sd = dict(llm_sd) if (rank == 0 and args.full and not args.no_cpu_baseline) else None
     llm = llama_mod.AudioLlamaForCausalLM(larch, llm_sd, torch_dtype=torch.bfloat16, device=dev, max_ctx=rope_ctx, max_batch=B, pack_decode=not args.no_pack_decode)
     del llm_sd
     wts = llm._dev()          # rope tables / split-attention workspace sized for the longest leg
@@ -761,7 +775,7 @@ def main():
     kd_state = {"kd": None, "hung": False}
 
     def run_kd_leg():
-        if args.kd_optimizer_steps <= 0:
+        if args.kd_optimizer_steps <= 0 or not args.full:
             return
 
         def run_kd():
@@ -809,9 +823,9 @@ def main():
             self.stream = torch.cuda.Stream(device=dev)
             self.x = torch.empty((B * S, larch.hidden_size), device=dev, dtype=torch.bfloat16)
             self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            self.last = None
+            self.last = self.kept = None
 
-        def step(self, record):
+        def step(self, record, keep_rows=None):
             with torch.cuda.stream(self.stream):
                 # prompt assembly: prefix/suffix rows are copied, the encoder writes the audio rows in place
                 xv = self.x.view(B, S, -1)
@@ -820,6 +834,8 @@ def main():
                 self.ev[0].record()
                 self.enc.encode_packed(waves, out=self.x, out_row_offsets=audio_rows)
                 self.ev[1].record()
+                if keep_rows is not None:      # --dump-outputs: generate overwrites x, so the sampled encoder rows are copied out first
+                    self.kept = self.x.index_select(0, keep_rows)
                 # shared_prefix: the n_pre template rows are the same in every prompt (what inference.generate_audio_responses passes)
                 ids, n_cols = self.llm.generate_packed(self.x, [S] * B, new, use_eos=False, shared_prefix=n_pre)   # syncs this stream at its end
                 if record:
@@ -829,45 +845,71 @@ def main():
                 self.last = (ids, n_cols)
 
     pipes = [Pipe(i) for i in range(n_pipe)]
+
+    def run_steps(n, record, keep_rows=None):
+        """n steps pulled from one counter by the pipes' threads; returns the pipe that ran the last one (keep_rows goes to that step)."""
+        counter, lock, last = {"next": 0}, threading.Lock(), {}
+
+        def worker(pp):
+            torch.cuda.set_device(dev)
+            while True:
+                with lock:
+                    k = counter["next"]
+                    counter["next"] += 1
+                if k >= n:
+                    return
+                pp.step(record, keep_rows if k == n - 1 else None)
+                if k == n - 1:
+                    last["pipe"] = pp
+
+        if n_pipe == 1:
+            worker(pipes[0])
+        else:
+            threads = [threading.Thread(target=worker, args=(pp,)) for pp in pipes]
+            for t_ in threads:
+                t_.start()
+            for t_ in threads:
+                t_.join()
+        return last.get("pipe")
+
+    # warm-up: every pipe's first step runs alone (graph captures, KV cache and workspace allocation, one batch at a time); the rest
+    # of the W steps run in flight like the timed ones, so that W warm-up steps cost about W timed steps
     torch.cuda.synchronize()
-    for _ in range(args.warmup):
+    if args.warmup > 0:
         for pp in pipes:
             pp.step(False)
+        run_steps(max(0, args.warmup - n_pipe), False)
 
     def barrier():
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
 
-    counter = {"next": 0}
-    lock = threading.Lock()
-
-    def worker(pp):
-        torch.cuda.set_device(dev)
-        while True:
-            with lock:
-                k = counter["next"]
-                counter["next"] += 1
-            if k >= args.steps:
-                return
-            pp.step(True)
-
+    keep_rows = None
+    if args.dump_outputs and rank == 0:
+        # a fixed seeded sample of the step's audio rows (row b * S + n_pre + f = utterance b, frame f), at most 2 048 rows (24 MiB at 3 072 wide)
+        g_ = torch.Generator().manual_seed(0)
+        pick = torch.randperm(B * P, generator=g_)[:2048].sort().values
+        keep_rows = ((pick // P) * S + n_pre + pick % P).to(dev)
     barrier()
     t0 = time.perf_counter()
-    if n_pipe == 1:
-        worker(pipes[0])
-    else:
-        threads = [threading.Thread(target=worker, args=(pp,)) for pp in pipes]
-        for t_ in threads:
-            t_.start()
-        for t_ in threads:
-            t_.join()
+    last_pipe = run_steps(args.steps, True, keep_rows)
     barrier()
     elapsed = time.perf_counter() - t0
     for pp in pipes:
         if pp.last is not None:
             ids, n_cols = pp.last
             assert n_cols == new and ids.shape == (B, new)
+    if keep_rows is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        ids = last_pipe.last[0]
+        assert int(ids.max()) < 2 ** 24          # token ids are exact in float32
+        outs = {"generated_ids": ids.float().numpy(), "audio_embeds_sample": last_pipe.kept.float().cpu().numpy()}
+        assert sum(a.nbytes for a in outs.values()) <= 64 * 2 ** 20
+        for name, arr in outs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+        print(f"[bench] wrote {', '.join(f'{k}.npy {tuple(v.shape)}' for k, v in outs.items())} to {args.dump_outputs}", file=sys.stderr, flush=True)
     # encoder stage alone (nothing else on the GPU): the audio-sec/s half of the metric
     enc_alone_ms = []
     with torch.cuda.stream(pipes[0].stream):
@@ -880,7 +922,7 @@ def main():
     # one whole step alone on the GPU (no second batch in flight): un-shared stage times, the decode step the roofline
     # fractions of DESIGN.md are quoted on
     seq_stage = None
-    if rank == 0:
+    if rank == 0 and args.full:
         n_e, n_p, n_d = len(enc_ms), len(prefill_ms), len(decode_ms)
         pipes[0].step(True)
         torch.cuda.synchronize()
@@ -906,7 +948,7 @@ def main():
     # ---- roofline probes: the two kernels that carry the decode step (gate/up weight-streaming GEMM, split attention over
     # the KV cache), launched as the decode graph launches them, timed with HIP events on the stream they run on
     probes = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ops = mod("ops")
         H, F_ = larch.hidden_size, larch.intermediate_size
         nh, nkv, D = larch.num_attention_heads, larch.num_key_value_heads, larch.head_dim
@@ -992,6 +1034,44 @@ def main():
     tokens = int(sum(r_[3] for r_ in per_rank))      # == B * new * steps * world: summed from what the ranks report
     assert tokens == B * new * args.steps * world and len(per_rank) == world
     mean = lambda v: sum(v) / max(1, len(v))
+    dec_step_ms = mean(decode_ms) / max(1, new - 1)
+    result = {
+        "metric": "generated tokens/s of end-to-end generate_audio_response steps (encode + prefill + 256-token greedy decode), HuBERT-large -> Llama-3.2-3B; "
+                  "audio-sec/s reported beside it, encoder stage alone and in the pipeline",
+        "value": round(tokens / elapsed, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic", "native_library": mod("_lib").LIB_PATH, "full": args.full,
+        "config": {"workload": "configs[1]: HuBERT-large + Llama-3.2-3B bf16 inference, batch of synthetic 16 kHz utterances",
+                   "utterances_per_gpu": B, "audio_sec": args.audio_sec, "prompt_tokens": S, "max_new_tokens": new,
+                   "shared_prompt_prefix_tokens": n_pre,   # the template rows in front of every utterance: decode attention reads their K/V once per batch
+                   "parallelism": f"replicas x{world} (sharded by utterance, no collective)", "batches_in_flight_per_gpu": n_pipe},
+        "per_rank": [{"rank": int(r_[0]), "utterances": int(r_[1]), "audio_sec": r_[2], "tokens": int(r_[3]), "elapsed_s": round(r_[4], 3)} for r_ in per_rank],
+        "collective_backend": (dist.get_backend() if dist is not None else None),
+        "audio_sec_per_s_encoder_alone": round(B * args.audio_sec * world / (min(enc_alone_ms) * 1e-3), 1),
+        "audio_sec_per_s_in_pipeline": round(B * args.audio_sec * args.steps * world / elapsed, 1),
+        "audio_sec_note": "encoder_alone = the encoder stage (conv stack + 24 layers + pool + projector) run on its own on one batch, HIP events; "
+                          "in_pipeline = audio seconds consumed per second of the timed end-to-end steps (encode + prefill + 256-token decode)",
+        "encoder_alone_ms": round(min(enc_alone_ms), 3),
+        "stage_ms": {"encode": round(mean(enc_ms), 3), "prefill": round(mean(prefill_ms), 3), "decode": round(mean(decode_ms), 3),
+                     "decode_per_step": round(dec_step_ms, 4)},
+        "stage_note": f"per-batch wall times; {n_pipe} batch(es) take turns on the GPU (kernels of different batches interleave; every kernel fills the chip, so this "
+                      "buys ~2 % over strictly sequential steps: compare stage_ms_one_batch_alone of a --full run)",
+    }
+
+    def emit():
+        try:      # memory head-room of the run, for the record (stderr; the JSON line stays the only stdout line)
+            free_b, total_b = torch.cuda.mem_get_info(dev)
+            print(f"[bench] peak torch allocation {torch.cuda.max_memory_allocated(dev) / 2**30:.1f} GiB, reserved {torch.cuda.max_memory_reserved(dev) / 2**30:.1f} GiB, "
+                  f"device total {total_b / 2**30:.1f} GiB", file=sys.stderr, flush=True)
+        except Exception:
+            pass
+        print(json.dumps(result), file=RESULT_OUT, flush=True)
+        leave()
+
+    if not args.full:
+        emit()
+        return
+    # ---- --full: roofline entries, the four graded fractions, the side legs and the CPU baseline
     # HBM bytes per launch from the PMC passes (FETCH_SIZE x2 + WRITE_SIZE, profiles/README.md), where measured for this batch
     streaming = B > 26   # SL_STREAM_MIN_M default (csrc/api.hip)
     # `traffic` cannot be measured inside this process (PMC counters need rocprofv3 around it): it is READ from the committed
@@ -1036,40 +1116,19 @@ def main():
         r_["launches_per_decode_step"] = n_lay
         r_["launches_in_timed_region"] = n_lay * (new - 1) * args.steps        # per rank; the rocprofv3 kernel stats of the same command show them
     dominant, other = (r_attn, r_gemm) if probes["attn"][1] > probes["gemm"][1] else (r_gemm, r_attn)
-    dec_step_ms = mean(decode_ms) / max(1, new - 1)
     # K/V rows a step has to pull from HBM: every sequence's own rows, the n_pre shared template rows once per batch (sl_kv_cache.shared_prefix)
     step_bytes = wts.weight_bytes_per_token() + (B * (S - n_pre + new / 2) + n_pre) * 2 * larch.num_key_value_heads * larch.head_dim * 2 * larch.num_hidden_layers
-    result = {
-        "metric": "generated tokens/s of end-to-end generate_audio_response steps (encode + prefill + 256-token greedy decode), HuBERT-large -> Llama-3.2-3B; "
-                  "audio-sec/s reported beside it, encoder stage alone and in the pipeline",
-        "value": round(tokens / elapsed, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16", "data": "synthetic", "native_library": mod("_lib").LIB_PATH,
-        "config": {"workload": "configs[1]: HuBERT-large + Llama-3.2-3B bf16 inference, batch of synthetic 16 kHz utterances",
-                   "utterances_per_gpu": B, "audio_sec": args.audio_sec, "prompt_tokens": S, "max_new_tokens": new,
-                   "shared_prompt_prefix_tokens": n_pre,   # the template rows in front of every utterance: decode attention reads their K/V once per batch
-                   "parallelism": f"replicas x{world} (sharded by utterance, no collective)", "batches_in_flight_per_gpu": n_pipe},
-        "per_rank": [{"rank": int(r_[0]), "utterances": int(r_[1]), "audio_sec": r_[2], "tokens": int(r_[3]), "elapsed_s": round(r_[4], 3)} for r_ in per_rank],
-        "collective_backend": (dist.get_backend() if dist is not None else None),
-        "audio_sec_per_s_encoder_alone": round(B * args.audio_sec * world / (min(enc_alone_ms) * 1e-3), 1),
-        "audio_sec_per_s_in_pipeline": round(B * args.audio_sec * args.steps * world / elapsed, 1),
-        "audio_sec_note": "encoder_alone = the encoder stage (conv stack + 24 layers + pool + projector) run on its own on one batch, HIP events; "
-                          "in_pipeline = audio seconds consumed per second of the timed end-to-end steps (encode + prefill + 256-token decode)",
-        "encoder_alone_ms": round(min(enc_alone_ms), 3),
+    result.update({
         "encoder_mfma": {"achieved": round(B * args.audio_sec * 38.46e9 / (min(enc_alone_ms) * 1e-3) / 1e12, 1), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(B * args.audio_sec * 38.46e9 / (min(enc_alone_ms) * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
                          "note": "38.46 GFLOP per audio-second at 10 s clips (SURVEY.md §8d)"},
-        "stage_ms": {"encode": round(mean(enc_ms), 3), "prefill": round(mean(prefill_ms), 3), "decode": round(mean(decode_ms), 3),
-                     "decode_per_step": round(dec_step_ms, 4)},
-        "stage_note": f"per-batch wall times; {n_pipe} batch(es) take turns on the GPU (kernels of different batches interleave; every kernel fills the chip, so this "
-                      "buys ~2 % over strictly sequential steps: compare stage_ms_one_batch_alone)",
         "stage_ms_one_batch_alone": seq_stage,
         "decode_step_hbm": {"algorithmic_GB": round(step_bytes / 1e9, 3), "concurrent_batches": n_pipe,
                             "achieved_GBps": round(n_pipe * step_bytes / (dec_step_ms * 1e-3) / 1e9, 1),
                             "frac_of_peak": round(n_pipe * step_bytes / (dec_step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                             "one_batch_alone_frac_of_peak": (round(step_bytes / (seq_stage["decode_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if seq_stage else None)},
         "roofline": dominant, "roofline_other": other,
-    }
+    })
     if seq_stage:
         a_ = larch
         body = a_.num_hidden_layers * ((a_.num_attention_heads + 2 * a_.num_key_value_heads) * a_.head_dim * a_.hidden_size
@@ -1157,14 +1216,7 @@ def main():
     if not args.no_cpu_baseline:
         del llm, wts
         result["cpu_baseline"] = cpu_baseline(enc_sd, keep_sd, harch, larch, waves[0].cpu(), prefix, suffix, args.cpu_decode_steps, new)
-    try:      # memory head-room of the run, for the record (stderr; the JSON line stays the only stdout line)
-        free_b, total_b = torch.cuda.mem_get_info(dev)
-        print(f"[bench] peak torch allocation {torch.cuda.max_memory_allocated(dev) / 2**30:.1f} GiB, reserved {torch.cuda.max_memory_reserved(dev) / 2**30:.1f} GiB, "
-              f"device total {total_b / 2**30:.1f} GiB", file=sys.stderr, flush=True)
-    except Exception:
-        pass
-    print(json.dumps(result), file=RESULT_OUT, flush=True)
-    leave()
+    emit()
 
 
 if __name__ == "__main__":

@@ -19,7 +19,7 @@ def run(extra_env, *argv):
 
 
 def test_gpus_2_launches_two_ranks_and_forwards_one_line():
-    r = run({}, "--gpus", "2", "--steps", "3", "--warmup", "1")
+    r = run({}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1                                   # the ranks' stray stdout went to stderr
@@ -37,7 +37,7 @@ def test_gpus_2_launches_two_ranks_and_forwards_one_line():
 def test_a_hung_kd_collective_still_prints_the_line_and_exits_non_zero():
     """a rank whose KD leg never returns (a stuck collective) prints its line — with kd_step.error — and then leaves
     with bench.EXIT_KD_HUNG through the same run_bounded / leave_process pair the GPU run uses; the launcher hands the status back."""
-    r = run({"SL_BENCH_DRY_KD_HUNG": "1"}, "--gpus", "2", "--steps", "2", "--warmup", "0")
+    r = run({"SL_BENCH_DRY_KD_HUNG": "1"}, "--gpus", "2", "--steps", "2", "--warmup", "0", "--full")
     assert r.returncode != 0, r.stdout
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1
@@ -86,3 +86,4 @@ def test_launched_by_torchrun_directly_as_the_driver_does():
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 2
+    assert rec["full"] is False and "kd_step" not in rec          # a plain run is the headline only: the KD leg belongs to --full

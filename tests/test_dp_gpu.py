@@ -227,7 +227,7 @@ def test_bench_line_describes_itself_small_batch(tmp_path):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--batch", "48", "--steps", "2", "--warmup", "1", "--kd-optimizer-steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--batch", "48", "--steps", "2", "--warmup", "1", "--kd-optimizer-steps", "1",
                         "--no-cpu-baseline", "--no-extra-legs", "--no-length-mix", "--max-new-tokens", "48"], capture_output=True, text=True, env=env,
                        timeout=1500, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
@@ -244,3 +244,44 @@ def test_bench_line_describes_itself_small_batch(tmp_path):
     e = rec["eos_stop_mix"]
     assert "error" not in e, e
     assert e["compacted"]["compactions"] >= 1 and e["compacted"]["row_steps"] < e["uncompacted"]["row_steps"] and e["useful_tokens"] == sum(12 + (61 * b) % 37 for b in range(48))
+
+
+def test_plain_bench_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """bench.py without --full at a small batch: the line carries the headline fields and none of the --full legs, --steps sets the timed
+    steps, and --dump-outputs writes the last timed step's ids and a seeded sample of its encoder rows (float32, under 64 MB).  Two runs
+    with the same arguments see the same inputs: their encoder rows agree to bf16 rounding and most id rows are identical (runs at 1 024
+    utterances that differed only in --steps / --warmup differed in whole utterances by bf16 rounding; a greedy row can part at a near tie)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--batch", "48", "--steps", "3", "--warmup", "1", "--max-new-tokens", "48",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=900, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec["full"] is False and rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["value"] > 0
+        assert rec["unit"] == "tokens/s" and rec["higher_is_better"] is True and rec["dtype"] == "bf16"
+        assert rec["per_rank"][0]["utterances"] == 48 * 3 and rec["per_rank"][0]["tokens"] == 48 * 48 * 3
+        assert not {"kd_step", "roofline", "latency_b1", "eos_stop_mix", "cpu_baseline", "graded"} & set(rec)
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["audio_embeds_sample.npy", "generated_ids.npy"]
+        d = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 * 2 ** 20
+        ids = d["generated_ids"]
+        assert ids.shape == (48, 48) and np.all(ids == np.round(ids)) and ids.min() >= 0 and ids.max() < 128256
+        emb = d["audio_embeds_sample"]
+        n_audio = 48 * (rec["config"]["prompt_tokens"] - 9 - 5)          # prefix 9 rows, suffix[1:] 5 rows around every utterance's audio
+        assert emb.shape == (min(2048, n_audio), 3072) and np.isfinite(emb).all() and float(np.abs(emb).mean()) > 0
+        dumps.append(d)
+    ea, eb = dumps[0]["audio_embeds_sample"], dumps[1]["audio_embeds_sample"]
+    assert np.linalg.norm(ea - eb) / np.linalg.norm(ea) < 1e-2          # other inputs would differ at ~1
+    assert (dumps[0]["generated_ids"] == dumps[1]["generated_ids"]).all(1).mean() >= 0.5
