@@ -20,7 +20,11 @@
  *         behind the asynchronous copy of the ids to the host (the call returns host results).
  *     Nothing synchronises the device or touches the null stream.
  *   - Return value: 0 on success, a negative sl_status otherwise; sl_last_error() gives the text.
- *   - dtype: SL_F32 (exact-fp32 MFMA, the parity mode) or SL_BF16 (bf16 storage, fp32 accumulate).
+ *   - dtype: SL_F32 (exact-fp32 MFMA, the parity mode), SL_BF16 (bf16 storage, fp32 accumulate) or SL_F16
+ *     (fp16 storage, fp32 accumulate; norms and softmax statistics in fp32, as for bf16; values beyond the fp16
+ *     range become +-inf, no clamping).  SL_F16 is an inference dtype: the forward entry points take it, the
+ *     training-only entry points (attention backward, the tapes, post_op / colsum_out / transposed products,
+ *     the AdamW dst_dtype, sl_allreduce_sum) return SL_ERR_ARG for it.
  *   - Layouts: activations row-major (tokens, channels); Linear weights in nn.Linear layout
  *     (out_features, in_features); conv weights re-laid out by the host as documented per call.
  */
@@ -36,7 +40,7 @@ extern "C" {
 
 typedef void* sl_stream; /* hipStream_t */
 
-enum sl_dtype { SL_F32 = 0, SL_BF16 = 1 };
+enum sl_dtype { SL_F32 = 0, SL_BF16 = 1, SL_F16 = 2 };
 enum sl_status {
   SL_OK = 0,
   SL_ERR_ARG = -1,      /* bad shape / alignment / enum */
@@ -399,7 +403,7 @@ typedef struct sl_adamw_tensor {
   float* v;            /* exp_avg_sq */
   void* dst;           /* NULL, or where the compute-dtype copy of p goes (same element order) */
   int64_t n;           /* elements */
-  int32_t dst_dtype;   /* SL_F32 / SL_BF16 */
+  int32_t dst_dtype;   /* SL_F32 / SL_BF16 (not SL_F16: training is fp32 / bf16) */
   int32_t reserved;
 } sl_adamw_tensor;
 size_t sl_adamw_blocks(int64_t n);

@@ -42,7 +42,7 @@ if __name__ == '__main__':
     import torch
     torch.cuda.set_device(args.gpu_idx)      # libspeechllm launches on the current HIP device / stream
     config = importlib.import_module("llm-speech-summarization_amd.config").load_config(args.config)
-    dtype = torch.float32 if str(config.get("runtime", {}).get("dtype", "bf16")) == "fp32" else torch.bfloat16
+    dtype = importlib.import_module("llm-speech-summarization_amd.config").runtime_dtype(config)
     llm_inferencer = LLMSpeechTextInference(config=config, audio_encoder_checkpoint=args.audio_encoder_checkpoint,
                                             device=torch.device(f"cuda:{args.gpu_idx}"), dtype=dtype)
     audio, sr = load_audio_16k(args.audio_file)

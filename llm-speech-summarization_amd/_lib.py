@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # bench.py records the resolved path in its JSON line (`native_library`), so a foreign build can never pass for the in-tree one.
 LIB_PATH = (os.environ.get("SL_LIB_PATH") if os.environ.get("SL_DEV") == "1" else None) or os.path.join(_HERE, "libspeechllm.so")
 
-SL_F32, SL_BF16 = 0, 1
+SL_F32, SL_BF16, SL_F16 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_SILU_MUL, ACT_ROPE_KV = 0, 1, 2, 3
 POST_NONE, POST_DROPOUT, POST_GELU_BWD, POST_SILU_MUL_BWD = 0, 1, 2, 3      # sl_gemm_ex_args.post_op
 W_ROWMAJOR, W_PACKED = 0, 1
@@ -307,7 +307,14 @@ def dtype_code(dt: torch.dtype) -> int:
         return SL_F32
     if dt == torch.bfloat16:
         return SL_BF16
-    raise SpeechLLMError(f"unsupported dtype {dt}: the HIP path computes in float32 or bfloat16")
+    if dt == torch.float16:
+        return SL_F16
+    raise SpeechLLMError(f"unsupported dtype {dt}: the HIP path computes in float32, bfloat16 or float16")
+
+
+def is16(dt: torch.dtype) -> bool:
+    """A 16-bit storage dtype (bf16 or fp16): both take the same fused kernel forms; fp32 is the parity mode."""
+    return dt == torch.bfloat16 or dt == torch.float16
 
 
 def ptr(t) -> int:

@@ -45,9 +45,9 @@ class _EmbedTokens:
 class AudioLlamaForCausalLM:
     def __init__(self, arch: LlamaArch, state_dict: Dict[str, torch.Tensor], torch_dtype: torch.dtype = torch.bfloat16,
                  device=None, max_ctx: int = 2048, max_batch: int = 16, pack_decode: bool = True):
-        if torch_dtype == torch.float16:
-            # the reference runs fp16 autocast (ref:inference.py:50); gfx950 MFMA path here is bf16 / exact fp32
-            torch_dtype = torch.bfloat16
+        # float16 computes in fp16 (the reference's torch_dtype=float16, ref:inference.py:47-51); bfloat16 in bf16; float32 is the
+        # exact parity mode.  Logits are fp32 in every mode.
+        L.dtype_code(torch_dtype)    # raises for anything else
         self.arch = arch
         self.dtype = torch_dtype
         self.config = SimpleNamespace(vocab_size=arch.vocab_size, hidden_size=arch.hidden_size,

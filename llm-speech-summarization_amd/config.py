@@ -41,3 +41,18 @@ def load_config(path: str) -> AttrDict:
 
 def from_dict(d: dict) -> AttrDict:
     return _wrap(d)
+
+
+_RUNTIME_DTYPES = {"fp32": "float32", "bf16": "bfloat16", "fp16": "float16"}
+
+
+def runtime_dtype(config) -> "torch.dtype":
+    """The compute dtype a config's `runtime.dtype` names (default bf16): fp32 (exact-fp32 parity mode), bf16, or fp16
+    (inference only, the reference's torch_dtype=float16 regime; training rejects it)."""
+    import torch
+
+    rt = config.get("runtime", {}) if hasattr(config, "get") else {}
+    name = str((rt or {}).get("dtype", "bf16"))
+    if name not in _RUNTIME_DTYPES:
+        raise ValueError(f"runtime.dtype: {name!r} is not one of {sorted(_RUNTIME_DTYPES)}")
+    return getattr(torch, _RUNTIME_DTYPES[name])

@@ -234,9 +234,9 @@ __device__ __forceinline__ int v_img_off(int row, int ch) {
 // per 64: the knock-outs of profiles/r06_i_attn_fwd_knockouts.txt put staging + barriers at 22 % of the kernel) and measured it EQUAL to ST = 1
 // (1 132-1 154 against 1 133-1 146 us at 512 x 499, encoder pass 107.9 against 107.8 ms, profiles/r06_l_attn_fwd_st_ab.txt): the barrier count is not what
 // the staging costs.  Default ST = 1; SL_ATTN_FWD_ST=2 selects the other form.
-template <int D, bool CAUSAL, int QT, bool DROP = false, int ST = 1>
+template <typename T, int D, bool CAUSAL, int QT, bool DROP = false, int ST = 1>
 __global__ __launch_bounds__(256, 2) void attn_fwd_tr_kernel(AttnP p) {
-  using T = bf16_t;
+  static_assert(sizeof(T) == 2, "the transposed-score kernel is built for the 16-bit types (bf16 / fp16)");
   constexpr int KS_D = D / 32;             // 32-wide steps across the head dim (S^T)
   constexpr int NF_O = D / 16;             // 16-wide output fragments
   constexpr int CPR = D / 8;               // 16-byte chunks per K / V row
@@ -408,8 +408,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_tr_kernel(AttnP p) {
         l_run[t] = l_run[t] * alpha + ls;   // per-lane partial sum; the four q lanes of a query meet in the epilogue
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
-          pb[t][kk] = make_uint4(pack2_bf16(s[t][2 * kk][0], s[t][2 * kk][1]), pack2_bf16(s[t][2 * kk][2], s[t][2 * kk][3]),
-                                 pack2_bf16(s[t][2 * kk + 1][0], s[t][2 * kk + 1][1]), pack2_bf16(s[t][2 * kk + 1][2], s[t][2 * kk + 1][3]));
+          pb[t][kk] = make_uint4(pack2<T>(s[t][2 * kk][0], s[t][2 * kk][1]), pack2<T>(s[t][2 * kk][2], s[t][2 * kk][3]),
+                                 pack2<T>(s[t][2 * kk + 1][0], s[t][2 * kk + 1][1]), pack2<T>(s[t][2 * kk + 1][2], s[t][2 * kk + 1][3]));
         // running rescale: skipped (exactly) while no query of the wave has a new maximum; scalar multiplies on purpose —
         // the compiler's v_pk_mul_f32 pairs cost more than two v_mul_f32 beside MFMAs (MI355X_MICROARCH issue-cost table)
         if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
@@ -470,7 +470,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_tr_kernel(AttnP p) {
     T* orow = ob + (int64_t)(q0 + qi) * p.o_rs + 4 * q;
 #pragma unroll
     for (int n = 0; n < NF_O; ++n)
-      *(uint2*)(orow + n * 16) = make_uint2(pack2_bf16(o[n][t][0] * inv, o[n][t][1] * inv), pack2_bf16(o[n][t][2] * inv, o[n][t][3] * inv));
+      *(uint2*)(orow + n * 16) = make_uint2(pack2<T>(o[n][t][0] * inv, o[n][t][1] * inv), pack2<T>(o[n][t][2] * inv, o[n][t][3] * inv));
   }
 }
 
@@ -490,15 +490,15 @@ static int launch_attn(const sl_attn_args* a, hipStream_t st) {
     p.drop_scale = 1.0f / (1.0f - a->dropout_p);
   }
   if constexpr (sizeof(T) == 2) {
-    // bf16: transposed-score kernel (8-byte output vectors need 4-element strides / an 8-byte aligned base)
+    // bf16 / fp16: transposed-score kernel (8-byte output vectors need 4-element strides / an 8-byte aligned base)
     const int generic = sl_env().attn_generic;
     if (!generic && a->o_row_stride % 4 == 0 && a->o_head_stride % 4 == 0 && ((uintptr_t)a->out & 7) == 0) {
       if (p.drop_thr) {   // training mode (HuBERT's attention dropout): one variant (32 queries per wave) with the mask applied to
                           // the packed probabilities; other shapes take the generic kernel, which applies the same mask
         if constexpr (D == 64 && !CAUSAL) {
           dim3 grid((a->max_qlen + 127) / 128, a->n_heads, a->nseq);
-          if (sl_env().attn_fwd_st == 2) hipLaunchKernelGGL((attn_fwd_tr_kernel<D, CAUSAL, 2, true, 2>), grid, dim3(256), 0, st, p);
-          else hipLaunchKernelGGL((attn_fwd_tr_kernel<D, CAUSAL, 2, true>), grid, dim3(256), 0, st, p);
+          if (sl_env().attn_fwd_st == 2) hipLaunchKernelGGL((attn_fwd_tr_kernel<T, D, CAUSAL, 2, true, 2>), grid, dim3(256), 0, st, p);
+          else hipLaunchKernelGGL((attn_fwd_tr_kernel<T, D, CAUSAL, 2, true>), grid, dim3(256), 0, st, p);
           SL_CHECK_LAUNCH("attn_fwd_tr");
           return 0;
         }
@@ -508,15 +508,15 @@ static int launch_attn(const sl_attn_args* a, hipStream_t st) {
           // 64 queries per wave where the sequences are long enough to fill such blocks: K / V fragments read once per 4 query tiles
           if (qt_env ? qt_env == 4 : a->max_qlen > 192) {
             dim3 grid((a->max_qlen + 255) / 256, a->n_heads, a->nseq);
-            if (sl_env().attn_fwd_st == 2) hipLaunchKernelGGL((attn_fwd_tr_kernel<D, CAUSAL, 4, false, 2>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((attn_fwd_tr_kernel<D, CAUSAL, 4>), grid, dim3(256), 0, st, p);
+            if (sl_env().attn_fwd_st == 2) hipLaunchKernelGGL((attn_fwd_tr_kernel<T, D, CAUSAL, 4, false, 2>), grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((attn_fwd_tr_kernel<T, D, CAUSAL, 4>), grid, dim3(256), 0, st, p);
             SL_CHECK_LAUNCH("attn_fwd_tr");
             return 0;
           }
         }
         constexpr int QT = 2;
         dim3 grid((a->max_qlen + QT * 64 - 1) / (QT * 64), a->n_heads, a->nseq);
-        hipLaunchKernelGGL((attn_fwd_tr_kernel<D, CAUSAL, QT>), grid, dim3(256), 0, st, p);
+        hipLaunchKernelGGL((attn_fwd_tr_kernel<T, D, CAUSAL, QT>), grid, dim3(256), 0, st, p);
         SL_CHECK_LAUNCH("attn_fwd_tr");
         return 0;
       }
@@ -538,7 +538,7 @@ extern "C" int sl_attn_fwd(const sl_attn_args* a, sl_stream stream) {
                    a->k_head_stride % vec == 0 && a->v_head_stride % vec == 0,
                "sl_attn_fwd: strides must keep 16-byte alignment");
   hipStream_t st = (hipStream_t)stream;
-  SL_DISPATCH_DTYPE(a->dtype, T, {
+  SL_DISPATCH_DTYPE_INF(a->dtype, T, {
     if (a->head_dim == 64) return a->causal ? launch_attn<T, 64, true>(a, st) : launch_attn<T, 64, false>(a, st);
     if (a->head_dim == 128) return a->causal ? launch_attn<T, 128, true>(a, st) : launch_attn<T, 128, false>(a, st);
     sl_set_error("sl_attn_fwd: head_dim %d not built (64, 128)", a->head_dim);

@@ -610,6 +610,7 @@ int launch_attn_bwd(const sl_attn_bwd_args* a, const AttnBwdP& p, hipStream_t st
 extern "C" int sl_attn_bwd(const sl_attn_bwd_args* a, sl_stream stream) {
   SL_CHECK_ARG(a && a->q && a->k && a->v && a->out && a->d_out && a->dq && a->dk && a->dv && a->lse && a->delta && a->cu_q && a->cu_k && a->klen,
                "sl_attn_bwd: null pointer");
+  SL_CHECK_ARG(a->dtype == SL_F32 || a->dtype == SL_BF16, "sl_attn_bwd: dtype %d is not a training dtype (SL_F32 / SL_BF16)", (int)a->dtype);
   SL_CHECK_ARG(a->nseq > 0 && a->max_qlen > 0 && a->max_klen > 0 && a->n_tok_q > 0 && a->n_heads > 0 && a->n_kv_heads > 0 &&
                    a->n_heads % a->n_kv_heads == 0, "sl_attn_bwd: bad shape");
   SL_CHECK_ARG(a->dropout_p >= 0.f && a->dropout_p < 1.f, "sl_attn_bwd: dropout_p=%f outside [0, 1)", (double)a->dropout_p);

@@ -47,13 +47,26 @@ void sl_set_error(const char* fmt, ...);
 // ----------------------------------------------------------------------------------------------
 // element types.  bf16 is carried as its 16 raw bits; conversion f32->bf16 is a plain cast so hipcc
 // emits v_cvt_pk_bf16_f32 (round-to-nearest-even, NaN-preserving: MI355X_MICROARCH "Correctness").
+// fp16 (f16_t) likewise: f32->fp16 through v_cvt_pk_f16_f32 (round-to-nearest-even; values beyond 65 504
+// become +-inf, as torch's .half() does — no clamping), fp16->f32 through v_cvt_f32_f16 (exact).
+// Code that is written once for both 16-bit types tests sizeof(T) == 2 and moves elements through the
+// type-generic helpers below (to_f32 / from_f32 / Vec16 / MMA / pack2 / unpack2); kernels built for bf16
+// only (the training tapes) say so with a static_assert on sl_is_bf16<T>.
 // ----------------------------------------------------------------------------------------------
 struct bf16_t {
   uint16_t bits;
 };
+struct f16_t {
+  uint16_t bits;
+};
+template <typename T> inline constexpr bool sl_is_bf16 = false;
+template <> inline constexpr bool sl_is_bf16<bf16_t> = true;
+template <typename T> inline constexpr bool sl_is_f16 = false;
+template <> inline constexpr bool sl_is_f16<f16_t> = true;
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
 
 // 16-byte streaming load with the non-temporal hint (weights read once per token: guide nt-weights)
@@ -79,11 +92,37 @@ __device__ __forceinline__ uint32_t pack2_bf16(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+__device__ __forceinline__ float f16_bits_to_f32(uint32_t b) { return (float)__builtin_bit_cast(_Float16, (uint16_t)b); }
+__device__ __forceinline__ uint16_t f32_to_f16_bits(float f) {
+  _Float16 h = (_Float16)f;
+  return __builtin_bit_cast(uint16_t, h);
+}
+// one v_cvt_pk_f16_f32
+__device__ __forceinline__ uint32_t pack2_f16(float lo, float hi) {
+  const f16x2_t v = __builtin_convertvector(f32x2_t{lo, hi}, f16x2_t);
+  return __builtin_bit_cast(uint32_t, v);
+}
+
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(bf16_t v) { return bf16_bits_to_f32(v.bits); }
+__device__ __forceinline__ float to_f32(f16_t v) { return f16_bits_to_f32(v.bits); }
 template <typename T> __device__ __forceinline__ T from_f32(float v);
 template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return bf16_t{f32_to_bf16_bits(v)}; }
+template <> __device__ __forceinline__ f16_t from_f32<f16_t>(float v) { return f16_t{f32_to_f16_bits(v)}; }
+
+// two 16-bit elements <-> one 32-bit word (element 0 in the low half)
+template <typename T> __device__ __forceinline__ uint32_t pack2(float lo, float hi);
+template <> __device__ __forceinline__ uint32_t pack2<bf16_t>(float lo, float hi) { return pack2_bf16(lo, hi); }
+template <> __device__ __forceinline__ uint32_t pack2<f16_t>(float lo, float hi) { return pack2_f16(lo, hi); }
+template <typename T> __device__ __forceinline__ f32x2_t unpack2(uint32_t w);
+template <> __device__ __forceinline__ f32x2_t unpack2<bf16_t>(uint32_t w) {
+  return f32x2_t{__builtin_bit_cast(float, w << 16), __builtin_bit_cast(float, w & 0xffff0000u)};
+}
+template <> __device__ __forceinline__ f32x2_t unpack2<f16_t>(uint32_t w) {
+  return __builtin_convertvector(__builtin_bit_cast(f16x2_t, w), f32x2_t);
+}
 
 // 16-byte vector of T: 4 floats or 8 bf16.  VEC = elements per 16 bytes.
 template <typename T> struct Vec16;
@@ -111,10 +150,25 @@ template <> struct Vec16<bf16_t> {
                       pack2_bf16(f[6], f[7]));
   }
 };
+template <> struct Vec16<f16_t> {
+  static constexpr int VEC = 8;
+  static __device__ __forceinline__ void unpack(const uint4& u, float* f) {
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const f32x2_t v = unpack2<f16_t>(w[i]);
+      f[2 * i] = v[0]; f[2 * i + 1] = v[1];
+    }
+  }
+  static __device__ __forceinline__ uint4 pack(const float* f) {
+    return make_uint4(pack2_f16(f[0], f[1]), pack2_f16(f[2], f[3]), pack2_f16(f[4], f[5]), pack2_f16(f[6], f[7]));
+  }
+};
 
 // ----------------------------------------------------------------------------------------------
 // MFMA 16x16 tile step, dtype-generic.  One "k-step" consumes 64 bytes of K per operand row:
 //   bf16: 32 k  -> one v_mfma_f32_16x16x32_bf16
+//   fp16: 32 k  -> one v_mfma_f32_16x16x32_f16 (same operand / accumulator layout, same cycles)
 //   f32 : 16 k  -> four v_mfma_f32_16x16x4_f32 (exact fp32 fma chain)
 // Lane l = (r = l & 15, q = l >> 4) supplies, for BOTH operands, the 16 bytes at k-offset q*VEC of
 // row r of its operand tile (A: output row, B: output column).  For f32 the four MFMAs take element
@@ -127,6 +181,12 @@ template <> struct MMA<bf16_t> {
   static __device__ __forceinline__ void step(f32x4& acc, const uint4& a, const uint4& b) {
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b),
                                                   acc, 0, 0, 0);
+  }
+};
+template <> struct MMA<f16_t> {
+  static constexpr int KSTEP = 32;
+  static __device__ __forceinline__ void step(f32x4& acc, const uint4& a, const uint4& b) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
   }
 };
 template <> struct MMA<float> {
@@ -172,7 +232,7 @@ __device__ __forceinline__ bool dropout_keep(int64_t i, uint64_t seed, uint32_t 
 __device__ __forceinline__ uint32_t drop_inner(uint32_t hi, uint64_t seed) { return lowbias32(hi ^ (uint32_t)seed) ^ (uint32_t)(seed >> 32); }
 __device__ __forceinline__ bool dropout_keep_lo(uint32_t lo, uint32_t inner, uint32_t thr24) { return (lowbias32(lo ^ inner) >> 8) >= thr24; }
 template <typename T> __device__ __forceinline__ float gelu_act(float x) {
-  if constexpr (sizeof(T) == 2) return gelu_fast(x);
+  if constexpr (sizeof(T) == 2) return gelu_fast(x);      // bf16 and fp16 (1.5e-7 is also far inside fp16's 4.9e-4 rounding)
   else return gelu_erf(x);
 }
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + __expf(-x)); }
@@ -198,7 +258,25 @@ constexpr int SL_MAX_DEVICES = 64;      // per-thread, per-device helper objects
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// dtype dispatch on the host
+// dtype dispatch on the host.  SL_DISPATCH_DTYPE: fp32 / bf16 (every entry point, the training ones included);
+// SL_DISPATCH_DTYPE_INF adds fp16 for the inference entry points only, so that the training kernels are not
+// instantiated a third time.
+#define SL_DISPATCH_DTYPE_INF(dtype, T, ...)                  \
+  do {                                                        \
+    if ((dtype) == SL_F32) {                                  \
+      using T = float;                                        \
+      __VA_ARGS__;                                            \
+    } else if ((dtype) == SL_BF16) {                          \
+      using T = bf16_t;                                       \
+      __VA_ARGS__;                                            \
+    } else if ((dtype) == SL_F16) {                           \
+      using T = f16_t;                                        \
+      __VA_ARGS__;                                            \
+    } else {                                                  \
+      sl_set_error("unknown dtype %d", (int)(dtype));         \
+      return SL_ERR_ARG;                                      \
+    }                                                         \
+  } while (0)
 #define SL_DISPATCH_DTYPE(dtype, T, ...)                      \
   do {                                                        \
     if ((dtype) == SL_F32) {                                  \
@@ -214,6 +292,8 @@ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b;
   } while (0)
 
 static inline size_t sl_dtype_size(int dtype) { return dtype == SL_F32 ? 4 : 2; }
+// a 16-bit storage type (bf16 or fp16): both run the same kernel families
+static inline bool sl_is16(int dtype) { return dtype == SL_BF16 || dtype == SL_F16; }
 
 // ----------------------------------------------------------------------------------------------
 // tuning switches: environment variables read ONCE (first use) into this table, never on a dispatch path;

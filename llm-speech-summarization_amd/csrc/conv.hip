@@ -110,7 +110,7 @@ extern "C" int sl_hubert_conv0_batch(const float* waves, const int64_t* sample_o
   SL_CHECK_ARG(waves && sample_offsets_dev && row_offsets_dev && w && bias && gamma && beta && out && n_utt > 0, "sl_hubert_conv0_batch: bad arguments");
   SL_CHECK_ARG(k == 10 && stride == 5, "sl_hubert_conv0_batch: only the HuBERT layer-0 geometry k=10, stride=5 is built (got k=%d s=%d)", k, stride);
   hipStream_t st = (hipStream_t)stream;
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     switch (C) {
       case 64: return launch_conv0_batch<T, 1>(waves, sample_offsets_dev, row_offsets_dev, n_utt, max_L, w, bias, gamma, beta, out, eps, st);
       case 128: return launch_conv0_batch<T, 2>(waves, sample_offsets_dev, row_offsets_dev, n_utt, max_L, w, bias, gamma, beta, out, eps, st);
@@ -140,7 +140,7 @@ extern "C" int sl_hubert_conv0(const float* wave, int64_t n_samples, const float
   SL_CHECK_ARG(n_samples >= k, "sl_hubert_conv0: n_samples=%lld shorter than the kernel", (long long)n_samples);
   const int64_t L = (n_samples - k) / stride + 1;
   hipStream_t st = (hipStream_t)stream;
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     switch (C) {
       case 64: return launch_conv0<T, 1>(wave, n_samples, w, bias, gamma, beta, out, L, eps, st);
       case 128: return launch_conv0<T, 2>(wave, n_samples, w, bias, gamma, beta, out, L, eps, st);
@@ -200,7 +200,7 @@ extern "C" int sl_posconv_stage_batch(const void* x, void* xg, const int32_t* cu
   SL_CHECK_ARG(x && xg && cu && klen && n_utt > 0 && groups > 0 && H % groups == 0 && (H / groups) % vec == 0, "sl_posconv_stage_batch: bad arguments");
   const int64_t total = (int64_t)groups * (max_T + k) * (H / groups / vec);
   const unsigned gx = (unsigned)(ceil_div64(total, 256) < 64 ? ceil_div64(total, 256) : 64);
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((posconv_stage_batch_kernel<T>), dim3(gx, n_utt), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)xg, cu, klen, H, groups, k);
   });
   SL_CHECK_LAUNCH("posconv_stage_batch");
@@ -214,7 +214,7 @@ extern "C" int sl_posconv_stage(const void* x, void* xg, int64_t T_, int32_t H, 
   SL_CHECK_ARG((H / groups) % vec == 0, "sl_posconv_stage: H/groups=%d must be a multiple of %d", H / groups, vec);
   const int64_t total = (int64_t)groups * (T_ + k) * (H / groups / vec);
   const unsigned grid = (unsigned)(ceil_div64(total, 256) < 4096 ? ceil_div64(total, 256) : 4096);
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((posconv_stage_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)xg, T_, H, groups, k);
   });
   SL_CHECK_LAUNCH("posconv_stage");
@@ -292,7 +292,7 @@ extern "C" int sl_avgpool_batch(const void* x, void* y, const int32_t* cu, const
   if (max_P <= 0) return 0;
   const int64_t total = max_P * (H / vec);
   const unsigned gx = (unsigned)(ceil_div64(total, 256) < 64 ? ceil_div64(total, 256) : 64);
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((avgpool_batch_kernel<T>), dim3(gx, n_utt), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, cu, klen, rec, H, kernel, stride);
   });
   SL_CHECK_LAUNCH("avgpool_batch");
@@ -308,7 +308,7 @@ extern "C" int sl_avgpool_rows(const void* x, void* y, int64_t T_, int32_t H, in
   if (P == 0) return 0;
   const int64_t total = P * (H / vec);
   const unsigned grid = (unsigned)(ceil_div64(total, 256) < 4096 ? ceil_div64(total, 256) : 4096);
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((avgpool_rows_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, T_, H, kernel, stride,
                        ranges, P);
   });

@@ -208,7 +208,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tiled_kernel(GemmP p) {
 // MFMA order, same bits.  SL_GLDS_DMAB=1 selects it; default off — with two blocks per CU the other block covers the burst (7 984 x 3 072 x 1 024: 795 against 845 TF/s, the rest within 1 %, profiles/r06_ah_gemm_vs_vendor_mid.txt); at ONE block per CU the same placement is worth +20 % (gemm128.hip).
 template <typename T>
 __device__ __forceinline__ void mfma_fence_step(f32x4& acc, const u32x4_t& a, const u32x4_t& b) {
-  if constexpr (sizeof(T) == 2) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "memory");
+  if constexpr (sl_is_f16<T>) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "memory");
+  else if constexpr (sizeof(T) == 2) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "memory");
 }
 
 template <typename T, int ACT, bool ASMLDS = false, bool DMAB = false>
@@ -731,7 +732,7 @@ static int splitk256_runs(const GemmP& p, int batch, int bk, size_t ws_bytes, in
 // leave CUs idle (two blocks per CU: 512 slots) and the caller supplied a workspace
 template <typename T>
 static bool tt_ok(const GemmP& p, int batch) {
-  if (sizeof(T) != 2 || !sl_env().wgrad_tr || !p.ta || !p.tw || p.grp || p.aux || p.ln_mr || p.stats_out || p.amax_val) return false;
+  if (!sl_is_bf16<T> || !sl_env().wgrad_tr || !p.ta || !p.tw || p.grp || p.aux || p.ln_mr || p.stats_out || p.amax_val) return false;
   // batched (round 6: the positional conv's weight gradient, 16 groups x 64 output rows per utterance, was 16 launches of the register-staged
   // loader at 84 TF/s): one K run, 64 output rows allowed (the tile's upper half reads zeros), no rider, 8-element aligned batch strides
   if (batch != 1) {
@@ -1019,7 +1020,7 @@ bool sl_gemm_post_ok(int64_t M, int N, int K, int dtype) {
 bool sl_gemm_rows_epilogue_ok(int M, int N, int K, int dtype) {
   // any row count: a product that carries ln_* / stats_out is kept on the tiled kernels even below 65 rows (gemm_typed), so that the fold is a
   // property of the MODEL — a short utterance encoded alone takes the same epilogues, hence the same bits, as inside a batch
-  if (dtype != SL_BF16 || M <= 0 || (N & 63) || sl_env().disable_glds != 0 || sl_env().direct_epilogue != 0) return false;
+  if (!sl_is16(dtype) || M <= 0 || (N & 63) || sl_env().disable_glds != 0 || sl_env().direct_epilogue != 0) return false;
   return K % (TROWB / 2) == 0;
 }
 
@@ -1027,7 +1028,7 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
   SL_CHECK_ARG(a != nullptr, "sl_gemm: null args");
   g_disable_glds = sl_env().disable_glds;   // 1: register staging, 2: glds with compiler-visible LDS reads
   SL_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0 && a->batch > 0, "sl_gemm: bad shape M=%d N=%d K=%d batch=%d", a->M, a->N, a->K, a->batch);
-  SL_CHECK_ARG(a->dtype == SL_F32 || a->dtype == SL_BF16, "sl_gemm: bad dtype %d", a->dtype);
+  SL_CHECK_ARG(a->dtype == SL_F32 || sl_is16(a->dtype), "sl_gemm: bad dtype %d", a->dtype);
   const int vec = a->dtype == SL_F32 ? 4 : 8;
   // a K-contiguous (non-transposed) operand is read in 16-byte chunks along K; transposed ones along the output index
   const bool both_t = ex && ex->trans_a && ex->trans_w;
@@ -1057,6 +1058,9 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
   const int gm_env = sl_env().gemm_gm;
   p.gm = gm_env;
   if (ex) {
+    // fp16 is an inference dtype: the training-tape features of sl_gemm_ex are built for fp32 / bf16 only
+    SL_CHECK_ARG(a->dtype != SL_F16 || !(ex->trans_a || ex->trans_w || ex->post_op || ex->colsum_out || ex->aux_out),
+                 "sl_gemm_ex: trans_a / trans_w / post_op / colsum_out / aux_out are training features, not built for SL_F16");
     p.ta = ex->trans_a; p.tw = ex->trans_w; p.aux = ex->aux_out; p.res_f32 = ex->residual_f32;
     p.grp = ex->groups; p.w_mod = ex->w_mod > 0 ? ex->w_mod : 1;
     if (ex->deferred_splits) { *ex->deferred_splits = 0; p.defer = ex->deferred_splits; }
@@ -1137,6 +1141,7 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
   const size_t sk_ws_bytes = ex ? ex->sk_ws_bytes : 0;
   SL_CHECK_ARG(!sk_ws || ((uintptr_t)sk_ws & 15) == 0, "sl_gemm_ex: sk_ws must be 16-byte aligned");
   if (a->dtype == SL_F32) return gemm_typed<float>(a, p, sx, st, sk_ws, sk_ws_bytes);
+  if (a->dtype == SL_F16) return gemm_typed<f16_t>(a, p, sx, st, sk_ws, sk_ws_bytes);
   return gemm_typed<bf16_t>(a, p, sx, st, sk_ws, sk_ws_bytes);
 }
 

@@ -29,15 +29,19 @@
 // register allocator rotate the accumulators through copies (92 v_accvgpr_* moves per slab beside 32 MFMAs); the asm form accumulates in
 // place, in the order written.  The compiler cannot see these as matrix instructions: mfma_asm_drain() covers the XDL-write -> VALU-read
 // wait states in front of the epilogue.
+// fp16 takes v_mfma_f32_16x16x32_f16: the same operand / accumulator layout, the same passes, hence the same XDL-write -> read wait
+// states as the bf16 form (the drain below is counted for either).
 template <typename T>
 __device__ __forceinline__ void mfma_asm(f32x4& acc, const u32x4_t& a, const u32x4_t& b) {
-  static_assert(std::is_same<T, bf16_t>::value, "the ring form is built for bf16");
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+  static_assert(sizeof(T) == 2, "the ring form is built for the 16-bit types");
+  if constexpr (sl_is_f16<T>) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+  else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
 }
 template <typename T>      // same, as a compiler-level memory fence: the DMA requests placed between two of these stay between them
 __device__ __forceinline__ void mfma_asm_fence(f32x4& acc, const u32x4_t& a, const u32x4_t& b) {
-  static_assert(std::is_same<T, bf16_t>::value, "the ring form is built for bf16");
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "memory");
+  static_assert(sizeof(T) == 2, "the ring form is built for the 16-bit types");
+  if constexpr (sl_is_f16<T>) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "memory");
+  else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b) : "memory");
 }
 __device__ __forceinline__ void mfma_asm_drain() { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); }
 
@@ -329,6 +333,9 @@ int sl_gemm128_ring_launch(const GemmP& p, int stages, dim3 grid, hipStream_t st
 template int sl_gemm128_ring_launch<bf16_t, SL_ACT_NONE>(const GemmP&, int, dim3, hipStream_t);
 template int sl_gemm128_ring_launch<bf16_t, SL_ACT_GELU>(const GemmP&, int, dim3, hipStream_t);
 template int sl_gemm128_ring_launch<bf16_t, SL_ACT_SILU_MUL>(const GemmP&, int, dim3, hipStream_t);
+template int sl_gemm128_ring_launch<f16_t, SL_ACT_NONE>(const GemmP&, int, dim3, hipStream_t);
+template int sl_gemm128_ring_launch<f16_t, SL_ACT_GELU>(const GemmP&, int, dim3, hipStream_t);
+template int sl_gemm128_ring_launch<f16_t, SL_ACT_SILU_MUL>(const GemmP&, int, dim3, hipStream_t);
 template int sl_gemm128_ring_launch<float, SL_ACT_NONE>(const GemmP&, int, dim3, hipStream_t);
 template int sl_gemm128_ring_launch<float, SL_ACT_GELU>(const GemmP&, int, dim3, hipStream_t);
 template int sl_gemm128_ring_launch<float, SL_ACT_SILU_MUL>(const GemmP&, int, dim3, hipStream_t);

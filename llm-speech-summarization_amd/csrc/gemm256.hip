@@ -33,7 +33,7 @@
 
 template <typename T, int ACT, bool SW = false>
 __global__ __launch_bounds__(512, 1) void gemm_tiled256_kernel(GemmP p) {
-  static_assert(!SW || (sizeof(T) == 2 && ACT != SL_ACT_SILU_MUL), "the swapped-operand form is the bf16 store epilogue");
+  static_assert(!SW || (sizeof(T) == 2 && ACT != SL_ACT_SILU_MUL), "the swapped-operand form is the 16-bit store epilogue");
   constexpr int VEC = Vec16<T>::VEC;
   constexpr int BK = TROWB / (int)sizeof(T);
   __shared__ __attribute__((aligned(16))) unsigned char smem[2][2][XBM * TROWB];   // [buf][A|W], 32 KiB each
@@ -147,11 +147,11 @@ __global__ __launch_bounds__(512, 1) void gemm_tiled256_kernel(GemmP p) {
     const int rb0 = bm * XBM + wm * 128, cb0 = bn * XBN + wn * 64;
     const float2* mrl = mr_s + wm * 128;
     const bool res = p.res != nullptr, ln = p.ln_mr != nullptr, st = p.stats_out != nullptr;    // launch_tiled admits these five forms only
-    if (p.aux) tile_epilogue_sw<ACT, EPI_AUX>(p, acc, rb0, cb0, lane, z, wz, mrl);
-    else if (ln) tile_epilogue_sw<ACT, EPI_LN>(p, acc, rb0, cb0, lane, z, wz, mrl);
-    else if (st) tile_epilogue_sw<ACT, EPI_RES | EPI_STATS>(p, acc, rb0, cb0, lane, z, wz, mrl);
-    else if (res) tile_epilogue_sw<ACT, EPI_RES>(p, acc, rb0, cb0, lane, z, wz, mrl);
-    else tile_epilogue_sw<ACT, 0>(p, acc, rb0, cb0, lane, z, wz, mrl);
+    if (p.aux) tile_epilogue_sw<T, ACT, EPI_AUX>(p, acc, rb0, cb0, lane, z, wz, mrl);
+    else if (ln) tile_epilogue_sw<T, ACT, EPI_LN>(p, acc, rb0, cb0, lane, z, wz, mrl);
+    else if (st) tile_epilogue_sw<T, ACT, EPI_RES | EPI_STATS>(p, acc, rb0, cb0, lane, z, wz, mrl);
+    else if (res) tile_epilogue_sw<T, ACT, EPI_RES>(p, acc, rb0, cb0, lane, z, wz, mrl);
+    else tile_epilogue_sw<T, ACT, 0>(p, acc, rb0, cb0, lane, z, wz, mrl);
     return;
   } else {
     if constexpr (ACT != SL_ACT_SILU_MUL) {
@@ -377,20 +377,20 @@ __device__ __forceinline__ void t256_epilogue(const GemmP& p, f32x4 (&acc)[8][4]
      if (p.post) {         // launch_tiled admits exactly these post-op forms on the swapped-operand kernels (the phased kernel only)
       done = true;
       if constexpr (ACT == SL_ACT_GELU) {
-        tile_epilogue_sw<ACT, EPI_AUX | EPI_DROP>(p, acc, rb0_, cb0, lane, z, wz, mrl);        // FFN1 forward: mid = dropout(gelu(pre)), pre kept
+        tile_epilogue_sw<T, ACT, EPI_AUX | EPI_DROP>(p, acc, rb0_, cb0, lane, z, wz, mrl);        // FFN1 forward: mid = dropout(gelu(pre)), pre kept
       } else {
-        if (p.post == SL_POST_DROPOUT) tile_epilogue_sw<ACT, EPI_RES | EPI_DROP>(p, acc, rb0_, cb0, lane, z, wz, mrl);   // h = residual + dropout(sublayer)
-        else if (p.post == SL_POST_GELU_BWD) tile_epilogue_sw<ACT, EPI_GBWD>(p, acc, rb0_, cb0, lane, z, wz, mrl);
-        else tile_epilogue_sw<ACT, EPI_SBWD>(p, acc, rb0_, cb0, lane, z, wz, mrl);
+        if (p.post == SL_POST_DROPOUT) tile_epilogue_sw<T, ACT, EPI_RES | EPI_DROP>(p, acc, rb0_, cb0, lane, z, wz, mrl);   // h = residual + dropout(sublayer)
+        else if (p.post == SL_POST_GELU_BWD) tile_epilogue_sw<T, ACT, EPI_GBWD>(p, acc, rb0_, cb0, lane, z, wz, mrl);
+        else tile_epilogue_sw<T, ACT, EPI_SBWD>(p, acc, rb0_, cb0, lane, z, wz, mrl);
       }
      }
     }
     if (done) return;
-    if (p.aux) tile_epilogue_sw<ACT, EPI_AUX>(p, acc, rb0_, cb0, lane, z, wz, mrl);
-    else if (ln) tile_epilogue_sw<ACT, EPI_LN>(p, acc, rb0_, cb0, lane, z, wz, mrl);
-    else if (st) tile_epilogue_sw<ACT, EPI_RES | EPI_STATS>(p, acc, rb0_, cb0, lane, z, wz, mrl);
-    else if (res) tile_epilogue_sw<ACT, EPI_RES>(p, acc, rb0_, cb0, lane, z, wz, mrl);
-    else tile_epilogue_sw<ACT, 0>(p, acc, rb0_, cb0, lane, z, wz, mrl);
+    if (p.aux) tile_epilogue_sw<T, ACT, EPI_AUX>(p, acc, rb0_, cb0, lane, z, wz, mrl);
+    else if (ln) tile_epilogue_sw<T, ACT, EPI_LN>(p, acc, rb0_, cb0, lane, z, wz, mrl);
+    else if (st) tile_epilogue_sw<T, ACT, EPI_RES | EPI_STATS>(p, acc, rb0_, cb0, lane, z, wz, mrl);
+    else if (res) tile_epilogue_sw<T, ACT, EPI_RES>(p, acc, rb0_, cb0, lane, z, wz, mrl);
+    else tile_epilogue_sw<T, ACT, 0>(p, acc, rb0_, cb0, lane, z, wz, mrl);
   } else {
     if constexpr (ACT != SL_ACT_SILU_MUL) {
       // the LDS-turned rows epilogue uses 16 KiB per wave of the piece slots (every DMA has landed: the last phases wait vmcnt(0))
@@ -404,7 +404,7 @@ __device__ __forceinline__ void t256_epilogue(const GemmP& p, f32x4 (&acc)[8][4]
 template <typename T, int ACT, bool SW = false, int DBG = 0>
 __global__ __launch_bounds__(512, 2) void gemm_tiled256p_kernel(GemmP p) {
   constexpr bool STAMP = (DBG & 8) != 0;
-  static_assert(!SW || (sizeof(T) == 2 && ACT != SL_ACT_SILU_MUL), "the swapped-operand form is the bf16 store epilogue");
+  static_assert(!SW || (sizeof(T) == 2 && ACT != SL_ACT_SILU_MUL), "the swapped-operand form is the 16-bit store epilogue");
   constexpr int BK = TROWB / (int)sizeof(T);
   constexpr int PIECE = 128 * TROWB;            // 16 KiB
   // one LDS object (a second one beside an LDS-DMA target can cost a vmcnt(0) per k-step, guide §5 item 4a): 8 piece slots + {mean, rstd}
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tiled256p_kernel(GemmP p) {
 
 template <typename T, int ACT, bool SW>
 __global__ __launch_bounds__(512, 2) void gemm_tiled256sk_kernel(GemmP p, unsigned char* ws) {
-  static_assert(!SW || (sizeof(T) == 2 && ACT != SL_ACT_SILU_MUL), "the swapped-operand form is the bf16 store epilogue");
+  static_assert(!SW || (sizeof(T) == 2 && ACT != SL_ACT_SILU_MUL), "the swapped-operand form is the 16-bit store epilogue");
   constexpr int BK = TROWB / (int)sizeof(T);
   constexpr int PIECE = 128 * TROWB;
   __shared__ __attribute__((aligned(16))) unsigned char smem[8 * PIECE + XBM * 8];
@@ -593,6 +593,9 @@ int sl_gemm256_launch(const GemmP& p, int kind, dim3 grid, void* sk_ws, hipStrea
 template int sl_gemm256_launch<bf16_t, SL_ACT_NONE>(const GemmP&, int, dim3, void*, hipStream_t);
 template int sl_gemm256_launch<bf16_t, SL_ACT_GELU>(const GemmP&, int, dim3, void*, hipStream_t);
 template int sl_gemm256_launch<bf16_t, SL_ACT_SILU_MUL>(const GemmP&, int, dim3, void*, hipStream_t);
+template int sl_gemm256_launch<f16_t, SL_ACT_NONE>(const GemmP&, int, dim3, void*, hipStream_t);
+template int sl_gemm256_launch<f16_t, SL_ACT_GELU>(const GemmP&, int, dim3, void*, hipStream_t);
+template int sl_gemm256_launch<f16_t, SL_ACT_SILU_MUL>(const GemmP&, int, dim3, void*, hipStream_t);
 template int sl_gemm256_launch<float, SL_ACT_NONE>(const GemmP&, int, dim3, void*, hipStream_t);
 template int sl_gemm256_launch<float, SL_ACT_GELU>(const GemmP&, int, dim3, void*, hipStream_t);
 template int sl_gemm256_launch<float, SL_ACT_SILU_MUL>(const GemmP&, int, dim3, void*, hipStream_t);

@@ -150,13 +150,27 @@ __device__ __forceinline__ void ld4(const bf16_t* ptr, float (&f)[4]) {
   f[0] = bf16_bits_to_f32(u.x & 0xffffu); f[1] = bf16_bits_to_f32(u.x >> 16);
   f[2] = bf16_bits_to_f32(u.y & 0xffffu); f[3] = bf16_bits_to_f32(u.y >> 16);
 }
+__device__ __forceinline__ void ld4(const f16_t* ptr, float (&f)[4]) {
+  const uint2 u = *(const uint2*)ptr;
+  const f32x2_t a = unpack2<f16_t>(u.x), b = unpack2<f16_t>(u.y);
+  f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1];
+}
 __device__ __forceinline__ void unpack4(const f32x4& v, float (&f)[4]) { f[0] = v[0]; f[1] = v[1]; f[2] = v[2]; f[3] = v[3]; }
-__device__ __forceinline__ void unpack4(const uint2& u, float (&f)[4]) {
+template <typename T> __device__ __forceinline__ void unpack4_16(const uint2& u, float (&f)[4]);
+template <> __device__ __forceinline__ void unpack4_16<bf16_t>(const uint2& u, float (&f)[4]) {
   f[0] = bf16_bits_to_f32(u.x & 0xffffu); f[1] = bf16_bits_to_f32(u.x >> 16);
   f[2] = bf16_bits_to_f32(u.y & 0xffffu); f[3] = bf16_bits_to_f32(u.y >> 16);
 }
+template <> __device__ __forceinline__ void unpack4_16<f16_t>(const uint2& u, float (&f)[4]) {
+  const f32x2_t a = unpack2<f16_t>(u.x), b = unpack2<f16_t>(u.y);
+  f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1];
+}
+// four elements of type T as loaded (RawT: f32x4 for fp32, uint2 for the 16-bit types)
+template <typename T> __device__ __forceinline__ void unpack4r(const f32x4& v, float (&f)[4]) { unpack4(v, f); }
+template <typename T> __device__ __forceinline__ void unpack4r(const uint2& u, float (&f)[4]) { unpack4_16<T>(u, f); }
 __device__ __forceinline__ void st4(float* ptr, const float (&f)[4]) { *(f32x4*)ptr = f32x4{f[0], f[1], f[2], f[3]}; }
 __device__ __forceinline__ void st4(bf16_t* ptr, const float (&f)[4]) { *(uint2*)ptr = make_uint2(pack2_bf16(f[0], f[1]), pack2_bf16(f[2], f[3])); }
+__device__ __forceinline__ void st4(f16_t* ptr, const float (&f)[4]) { *(uint2*)ptr = make_uint2(pack2_f16(f[0], f[1]), pack2_f16(f[2], f[3])); }
 
 // Sum over the 16 lanes of a DPP row (lanes 16k .. 16k+15), left in every lane: four rotate-and-add steps on the VALU's DPP path
 // (row_ror 8, 4, 2, 1), no LDS crossbar traffic — the order of the additions is fixed, so the result is reproducible.
@@ -186,7 +200,7 @@ enum : int { EPI_GENERIC = 1, EPI_RES = 2, EPI_LN = 4, EPI_STATS = 8, EPI_AUX = 
 template <typename T, int ACT, int MT, int F>
 __device__ __forceinline__ void tile_epilogue_rows_impl(const GemmP& p, f32x4 (&acc)[MT][4], int row_base, int col_base, int lane, int wz, float* wsm,
                                                         const float2* mr_lds, int64_t co, int64_t ro) {
-  constexpr bool G = (F & EPI_GENERIC) != 0, BF = sizeof(T) == 2;      // the LayerNorm fold is a bf16 form (sl_gemm_impl checks)
+  constexpr bool G = (F & EPI_GENERIC) != 0, BF = sizeof(T) == 2;      // the LayerNorm fold is a 16-bit form (sl_gemm_impl checks)
   const bool f_aux = G && p.aux != nullptr, f_out32 = G && p.out_f32, f_res32 = G && p.res && p.res_f32;
   const bool f_rest = G ? (p.res && !p.res_f32) : (F & EPI_RES) != 0;
   const bool f_ln = BF && (G ? p.ln_mr != nullptr : (F & EPI_LN) != 0);
@@ -307,8 +321,8 @@ __device__ __forceinline__ void tile_epilogue_rows_impl(const GemmP& p, f32x4 (&
           }
           if constexpr (SB) {     // (M, 2 N) output, interleaved [16 gate | 16 up]: the lane's four columns sit in one 16-group
             float g4[4], up4[4], dg[4], du[4];
-            unpack4(raw[t], g4);
-            unpack4(raw2[t], up4);
+            unpack4r<T>(raw[t], g4);
+            unpack4r<T>(raw2[t], up4);
 #pragma unroll
             for (int j = 0; j < 4; ++j) post_silu_bwd<T>(v[j], g4[j], up4[j], dg[j], du[j]);
             T* op = (T*)p.C + co + row * p.ldc + 32 * (col >> 4) + (col & 15);
@@ -321,13 +335,13 @@ __device__ __forceinline__ void tile_epilogue_rows_impl(const GemmP& p, f32x4 (&
           } else if (f_pin) {
             post_drop<T, 4>(p, row, col, v);
             float pre4[4];
-            unpack4(raw[t], pre4);
+            unpack4r<T>(raw[t], pre4);
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = round_as<T>(v[j]) * gelu_grad(pre4[j]);
           }
           if (f_rest) {
             float rr[4];
-            unpack4(raw[t], rr);
+            unpack4r<T>(raw[t], rr);
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] += rr[j];
           } else if (f_res32) {
@@ -342,10 +356,12 @@ __device__ __forceinline__ void tile_epilogue_rows_impl(const GemmP& p, f32x4 (&
           }
           if (f_stats) {
             f32x2_t f01 = {v[0], v[1]}, f23 = {v[2], v[3]};
-            if (!f_out32) {               // the values as stored: the same v_cvt_pk_bf16_f32 st4 issued, its halves shifted back up
-              const uint32_t lo = pack2_bf16(v[0], v[1]), hi = pack2_bf16(v[2], v[3]);
-              f01 = f32x2_t{__builtin_bit_cast(float, lo << 16), __builtin_bit_cast(float, lo & 0xffff0000u)};
-              f23 = f32x2_t{__builtin_bit_cast(float, hi << 16), __builtin_bit_cast(float, hi & 0xffff0000u)};
+            if constexpr (BF) {
+              if (!f_out32) {             // the values as stored: the same pack st4 issued, unpacked again
+                const uint32_t lo = pack2<T>(v[0], v[1]), hi = pack2<T>(v[2], v[3]);
+                f01 = unpack2<T>(lo);
+                f23 = unpack2<T>(hi);
+              }
             }
             const f32x2_t a2 = f01 + f23, q2 = __builtin_elementwise_fma(f23, f23, f01 * f01);
             s1 = a2[0] + a2[1];
@@ -415,7 +431,7 @@ __device__ __forceinline__ bool tile_epilogue_rows(const GemmP& p, f32x4 (&acc)[
 }
 
 // ----------------------------------------------------------------------------------------------
-// Register epilogue of the swapped-operand 256-tile kernel (bf16).  With the MFMA operands exchanged (D = W_frag . A_frag^T)
+// Register epilogue of the swapped-operand 256-tile kernel (bf16 / fp16).  With the MFMA operands exchanged (D = W_frag . A_frag^T)
 // a lane holds four consecutive COLUMNS of one output row; the kernel reads W fragment n of lane r from tile row
 // 32 (n >> 1) + 8 (r >> 2) + 4 (n & 1) + (r & 3), which makes lane (q, r)'s sixteen values of row m*16 + r the columns
 // [8q, 8q + 8) and [32 + 8q, 32 + 8q + 8) of the wave's 64: two 16-byte stores per row, the four q's of a row filling 64
@@ -424,9 +440,9 @@ __device__ __forceinline__ bool tile_epilogue_rows(const GemmP& p, f32x4 (&acc)[
 // vectors stay in registers per column, the residual arrives as 16-byte loads, four rows requested at a time.
 // The launch code guarantees: N, ldc, ldr, the batch strides multiples of 8, 16-byte aligned C / residual, no aux / fp32 forms.
 // ----------------------------------------------------------------------------------------------
-template <int ACT, int F>
+template <typename T, int ACT, int F>
 __device__ __forceinline__ void tile_epilogue_sw(const GemmP& p, f32x4 (&acc)[8][4], int row_base, int col_base, int lane, int z, int wz, const float2* mr_lds) {
-  using T = bf16_t;
+  static_assert(sizeof(T) == 2, "the swapped-operand epilogue stores a 16-bit type");
   constexpr bool RES = (F & EPI_RES) != 0, LN = (F & EPI_LN) != 0, ST = (F & EPI_STATS) != 0, AUX = (F & EPI_AUX) != 0;
   // training-tape post-ops (sl_gemm_ex_args.post_op): dropout of the value before the residual add; GELU' x dropout behind a data-gradient product
   // (+ the bias gradient's column sums); SwiGLU' writing the (M, 2 N) interleaved gate / up gradient
@@ -566,8 +582,8 @@ __device__ __forceinline__ void tile_epilogue_sw(const GemmP& p, f32x4 (&acc)[8]
             const uint32_t w[4] = {pk.x, pk.y, pk.z, pk.w};   // exactly as the rows epilogue forms them: the tree below is its tree
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
-              const f32x2_t f01 = {__builtin_bit_cast(float, w[2 * g] << 16), __builtin_bit_cast(float, w[2 * g] & 0xffff0000u)};
-              const f32x2_t f23 = {__builtin_bit_cast(float, w[2 * g + 1] << 16), __builtin_bit_cast(float, w[2 * g + 1] & 0xffff0000u)};
+              const f32x2_t f01 = unpack2<T>(w[2 * g]);
+              const f32x2_t f23 = unpack2<T>(w[2 * g + 1]);
               const f32x2_t a2 = f01 + f23, q2 = __builtin_elementwise_fma(f23, f23, f01 * f01);
               la[h][g] = a2[0] + a2[1];
               lq[h][g] = q2[0] + q2[1];

@@ -682,7 +682,7 @@ __global__ __launch_bounds__(ROWSTAT ? 1024 : 256) void gemm_stream_reduce_kerne
 #pragma unroll
           for (int i = 0; i < 4; ++i) o[i] = to_f32(((const T*)sx.norm_gain)[col0 + i]) * to_f32(from_f32<T>(kept[i] * rstd));
           T* dst = (T*)sx.norm_out + (int64_t)m * p.N + col0;        // 8 (bf16) / 16 (f32) bytes per lane, 64 / 128 contiguous bytes per fragment
-          if constexpr (sizeof(T) == 2) *(uint2*)dst = make_uint2(pack2_bf16(o[0], o[1]), pack2_bf16(o[2], o[3]));
+          if constexpr (sizeof(T) == 2) *(uint2*)dst = make_uint2(pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3]));
           else *(f32x4*)dst = f32x4{o[0], o[1], o[2], o[3]};
         } else {
           for (int i = 0; i < 4 && col0 + i < p.N; ++i)
@@ -733,7 +733,7 @@ static StreamCfg stream_cfg(int M, int N, int K, int kstep, bool have_ws, int dt
   c.splits = splits;
   // the 256 x 128 form (bf16, > 384 rows): unsplit when its blocks cover at least half the CUs, else K split towards ~240 blocks of >= 6 stages
   c.wide = 0; c.wsplits = 1;
-  if (dtype == SL_BF16 && M > 384 && sl_env().stream_wide != 0) {
+  if (sl_is16(dtype) && M > 384 && sl_env().stream_wide != 0) {
     const int wbase = ((M + 255) / 256) * ((nfrag + 7) / 8);
     if (wbase >= 128 || sl_env().stream_wide == 2) {   // unsplit from half the CUs up (qkv at 1024 rows: 160 blocks, 53 us; 61 us split in two)
       c.wide = 1;
@@ -848,7 +848,7 @@ static bool stream_wide_ok(const SkinnyX& sx, int act, const StreamCfg& c, bool 
   return c.wsplits == 1 || have_ws;
 }
 
-template <int ACT>
+template <typename T, int ACT>
 static int launch_stream_wide_act(GemmP& p, const SkinnyX& sx, const StreamX& s, hipStream_t st) {
   const int nfrag = (p.N + 15) / 16, mblocks = (p.M + 255) / 256, nblocks = (nfrag + 7) / 8;
   constexpr int LDS_BYTES = 3 * (256 * TROWB + 8 * 2 * 1024);
@@ -857,20 +857,21 @@ static int launch_stream_wide_act(GemmP& p, const SkinnyX& sx, const StreamX& s,
   int devid = 0;
   SL_HIP(hipGetDevice(&devid));
   if (devid < 0 || devid >= 64 || !((attr_set.load(std::memory_order_relaxed) >> devid) & 1)) {
-    SL_HIP(hipFuncSetAttribute((const void*)gemm_stream_wide_kernel<bf16_t, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+    SL_HIP(hipFuncSetAttribute((const void*)gemm_stream_wide_kernel<T, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     if (devid >= 0 && devid < 64) attr_set.fetch_or(1ull << devid, std::memory_order_relaxed);
   }
-  hipLaunchKernelGGL((gemm_stream_wide_kernel<bf16_t, ACT>), grid, dim3(768), LDS_BYTES, st, p, sx, s);
+  hipLaunchKernelGGL((gemm_stream_wide_kernel<T, ACT>), grid, dim3(768), LDS_BYTES, st, p, sx, s);
   SL_CHECK_LAUNCH("gemm_stream_wide");
   if (s.cnt) return 0;   // the kernel's last-arriving blocks did the reduce pass
-  return launch_stream_reduce<bf16_t, ACT>(p, sx, s, st);
+  return launch_stream_reduce<T, ACT>(p, sx, s, st);
 }
 
+template <typename T>
 static int launch_stream_wide(GemmP& p, const SkinnyX& sx, int act, const StreamX& s, hipStream_t st) {
   switch (act) {
-    case SL_ACT_SILU_MUL: return launch_stream_wide_act<SL_ACT_SILU_MUL>(p, sx, s, st);
-    case SL_ACT_ROPE_KV: return launch_stream_wide_act<SL_ACT_ROPE_KV>(p, sx, s, st);
-    default: return launch_stream_wide_act<SL_ACT_NONE>(p, sx, s, st);
+    case SL_ACT_SILU_MUL: return launch_stream_wide_act<T, SL_ACT_SILU_MUL>(p, sx, s, st);
+    case SL_ACT_ROPE_KV: return launch_stream_wide_act<T, SL_ACT_ROPE_KV>(p, sx, s, st);
+    default: return launch_stream_wide_act<T, SL_ACT_NONE>(p, sx, s, st);
   }
 }
 
@@ -910,6 +911,10 @@ int sl_gemm_stream_launch(GemmP& p, const SkinnyX& sx, int dtype, int act, void*
     }
   }
   if (dtype == SL_F32) return stream_typed<float>(p, sx, act, s, c, st);
-  if (wide) return launch_stream_wide(p, sx, act, s, st);
+  if (dtype == SL_F16) {
+    if (wide) return launch_stream_wide<f16_t>(p, sx, act, s, st);
+    return stream_typed<f16_t>(p, sx, act, s, c, st);
+  }
+  if (wide) return launch_stream_wide<bf16_t>(p, sx, act, s, st);
   return stream_typed<bf16_t>(p, sx, act, s, c, st);
 }

@@ -26,7 +26,7 @@ extern "C" int sl_embed_gather(const void* table, const int32_t* ids, void* out,
   if (n == 0) return 0;
   const int64_t total = n * (cols / vec);
   const unsigned grid = (unsigned)(ceil_div64(total, 256) < 4096 ? ceil_div64(total, 256) : 4096);
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((embed_gather_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)table, ids, (T*)out, n, cols);
   });
   SL_CHECK_LAUNCH("embed_gather");
@@ -89,7 +89,7 @@ extern "C" int sl_rope_kv_append(void* qkv, void* k_cache, void* v_cache, const 
   if (n_tok == 0) return 0;
   const int64_t total = n_tok * (n_heads + 2 * n_kv) * (D / 2 / vec);
   const unsigned grid = (unsigned)(ceil_div64(total, 256) < 8192 ? ceil_div64(total, 256) : 8192);
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((rope_kv_append_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (T*)qkv, (T*)k_cache, (T*)v_cache,
                        tok_seq, tok_pos, cos, sin, n_tok, n_heads, n_kv, D, max_ctx);
   });
@@ -218,7 +218,7 @@ int sl_attn_decode_impl(const void* q, int64_t q_stride, const void* k_cache, co
   SL_CHECK_ARG(D == 128, "sl_attn_decode: head_dim %d not built (Llama family uses 128)", D);
   SL_CHECK_ARG(n_kv > 0 && n_heads % n_kv == 0, "sl_attn_decode: n_heads %% n_kv != 0");
   const int rep = n_heads / n_kv;
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     switch (rep) {
       case 1: return launch_attn_decode<T, 1>(q, q_stride, k_cache, v_cache, out, ctx_len, ctx_add, B, n_heads, n_kv, max_ctx, scale, st);
       case 2: return launch_attn_decode<T, 2>(q, q_stride, k_cache, v_cache, out, ctx_len, ctx_add, B, n_heads, n_kv, max_ctx, scale, st);
@@ -618,7 +618,7 @@ extern "C" int sl_pack_weight(const void* src, int64_t ld_src, void* dst, int32_
   SL_CHECK_ARG(K % (4 * vec) == 0 && ld_src % vec == 0, "sl_pack_weight: K=%d must be a multiple of %d", K, 4 * vec);
   const int64_t total = (int64_t)((N + 15) / 16) * (K / (4 * vec)) * 64;
   const unsigned grid = (unsigned)(ceil_div64(total, 256) < 16384 ? ceil_div64(total, 256) : 16384);
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((pack_weight_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const T*)src, ld_src, (T*)dst, N, K);
   });
   SL_CHECK_LAUNCH("pack_weight");
@@ -926,12 +926,12 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const T* __restr
 // small enough to sit on a CU BESIDE a 256 x 256 GEMM block of another stream (130 of the 160 KiB of LDS, half the register file):
 // the HBM-bound attention of one in-flight batch can then run under the matrix-core-bound encode / prefill of the other
 // (SL_ATTN_DECODE_KS=64; DESIGN §8.10 has what it measured).
-template <int REP, bool PREFETCH, int KS_ = 128>
-__global__ __launch_bounds__(256) void attn_decode_full_kernel(const bf16_t* __restrict__ q, int64_t q_stride, const bf16_t* __restrict__ kc,
-                                                               const bf16_t* __restrict__ vc, bf16_t* __restrict__ out,
+template <typename T, int REP, bool PREFETCH, int KS_ = 128>
+__global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restrict__ q, int64_t q_stride, const T* __restrict__ kc,
+                                                               const T* __restrict__ vc, T* __restrict__ out,
                                                                const int32_t* __restrict__ ctx_len, int ctx_add, int nh, int nkv, int max_ctx,
                                                                float scale, int shared_prefix) {
-  using T = bf16_t;
+  static_assert(sizeof(T) == 2, "the single-pass form is built for the 16-bit types (bf16 / fp16)");
   constexpr int D = 128, KS = KS_, NPS = KS / 16;
   static_assert(KS == 64 || KS == 128, "chunks of 64 or 128 keys");
   constexpr int PROW = KS * 2 + 16;
@@ -1114,14 +1114,14 @@ static int launch_attn_decode_split(const void* q, int64_t q_stride, const void*
     const bool long_thin = max_ctx >= 1024 && Bf * nkv < 768;
     if (Bf * nkv >= full_min && !long_thin && !sl_env().attn_force_split) {
       if (sl_env().attn_decode_ks == 65)        // 64-key chunks with the NEXT chunk's K / V rows held in a second register set (twice the bytes in flight per block)
-        hipLaunchKernelGGL((attn_decode_full_kernel<REP, true, 64>), dim3(nkv, B), dim3(256), 0, st, (const bf16_t*)q, q_stride, (const bf16_t*)kc,
-                           (const bf16_t*)vc, (bf16_t*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
+        hipLaunchKernelGGL((attn_decode_full_kernel<T, REP, true, 64>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride, (const T*)kc,
+                           (const T*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
       else if (sl_env().attn_decode_ks == 64)
-        hipLaunchKernelGGL((attn_decode_full_kernel<REP, false, 64>), dim3(nkv, B), dim3(256), 0, st, (const bf16_t*)q, q_stride, (const bf16_t*)kc,
-                           (const bf16_t*)vc, (bf16_t*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
+        hipLaunchKernelGGL((attn_decode_full_kernel<T, REP, false, 64>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride, (const T*)kc,
+                           (const T*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
       else
-        hipLaunchKernelGGL((attn_decode_full_kernel<REP, false>), dim3(nkv, B), dim3(256), 0, st, (const bf16_t*)q, q_stride, (const bf16_t*)kc,
-                           (const bf16_t*)vc, (bf16_t*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
+        hipLaunchKernelGGL((attn_decode_full_kernel<T, REP, false>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride, (const T*)kc,
+                           (const T*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
       SL_CHECK_LAUNCH("attn_decode_full");
       return 0;
     }
@@ -1164,7 +1164,7 @@ int sl_attn_decode_split_impl(const void* q, int64_t q_stride, const void* k_cac
   if (mode == 0 || (mode < 0 && (int64_t)sl_family_rows(B) * n_kv > 32)) counters = 0;
   int32_t* cnt = counters ? (int32_t*)((unsigned char*)workspace + attn_split_records_bytes(B, n_heads, n_kv, max_ctx)) : nullptr;
   if (counters == 2) SL_TRY(sl_attn_decode_split_zero_counters(workspace, B, n_heads, n_kv, max_ctx, st));
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     switch (rep) {
       case 1: return launch_attn_decode_split<T, 1>(q, q_stride, k_cache, v_cache, out, part, ctx_len, ctx_add, B, n_heads, n_kv, max_ctx, scale, st, cnt, shared_prefix);
       case 2: return launch_attn_decode_split<T, 2>(q, q_stride, k_cache, v_cache, out, part, ctx_len, ctx_add, B, n_heads, n_kv, max_ctx, scale, st, cnt, shared_prefix);

@@ -187,13 +187,13 @@ static int launch_norm(const void* x, void* y, const void* g, const void* b, int
 extern "C" int sl_layernorm(const void* x, void* y, const void* gamma, const void* beta, int64_t rows, int32_t cols, float eps,
                             int32_t gelu, int32_t dtype, sl_stream stream) {
   SL_CHECK_ARG(x && y && gamma && beta && rows >= 0 && cols > 0, "sl_layernorm: bad arguments");
-  SL_DISPATCH_DTYPE(dtype, T, return (launch_norm<T, false>(x, y, gamma, beta, rows, cols, eps, gelu, (hipStream_t)stream)));
+  SL_DISPATCH_DTYPE_INF(dtype, T, return (launch_norm<T, false>(x, y, gamma, beta, rows, cols, eps, gelu, (hipStream_t)stream)));
 }
 
 extern "C" int sl_rmsnorm(const void* x, void* y, const void* w, int64_t rows, int32_t cols, float eps, int32_t dtype,
                           sl_stream stream) {
   SL_CHECK_ARG(x && y && w && rows >= 0 && cols > 0, "sl_rmsnorm: bad arguments");
-  SL_DISPATCH_DTYPE(dtype, T, return (launch_norm<T, true>(x, y, w, nullptr, rows, cols, eps, 0, (hipStream_t)stream)));
+  SL_DISPATCH_DTYPE_INF(dtype, T, return (launch_norm<T, true>(x, y, w, nullptr, rows, cols, eps, 0, (hipStream_t)stream)));
 }
 
 // RMSNorm scale of every row (rstd_out, fp32) and / or the normalised rows (y with gain w; y = w = NULL: the scale only).  The
@@ -202,7 +202,7 @@ extern "C" int sl_rmsnorm(const void* x, void* y, const void* w, int64_t rows, i
 int sl_rmsnorm_rstd_impl(const void* x, void* y, const void* w, float* rstd_out, int64_t rows, int32_t cols, float eps, int32_t dtype, hipStream_t st) {
   SL_CHECK_ARG(x && rows >= 0 && cols > 0 && (y == nullptr) == (w == nullptr) && (y || rstd_out), "sl_rmsnorm_rstd: bad arguments");
   if (rows == 0) return 0;
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     constexpr int VEC = Vec16<T>::VEC;
     SL_CHECK_ARG(cols % VEC == 0 && cols <= 64 * NORM_MAXF, "norm: cols=%d must be a multiple of %d and <= %d", cols, VEC, 64 * NORM_MAXF);
     hipLaunchKernelGGL((norm_rows_kernel<T, true>), dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, st, (const T*)x, (T*)y, (const T*)w, (const T*)nullptr,
@@ -282,7 +282,7 @@ extern "C" int sl_layernorm_stats(const void* x, int64_t rows, int32_t cols, flo
   const int vec = dtype == SL_F32 ? 4 : 8;
   SL_CHECK_ARG(cols % vec == 0 && cols <= 64 * NORM_MAXF, "sl_layernorm_stats: cols=%d must be a multiple of %d and <= %d", cols, vec, 64 * NORM_MAXF);
   if (rows == 0) return 0;
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((ln_rowstats_kernel<T>), dim3((unsigned)ceil_div64(rows, 4)), dim3(256), 0, (hipStream_t)stream, (const T*)x, rows, cols, eps, mr);
   });
   SL_CHECK_LAUNCH("ln_rowstats");
@@ -322,7 +322,7 @@ extern "C" int sl_layernorm_fold_build(const void* W, const void* gain, const vo
   SL_CHECK_ARG(W && gain && beta && Wf && u && c && N > 0 && K > 0, "sl_layernorm_fold_build: bad arguments");
   const int vec = dtype == SL_F32 ? 4 : 8;
   SL_CHECK_ARG(K % vec == 0, "sl_layernorm_fold_build: K=%d must be a multiple of %d", K, vec);
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((ln_fold_build_kernel<T>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const T*)W, (const T*)gain, (const T*)beta,
                        (const T*)bias, (T*)Wf, u, c, N, K);
   });

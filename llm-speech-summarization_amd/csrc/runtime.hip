@@ -157,7 +157,7 @@ static int encoder_tail(const sl_hubert_model* m, HubertWs& w, const HubertPlan&
   // x -> [q|k|v Linear with ln1 folded in, row statistics applied in its epilogue] -> attention -> out_proj (+ bias + residual;
   // its epilogue leaves the row statistics of the new x) -> [FFN1 with ln2 folded in, GELU] -> FFN2 (+ bias + residual, statistics
   // again).  Two LayerNorm launches per layer (160 us each at 255 k frames, HBM-bound) become two 8 us finalize launches.
-  const bool fold = m->fold != nullptr && dt == SL_BF16 && !sl_env().no_ln_fold && H % 64 == 0 && m->ffn % 64 == 0 &&
+  const bool fold = m->fold != nullptr && sl_is16(dt) && !sl_env().no_ln_fold && H % 64 == 0 && m->ffn % 64 == 0 &&
                     sl_gemm_rows_epilogue_ok(NT, 3 * H, H, dt) && sl_gemm_rows_epilogue_ok(NT, H, H, dt) &&
                     sl_gemm_rows_epilogue_ok(NT, m->ffn, H, dt) && sl_gemm_rows_epilogue_ok(NT, H, m->ffn, dt);
   auto gemm_x = [&](const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* bias, const void* res, int N, int K, int act,
@@ -627,7 +627,7 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
         fn.fuse_rms = 1; fn.rms_eps = m->rms_eps;
         SL_TRY(dec_gemm(m, w, x, H, L.wgu_dec, w.mid, m->ffn, nullptr, (int)n, 2 * m->ffn, H, SL_ACT_SILU_MUL, 0, &fn, st, w.rstd_a));
       }
-    } else if (sl_family_rows((int)n) > 896 && dt == SL_BF16 && L.wgu && rstd_chain && sl_env().decode_tiled) {
+    } else if (sl_family_rows((int)n) > 896 && sl_is16(dt) && L.wgu && rstd_chain && sl_env().decode_tiled) {
       SL_TRY(dec_gemm(m, w, w.att, (int64_t)nh * D, L.wo_dec, x, H, x, (int)n, H, nh * D, SL_ACT_NONE, 0, nullptr, st, nullptr, w.rstd_a, w.h, L.norm2));
       SL_TRY(gemm(dt, w.h, H, L.wgu, H, w.mid, m->ffn, nullptr, nullptr, 0, (int)n, 2 * m->ffn, H, SL_ACT_SILU_MUL, 0, st));
     } else {
@@ -790,7 +790,7 @@ static int decode_step(const sl_llama_model* m, const sl_kv_cache* kv, const int
   }
   // rows whose o / down projections run UNSPLIT on the 256 x 128 blocks (from ~1 500 rows at Llama-3.2-3B's widths: 8 x 24 = 192 blocks
   // at 2 048): no reduce pass exists to take the RMSNorm scales in, a one-read pass in front of qkv and gate/up leaves them instead
-  bool rstd_pass = !chain && dt == SL_BF16 && m->dec_fused_norm && sl_family_rows(B) > 384 && sl_gemm_split_count(B, H, m->n_heads * m->head_dim, dt) == 1 &&
+  bool rstd_pass = !chain && sl_is16(dt) && m->dec_fused_norm && sl_family_rows(B) > 384 && sl_gemm_split_count(B, H, m->n_heads * m->head_dim, dt) == 1 &&
                    sl_gemm_split_count(B, H, m->ffn, dt) == 1;
   for (int l = 0; l < m->n_layers && rstd_pass; ++l) {
     const sl_llama_layer& L = m->layers[l];

@@ -1249,7 +1249,7 @@ extern "C" int sl_silu_mul(const void* gu, void* out, int64_t M, int32_t F_, int
   SL_CHECK_ARG(gu && out && M >= 0 && F_ > 0 && F_ % 16 == 0, "sl_silu_mul: bad arguments");
   if (M == 0) return 0;
   const int vec = dtype == SL_F32 ? 4 : 8;
-  SL_DISPATCH_DTYPE(dtype, T, { hipLaunchKernelGGL((silu_mul_kernel<T, false>), dim3(grid_for(M * (F_ / vec))), dim3(256), 0, (hipStream_t)stream, (const T*)gu, (const T*)nullptr, (T*)out, M, F_); });
+  SL_DISPATCH_DTYPE_INF(dtype, T, { hipLaunchKernelGGL((silu_mul_kernel<T, false>), dim3(grid_for(M * (F_ / vec))), dim3(256), 0, (hipStream_t)stream, (const T*)gu, (const T*)nullptr, (T*)out, M, F_); });
   SL_CHECK_LAUNCH("silu_mul");
   return 0;
 }
@@ -1269,7 +1269,7 @@ extern "C" int sl_rope_inplace(void* x, const int32_t* tok_pos, const float* cos
   const int vec = dtype == SL_F32 ? 4 : 8;
   SL_CHECK_ARG(D % (2 * vec) == 0, "sl_rope_inplace: head_dim=%d must be a multiple of %d", D, 2 * vec);
   if (n_tok == 0 || n_rot == 0) return 0;
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((rope_inplace_kernel<T>), dim3(grid_for(n_tok * n_rot * (D / 2 / vec))), dim3(256), 0, (hipStream_t)stream, (T*)x, tok_pos, cos, sin,
                        n_tok, heads, n_rot, D, inverse ? -1.0f : 1.0f);
   });
@@ -1498,7 +1498,7 @@ extern "C" int sl_ce_loss(const float* logits, const int32_t* labels, int64_t ro
                           int32_t accumulate, int32_t dtype, sl_stream stream) {
   SL_CHECK_ARG(logits && labels && loss && rows >= 0 && V > 0, "sl_ce_loss: bad arguments");
   if (rows == 0) return 0;
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((logit_loss_kernel<T>), dim3((unsigned)rows), dim3(1024), 0, (hipStream_t)stream, logits, (const float*)nullptr, labels, V, coef, loss,
                        (T*)dlogits, accumulate);
   });
@@ -1797,7 +1797,9 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const sl_adamw_tensor*
       for (int e = 0; e < nv; ++e) { t.p[i + e] = p[e]; t.m[i + e] = m[e]; t.v[i + e] = v[e]; }
     }
     if (t.dst) {
-      if (t.dst_dtype == SL_BF16) adamw_store_dst<true>(t.dst, i, p, nv); else adamw_store_dst<false>(t.dst, i, p, nv);
+      // SL_F32 / SL_BF16 only: training is not built for SL_F16, and a record with any other dst_dtype leaves dst untouched (the records
+      // live on the device: the host entry cannot refuse them; the Python optimizer checks dst_dtype before it uploads them)
+      if (t.dst_dtype == SL_BF16) adamw_store_dst<true>(t.dst, i, p, nv); else if (t.dst_dtype == SL_F32) adamw_store_dst<false>(t.dst, i, p, nv);
     }
   }
 }

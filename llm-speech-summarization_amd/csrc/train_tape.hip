@@ -310,6 +310,7 @@ extern "C" size_t sl_encoder_stack_train_workspace_bytes(const sl_enc_stack_cfg*
 extern "C" int sl_encoder_stack_train_fwd(const sl_hubert_layer* layers, const sl_enc_stack_cfg* c, const void* x_in, sl_enc_layer_saved* saved,
                                           const void** x_out, void* workspace, size_t workspace_bytes, sl_stream stream) {
   SL_CHECK_ARG(layers && c && x_in && saved && x_out && workspace && c->cu && c->klen && c->seeds && c->skip, "sl_encoder_stack_train_fwd: null pointer");
+  SL_CHECK_ARG(c->dtype == SL_F32 || c->dtype == SL_BF16, "sl_encoder_stack_train_fwd: dtype %d is not a training dtype (SL_F32 / SL_BF16)", (int)c->dtype);
   SL_CHECK_ARG(c->hidden % c->n_heads == 0 && c->hidden / c->n_heads == 64, "sl_encoder_stack_train_fwd: head_dim must be 64");
   EncWs w;
   SL_CHECK_ARG(enc_carve(c, workspace, workspace_bytes, w) <= workspace_bytes, "sl_encoder_stack_train_fwd: workspace too small");
@@ -398,6 +399,7 @@ extern "C" int sl_encoder_stack_train_bwd(const sl_hubert_layer* layers, const s
                                           const sl_enc_layer_grads* grads, int32_t layer_begin, int32_t layer_end, void* dx, void* workspace,
                                           size_t workspace_bytes, sl_stream stream) {
   SL_CHECK_ARG(layers && c && saved && grads && dx && workspace && c->cu && c->klen && c->seeds && c->skip, "sl_encoder_stack_train_bwd: null pointer");
+  SL_CHECK_ARG(c->dtype == SL_F32 || c->dtype == SL_BF16, "sl_encoder_stack_train_bwd: dtype %d is not a training dtype (SL_F32 / SL_BF16)", (int)c->dtype);
   SL_CHECK_ARG(0 <= layer_begin && layer_begin <= layer_end && layer_end <= c->n_layers, "sl_encoder_stack_train_bwd: bad layer range");
   EncWs w;
   SL_CHECK_ARG(enc_carve(c, workspace, workspace_bytes, w) <= workspace_bytes, "sl_encoder_stack_train_bwd: workspace too small");
@@ -547,6 +549,7 @@ extern "C" size_t sl_llama_stack_train_workspace_bytes(const sl_llama_stack_cfg*
 extern "C" int sl_llama_stack_train_fwd(const sl_llama_train_layer* layers, const sl_llama_stack_cfg* c, void* const* hidden,
                                         const sl_llama_layer_saved* saved, void* workspace, size_t workspace_bytes, sl_stream stream) {
   SL_CHECK_ARG(layers && c && hidden && workspace && c->cu && c->klen && c->pos && c->rope_cos && c->rope_sin, "sl_llama_stack_train_fwd: null pointer");
+  SL_CHECK_ARG(c->dtype == SL_F32 || c->dtype == SL_BF16, "sl_llama_stack_train_fwd: dtype %d is not a training dtype (SL_F32 / SL_BF16)", (int)c->dtype);
   SL_CHECK_ARG(c->head_dim == 128, "sl_llama_stack_train_fwd: head_dim %d not built (128)", c->head_dim);
   LlamaTrainWs w;
   SL_CHECK_ARG(llama_train_carve(c, workspace, workspace_bytes, w) <= workspace_bytes, "sl_llama_stack_train_fwd: workspace too small");
@@ -587,6 +590,7 @@ extern "C" int sl_llama_stack_train_bwd(const sl_llama_train_layer* layers, cons
                                         sl_stream stream) {
   SL_CHECK_ARG(layers && c && hidden && saved && dx && workspace && c->cu && c->klen && c->pos && c->rope_cos && c->rope_sin,
                "sl_llama_stack_train_bwd: null pointer");
+  SL_CHECK_ARG(c->dtype == SL_F32 || c->dtype == SL_BF16, "sl_llama_stack_train_bwd: dtype %d is not a training dtype (SL_F32 / SL_BF16)", (int)c->dtype);
   SL_CHECK_ARG(c->head_dim == 128, "sl_llama_stack_train_bwd: head_dim %d not built (128)", c->head_dim);
   LlamaTrainWs w;
   SL_CHECK_ARG(llama_train_carve(c, workspace, workspace_bytes, w) <= workspace_bytes, "sl_llama_stack_train_bwd: workspace too small");

@@ -95,7 +95,7 @@ extern "C" int sl_whisper_logmel(const float* audio, int64_t n_samples, const fl
   SL_TRY(sl_gemm_impl(&a, nullptr, nullptr, st));
   hipLaunchKernelGGL(whisper_log_max_kernel, dim3(1), dim3(1024), 0, st, mel, (int64_t)n_frames * n_mel, gmax);
   SL_CHECK_LAUNCH("whisper_log_max");
-  SL_DISPATCH_DTYPE(dtype, T, {
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
     hipLaunchKernelGGL((whisper_finish_kernel<T>), dim3(512), dim3(256), 0, st, mel, gmax, (T*)mel_out, (int64_t)n_frames * n_mel);
   });
   SL_CHECK_LAUNCH("whisper_finish");

@@ -34,6 +34,8 @@ class Trainer():
     def __init__(self, args, config, device, *, tokenizer=None, llm: Optional[AudioLlamaForCausalLM] = None,
                  audio_encoder: Optional[AudioEncoder] = None, train_dataset: Optional[Sequence[dict]] = None,
                  val_dataset: Optional[Sequence[dict]] = None, dtype: torch.dtype = torch.bfloat16) -> None:
+        from .training import check_training_dtype
+        check_training_dtype(dtype)      # before anything is built: fp16 KD is not supported (needs a loss scaler)
         self.args, self.config = args, config
         self.run_name = args.run_name
         self.device = torch.device(device)

@@ -41,6 +41,16 @@ from .weights import HubertDeviceWeights, fold_pos_conv_weight
 # training-mode regularisers of the HF HuBERT encoder (hf:models/hubert/modeling_hubert.py: feature projection dropout,
 # _mask_hidden_states, encoder dropout + LayerDrop, layer dropouts)
 # ------------------------------------------------------------------------------------------------
+def check_training_dtype(dtype: torch.dtype) -> None:
+    """KD training runs in float32 or bfloat16.  float16 is an inference dtype: fp16 KD would need a loss scaler (a GradScaler
+    equivalent), which is not built, nor are fp16 instances of the tapes, the attention backward or the optimizer's weight stores."""
+    if dtype == torch.float16:
+        raise L.SpeechLLMError("float16 training is not supported: fp16 KD needs a loss scaler (GradScaler equivalent), which is not "
+                               "built; train in bfloat16 (runtime.dtype: bf16) or float32 and run inference in float16")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise L.SpeechLLMError(f"unsupported training dtype {dtype}: float32 or bfloat16")
+
+
 @dataclass
 class TrainRegularizers:
     """hubert-large-ls960-ft config values (SURVEY.md §8 model constants)."""
@@ -790,6 +800,9 @@ class FusedAdamW:
 
     def __init__(self, optimizer: torch.optim.AdamW, named_params: Sequence[Tuple[str, torch.nn.Parameter]], dst_of: Dict[str, Tuple[torch.Tensor, int]]):
         self.opt, self.named, self.dst_of = optimizer, list(named_params), dst_of
+        for name, (dst, _) in dst_of.items():      # (kernel weight copy, element offset)
+            if dst.dtype not in (torch.float32, torch.bfloat16):
+                raise L.SpeechLLMError(f"FusedAdamW: {name}: weight copies are written as fp32 or bf16, not {dst.dtype}")
         g = optimizer.param_groups[0]
         if g.get("amsgrad") or g.get("maximize") or len(optimizer.param_groups) != 1:
             raise L.SpeechLLMError("FusedAdamW covers plain AdamW (one param group, amsgrad / maximize off)")
@@ -883,6 +896,8 @@ class KDTrainer:
     def __init__(self, config, encoder: AudioEncoder, llm: AudioLlamaForCausalLM, prefix_ids: torch.Tensor, suffix_ids: torch.Tensor,
                  total_optimizer_steps: int = 1000, process_group=None, regularizers: Optional[TrainRegularizers] = None,
                  overlap_optimizer: Optional[bool] = None):
+        check_training_dtype(encoder.dtype)
+        check_training_dtype(llm.dtype)
         tr = config.train
         self.enc, self.llm = encoder, llm
         self.ntp_w, self.ld_w, self.fd_w = tr.ntp_loss_weight, tr.ld_loss_weight, tr.fd_loss_weight

@@ -300,13 +300,13 @@ def fold_pos_conv_weight(sd: Dict[str, torch.Tensor], prefix: str) -> torch.Tens
 
 
 def build_layernorm_fold(w) -> None:
-    """LayerNorm-folded copies of every layer's q|k|v and FFN1 weights for the inference path (sl_hubert_fold, bf16 only): the
-    gain goes into the weight's columns (rounded to bf16 once), u = the row sums of that rounded matrix, c = W . beta + bias in
+    """LayerNorm-folded copies of every layer's q|k|v and FFN1 weights for the inference path (sl_hubert_fold, bf16 / fp16 only): the
+    gain goes into the weight's columns (rounded to the compute dtype once), u = the row sums of that rounded matrix, c = W . beta + bias in
     fp32 — Linear(LayerNorm(x)) = rstd (x W'^T - mean u) + c, so sl_hubert_forward needs no LayerNorm pass inside the layers
     (hf:models/hubert/modeling_hubert.py:515-517,612).  Built from the DEVICE tensors (the values the unfused kernels would
     read); the first call allocates, later calls (weights moved: KD optimizer steps) update in place."""
     w.fold_stale = False
-    if w.dtype != torch.bfloat16 or torch.device(w.device).type != "cuda":
+    if not L.is16(w.dtype) or torch.device(w.device).type != "cuda":
         return
     first = not hasattr(w, "_fold_t")
     if first:
@@ -534,9 +534,9 @@ class LlamaDeviceWeights:
             return
         a, dt, dev_ = self.arch, self.dtype, self.device
         if fuse_norm is None:
-            fuse_norm = dt == torch.bfloat16  # fp32 = parity mode: keep the reference's op order exactly
+            fuse_norm = L.is16(dt)  # fp32 = parity mode: keep the reference's op order exactly
         lib, code = L.lib(), L.dtype_code(dt)
-        kstep = 32 if dt == torch.bfloat16 else 16
+        kstep = 32 if L.is16(dt) else 16
         H, D, nh, nkv, F_ = a.hidden_size, a.head_dim, a.num_attention_heads, a.num_key_value_heads, a.intermediate_size
         if H % kstep or (nh * D) % kstep or F_ % kstep:
             return  # shapes the packed kernel does not take: decode stays on the row-major path
@@ -581,7 +581,7 @@ class LlamaDeviceWeights:
         per_layer = (a.num_attention_heads + 2 * a.num_key_value_heads) * a.head_dim * a.hidden_size \
             + a.num_attention_heads * a.head_dim * a.hidden_size + 3 * a.intermediate_size * a.hidden_size + 2 * a.hidden_size
         total = per_layer * a.num_hidden_layers + a.hidden_size + a.vocab_size * a.hidden_size
-        return total * (2 if self.dtype == torch.bfloat16 else 4)
+        return total * (2 if L.is16(self.dtype) else 4)
 
 
 # ------------------------------------------------------------------------------------------------

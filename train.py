@@ -34,7 +34,7 @@ if __name__ == '__main__':
         torch.distributed.init_process_group("nccl", device_id=torch.device(f"cuda:{args.gpu_idx}"), timeout=datetime.timedelta(hours=2))
     device = torch.device(f"cuda:{args.gpu_idx}")
     config = importlib.import_module("llm-speech-summarization_amd.config").load_config(args.config)
-    dtype = torch.float32 if str(config.get("runtime", {}).get("dtype", "bf16")) == "fp32" else torch.bfloat16
+    dtype = importlib.import_module("llm-speech-summarization_amd.config").runtime_dtype(config)
     Trainer = importlib.import_module("llm-speech-summarization_amd.trainer").Trainer
     trainer = Trainer(args, config, device, dtype=dtype)
     try:
