@@ -607,7 +607,9 @@ typedef struct {
 
 /* LlamaModel.forward over packed prompt embeddings + last-token logits
  * (hf:...llama.py:367-417 + ref:model/audio_llama.py:67 with logits for the last position only).
- *   x: (n_tok, hidden) packed prompts (modified in place: residual stream);  cu_seqlens (nseq+1)
+ *   x: (n_tok, hidden) packed prompts (overwritten: the residual stream runs in it, and its contents on return
+ *   are unspecified — without hidden_taps the final layer computes its o / FFN part for each sequence's last row
+ *   only, in the workspace);  cu_seqlens (nseq+1)
  *   host array.  Writes K/V for positions [0, len) of slot s, logits (nseq, vocab) fp32, and
  *   ctx_len[s] = len (device int32).  hidden_taps, if non-NULL, receives the (n_layers+1) hidden
  *   states (each (n_tok, hidden), last one post-norm) like output_hidden_states=True. */

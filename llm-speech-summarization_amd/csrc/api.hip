@@ -82,6 +82,7 @@ static const SlEnv* env_load() {
   e.lnbwd_nw = env_int("SL_LNBWD_NW", 16);
   e.skinny_alt = env_int("SL_SKINNY_ALT", 0);
   e.prefill_share_prefix = env_int("SL_PREFILL_SHARE_PREFIX", 1);
+  e.prefill_prune_last = env_int("SL_PREFILL_PRUNE_LAST", 1);
   e.gemm_ko = env_int("SL_GEMM_KO", 0);
   { const char* sp = getenv("SL_GEMM_STAMP_PTR"); e.gemm_stamp_ptr = (sp && sp[0]) ? strtoull(sp, nullptr, 16) : 0ull; }
   const char* g = getenv("SL_DISABLE_GLDS");

@@ -340,6 +340,7 @@ struct SlEnv {
   int no_swap_epilogue;    // SL_NO_SWAP_EPILOGUE  1 = the 256-tile GEMM keeps the LDS-turned rows epilogue where the swapped-operand form applies (A/B)
   int decode_tiled;        // SL_DECODE_TILED      1 (default) = decode steps above ~900 rows run o and gate/up on the row-major 256-tile kernels, 0 = streaming forms
   int prefill_share_prefix; // SL_PREFILL_SHARE_PREFIX 1 (default) = prefill computes a shared prompt prefix (sl_kv_cache.shared_prefix) once per batch, 0 = per sequence (A/B)
+  int prefill_prune_last;  // SL_PREFILL_PRUNE_LAST 1 (default) = prefill's final layer runs o / FFN on each sequence's last row only (the one row lm_head reads), 0 = on every row (A/B, same bits)
   int skinny_alt;          // SL_SKINNY_ALT        1 = o / down at M <= 8 keep the two-steps-in-flight structure of the larger row counts (A/B)
   int tt_max_splits;       // SL_TT_MAX_SPLITS     8 (default): most K runs of a token-major weight-gradient product (tuning)
   int lnbwd_nw;            // SL_LNBWD_NW          16 (default) | 8 | 4: waves per block of the LayerNorm backward for rows <= 1 024 elements (tuning)

@@ -10,12 +10,13 @@
 //   * weight fragments go global -> VGPR -> MFMA (one contiguous 1 KiB per wave-load, packed layout), D stages
 //     ahead in a register ring; nothing of W ever touches LDS.
 //   * when the grid would not fill the CUs, K is split over `splits` blocks: those write fp32 partials and
-//     gemm_stream_reduce_kernel applies the epilogue.
+//     gemm_stream_reduce_kernel (with row statistics: gemm_stream_reduce_rowstat_kernel) applies the epilogue.
 // (Tried at 384+ rows against 8192+ weight rows: 256-weight-row blocks — 4 waves x 4 fragments, all waves DMA-ing the slab
 // and reading it with compiler-invisible ds_read_b128, no loader wave — to halve the activation bytes per CU: 74 vs 67 us
 // at M = 512, 137 vs 102 us at M = 768; dropped.)
 // Epilogues are the decode ones of gemm.hip: +bias/+residual, SILU_MUL (fragment pairs gate/up), ROPE_KV (q rotated,
 // k/v appended to the cache), and the fused RMSNorm row scale (sum of squares taken from the staged x slabs).
+#include <type_traits>
 #include <stdlib.h>
 
 #include <atomic>
@@ -521,7 +522,7 @@ __global__ __launch_bounds__(768) void gemm_stream_wide_kernel(GemmP p, SkinnyX 
   if (!rowstat) return;
   if constexpr (ACT == SL_ACT_NONE) {
     if (cw) {
-      // plain (+bias, +residual) epilogue that keeps the stored values for the row statistics (as gemm_stream_reduce_kernel<ROWSTAT>)
+      // plain (+bias, +residual) epilogue that keeps the stored values for the row statistics (as gemm_stream_reduce_rowstat_kernel)
       const T* bias = (const T*)p.bias;
 #pragma unroll
       for (int t = 0; t < MTW; ++t) {
@@ -583,115 +584,283 @@ __global__ __launch_bounds__(768) void gemm_stream_wide_kernel(GemmP p, SkinnyX 
   }
 }
 
-// sums the K-split partials and applies the epilogue: one thread per (row, fragment or fragment pair, 4-column group).
-// ROWSTAT: one block per output row (blockDim = 4 * fragments <= 1024); the block also reduces the squares of the values
-// it stores (as rounded to T) and emits the row's RMSNorm scale for the GEMM that consumes these rows next.
-template <typename T, int ACT, bool ROWSTAT>
-__global__ __launch_bounds__(ROWSTAT ? 1024 : 256) void gemm_stream_reduce_kernel(GemmP p, SkinnyX sx, StreamX s) {
+// ---- second pass of a K-split launch: sums the partial records in split order and applies the epilogue ----
+// The records of splits [sp0, sp0 + UN) are added to the accumulators of NCH column chunks: `rec` is split 0's record of the row (uniform
+// per block where the block owns one row, so the loads take the scalar-base form), voff[j] the lane's float offset in chunk j.  Only live
+// splits are loaded, and the UN * NCH (PAIRS: twice that) 16-byte loads are requested before the first add.
+template <int UN, int NCH, bool PAIRS>
+__device__ __forceinline__ void reduce_add_splits(const float* rec, int64_t split_stride, int sp0, const uint32_t (&voff)[NCH], f32x4 (&a4)[NCH],
+                                                  f32x4 (&b4)[NCH]) {
+  f32x4 va[NCH][UN], vb[NCH][UN];
+#pragma unroll
+  for (int u = 0; u < UN; ++u) {
+    const float* row = rec + (int64_t)(sp0 + u) * split_stride;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      va[j][u] = *(const f32x4*)(row + voff[j]);
+      if constexpr (PAIRS) vb[j][u] = *(const f32x4*)(row + voff[j] + 16);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < UN; ++u)
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      a4[j] += va[j][u];
+      if constexpr (PAIRS) b4[j] += vb[j][u];
+    }
+}
+// all `splits` records, UNMAX at a time, the tail in groups of 4 / 2 / 1 (a clamped index in a fixed 8-way unroll re-loaded the last
+// record up to seven times: with two splits, four times the vector-memory instructions the sum needs)
+template <int UNMAX, int NCH, bool PAIRS>
+__device__ __forceinline__ void reduce_sum_splits(const float* rec, int64_t split_stride, int splits, const uint32_t (&voff)[NCH], f32x4 (&a4)[NCH],
+                                                  f32x4 (&b4)[NCH]) {
+  int sp0 = 0;
+  for (; sp0 + UNMAX <= splits; sp0 += UNMAX) reduce_add_splits<UNMAX, NCH, PAIRS>(rec, split_stride, sp0, voff, a4, b4);
+  if constexpr (UNMAX > 4) {
+    if (splits - sp0 >= 4) { reduce_add_splits<4, NCH, PAIRS>(rec, split_stride, sp0, voff, a4, b4); sp0 += 4; }
+  }
+  if constexpr (UNMAX > 2) {
+    if (splits - sp0 >= 2) { reduce_add_splits<2, NCH, PAIRS>(rec, split_stride, sp0, voff, a4, b4); sp0 += 2; }
+  }
+  if constexpr (UNMAX > 1) {
+    if (splits - sp0 >= 1) reduce_add_splits<1, NCH, PAIRS>(rec, split_stride, sp0, voff, a4, b4);
+  }
+}
+
+// one thread per (row, fragment or fragment pair, 4-column group)
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void gemm_stream_reduce_kernel(GemmP p, SkinnyX sx, StreamX s) {
   constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || ACT == SL_ACT_ROPE_KV);
-  static_assert(!ROWSTAT || ACT == SL_ACT_NONE, "row statistics ride on the plain (+residual) epilogue");
   const int nfrag = (p.N + 15) >> 4;
   const int nunits = PAIRS ? (nfrag + 1) / 2 : nfrag;
-  int q, unit, m;
-  if constexpr (ROWSTAT) {
-    m = blockIdx.x; q = threadIdx.x & 3; unit = threadIdx.x >> 2;
-  } else {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    q = (int)(idx & 3);
-    unit = (int)((idx >> 2) % nunits);
-    m = (int)(idx / (4 * (int64_t)nunits));
-    if (m >= p.M) return;
-  }
-  const bool live = unit < nunits;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int q = (int)(idx & 3);
+  const int unit = (int)((idx >> 2) % nunits);
+  const int m = (int)(idx / (4 * (int64_t)nunits));
+  if (m >= p.M) return;
   const int gf = PAIRS ? 2 * unit : unit;
-  f32x4 a4 = {0.f, 0.f, 0.f, 0.f}, b4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 a4[1] = {{0.f, 0.f, 0.f, 0.f}}, b4[1] = {{0.f, 0.f, 0.f, 0.f}};
+  const uint32_t voff[1] = {0u};
+  reduce_sum_splits<8, 1, PAIRS>(s.part + (int64_t)m * s.np + gf * 16 + 4 * q, (int64_t)p.M * s.np, s.splits, voff, a4, b4);
   float ssum = 0.f;
   const bool stats_here = sx.fuse_rms && !sx.rstd_in;
-  if (live) {
-    // the partial records of up to 8 splits are requested together (a load-add chain per split left one 16-byte load in
-    // flight per thread); summed in split order
-    constexpr int UN = 8;
-    for (int sp0 = 0; sp0 < s.splits; sp0 += UN) {
-      f32x4 va[UN], vb[UN];
-#pragma unroll
-      for (int u = 0; u < UN; ++u) {
-        const int sp = sp0 + u < s.splits ? sp0 + u : s.splits - 1;
-        const float* row = s.part + ((int64_t)sp * p.M + m) * s.np + gf * 16 + 4 * q;
-        va[u] = *(const f32x4*)row;
-        if constexpr (PAIRS) vb[u] = *(const f32x4*)(row + 16);
-      }
-#pragma unroll
-      for (int u = 0; u < UN; ++u) {
-        if (sp0 + u < s.splits) {
-          a4 += va[u];
-          if constexpr (PAIRS) b4 += vb[u];
-        }
-      }
-    }
-    if (stats_here)
-      for (int sp = 0; sp < s.splits; ++sp) ssum += s.part_ss[(int64_t)sp * p.M + m];
-  }
+  if (stats_here)
+    for (int sp = 0; sp < s.splits; ++sp) ssum += s.part_ss[(int64_t)sp * p.M + m];
   const float rs = sx.rstd_in ? sx.rstd_in[m] : (stats_here ? rsqrtf(ssum / (float)p.K + sx.eps) : 1.0f);
   float a[4], b[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) { a[i] = a4[i] * rs; b[i] = b4[i] * rs; }
-  if constexpr (ROWSTAT) {
-    // same arithmetic as stream_epilogue4's plain branch, keeping the stored values for the statistics
-    __shared__ float wsum[17];
+  for (int i = 0; i < 4; ++i) { a[i] = a4[0][i] * rs; b[i] = b4[0][i] * rs; }
+  stream_epilogue4<T, ACT>(p, sx, m, gf, 4 * q, a, b);
+}
+
+// (x * rstd) rounded to fp32 and THEN to T, as HF's (x * rstd).to(dtype) is: left to itself the fp16 build fuses the product and the
+// conversion into one v_fma_mixlo_f16, a single rounding that lands one unit off at ties (two after the gain)
+template <typename T>
+__device__ __forceinline__ float norm_round(float x, float rstd) {
+  float y = x * rstd;
+  asm volatile("" : "+v"(y));
+  return to_f32(from_f32<T>(y));
+}
+
+// The plain (+bias, +residual) epilogue with row statistics: the block owns one output row, also reduces the squares of the values it
+// stores (as rounded to T), emits the row's RMSNorm scale for the GEMM that consumes these rows next and, with sx.norm_out, the
+// normalised row.  The row is cut into 64-lane groups of four columns per lane (group g = columns [256 g, 256 g + 256), <= 16 groups);
+// wave w of the four takes groups w, w + 4, ... (NCH of them), so that a 1 024-row pass is resident in one round of the chip (four
+// 256-thread blocks per CU; one 768-thread block per row was two per CU and two rounds) and every load of a row — its residual and the
+// live partial records of all its chunks — is in flight before the first add.  The stored bits do not depend on that mapping: x is the
+// fixed-order sum (0 + p0) + p1 + ..., then the residual, rounded once; each group's squares are reduced by the same wave_sum over the
+// same lanes, and the group sums are added in group order (by every thread, from LDS: no second barrier, no one-thread tail).
+// FAST (the launcher's choice; the decode chain's o / down projections): residual and output rows of T in whole aligned 4-column pieces,
+// no bias, no row scale on the way in — one straight line of code from the loads to the stores, the shape below is for everything else.
+template <typename T, int NCH, bool FAST>
+__global__ __launch_bounds__(256) void gemm_stream_reduce_rowstat_kernel(GemmP p, SkinnyX sx, StreamX s) {
+  __shared__ float wsum[16];
+  const int nfrag = (p.N + 15) >> 4;
+  const int ngroups = (4 * nfrag + 63) >> 6;
+  const int m = blockIdx.x, tid = threadIdx.x;
+  uint32_t col0[NCH], voff[NCH];
+  bool live[NCH];
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) {
+    col0[j] = 4u * (uint32_t)(j * 256 + tid);
+    live[j] = col0[j] < (FAST ? (uint32_t)p.N : 16u * (uint32_t)nfrag);
+    voff[j] = live[j] ? col0[j] : 0u;          // lanes past the row's last fragment re-read its first columns and store nothing
+  }
+  float kept[NCH][4];       // the values as stored, for the normalised copy (sx.norm_out)
+  if constexpr (FAST) {
+    typedef typename std::conditional<sizeof(T) == 2, uint2, f32x4>::type Piece;      // four elements of T
+    Piece rr[NCH];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) rr[j] = *(const Piece*)((const T*)p.res + (int64_t)m * p.ldr + voff[j]);
+    f32x4 a4[NCH], b4[NCH];
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) a4[j] = b4[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    reduce_sum_splits<(NCH >= 3 ? 2 : 4), NCH, false>(s.part + (int64_t)m * s.np, (int64_t)p.M * s.np, s.splits, voff, a4, b4);
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      float v[4];
+      if constexpr (sizeof(T) == 2) {
+        const f32x2_t lo = unpack2<T>(rr[j].x), hi = unpack2<T>(rr[j].y);
+        v[0] = a4[j][0] + lo.x; v[1] = a4[j][1] + lo.y; v[2] = a4[j][2] + hi.x; v[3] = a4[j][3] + hi.y;
+        const uint32_t plo = pack2<T>(v[0], v[1]), phi = pack2<T>(v[2], v[3]);
+        if (live[j]) *(uint2*)((T*)p.C + (int64_t)m * p.ldc + col0[j]) = make_uint2(plo, phi);
+        const f32x2_t f01 = unpack2<T>(plo), f23 = unpack2<T>(phi);
+        v[0] = f01.x; v[1] = f01.y; v[2] = f23.x; v[3] = f23.y;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = a4[j][i] + rr[j][i];
+        if (live[j]) *(f32x4*)((float*)p.C + (int64_t)m * p.ldc + col0[j]) = f32x4{v[0], v[1], v[2], v[3]};
+      }
+      float sq = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { kept[j][i] = v[i]; sq = fmaf(v[i], v[i], sq); }
+      sq = wave_sum(live[j] ? sq : 0.f);
+      if ((tid & 63) == 0) wsum[j * 4 + (tid >> 6)] = sq;
+    }
+  } else {
+  // 16-bit rows move as 8-byte pieces, fp32 rows as 16-byte pieces, where the row pitches and base addresses allow
+  const bool res16 = !p.res_f32 && sizeof(T) == 2;
+  const bool vec_res = p.res && !(p.ldr & 3) && !((uintptr_t)p.res & (res16 ? 7 : 15));
+  const bool vec_c = !(p.ldc & 3) && !((uintptr_t)p.C & ((p.out_f32 || sizeof(T) == 4) ? 15 : 7));
+  float r[NCH][4];
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[j][i] = 0.f;
+    if (!p.res || !live[j]) continue;
+    const int64_t off = (int64_t)m * p.ldr + col0[j];
+    if (vec_res && col0[j] + 3 < (uint32_t)p.N) {
+      if (res16) {
+        if constexpr (sizeof(T) == 2) {
+          const uint2 w = *(const uint2*)((const T*)p.res + off);
+          const f32x2_t lo = unpack2<T>(w.x), hi = unpack2<T>(w.y);
+          r[j][0] = lo.x; r[j][1] = lo.y; r[j][2] = hi.x; r[j][3] = hi.y;
+        }
+      } else {
+        const f32x4 w = *(const f32x4*)((const float*)p.res + off);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[j][i] = w[i];
+      }
+    } else {
+      for (int i = 0; i < 4 && col0[j] + i < (uint32_t)p.N; ++i)
+        r[j][i] = p.res_f32 ? ((const float*)p.res)[off + i] : to_f32(((const T*)p.res)[off + i]);
+    }
+  }
+  f32x4 a4[NCH], b4[NCH];
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) a4[j] = b4[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // (load groups of 4 splits, of 2 from three chunks per lane up: the block stays within 128 VGPRs, four blocks per CU)
+  reduce_sum_splits<(NCH >= 3 ? 2 : 4), NCH, false>(s.part + (int64_t)m * s.np, (int64_t)p.M * s.np, s.splits, voff, a4, b4);
+  float ssum = 0.f;
+  const bool stats_here = sx.fuse_rms && !sx.rstd_in;
+  if (stats_here)
+    for (int sp = 0; sp < s.splits; ++sp) ssum += s.part_ss[(int64_t)sp * p.M + m];
+  const float rs = sx.rstd_in ? sx.rstd_in[m] : (stats_here ? rsqrtf(ssum / (float)p.K + sx.eps) : 1.0f);
+  // same arithmetic as stream_epilogue4's plain branch, keeping the stored values for the statistics and the normalised copy
+  const T* bias = (const T*)p.bias;
+#pragma unroll
+  for (int j = 0; j < NCH; ++j) {
     float sq = 0.f;
-    float kept[4] = {0.f, 0.f, 0.f, 0.f};      // the values as stored, for the normalised copy (sx.norm_out)
-    if (live) {
-      const T* bias = (const T*)p.bias;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) kept[j][i] = 0.f;
+    if (live[j]) {
+      const int64_t off = (int64_t)m * p.ldc + col0[j];
+      const bool whole = col0[j] + 3 < (uint32_t)p.N;
+      float v[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int col = gf * 16 + 4 * q + i;
-        if (col >= p.N) continue;
-        float v = a[i];
-        if (bias) v += to_f32(bias[col]);
-        if (p.res) v += p.res_f32 ? ((const float*)p.res)[(int64_t)m * p.ldr + col] : to_f32(((const T*)p.res)[(int64_t)m * p.ldr + col]);
+        v[i] = a4[j][i] * rs;
+        if (bias && col0[j] + i < (uint32_t)p.N) v[i] += to_f32(bias[col0[j] + i]);
+        if (p.res) v[i] += r[j][i];
+      }
+      if (whole && vec_c) {
         if (p.out_f32) {
-          ((float*)p.C)[(int64_t)m * p.ldc + col] = v;
+          *(f32x4*)((float*)p.C + off) = f32x4{v[0], v[1], v[2], v[3]};
+        } else if constexpr (sizeof(T) == 2) {
+          const uint32_t lo = pack2<T>(v[0], v[1]), hi = pack2<T>(v[2], v[3]);
+          *(uint2*)((T*)p.C + off) = make_uint2(lo, hi);
+          const f32x2_t f01 = unpack2<T>(lo), f23 = unpack2<T>(hi);
+          v[0] = f01.x; v[1] = f01.y; v[2] = f23.x; v[3] = f23.y;
         } else {
-          const T o = from_f32<T>(v);
-          ((T*)p.C)[(int64_t)m * p.ldc + col] = o;
-          v = to_f32(o);
+          *(f32x4*)((float*)p.C + off) = f32x4{v[0], v[1], v[2], v[3]};
         }
-        kept[i] = v;
-        sq = fmaf(v, v, sq);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { kept[j][i] = v[i]; sq = fmaf(v[i], v[i], sq); }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          if (col0[j] + i >= (uint32_t)p.N) continue;
+          if (p.out_f32) {
+            ((float*)p.C)[off + i] = v[i];
+          } else {
+            const T o = from_f32<T>(v[i]);
+            ((T*)p.C)[off + i] = o;
+            v[i] = to_f32(o);
+          }
+          kept[j][i] = v[i];
+          sq = fmaf(v[i], v[i], sq);
+        }
       }
     }
     sq = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      float t = 0.f;
-      for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += wsum[w];
-      const float rstd = rsqrtf(t / (float)p.N + sx.eps);
-      sx.rstd_out[m] = rstd;
-      wsum[16] = rstd;
-    }
+    if ((tid & 63) == 0) wsum[j * 4 + (tid >> 6)] = sq;
+  }
+  }
+  typedef typename std::conditional<sizeof(T) == 2, uint2, f32x4>::type GainPiece;
+  GainPiece gg[NCH];
+  if constexpr (FAST) {     // the gains are requested before the barrier
     if (sx.norm_out) {
-      // the RMS-normalised row beside the row itself, in HF's rounding order: weight * (x * rstd).to(dtype) (hf:...llama.py:60-71) —
-      // what a separate sl_rmsnorm launch over these rows would write (11 us per 1 024 x 3 072 in the decode graph)
-      __syncthreads();
-      const float rstd = wsum[16];
-      if (live) {
-        const int col0 = gf * 16 + 4 * q;
-        if (col0 + 3 < p.N) {
-          float o[4];
 #pragma unroll
-          for (int i = 0; i < 4; ++i) o[i] = to_f32(((const T*)sx.norm_gain)[col0 + i]) * to_f32(from_f32<T>(kept[i] * rstd));
-          T* dst = (T*)sx.norm_out + (int64_t)m * p.N + col0;        // 8 (bf16) / 16 (f32) bytes per lane, 64 / 128 contiguous bytes per fragment
-          if constexpr (sizeof(T) == 2) *(uint2*)dst = make_uint2(pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3]));
-          else *(f32x4*)dst = f32x4{o[0], o[1], o[2], o[3]};
+      for (int j = 0; j < NCH; ++j) gg[j] = *(const GainPiece*)((const T*)sx.norm_gain + voff[j]);
+    }
+  }
+  __syncthreads();
+  float t = 0.f;
+  for (int g = 0; g < ngroups; ++g) t += wsum[g];
+  const float rstd = rsqrtf(t / (float)p.N + sx.eps);
+  if (tid == 0) sx.rstd_out[m] = rstd;
+  if (sx.norm_out) {
+    // the RMS-normalised row beside the row itself, in HF's rounding order: weight * (x * rstd).to(dtype) (hf:...llama.py:60-71) —
+    // what a separate sl_rmsnorm launch over these rows would write (11 us per 1 024 x 3 072 in the decode graph)
+    const bool vec_g = FAST || !((uintptr_t)sx.norm_gain & (sizeof(T) == 2 ? 7 : 15));
+    const bool vec_n = FAST || (!(p.N & 3) && !((uintptr_t)sx.norm_out & (sizeof(T) == 2 ? 7 : 15)));
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) {
+      if (!live[j]) continue;
+      const T* gain = (const T*)sx.norm_gain + col0[j];
+      T* dst = (T*)sx.norm_out + (int64_t)m * p.N + col0[j];
+      if (FAST || (col0[j] + 3 < (uint32_t)p.N && vec_n)) {
+        float g4[4], o[4];
+        if constexpr (FAST) {
+          if constexpr (sizeof(T) == 2) {
+            const f32x2_t lo = unpack2<T>(gg[j].x), hi = unpack2<T>(gg[j].y);
+            g4[0] = lo.x; g4[1] = lo.y; g4[2] = hi.x; g4[3] = hi.y;
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) g4[i] = gg[j][i];
+          }
+        } else if constexpr (sizeof(T) == 2) {
+          if (vec_g) {
+            const uint2 w = *(const uint2*)gain;
+            const f32x2_t lo = unpack2<T>(w.x), hi = unpack2<T>(w.y);
+            g4[0] = lo.x; g4[1] = lo.y; g4[2] = hi.x; g4[3] = hi.y;
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) g4[i] = to_f32(gain[i]);
+          }
         } else {
-          for (int i = 0; i < 4 && col0 + i < p.N; ++i)
-            ((T*)sx.norm_out)[(int64_t)m * p.N + col0 + i] = from_f32<T>(to_f32(((const T*)sx.norm_gain)[col0 + i]) * to_f32(from_f32<T>(kept[i] * rstd)));
+#pragma unroll
+          for (int i = 0; i < 4; ++i) g4[i] = to_f32(gain[i]);
         }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = g4[i] * norm_round<T>(kept[j][i], rstd);
+        if constexpr (sizeof(T) == 2) *(uint2*)dst = make_uint2(pack2<T>(o[0], o[1]), pack2<T>(o[2], o[3]));
+        else *(f32x4*)dst = f32x4{o[0], o[1], o[2], o[3]};
+      } else {
+        for (int i = 0; i < 4 && col0[j] + i < (uint32_t)p.N; ++i)
+          dst[i] = from_f32<T>(to_f32(gain[i]) * norm_round<T>(kept[j][i], rstd));
       }
     }
-  } else {
-    if (live) stream_epilogue4<T, ACT>(p, sx, m, gf, 4 * q, a, b);
   }
 }
 
@@ -776,13 +945,24 @@ static int launch_stream_reduce(GemmP& p, const SkinnyX& sx, const StreamX& s, h
   const int64_t nunits = PAIRS ? (nfrag + 1) / 2 : nfrag;
   const int64_t threads = (int64_t)p.M * nunits * 4;
   if constexpr (ACT == SL_ACT_NONE) {
-    if (sx.rstd_out) {   // checked by the caller: 4 * fragments <= 1024
-      hipLaunchKernelGGL((gemm_stream_reduce_kernel<T, ACT, true>), dim3(p.M), dim3((unsigned)((nunits * 4 + 63) / 64 * 64)), 0, st, p, sx, s);
+    if (sx.rstd_out) {   // checked by the caller: 4 * fragments <= 1024, i.e. at most 16 groups of 64 lanes = 4 chunks per wave
+      const uintptr_t al = sizeof(T) == 2 ? 7 : 15;
+      const bool fast = !p.bias && p.res && !p.res_f32 && !p.out_f32 && !sx.fuse_rms && !sx.rstd_in && !(p.N & 3) && !(p.ldc & 3) && !(p.ldr & 3) &&
+                        !((uintptr_t)p.C & al) && !((uintptr_t)p.res & al) && (!sx.norm_out || (!((uintptr_t)sx.norm_out & al) && !((uintptr_t)sx.norm_gain & al)));
+      const int nch = (nfrag * 4 + 255) / 256;
+#define SL_ROWSTAT_LAUNCH(NCH_)                                                                                                              \
+  if (fast) hipLaunchKernelGGL((gemm_stream_reduce_rowstat_kernel<T, NCH_, true>), dim3(p.M), dim3(256), 0, st, p, sx, s);                   \
+  else hipLaunchKernelGGL((gemm_stream_reduce_rowstat_kernel<T, NCH_, false>), dim3(p.M), dim3(256), 0, st, p, sx, s)
+      if (nch <= 1) { SL_ROWSTAT_LAUNCH(1); }
+      else if (nch == 2) { SL_ROWSTAT_LAUNCH(2); }
+      else if (nch == 3) { SL_ROWSTAT_LAUNCH(3); }
+      else { SL_ROWSTAT_LAUNCH(4); }
+#undef SL_ROWSTAT_LAUNCH
       SL_CHECK_LAUNCH("gemm_stream_reduce(rowstat)");
       return 0;
     }
   }
-  hipLaunchKernelGGL((gemm_stream_reduce_kernel<T, ACT, false>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, sx, s);
+  hipLaunchKernelGGL((gemm_stream_reduce_kernel<T, ACT>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, sx, s);
   SL_CHECK_LAUNCH("gemm_stream_reduce");
   return 0;
 }

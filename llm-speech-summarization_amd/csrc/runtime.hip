@@ -431,6 +431,7 @@ struct LlamaWs {
   size_t split_bytes;
   float *rstd_a, *rstd_b;   // RMSNorm scales handed from the o / down projection's reduce pass to the next fused GEMM
   int32_t *tok_seq, *tok_pos, *cu, *cuk, *klen;
+  int32_t* last_row;        // prefill: row of every sequence's last token (the rows lm_head reads)
 };
 
 static size_t llama_carve(const sl_llama_model* m, int64_t n_tok, int nseq, void* base, size_t cap, LlamaWs& w) {
@@ -460,6 +461,7 @@ static size_t llama_carve(const sl_llama_model* m, int64_t n_tok, int nseq, void
   w.cu = (int32_t*)c.take((nseq + 2) * sizeof(int32_t));     // + 1: the shared prompt prefix is one more attention sequence in prefill
   w.cuk = (int32_t*)c.take((nseq + 1) * sizeof(int32_t));
   w.klen = (int32_t*)c.take((nseq + 1) * sizeof(int32_t));
+  w.last_row = (int32_t*)c.take((size_t)nseq * sizeof(int32_t));
   return c.off + 256;
 }
 
@@ -490,6 +492,12 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4* __restric
   const int64_t r = i / row_vec;
   const int c = (int)(i - r * row_vec);
   dst[i] = src[(int64_t)map[r] * row_vec + c];
+}
+static int gather_rows(const void* src, void* dst, const int32_t* map, int64_t n_rows, size_t row_bytes, hipStream_t st) {
+  const int row_vec = (int)(row_bytes / 16);
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n_rows * row_vec + 255) / 256)), dim3(256), 0, st, (const uint4*)src, (uint4*)dst, map, n_rows, row_vec);
+  SL_CHECK_LAUNCH("gather_rows");
+  return 0;
 }
 // K / V rows [0, P) of slot 0 copied to slots 1 .. nseq-1 of one layer's cache: grid (P, n_kv, nseq - 1); lanes 0..31 move the K row,
 // 32..63 the V row, 16 bytes each (rows of 256 B in bf16, 512 B in fp32)
@@ -579,9 +587,13 @@ static int dec_gemm(const sl_llama_model* m, const LlamaWs& w, const void* A, in
 // rstd_qkv = scale of x on entry (NULL: this layer's qkv takes its own statistics)
 // prefix_bcast = P > 0 (prefill with a shared prompt prefix): the P prefix rows were appended to slot 0 only and are copied to the other
 // bcast_slots - 1 slots before attention, in which the prefix is one more sequence (nseq counts it)
+// tail_rows (prefill's final layer, n_tail device indices): the only rows of this layer's output that anything reads.  Norm, qkv, RoPE /
+// append and attention run over all n rows (the cache needs every K / V row); the n_tail rows of the attention output and of x are then
+// gathered, and o + residual, norm, gate/up and down + residual run on those alone, their result left in w.last (x is not updated).
+// The products stay pinned to the family of n rows, so a row goes through the kernel — and the K order — it goes through in the full pass.
 static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, void* x, int64_t n, LlamaWs& w, bool decode, int nseq,
                        int max_qlen, const int32_t* ctx_len_dev, hipStream_t st, bool rstd_chain = false, const float* rstd_qkv = nullptr,
-                       int prefix_bcast = 0, int bcast_slots = 0, bool rstd_pass = false) {
+                       int prefix_bcast = 0, int bcast_slots = 0, bool rstd_pass = false, const int32_t* tail_rows = nullptr, int n_tail = 0) {
   const sl_llama_layer& L = m->layers[l];
   const int dt = m->dtype, H = m->hidden, D = m->head_dim, nh = m->n_heads, nkv = m->n_kv_heads;
   const int qkv_w = (nh + 2 * nkv) * D;
@@ -670,6 +682,18 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     a.nseq = nseq; a.max_qlen = max_qlen; a.n_heads = nh; a.n_kv_heads = nkv; a.head_dim = D; a.causal = 1; a.dtype = dt; a.scale = scale;
     SL_TRY(sl_attn_fwd(&a, (sl_stream)st));
   }
+  if (tail_rows && !decode) {
+    const size_t esz = sl_dtype_size(dt);
+    void* att_t = w.qkv;      // q / k / v are consumed: the gathered attention rows take their place, the normalised rows take w.h
+    SL_TRY(gather_rows(w.att, att_t, tail_rows, n_tail, (size_t)nh * D * esz, st));
+    SL_TRY(gather_rows(x, w.last, tail_rows, n_tail, (size_t)H * esz, st));
+    SlFamilyPin pin((int)n);
+    SL_TRY(gemm(dt, att_t, (int64_t)nh * D, L.wo, (int64_t)nh * D, w.last, H, nullptr, w.last, H, n_tail, H, nh * D, SL_ACT_NONE, 0, st));
+    SL_TRY(sl_rmsnorm(w.last, w.h, L.norm2, n_tail, H, m->rms_eps, dt, (sl_stream)st));
+    SL_TRY(gemm(dt, w.h, H, L.wgu, H, w.mid, m->ffn, nullptr, nullptr, 0, n_tail, 2 * m->ffn, H, SL_ACT_SILU_MUL, 0, st));
+    SL_TRY(gemm(dt, w.mid, m->ffn, L.wdown, m->ffn, w.last, H, nullptr, w.last, H, n_tail, H, m->ffn, SL_ACT_NONE, 0, st));
+    return 0;
+  }
   SL_TRY(gemm(dt, w.att, (int64_t)nh * D, L.wo, (int64_t)nh * D, x, H, nullptr, x, H, (int)n, H, nh * D, SL_ACT_NONE, 0, st));
   SL_TRY(sl_rmsnorm(x, w.h, L.norm2, n, H, m->rms_eps, dt, (sl_stream)st));
   SL_TRY(gemm(dt, w.h, H, L.wgu, H, w.mid, m->ffn, nullptr, nullptr, 0, (int)n, 2 * m->ffn, H, SL_ACT_SILU_MUL, 0, st));
@@ -689,6 +713,7 @@ extern "C" int sl_llama_prefill(const sl_llama_model* m, const sl_kv_cache* kv, 
   LlamaWs w;
   const size_t need = llama_carve(m, n_tok, nseq, workspace, workspace_bytes, w);
   SL_CHECK_ARG(need <= workspace_bytes, "sl_llama_prefill: workspace %zu B < required %zu B", workspace_bytes, need);
+  SL_CHECK_ARG(((size_t)H * sz) % 16 == 0, "sl_llama_prefill: hidden rows must be a multiple of 16 bytes");
   std::vector<int32_t> tseq(n_tok), tpos(n_tok), cuk(nseq + 1), kl(nseq + 1), ctx(nseq), cuq(nseq + 2), last_row(nseq);
   int max_q = 0;
   // Shared prompt prefix (sl_kv_cache.shared_prefix = P, the caller's promise that rows [0, P) of every sequence are the same rows): they
@@ -726,11 +751,8 @@ extern "C" int sl_llama_prefill(const sl_llama_model* m, const sl_kv_cache* kv, 
     n_run = (int64_t)map.size();
     nseq_attn = nseq + 1;
     // x -> compact rows: gathered into the (still unused) FFN scratch, then copied back to the head of x
-    const int row_vec = (int)((size_t)H * sz / 16);
-    SL_CHECK_ARG(((size_t)H * sz) % 16 == 0, "sl_llama_prefill: hidden rows must be a multiple of 16 bytes");
     SL_HIP(hipMemcpyAsync(w.tok_pos, map.data(), n_run * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n_run * row_vec + 255) / 256)), dim3(256), 0, st, (const uint4*)x, (uint4*)w.mid, w.tok_pos, n_run, row_vec);
-    SL_CHECK_LAUNCH("gather_rows");
+    SL_TRY(gather_rows(x, w.mid, w.tok_pos, n_run, (size_t)H * sz, st));
     SL_HIP(hipMemcpyAsync(x, w.mid, (size_t)n_run * H * sz, hipMemcpyDeviceToDevice, st));
     SL_HIP(hipStreamSynchronize(st));      // `map` leaves scope / tok_pos is rewritten below
   } else {
@@ -751,17 +773,22 @@ extern "C" int sl_llama_prefill(const sl_llama_model* m, const sl_kv_cache* kv, 
   SL_HIP(hipMemcpyAsync(w.cuk, cuk.data(), nseq_attn * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipMemcpyAsync(w.klen, kl.data(), nseq_attn * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipMemcpyAsync(ctx_len_dev, ctx.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(w.last_row, last_row.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipStreamSynchronize(st));
+  // Only each sequence's last row is read after the final layer (lm_head below): without hidden_taps that layer runs everything behind
+  // attention on those nseq rows alone (llama_layer tail_rows) — at 137-row prompts, 136 of 137 rows of o / gate/up / down of one layer
+  // in 28.  SL_PREFILL_PRUNE_LAST=0 restores the full layer (same logits and cache, bit for bit: tests/test_prefill_prune_gpu.py).
+  const bool prune = !hidden_taps && m->n_layers > 0 && sl_env().prefill_prune_last != 0;
   for (int l = 0; l < m->n_layers; ++l) {
     if (hidden_taps) SL_HIP(hipMemcpyAsync(bptr(hidden_taps) + (size_t)l * n_tok * H * sz, x, n_tok * H * sz, hipMemcpyDeviceToDevice, st));
-    SL_TRY(llama_layer(m, kv, l, x, n_run, w, false, nseq_attn, max_q, nullptr, st, false, nullptr, P, nseq));
+    const bool tail = prune && l == m->n_layers - 1;
+    SL_TRY(llama_layer(m, kv, l, x, n_run, w, false, nseq_attn, max_q, nullptr, st, false, nullptr, P, nseq, false, tail ? w.last_row : nullptr, nseq));
   }
   if (hidden_taps) {
     SL_TRY(sl_rmsnorm(x, bptr(hidden_taps) + (size_t)m->n_layers * n_tok * H * sz, m->final_norm, n_tok, H, m->rms_eps, dt, stream));
   }
-  // last-token rows -> final norm -> lm_head (fp32 logits)
-  for (int s = 0; s < nseq; ++s)
-    SL_HIP(hipMemcpyAsync(bptr(w.last) + (size_t)s * H * sz, bptr(x) + (size_t)last_row[s] * H * sz, H * sz, hipMemcpyDeviceToDevice, st));
+  // last-token rows (one gather launch; the pruned final layer has left them in w.last already) -> final norm -> lm_head (fp32 logits)
+  if (!prune) SL_TRY(gather_rows(x, w.last, w.last_row, nseq, (size_t)H * sz, st));
   SL_TRY(sl_rmsnorm(w.last, w.last, m->final_norm, nseq, H, m->rms_eps, dt, stream));
   SL_TRY(gemm(dt, w.last, H, m->lm_head, H, logits, m->vocab, nullptr, nullptr, 0, nseq, m->vocab, H, SL_ACT_NONE, 1, st));
   return 0;
