@@ -4,7 +4,10 @@ torch_dtype=float16 regime (ref:inference.py:47-51).
 Kernel level: every GEMM family (skinny packed, streaming packed split / unsplit, streaming wide, tiled 256, 128 ring), attention,
 decode attention, norms, RoPE, silu_mul, the conv feature extractor and pooling against fp64 math on the SAME fp16-rounded inputs.
 An op with one output rounding must land within 5e-4 relative L2: fp16 output rounding alone is ~1.4e-4 rms, bf16 ~1.1e-3, so a
-stage that still rounds through bf16 fails.  Model level: the tiny fixtures of test_models_gpu.py at BF16_TOL / 4, and the full
+stage that still rounds through bf16 fails.  The shapes here are aligned and the data N(0, 1): one pass per family.  The edge
+shapes of every form (ragged M / N, 1-3 K slabs, odd N, lda > K, ring stages, split-K / stream-K, fix-up, RoPE / KV, 64-key
+chunks, split + merge), per element, with exact integer data, fp16 overflow / subnormals, guard bands and poisoned padding, are
+in tests/test_kernel_edges_gpu.py.  Model level: the tiny fixtures of test_models_gpu.py at BF16_TOL / 4, and the full
 depth run against the reference's own fp16-autocast outputs.
 """
 import os
