@@ -231,6 +231,36 @@ int main() {
     gx.trans_a = gx.trans_w = 1; ga.M = 192; ga.N = 128; ga.K = 512;        // the bias-gradient rider needs the token-major kernel's shapes (M % 128)
     EXPECT_ARG_ERROR(sl_gemm_ex(&ga, &gx, nullptr));
   }
+  {   // SL_GEMM_LOG=2, the dispatcher's dry run: plan_tiled under the sanitizers (every rule, the recursion of the 128-tile split, the token-major
+      // runs), the plan printed, 0 returned before any HIP call — the operand pointers are never read
+    setenv("SL_GEMM_LOG", "2", 1);
+    EXPECT(sl_tuning_reload() == 0, "tuning reload (dry run)");
+    sl_gemm_args ga;
+    memset(&ga, 0, sizeof(ga));
+    alignas(16) static char ops[64];      // stands for every operand: 16-byte aligned as the argument checks ask, never read
+    ga.A = ops; ga.W = ops; ga.C = ops; ga.batch = 1; ga.dtype = SL_BF16;
+    sl_gemm_ex_args gx;
+    memset(&gx, 0, sizeof(gx));
+    gx.w_mod = 1; gx.sk_ws = ops; gx.sk_ws_bytes = sl_gemm_streamk_workspace_bytes();
+    int32_t runs = -1;
+    const int shapes[][3] = {{300, 256, 200}, {2048, 2048, 512}, {5072, 3072, 3072}, {634, 3072, 8192}, {634, 3072, 16384}, {3200, 3072, 16384}, {400, 3072, 16384}, {16, 3072, 3072}};
+    for (const auto& s : shapes) {
+      ga.M = s[0]; ga.N = s[1]; ga.K = s[2]; ga.lda = ga.ldw = s[2]; ga.ldc = s[1];
+      for (int dt : {SL_BF16, SL_F32}) {
+        ga.dtype = dt;
+        EXPECT(sl_gemm(&ga, nullptr) == 0, "dry run: plain product");
+        EXPECT(sl_gemm_ex(&ga, &gx, nullptr) == 0, "dry run: product with a workspace");
+      }
+    }
+    ga.dtype = SL_BF16; ga.M = 3200; ga.N = 3072; ga.K = 16384; ga.lda = ga.ldw = 16384; ga.ldc = 3072;
+    gx.deferred_splits = &runs;
+    EXPECT(sl_gemm_ex(&ga, &gx, nullptr) == 0 && runs == 0, "dry run: deferred K runs are planned, not handed over");
+    gx.deferred_splits = nullptr;
+    gx.trans_a = gx.trans_w = 1; ga.M = 1024; ga.N = 1024; ga.K = 7984; ga.lda = ga.ldw = ga.ldc = 1024;
+    EXPECT(sl_gemm_ex(&ga, &gx, nullptr) == 0, "dry run: token-major product in K runs");
+    unsetenv("SL_GEMM_LOG");
+    EXPECT(sl_tuning_reload() == 0, "tuning reload (defaults)");
+  }
   EXPECT_ARG_ERROR(sl_col2im_batch(nullptr, nullptr, nullptr, 4, 100, 64, 3, 2, SL_BF16, nullptr));
   EXPECT_ARG_ERROR(sl_col2im_batch(ws, ws, (const int64_t*)ws, 4, 100, 60, 3, 2, SL_BF16, nullptr));            // C not a multiple of 8
   EXPECT_ARG_ERROR(sl_avgpool_bwd_batch(ws, ws, (const int64_t*)ws, 0, 100, 128, 8, 4, SL_BF16, nullptr));      // no utterances

@@ -336,7 +336,9 @@ struct SlEnv {
   int norm_single_row;     // SL_NORM_SINGLE_ROW
   int no_ln_fold;          // SL_NO_LN_FOLD        1 = the encoder runs its LayerNorm kernels even when folded weights are supplied (A/B)
   int no_wgrad_stream;     // SL_NO_WGRAD_STREAM   1 = the encoder backward keeps its parameter-gradient products on the caller's stream (A/B)
-  int gemm_log;            // SL_GEMM_LOG          1 = every sl_gemm* call prints its shape and flags on stderr (shape census for tuning)
+  int gemm_log;            // SL_GEMM_LOG          1 = every sl_gemm* call prints its shape and flags on stderr (`SLGEMM ...`, shape census for tuning) and, on the tiled path, the plan the
+                           //                      dispatcher chose (`SLPLAN fam= form= tm= tn= grid= S= krun= close=`: kernel family and form, tiles, grid, K runs and what closes them; gemm.hip plan_tiled);
+                           //                      2 = dry run: both lines, then return 0 before any HIP call — nothing is launched, no pointer is dereferenced, the plan assumes 256 CUs (tests/test_gemm_plan_cpu.py)
   int no_swap_epilogue;    // SL_NO_SWAP_EPILOGUE  1 = the 256-tile GEMM keeps the LDS-turned rows epilogue where the swapped-operand form applies (A/B)
   int decode_tiled;        // SL_DECODE_TILED      1 (default) = decode steps above ~900 rows run o and gate/up on the row-major 256-tile kernels, 0 = streaming forms
   int prefill_share_prefix; // SL_PREFILL_SHARE_PREFIX 1 (default) = prefill computes a shared prompt prefix (sl_kv_cache.shared_prefix) once per batch, 0 = per sequence (A/B)
@@ -377,7 +379,6 @@ struct SlTransposeBatch {
   int32_t n, pad;
 };
 int sl_transpose_pad_batch_impl(const SlTransposeRec* recs, int n, int32_t dtype, sl_stream stream);
-bool sl_gemm_post_ok(int64_t M, int N, int K, int dtype);      // gemm.hip: a product of this shape may carry sl_gemm_ex_args.post_op / colsum_out
 int sl_family_rows(int rows);
 int sl_family_pin(int rows);      // returns the previous pin (0 = none)
 struct SlFamilyPin {

@@ -12,11 +12,6 @@
 #include "common.h"
 #include "gemm_internal.h"
 
-static int g_disable_glds = 0;  // tuning switch (SL_DISABLE_GLDS=1): A/B the two staging paths in one process
-
-// packed-weight GEMMs with more rows than this run the streaming kernel; SL_STREAM_MIN_M overrides (tuning)
-static int stream_min_m() { return sl_env().stream_min_m; }
-
 #include "gemm_epilogue.h"
 
 template <typename T, int ACT>
@@ -31,21 +26,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tiled_kernel(GemmP p) {
 
   // XCD-aware tile order: consecutive blocks of one XCD (blockIdx % 8 equal) walk tiles that share
   // the same W panel, so the panel stays in that XCD's L2 (bijective remap, guide §5 T1).
-  const int nt = p.tiles_m * p.tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int qn = nt >> 3, rn = nt & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
-  }
-  int bm, bn;   // 8 x 8 patches of tiles per XCD at a time (see gemm_tiled256_kernel)
-  {
-    constexpr int GM = 8;
-    const int per = GM * p.tiles_n, grp = bid / per, first = grp * GM;
-    const int gsz = (p.tiles_m - first) < GM ? (p.tiles_m - first) : GM;
-    const int in = bid - grp * per;
-    bm = first + in % gsz;
-    bn = in / gsz;
-  }
+  int bm, bn;   // 8-row patches of tiles per XCD
+  tile_patch_coords(xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n), p.tiles_m, p.tiles_n, 8, bm, bn);
   const int z = blockIdx.y;
 
   int64_t a_off; int wz;
@@ -222,21 +204,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tiled_glds_kernel(GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int r = lane & 15, q = lane >> 4;
-  const int nt = p.tiles_m * p.tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int qn = nt >> 3, rn = nt & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
-  }
-  int bm, bn;   // 8 x 8 patches of tiles per XCD at a time (see gemm_tiled256_kernel)
-  {
-    constexpr int GM = 8;
-    const int per = GM * p.tiles_n, grp = bid / per, first = grp * GM;
-    const int gsz = (p.tiles_m - first) < GM ? (p.tiles_m - first) : GM;
-    const int in = bid - grp * per;
-    bm = first + in % gsz;
-    bn = in / gsz;
-  }
+  int bm, bn;   // 8-row patches of tiles per XCD
+  tile_patch_coords(xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n), p.tiles_m, p.tiles_n, 8, bm, bn);
   const int z = blockIdx.y;
   int64_t a_off; int wz;
   if (!resolve_group(p, z, bm, a_off, wz)) return;
@@ -596,10 +565,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
 }
 
 // ----------------------------------------------------------------------------------------------
-// host dispatch
-// ----------------------------------------------------------------------------------------------
-// ----------------------------------------------------------------------------------------------
-// stream-K admission (sl_gemm_ex_args.sk_ws): returns the grid size, 0 = keep one block per tile
+// host dispatch of the tiled kernels: plan_tiled holds the rules and chooses (pure: it launches nothing and writes nothing), run_tiled holds
+// the launches.  SL_GEMM_LOG prints the plan (log_plan); tests/test_gemm_plan_cpu.py pins it per shape.
 // ----------------------------------------------------------------------------------------------
 static int sk_cu_count() {
   static int cus[SL_MAX_DEVICES] = {0};
@@ -613,10 +580,65 @@ static int sk_cu_count() {
 }
 extern "C" size_t sl_gemm_streamk_workspace_bytes(void) { return SK_FLAG_BYTES + (size_t)SK_WS_SLOTS * SK_SLOT_BYTES; }
 
-static int sk_grid(const GemmP& p, int batch, int bk, size_t ws_bytes) {
-  const int mode = sl_env().stream_k;          // SL_STREAM_K: 0 = never, 1 = rule (default), 2 = whenever the form allows
-  if (!mode || p.ta || p.tw || p.grp || batch != 1 || p.K % bk || p.ln_mr || p.stats_out || p.amax_val || p.aux || p.N < 192 || p.post || p.colsum) return 0;
-  const int cus = sk_cu_count() < 256 ? sk_cu_count() : 256;
+enum : int { TP_REG128, TP_GLDS128, TP_RING128, TP_T256, TP_SK, TP_TT, TP_UNSUPPORTED };      // TiledPlan.fam
+enum : int { GLDS_ASM, GLDS_DMAB, GLDS_PLAIN };                                               // TiledPlan.form of TP_GLDS128
+enum : int { RUNS_NONE, RUNS_BATCH, RUNS_KRUN, RUNS_TT };                                     // how the kernel finds its K run
+enum : int { CLOSE_NONE, CLOSE_REDUCE, CLOSE_DEFER };
+struct TiledPlan {
+  int fam = TP_REG128;
+  int form = 0;            // GLDS_* | stage code of the ring (SL_GLDS_RING) | SL_T256_* | SL_TT_*
+  int tiles_m = 0, tiles_n = 0;
+  dim3 grid;
+  int S = 1;               // K runs; with S > 1 the launch above is the one of the S fp32 partial products (partial_gemm)
+  int runs = RUNS_NONE;    // RUNS_BATCH: equal runs of `krun` slabs, the run is the launch's batch index; RUNS_KRUN: uneven runs of <= krun slabs (GemmP.krun);
+  int krun = 0;            // RUNS_TT: the token-major kernels' slabs_per_run argument (krun is set for their single run too)
+  int close = CLOSE_NONE;  // what turns the partial products into C: a splitk_reduce_kernel launch, or the consumer (*GemmP.defer = S)
+  void tile(const GemmP& p, int t) { tiles_m = (p.M + t - 1) / t; tiles_n = (p.N + t - 1) / t; }
+};
+
+// ---- conditions the rules share
+static int slab_elems(int dtype) { return TROWB / (dtype == SL_F32 ? 4 : 2); }      // elements of a 128-byte K slab
+// whole K slabs of untransposed operands: what the LDS-DMA kernels stage
+static bool whole_slabs(const GemmP& p, int bk) { return !p.ta && !p.tw && p.K % bk == 0; }
+// ... of ONE plain product
+static bool plain_single(const GemmP& p, int batch, int bk) { return whole_slabs(p, bk) && !p.grp && batch == 1; }
+// nothing rides in the epilogue besides bias / residual / post-op
+static bool no_rider(const GemmP& p) { return !p.ln_mr && !p.stats_out && !p.amax_val && !p.aux; }
+// SL_DISABLE_GLDS: 1 forces the register-staged loader, 2 the two-stage LDS-DMA kernel with compiler-visible LDS reads (A/B); everything else
+// (256 tiles, ring, post-ops, the LayerNorm fold) needs 0
+static bool glds_on(const SlEnv& e) { return e.disable_glds == 0; }
+// the ring form of the 128-tile kernel is on
+static bool ring_on(const GemmP& p, const SlEnv& e) { return e.glds_ring && glds_on(e) && !p.amax_val; }
+// swapped-operand forms of the 256-tile kernels (register epilogue, 16-byte stores): plain 16-bit stores on 8-element aligned rows;
+// `strides`: the launch indexes C / residual by a batch stride
+static bool swap_store_ok(const GemmP& p, const SlEnv& e, bool strides) {
+  const bool al = !(p.N & 7) && !(p.ldc & 7) && !(strides && (p.sC & 7)) && !((uintptr_t)p.C & 15) &&
+                  (!p.res || (!(p.ldr & 7) && !(strides && (p.sR & 7)) && !((uintptr_t)p.res & 15)));
+  return al && !p.out_f32 && !p.res_f32 && !p.direct_epi && !e.no_swap_epilogue;
+}
+static int64_t tiles_of(int M, int N, int tile) { return (int64_t)((M + tile - 1) / tile) * ((N + tile - 1) / tile); }
+
+// shapes for which the training tapes may hand a product its post-ops (train_tape.hip fuse_ok): the tiled kernels' row range, whole K slabs
+static bool post_ok(const SlEnv& e, int64_t M, int N, int K, int dtype) {
+  return sl_family_rows((int)(M > 0x7fffffff ? 0x7fffffff : M)) > 64 && M > 64 && N % 16 == 0 && K % slab_elems(dtype) == 0 && glds_on(e);
+}
+// true when a plain (M, N, K) product of this dtype is served by one of the LDS-DMA tiled kernels, whose rows epilogue carries the
+// LayerNorm fold (ln_* / stats_out)
+static bool rows_epilogue_ok(const SlEnv& e, int M, int N, int K, int dtype) {
+  // any row count: a product that carries ln_* / stats_out is kept on the tiled kernels even below 65 rows (gemm_typed), so that the fold is a
+  // property of the MODEL — a short utterance encoded alone takes the same epilogues, hence the same bits, as inside a batch
+  return sl_is16(dtype) && M > 0 && !(N & 63) && glds_on(e) && e.direct_epilogue == 0 && K % slab_elems(dtype) == 0;
+}
+bool sl_gemm_post_ok(int64_t M, int N, int K, int dtype) { return post_ok(sl_env(), M, N, K, dtype); }
+bool sl_gemm_rows_epilogue_ok(int M, int N, int K, int dtype) { return rows_epilogue_ok(sl_env(), M, N, K, dtype); }
+
+// ----------------------------------------------------------------------------------------------
+// stream-K admission (sl_gemm_ex_args.sk_ws): returns the grid size, 0 = keep one block per tile
+// ----------------------------------------------------------------------------------------------
+static int sk_grid(const GemmP& p, int batch, int bk, size_t ws_bytes, const SlEnv& e, int cu_count) {
+  const int mode = e.stream_k;          // SL_STREAM_K: 0 = never, 1 = rule (default), 2 = whenever the form allows
+  if (!mode || !plain_single(p, batch, bk) || !no_rider(p) || p.N < 192 || p.post || p.colsum) return 0;
+  const int cus = cu_count < 256 ? cu_count : 256;
   const int64_t tm = (p.M + XBM - 1) / XBM, tn = (p.N + XBN - 1) / XBN, nt = tm * tn, nkt = p.K / bk;
   if (nkt < 8 || tm * XBM * 4 > (int64_t)p.M * 5 + 4 * XBM) return 0;      // short reductions; rows padded by more than a quarter (+ one tile)
   int G = cus;
@@ -672,25 +694,25 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 
 // the ring form of the 128-tile kernel (gemm128.hip): whole-slab untransposed ungrouped products whose 128 x 128 tiles (x batch) give every CU
 // at most one block, with enough slabs behind the ring's prologue
-static bool ring_ok(const GemmP& p, int batch, int bk) {
-  if (!sl_env().glds_ring || g_disable_glds || p.ta || p.tw || p.grp || p.K % bk || p.amax_val) return false;
-  const int64_t t128 = (int64_t)((p.M + TBM - 1) / TBM) * ((p.N + TBN - 1) / TBN) * batch;
+static bool ring_ok(const GemmP& p, int batch, int bk, const SlEnv& e, int cus) {
+  if (!ring_on(p, e) || !whole_slabs(p, bk) || p.grp) return false;
+  const int64_t t128 = tiles_of(p.M, p.N, TBM) * batch;
   // up to `ring_max_tiles` (default 256 = one block per CU; above it the blocks beyond the first round wait for a CU: SL_GLDS_RING_MAX_TILES)
-  const int64_t cap = sl_env().ring_max_tiles > 0 ? sl_env().ring_max_tiles : sk_cu_count();
+  const int64_t cap = e.ring_max_tiles > 0 ? e.ring_max_tiles : cus;
   return t128 <= cap && p.K / bk >= 8;
 }
 
-static int splitk_runs(const GemmP& p, int batch, int bk, size_t ws_bytes) {
+static int splitk_runs(const GemmP& p, int batch, int bk, size_t ws_bytes, const SlEnv& e) {
   if (p.colsum) return 0;        // column sums are taken in the tile epilogues (one adder per wave and column), not in the reduce pass
-  if (!sl_env().split_k || p.ta || p.tw || p.grp || batch != 1 || p.K % bk || p.ln_mr || p.stats_out || p.amax_val || p.aux || p.N < 128 || (p.N & 3)) return 0;
-  const int64_t t128 = (int64_t)((p.M + TBM - 1) / TBM) * ((p.N + TBN - 1) / TBN);
+  if (!e.split_k || !plain_single(p, batch, bk) || !no_rider(p) || p.N < 128 || (p.N & 3)) return 0;
+  const int64_t t128 = tiles_of(p.M, p.N, TBM);
   const int nkt = p.K / bk;
   if (t128 > 256 || nkt < 32) return 0;          // above half the 512 slots (two blocks per CU) the chip is busy enough; short reductions
   // slots: two blocks per CU of the two-stage kernel, ONE of the ring form (whose runs then also need no second round)
   // Measured with the ring form (profiles/r06_ag_gemm_vs_vendor_small.txt): one block per CU wins up to K = 8 192 (634 x 3 072 x 8 192: 725 against
   // 707 TF/s on two blocks per CU of the two-stage kernel), two blocks per CU from 192 slabs (x 16 384: 786 against 724)
-  const bool ring = sl_env().glds_ring && !g_disable_glds && !p.amax_val;
-  const int slots = sl_env().splitk_slots > 0 ? sl_env().splitk_slots : ((ring && nkt < 192) ? 256 : 512);
+  const bool ring = ring_on(p, e);
+  const int slots = e.splitk_slots > 0 ? e.splitk_slots : ((ring && nkt < 192) ? 256 : 512);
   int S = (int)(slots / t128);
   if (S > 8) S = 8;
   if (S > nkt / 12) S = nkt / 12;                // every run keeps >= 12 slabs (768 k) behind its prologue
@@ -708,11 +730,11 @@ static int splitk_runs(const GemmP& p, int batch, int bk, size_t ws_bytes) {
 // a caller without deferred_splits gets the reduce launch (the same bits: the unfused tape of the A/B tests), which gives most of the gain back.
 // From 48 slabs per run up.  Measured: 16-sample KD window 88.7 -> 88.4 ms (profiles/r06_an_kd_windows.txt) — a third of what the round count
 // promises: 118 MB of partial tiles are written and read back per product.
-static int splitk256_runs(const GemmP& p, int batch, int bk, size_t ws_bytes, int* krun) {
-  if (!sl_env().split_k256 || p.colsum || p.ta || p.tw || p.grp || batch != 1 || p.K % bk || p.ln_mr || p.stats_out || p.amax_val || p.aux || p.post ||
-      p.bias || p.res || p.out_f32 || (p.N & 3) || g_disable_glds || sl_env().disable_t256 || !sl_env().t256_phased)
+static int splitk256_runs(const GemmP& p, int batch, int bk, size_t ws_bytes, const SlEnv& e, int* krun) {
+  if (!e.split_k256 || p.colsum || !plain_single(p, batch, bk) || !no_rider(p) || p.post || p.bias || p.res || p.out_f32 || (p.N & 3) || !glds_on(e) ||
+      e.disable_t256 || !e.t256_phased)
     return 0;
-  const int64_t t256 = (int64_t)((p.M + XBM - 1) / XBM) * ((p.N + XBN - 1) / XBN);
+  const int64_t t256 = tiles_of(p.M, p.N, XBM);
   // 129 ... 200 tiles only: fewer tiles belong to the 128-tile rule below (more blocks, the ring form), and the admission must not depend on
   // whether the product carries a post-op (the fused and the unfused tape cut the same products the same way)
   if (t256 <= 128 || t256 > 200) return 0;
@@ -728,122 +750,103 @@ static int splitk256_runs(const GemmP& p, int batch, int bk, size_t ws_bytes, in
   return best;
 }
 
-// both operands K-major (weight gradients): gemm_tiled_tt_kernel, with the reduction cut into S runs of whole slabs when the tiles alone
-// leave CUs idle (two blocks per CU: 512 slots) and the caller supplied a workspace
-template <typename T>
-static bool tt_ok(const GemmP& p, int batch) {
-  if (!sl_is_bf16<T> || !sl_env().wgrad_tr || !p.ta || !p.tw || p.grp || p.aux || p.ln_mr || p.stats_out || p.amax_val) return false;
+// both operands K-major (weight gradients): gemm_tiled_tt_kernel
+static bool tt_ok(const GemmP& p, int batch, int dtype, const SlEnv& e) {
+  if (dtype != SL_BF16 || !e.wgrad_tr || !p.ta || !p.tw || p.grp || !no_rider(p)) return false;
   // batched (round 6: the positional conv's weight gradient, 16 groups x 64 output rows per utterance, was 16 launches of the register-staged
   // loader at 84 TF/s): one K run, 64 output rows allowed (the tile's upper half reads zeros), no rider, 8-element aligned batch strides
-  if (batch != 1) {
-    if (!sl_env().tt_batched || p.colsum || p.bias || (p.M != 64 && p.M % TBM) || p.N % TBN || p.lda % 8 || p.ldw % 8 || p.K < 128 || (p.sA & 7) || (p.sW & 7) ||
-        p.wx || p.cx || p.rx)
-      return false;
-    return true;
-  }
+  if (batch != 1)
+    return e.tt_batched && !p.colsum && !p.bias && (p.M == 64 || p.M % TBM == 0) && p.N % TBN == 0 && p.lda % 8 == 0 && p.ldw % 8 == 0 && p.K >= 128 && !(p.sA & 7) &&
+           !(p.sW & 7) && !p.wx && !p.cx && !p.rx;
   return p.M % TBM == 0 && p.N % TBN == 0 && p.lda % 8 == 0 && p.ldw % 8 == 0 && p.K >= 128 && p.wx == 0 && p.cx == 0 && p.rx == 0;
 }
 
-template <typename T>
-static int launch_tt(GemmP& p, hipStream_t st, void* sk_ws, size_t sk_ws_bytes, int batch = 1) {
-  p.tiles_m = (p.M + TBM - 1) / TBM;
-  p.tiles_n = p.N / TBN;
-  const int nt = p.tiles_m * p.tiles_n, nkt = (p.K + 63) / 64;
-  if (batch > 1) return sl_gemm_tt_kernel_launch(p, nt, 1, nkt, st, batch);
+// ... with the reduction cut into S runs of whole slabs when the tiles alone leave CUs idle (two blocks per CU: 512 slots) and the caller
+// supplied a workspace of `part_bytes` for the partial products
+static TiledPlan plan_tt(const GemmP& p, int batch, size_t part_bytes, const SlEnv& e) {
+  TiledPlan pl;
+  pl.fam = TP_TT;
+  pl.tile(p, TBM);      // (N is a multiple of the tile)
+  const int nt = pl.tiles_m * pl.tiles_n, nkt = (p.K + 63) / 64;
+  if (batch > 1) {
+    pl.form = SL_TT_BATCHED; pl.krun = nkt; pl.grid = dim3(nt, 1, batch);
+    return pl;
+  }
   int S = 1;
-  const size_t ws = sk_ws && sk_ws_bytes > SK_FLAG_BYTES ? sk_ws_bytes - SK_FLAG_BYTES : 0;
   // K runs fill 512 block slots (two blocks per CU of the two-stage kernel); launches that end at <= 256 blocks take the ring form (gemm_tt.hip).
   // Filling only 256 slots so that every product rides the ring was measured mixed at 7 984 tokens (4 096 x 1 024: 746 against 675 TF/s,
   // 3 072 x 1 024: 571 against 622, 1 024 x 4 096: 749 against 824; profiles/r06_ak_wgrad_ring.txt) — SL_SPLITK_SLOTS=256 selects it.
-  const int slots = sl_env().splitk_slots > 0 ? sl_env().splitk_slots : 512;
-  if (ws && nt < slots && !(p.N & 3)) {
+  const int slots = e.splitk_slots > 0 ? e.splitk_slots : 512;
+  if (part_bytes && nt < slots && !(p.N & 3)) {
     S = slots / nt;
-    const int smax = sl_env().tt_max_splits > 0 ? sl_env().tt_max_splits : 8;
+    const int smax = e.tt_max_splits > 0 ? e.tt_max_splits : 8;
     if (S > smax) S = smax;
     if (S > nkt / 12) S = nkt / 12;
-    while (S > 1 && (size_t)S * p.M * p.N * sizeof(float) > ws) --S;
+    while (S > 1 && (size_t)S * p.M * p.N * sizeof(float) > part_bytes) --S;
     if (S < 1) S = 1;
   }
-  const int spr = (nkt + S - 1) / S;
-  S = (nkt + spr - 1) / spr;
-  if (S == 1) return sl_gemm_tt_kernel_launch(p, nt, 1, spr, st);
-  float* part = (float*)((unsigned char*)sk_ws + SK_FLAG_BYTES);
+  pl.krun = (nkt + S - 1) / S;
+  pl.S = (nkt + pl.krun - 1) / pl.krun;
+  if (pl.S > 1) { pl.runs = RUNS_TT; pl.close = CLOSE_REDUCE; }
+  pl.form = (e.glds_ring && e.tt_ring && (int64_t)nt * pl.S <= 256 && pl.krun >= 8) ? SL_TT_RING : SL_TT_TWO_STAGE;       // at most one block per CU: the ring form
+  pl.grid = dim3(nt, pl.S);
+  return pl;
+}
+
+// The partial-product GemmP of a plan with K runs: run z leaves its fp32 partial tile at part + z M N, and everything the epilogue would
+// apply (bias, residual, post-op, rounding) is left to what closes the runs.  The bias-gradient rider of the token-major kernel stays in
+// the runs (one adder per run).
+static GemmP partial_gemm(const GemmP& p, int runs, int S, int krun, void* part) {
   GemmP q = p;
   q.C = part; q.ldc = p.N; q.sC = (int64_t)p.M * p.N; q.out_f32 = 1;
   q.bias = nullptr; q.sBias = 0; q.res = nullptr; q.ldr = 0; q.sR = 0; q.res_f32 = 0;
-  SL_TRY(sl_gemm_tt_kernel_launch(q, nt, S, spr, st));
-  const int64_t vecs = ((int64_t)p.M * p.N + 3) / 4;
-  hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, st, part, S, (int64_t)p.M * p.N, p);
-  SL_CHECK_LAUNCH("splitk_reduce");
-  return 0;
+  q.post = 0; q.drop_thr24 = 0; q.post_in = nullptr; q.defer = nullptr;
+  if (runs != RUNS_TT) q.colsum = nullptr;
+  if (runs == RUNS_BATCH) { q.K = p.K / S; q.sA = q.K; q.sW = q.K; }      // run z reads columns [z K/S, (z+1) K/S) of A and W
+  if (runs == RUNS_KRUN) { q.krun = krun; q.sA = 0; q.sW = 0; }           // run z takes slabs [z krun, (z + 1) krun) of the same A / W
+  return q;
 }
 
-template <typename T, int ACT>
-static int launch_tiled(GemmP& p, int batch, hipStream_t st, void* sk_ws = nullptr, size_t sk_ws_bytes = 0) {
-  constexpr int BK_ = TROWB / (int)sizeof(T);
-  if constexpr (ACT == SL_ACT_NONE && sizeof(T) == 2) {
-    if (tt_ok<T>(p, batch)) return launch_tt<T>(p, st, sk_ws, sk_ws_bytes, batch);
-  }
-  if constexpr (ACT == SL_ACT_NONE && sizeof(T) == 2) {
-    if (sk_ws) {
-      int krun = 0;
-      const int S = splitk256_runs(p, batch, BK_, sk_ws_bytes > SK_FLAG_BYTES ? sk_ws_bytes - SK_FLAG_BYTES : 0, &krun);
-      if (S) {
-        GemmP q = p;
-        q.krun = krun; q.sA = 0; q.sW = 0;
-        q.C = (unsigned char*)sk_ws + SK_FLAG_BYTES; q.ldc = p.N; q.sC = (int64_t)p.M * p.N; q.out_f32 = 1;
-        q.defer = nullptr;
-        q.tiles_m = (p.M + XBM - 1) / XBM;
-        q.tiles_n = (p.N + XBN - 1) / XBN;
-        SL_TRY((sl_gemm256_launch<T, SL_ACT_NONE>(q, SL_T256_PHASED, dim3(q.tiles_m * q.tiles_n, S), nullptr, st)));
-        if (p.defer) { *p.defer = S; return 0; }      // the consumer sums the runs (speechllm.h deferred_splits)
-        const int64_t vecs = ((int64_t)p.M * p.N + 3) / 4;
-        hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, st, (const float*)q.C, S, (int64_t)p.M * p.N, p);
-        SL_CHECK_LAUNCH("splitk_reduce");
-        return 0;
-      }
+// The choice.  `ws_bytes`: the caller's sk_ws workspace (0 = none); `cus`: the device's CU count.
+static TiledPlan plan_tiled(const GemmP& p, int batch, int dtype, int act, size_t ws_bytes, const SlEnv& e, int cus) {
+  const int es = dtype == SL_F32 ? 4 : 2, bk = slab_elems(dtype);
+  const size_t part_bytes = ws_bytes > SK_FLAG_BYTES ? ws_bytes - SK_FLAG_BYTES : 0;      // the partial products lie behind the stream-K flags (which stay zero)
+  TiledPlan pl;
+  if (act == SL_ACT_NONE && tt_ok(p, batch, dtype, e)) return plan_tt(p, batch, part_bytes, e);
+  if (act == SL_ACT_NONE && es == 2 && part_bytes) {
+    const int S = splitk256_runs(p, batch, bk, part_bytes, e, &pl.krun);
+    if (S) {
+      pl.fam = TP_T256; pl.form = SL_T256_PHASED;
+      pl.tile(p, XBM);
+      pl.grid = dim3(pl.tiles_m * pl.tiles_n, S);
+      pl.S = S; pl.runs = RUNS_KRUN;
+      pl.close = p.defer ? CLOSE_DEFER : CLOSE_REDUCE;      // the consumer sums the runs (speechllm.h deferred_splits)
+      return pl;
     }
   }
-  if constexpr (ACT == SL_ACT_NONE) {
-    if (sk_ws) {
-      const int S = splitk_runs(p, batch, BK_, sk_ws_bytes > SK_FLAG_BYTES ? sk_ws_bytes - SK_FLAG_BYTES : 0);
-      if (S) {
-        float* part = (float*)((unsigned char*)sk_ws + SK_FLAG_BYTES);      // behind the stream-K flags (which stay zero)
-        GemmP q = p;
-        q.K = p.K / S; q.sA = q.K; q.sW = q.K;                                // run z reads columns [z K/S, (z+1) K/S) of A and W
-        q.C = part; q.ldc = p.N; q.sC = (int64_t)p.M * p.N; q.out_f32 = 1;
-        q.bias = nullptr; q.sBias = 0; q.res = nullptr; q.ldr = 0; q.sR = 0; q.res_f32 = 0;
-        q.post = 0; q.drop_thr24 = 0; q.post_in = nullptr; q.colsum = nullptr;      // the reduce pass applies them
-        q.defer = nullptr;
-        SL_TRY((launch_tiled<T, SL_ACT_NONE>(q, S, st)));
-        if (p.defer && !p.bias && !p.res && !p.post && !p.colsum && !p.out_f32) { *p.defer = S; return 0; }      // the consumer sums the runs (speechllm.h deferred_splits)
-        const int64_t vecs = ((int64_t)p.M * p.N + 3) / 4;
-        hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, st, part, S, (int64_t)p.M * p.N, p);
-        SL_CHECK_LAUNCH("splitk_reduce");
-        return 0;
-      }
+  if (act == SL_ACT_NONE && part_bytes) {
+    const int S = splitk_runs(p, batch, bk, part_bytes, e);
+    if (S) {      // the batched partial product is planned like any other batched product
+      pl = plan_tiled(partial_gemm(p, RUNS_BATCH, S, 0, nullptr), S, dtype, SL_ACT_NONE, 0, e, cus);
+      pl.S = S; pl.runs = RUNS_BATCH; pl.krun = p.K / S / bk;
+      pl.close = (p.defer && !p.bias && !p.res && !p.post && !p.colsum && !p.out_f32) ? CLOSE_DEFER : CLOSE_REDUCE;
+      return pl;
     }
   }
-  if (sk_ws) {
-    const int G = sk_grid(p, batch, BK_, sk_ws_bytes);
+  if (ws_bytes) {
+    const int G = sk_grid(p, batch, bk, ws_bytes, e, cus);
     if (G) {
-      p.tiles_m = (p.M + XBM - 1) / XBM;
-      p.tiles_n = (p.N + XBN - 1) / XBN;
-      if constexpr (sizeof(T) == 2 && ACT != SL_ACT_SILU_MUL) {
-        const bool al = !(p.N & 7) && !(p.ldc & 7) && !((uintptr_t)p.C & 15) && (!p.res || (!(p.ldr & 7) && !((uintptr_t)p.res & 15)));
-        if (al && !p.out_f32 && !p.res_f32 && !p.direct_epi && !sl_env().no_swap_epilogue) {
-          return sl_gemm256_launch<T, ACT>(p, SL_T256_SK_SW, dim3(G), sk_ws, st);
-        }
-      }
-      return sl_gemm256_launch<T, ACT>(p, SL_T256_SK, dim3(G), sk_ws, st);
+      pl.fam = TP_SK;
+      pl.form = (es == 2 && act != SL_ACT_SILU_MUL && swap_store_ok(p, e, false)) ? SL_T256_SK_SW : SL_T256_SK;
+      pl.tile(p, XBM);
+      pl.grid = dim3(G);
+      return pl;
     }
   }
   // large products: 256^2 tiles once they alone give every CU >= 2 tiles (ragged batches: sized by the largest group)
-  if (!p.ta && !p.tw && p.K % BK_ == 0 && !p.grp_ext && g_disable_glds == 0 && !sl_env().disable_t256 && !((p.post || p.colsum) && !sl_env().t256_phased)) {
+  if (whole_slabs(p, bk) && !p.grp_ext && glds_on(e) && !e.disable_t256 && !((p.post || p.colsum) && !e.t256_phased)) {
     const int famM = (p.grp || batch != 1) ? p.M : sl_family_rows(p.M);      // the tile family follows the pinned rows (common.h sl_family_rows)
-    const int64_t t256 = (int64_t)((famM + XBM - 1) / XBM) * ((p.N + XBN - 1) / XBN) * batch;
-    const int64_t min_tiles = sl_env().t256_min_tiles;   // tuning switches
-    const int min_k = sl_env().t256_min_k;
+    const int64_t t256 = tiles_of(famM, p.N, XBM) * batch;
     // rows padded to 256 vs to 128: short (grouped) products such as the 123-row projector would half-fill the big tile
     const int64_t m128 = (int64_t)((famM + TBM - 1) / TBM) * TBM, m256 = (int64_t)((famM + XBM - 1) / XBM) * XBM;
     // Mid-size products (KD windows: M = 2-8 k rows): neither tile count fills the chip evenly, so the choice is made on whole
@@ -851,76 +854,98 @@ static int launch_tiled(GemmP& p, int batch, hipStream_t st, void* sk_ws = nullp
     // the big tile's rate per flop): 5072 x 3072 is 240 big tiles = one round (1.09 PF/s; 960 small ones = two rounds, 0.99),
     // 3200 x 5120 is 260 big tiles = two rounds, the second almost empty (0.63 PF/s; small tiles 0.98).  tools/sweep_t256.py.
     bool by_rounds = false;
-    if (t256 < min_tiles && !p.grp && batch == 1) {
-      const int64_t t128 = (int64_t)((famM + TBM - 1) / TBM) * ((p.N + TBN - 1) / TBN);
-      const int64_t r256 = (t256 + 255) / 256, r128 = (t128 + 511) / 512;
+    if (t256 < e.t256_min_tiles && !p.grp && batch == 1) {
+      const int64_t r256 = (t256 + 255) / 256, r128 = (tiles_of(famM, p.N, TBM) + 511) / 512;
       by_rounds = (double)r256 * (XBM * XBN) * 0.85 < (double)r128 * 2.0 * (TBM * TBN);
     }
     // rows padded to 256: the whole-rounds comparison above already prices the padding (it counts TILES), so a product it picks may pad
     // freely — 634 x 16 384 x 3 072 (the per-rank KD window) is 192 big tiles = one round against 640 small ones = two; only products
     // admitted by their tile count alone (grouped / batched: the 123-row projector) keep the 1/8 bound
-    const bool pad_ok = m256 <= m128 + m128 / 8 || (by_rounds && sl_env().t256_by_rounds_pad);
-    if ((t256 >= min_tiles || by_rounds) && p.N >= 192 && p.K >= min_k && pad_ok) {   // 1024: with the row epilogue the big tile also wins at K = 1024..1536 (+10..20 %)
-      p.tiles_m = (p.M + XBM - 1) / XBM;
-      p.tiles_n = (p.N + XBN - 1) / XBN;
-      const int phased = sl_env().t256_phased;   // 0: round-3 one-barrier-per-slab loop (A/B)
-      if constexpr (sizeof(T) == 2 && ACT != SL_ACT_SILU_MUL) {
-        // swapped-operand form (register epilogue, 16-byte stores): plain bf16 stores on 8-element aligned rows, one of the forms
-        // {bias}, {bias, residual}, {LayerNorm fold}, {bias, residual, row statistics}, {bias, pre-activation copy}
-        const bool al = !(p.N & 7) && !(p.ldc & 7) && !(p.sC & 7) && !((uintptr_t)p.C & 15) &&
-                        (!p.res || (!(p.ldr & 7) && !(p.sR & 7) && !((uintptr_t)p.res & 15)));
+    const bool pad_ok = m256 <= m128 + m128 / 8 || (by_rounds && e.t256_by_rounds_pad);
+    if ((t256 >= e.t256_min_tiles || by_rounds) && p.N >= 192 && p.K >= e.t256_min_k && pad_ok) {   // 1024: with the row epilogue the big tile also wins at K = 1024..1536 (+10..20 %)
+      pl.fam = TP_T256;
+      pl.tile(p, XBM);
+      pl.grid = dim3(pl.tiles_m * pl.tiles_n, batch);
+      const int phased = e.t256_phased;   // 0: round-3 one-barrier-per-slab loop (A/B)
+      pl.form = phased ? SL_T256_PHASED : SL_T256_PLAIN;
+      if (es == 2 && act != SL_ACT_SILU_MUL) {
+        // swapped-operand form: one of the forms {bias}, {bias, residual}, {LayerNorm fold}, {bias, residual, row statistics}, {bias, pre-activation copy}
         const bool form = p.aux ? (!p.ln_mr && !p.stats_out && !p.res && !((uintptr_t)p.aux & 15))        // {bias, pre-activation copy}: the training forward's FFN1
                                 : !p.ln_mr ? (!p.stats_out || p.res) : (!p.res && !p.stats_out);
         // post-ops on the swapped-operand kernels: dropout in {bias, pre-activation copy, GELU} or {bias, residual}; GELU' (+ colsum_out) and SwiGLU' on
         // the plain product; operand rows 16-byte aligned.  Everything else with a post-op takes the LDS-turned rows epilogue.
         bool post_ok = !p.post && !p.colsum;      // (the phased kernel only: the one-barrier-per-slab A/B form keeps the plain epilogues)
-        if (p.post == SL_POST_DROPOUT) post_ok = !p.colsum && !p.ln_mr && !p.stats_out && (ACT == SL_ACT_GELU ? (p.aux && !p.res) : (p.res && !p.aux));
+        if (p.post == SL_POST_DROPOUT) post_ok = !p.colsum && !p.ln_mr && !p.stats_out && (act == SL_ACT_GELU ? (p.aux && !p.res) : (p.res && !p.aux));
         if (p.post == SL_POST_GELU_BWD || p.post == SL_POST_SILU_MUL_BWD)
-          post_ok = ACT == SL_ACT_NONE && !(p.post_ld & 7) && !((uintptr_t)p.post_in & 15) && (p.post == SL_POST_GELU_BWD || !p.colsum);
-        if (al && form && !p.grp && !p.out_f32 && !p.res_f32 && !p.amax_val && !p.direct_epi && !sl_env().no_swap_epilogue && post_ok && (phased || (!p.post && !p.colsum))) {
+          post_ok = act == SL_ACT_NONE && !(p.post_ld & 7) && !((uintptr_t)p.post_in & 15) && (p.post == SL_POST_GELU_BWD || !p.colsum);
+        if (swap_store_ok(p, e, true) && form && !p.grp && !p.amax_val && post_ok && (phased || (!p.post && !p.colsum))) {
+          pl.form = phased ? SL_T256_PHASED_SW : SL_T256_PLAIN_SW;
 #ifdef SL_GEMM_DEBUG
-          if constexpr (ACT == SL_ACT_NONE) {       // instrumented / knocked-out builds (tools/gemm_stamps.py, tools/gemm_knockout.py), never in the product .so
-            const int ko = sl_env().gemm_ko;
-            if (phased && !p.ln_mr && (sl_env().gemm_stamp_ptr || ko)) {
-              p.stamp = (uint32_t*)(uintptr_t)sl_env().gemm_stamp_ptr;
-              const dim3 g(p.tiles_m * p.tiles_n, batch);
-              return sl_gemm256_launch<T, ACT>(p, SL_T256_DBG + (p.stamp ? 8 : (ko >= 1 && ko <= 4 ? ko : 6)), g, nullptr, st);
-            }
-          }
+          // instrumented / knocked-out builds (tools/gemm_stamps.py, tools/gemm_knockout.py), never in the product .so
+          if (act == SL_ACT_NONE && phased && !p.ln_mr && (e.gemm_stamp_ptr || e.gemm_ko))
+            pl.form = SL_T256_DBG + (e.gemm_stamp_ptr ? 8 : (e.gemm_ko >= 1 && e.gemm_ko <= 4 ? e.gemm_ko : 6));
 #endif
-          return sl_gemm256_launch<T, ACT>(p, phased ? SL_T256_PHASED_SW : SL_T256_PLAIN_SW, dim3(p.tiles_m * p.tiles_n, batch), nullptr, st);
         }
       }
-      return sl_gemm256_launch<T, ACT>(p, phased ? SL_T256_PHASED : SL_T256_PLAIN, dim3(p.tiles_m * p.tiles_n, batch), nullptr, st);
+      return pl;
     }
   }
-  p.tiles_m = (p.M + TBM - 1) / TBM;
-  p.tiles_n = (p.N + TBN - 1) / TBN;
-  dim3 grid(p.tiles_m * p.tiles_n, batch);
-  constexpr int BK = TROWB / (int)sizeof(T);
-  if ((p.post || p.colsum) && !(!p.ta && !p.tw && p.K % BK == 0 && (!p.grp_ext || p.grp_kslab) && !g_disable_glds)) {
-    sl_set_error("sl_gemm_ex: post_op / colsum_out need whole 128-byte K slabs (K %% %d == 0) and the LDS-DMA kernels (SL_DISABLE_GLDS unset)", BK);
+  pl.tile(p, TBM);
+  pl.grid = dim3(pl.tiles_m * pl.tiles_n, batch);
+  // per-group K: only the register path handles K tails (groups_ext = 2: the caller vouches for whole slabs)
+  const bool glds = whole_slabs(p, bk) && (!p.grp_ext || p.grp_kslab) && glds_on(e);
+  if ((p.post || p.colsum) && !glds) { pl.fam = TP_UNSUPPORTED; return pl; }
+  // at most one block per CU: the ring form keeps NS - 1 slabs of DMA in flight per block (gemm128.hip; same bits as the two-stage kernel)
+  if (es == 2 && ring_ok(p, batch, bk, e, cus)) { pl.fam = TP_RING128; pl.form = e.glds_ring; }
+  else if (whole_slabs(p, bk) && !p.grp_ext && e.disable_glds == 2) { pl.fam = TP_GLDS128; pl.form = GLDS_PLAIN; }
+  else if (glds) { pl.fam = TP_GLDS128; pl.form = (es == 2 && e.glds_dmab && !p.grp_ext) ? GLDS_DMAB : GLDS_ASM; }
+  else pl.fam = TP_REG128;
+  return pl;
+}
+
+// SL_GEMM_LOG: the plan of one product as key=value pairs (with K runs: the plan of the partial products' launch, then the runs)
+static void log_plan(const TiledPlan& pl) {
+  static const char* const fam[] = {"reg128", "glds128", "ring128", "t256", "sk", "tt", "unsupported"};
+  static const char* const glds[] = {"asm", "dmab", "plain"}, * const t256[] = {"phased", "phased_sw", "plain", "plain_sw", "sk", "sk_sw"};
+  static const char* const tt[] = {"two_stage", "ring", "batched"}, * const close[] = {"none", "reduce", "defer"};
+  char num[16];
+  snprintf(num, sizeof(num), pl.fam == TP_T256 ? "dbg%d" : "%d", pl.form);
+  const bool k256 = (pl.fam == TP_T256 || pl.fam == TP_SK) && pl.form < 6;
+  const char* form = pl.fam == TP_GLDS128 ? glds[pl.form] : k256 ? t256[pl.form] : pl.fam == TP_TT ? tt[pl.form] : (pl.fam == TP_RING128 || pl.fam == TP_T256) ? num : "none";
+  fprintf(stderr, "SLPLAN fam=%s form=%s tm=%d tn=%d grid=%u,%u,%u S=%d krun=%d close=%s\n", fam[pl.fam], form, pl.tiles_m, pl.tiles_n, pl.grid.x, pl.grid.y,
+          pl.grid.z, pl.S, pl.krun, close[pl.close]);
+}
+
+// The launches: the kernel the plan names (on the partial-product GemmP where the plan has K runs), then what closes the runs.
+template <typename T, int ACT>
+static int run_tiled(const GemmP& p0, const TiledPlan& pl, void* sk_ws, const SlEnv& e, hipStream_t st) {
+  if (pl.fam == TP_UNSUPPORTED) {
+    sl_set_error("sl_gemm_ex: post_op / colsum_out need whole 128-byte K slabs (K %% %d == 0) and the LDS-DMA kernels (SL_DISABLE_GLDS unset)", TROWB / (int)sizeof(T));
     return SL_ERR_UNSUPPORTED;
   }
-  // at most one block per CU: the ring form keeps NS - 1 slabs of DMA in flight per block (gemm128.hip; same bits as the two-stage kernel)
-  if constexpr (sizeof(T) == 2) {
-    if (ring_ok(p, batch, BK)) return sl_gemm128_ring_launch<T, ACT>(p, sl_env().glds_ring, grid, st);
+  float* part = (float*)((unsigned char*)sk_ws + SK_FLAG_BYTES);
+  GemmP p = pl.runs ? partial_gemm(p0, pl.runs, pl.S, pl.krun, part) : p0;
+  p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n;
+#ifdef SL_GEMM_DEBUG
+  if (pl.fam == TP_T256 && pl.form >= SL_T256_DBG) p.stamp = (uint32_t*)(uintptr_t)e.gemm_stamp_ptr;
+#endif
+  if (pl.fam == TP_TT) SL_TRY(sl_gemm_tt_kernel_launch(p, pl.form, pl.grid, pl.krun, st));
+  else if (pl.fam == TP_T256 || pl.fam == TP_SK)      // the stream-K form keeps its flags and hand-off slots in the workspace
+    SL_TRY((sl_gemm256_launch<T, ACT>(p, pl.form, pl.grid, pl.fam == TP_SK ? sk_ws : nullptr, st)));
+  else if (pl.fam == TP_RING128) SL_TRY((sl_gemm128_ring_launch<T, ACT>(p, pl.form, pl.grid, st)));
+  else {
+    if (pl.fam == TP_REG128) hipLaunchKernelGGL((gemm_tiled_kernel<T, ACT>), pl.grid, dim3(256), 0, st, p);
+    else if (pl.form == GLDS_PLAIN) hipLaunchKernelGGL((gemm_tiled_glds_kernel<T, ACT, false>), pl.grid, dim3(256), 0, st, p);
+    else if (pl.form == GLDS_ASM) hipLaunchKernelGGL((gemm_tiled_glds_kernel<T, ACT, true>), pl.grid, dim3(256), 0, st, p);
+    else if constexpr (sizeof(T) == 2) hipLaunchKernelGGL((gemm_tiled_glds_kernel<T, ACT, true, true>), pl.grid, dim3(256), 0, st, p);
+    SL_CHECK_LAUNCH("gemm_tiled");
   }
-  if (!p.ta && !p.tw && p.K % BK == 0 && !p.grp_ext && g_disable_glds == 2)
-    hipLaunchKernelGGL((gemm_tiled_glds_kernel<T, ACT, false>), grid, dim3(256), 0, st, p);
-  else if (!p.ta && !p.tw && p.K % BK == 0 && (!p.grp_ext || p.grp_kslab) && !g_disable_glds) {   // per-group K: only the register path handles K tails (groups_ext = 2: the caller vouches for whole slabs)
-    if constexpr (sizeof(T) == 2) {
-      if (sl_env().glds_dmab && !p.grp_ext) {
-        hipLaunchKernelGGL((gemm_tiled_glds_kernel<T, ACT, true, true>), grid, dim3(256), 0, st, p);
-        SL_CHECK_LAUNCH("gemm_tiled");
-        return 0;
-      }
-    }
-    hipLaunchKernelGGL((gemm_tiled_glds_kernel<T, ACT, true>), grid, dim3(256), 0, st, p);
+  if (pl.close == CLOSE_DEFER) *p0.defer = pl.S;
+  if (pl.close == CLOSE_REDUCE) {
+    const int64_t vecs = ((int64_t)p0.M * p0.N + 3) / 4;
+    hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, st, part, pl.S, (int64_t)p0.M * p0.N, p0);
+    SL_CHECK_LAUNCH("splitk_reduce");
   }
-  else
-    hipLaunchKernelGGL((gemm_tiled_kernel<T, ACT>), grid, dim3(256), 0, st, p);
-  SL_CHECK_LAUNCH("gemm_tiled");
   return 0;
 }
 
@@ -940,7 +965,7 @@ static int launch_skinny_cfg(GemmP& p, const SkinnyX& sx, int batch, hipStream_t
 //              real kernel with its fused-norm / pair epilogues: decode step 2.19 vs 1.98 ms)
 //   M 17..64: activations are re-read per fragment from L2, so fewer fragments per wave and wide K splits win.
 template <typename T, int MT, int ACT, bool PACKED>
-static int launch_skinny_mt(GemmP& p, const SkinnyX& sx, int batch, hipStream_t st) {
+static int launch_skinny_mt(GemmP& p, const SkinnyX& sx, int batch, const SlEnv& e, hipStream_t st) {
   constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || ACT == SL_ACT_ROPE_KV);
   const int nfrag = (p.N + 15) / 16 * batch;
   if constexpr (MT == 1) {
@@ -949,7 +974,7 @@ static int launch_skinny_mt(GemmP& p, const SkinnyX& sx, int batch, hipStream_t 
       // of K divides evenly (o: 6 steps = 2 x 3, down: 16 = 4 x 4): 1.575 -> 1.49 ms per decode step at M = 1, +3 % at M = 16
       // where the x fragments crowd the loads.  The same sweep over the qkv and gate/up structures (2x16x3, 2x8x6, 2x8x3;
       // 4x4x6, 4x4x3, 2x8x3, 2x8x6, 4x8x3) moved nothing (profiles/r04_r_skinny_small_m.txt).  SL_SKINNY_ALT=1: old structure.
-      if (nfrag < 256 && sl_family_rows(p.M) <= 8 && !(sl_env().skinny_alt & 1)) {
+      if (nfrag < 256 && sl_family_rows(p.M) <= 8 && !(e.skinny_alt & 1)) {
         const int per_wave = p.K / 32 / 16;
         if (per_wave % 3 == 0) return launch_skinny_cfg<T, MT, ACT, 1, 16, 3, PACKED>(p, sx, batch, st);
         return launch_skinny_cfg<T, MT, ACT, 1, 16, 4, PACKED>(p, sx, batch, st);
@@ -971,62 +996,57 @@ static int launch_skinny_mt(GemmP& p, const SkinnyX& sx, int batch, hipStream_t 
 }
 
 template <typename T, int ACT>
-static int launch_skinny(GemmP& p, const SkinnyX& sx, int batch, bool packed, hipStream_t st) {
+static int launch_skinny(GemmP& p, const SkinnyX& sx, int batch, bool packed, const SlEnv& e, hipStream_t st) {
   if (packed) {
     if constexpr (ACT == SL_ACT_GELU) {
       sl_set_error("sl_gemm: packed weights are not built with the GELU epilogue");
       return SL_ERR_UNSUPPORTED;
     } else {
-      if (sl_family_rows(p.M) <= 16) return launch_skinny_mt<T, 1, ACT, true>(p, sx, batch, st);
-      if (sl_family_rows(p.M) <= 32) return launch_skinny_mt<T, 2, ACT, true>(p, sx, batch, st);
-      return launch_skinny_mt<T, 4, ACT, true>(p, sx, batch, st);
+      if (sl_family_rows(p.M) <= 16) return launch_skinny_mt<T, 1, ACT, true>(p, sx, batch, e, st);
+      if (sl_family_rows(p.M) <= 32) return launch_skinny_mt<T, 2, ACT, true>(p, sx, batch, e, st);
+      return launch_skinny_mt<T, 4, ACT, true>(p, sx, batch, e, st);
     }
   }
   if constexpr (ACT == SL_ACT_ROPE_KV) {
     sl_set_error("sl_gemm: the ROPE_KV epilogue needs packed weights");
     return SL_ERR_UNSUPPORTED;
   } else {
-    if (sl_family_rows(p.M) <= 16) return launch_skinny_mt<T, 1, ACT, false>(p, sx, batch, st);
-    if (sl_family_rows(p.M) <= 32) return launch_skinny_mt<T, 2, ACT, false>(p, sx, batch, st);
-    return launch_skinny_mt<T, 4, ACT, false>(p, sx, batch, st);
+    if (sl_family_rows(p.M) <= 16) return launch_skinny_mt<T, 1, ACT, false>(p, sx, batch, e, st);
+    if (sl_family_rows(p.M) <= 32) return launch_skinny_mt<T, 2, ACT, false>(p, sx, batch, e, st);
+    return launch_skinny_mt<T, 4, ACT, false>(p, sx, batch, e, st);
   }
 }
 
 template <typename T>
-static int gemm_typed(const sl_gemm_args* a, GemmP& p, const SkinnyX& sx, hipStream_t st, void* sk_ws, size_t sk_ws_bytes) {
-  const bool skinny = sl_family_rows(a->M) <= 64 && !p.ta && !p.tw && !p.aux && !p.res_f32 && !p.grp && !p.ln_mr && !p.stats_out && !p.post && !p.colsum;  // backward features and the LayerNorm fold live in the tiled kernel
+static int gemm_typed(const sl_gemm_args* a, GemmP& p, const SkinnyX& sx, hipStream_t st, void* sk_ws, size_t sk_ws_bytes, const SlEnv& e) {
+  const bool skinny = sl_family_rows(a->M) <= 64 && !p.ta && !p.tw && !p.res_f32 && !p.grp && no_rider(p) && !p.post && !p.colsum;  // backward features and the LayerNorm fold live in the tiled kernel
   const bool packed = a->w_layout == SL_W_PACKED;
   if (!skinny && (packed || a->act == SL_ACT_ROPE_KV || sx.fuse_rms)) {
     sl_set_error("sl_gemm: packed weights / ROPE_KV / fused RMSNorm need plain operands (no transposes / groups), M=%d", a->M);
     return SL_ERR_UNSUPPORTED;
   }
-  switch (a->act) {
-    case SL_ACT_NONE: return skinny ? launch_skinny<T, SL_ACT_NONE>(p, sx, a->batch, packed, st) : launch_tiled<T, SL_ACT_NONE>(p, a->batch, st, sk_ws, sk_ws_bytes);
-    case SL_ACT_GELU: return skinny ? launch_skinny<T, SL_ACT_GELU>(p, sx, a->batch, packed, st) : launch_tiled<T, SL_ACT_GELU>(p, a->batch, st, sk_ws, sk_ws_bytes);
-    case SL_ACT_SILU_MUL: return skinny ? launch_skinny<T, SL_ACT_SILU_MUL>(p, sx, a->batch, packed, st) : launch_tiled<T, SL_ACT_SILU_MUL>(p, a->batch, st, sk_ws, sk_ws_bytes);
-    case SL_ACT_ROPE_KV: return launch_skinny<T, SL_ACT_ROPE_KV>(p, sx, a->batch, packed, st);
+  SL_CHECK_ARG(a->act >= SL_ACT_NONE && a->act <= SL_ACT_ROPE_KV, "sl_gemm: unknown act %d", a->act);
+  const bool dry = e.gemm_log == 2;      // SL_GEMM_LOG=2: plan, print, launch nothing
+  if (!skinny) {
+    const TiledPlan pl = plan_tiled(p, a->batch, a->dtype, a->act, sk_ws ? sk_ws_bytes : 0, e, dry ? 256 : sk_cu_count());
+    if (e.gemm_log) log_plan(pl);
+    if (dry && pl.fam != TP_UNSUPPORTED) return 0;
+    if (a->act == SL_ACT_NONE) return run_tiled<T, SL_ACT_NONE>(p, pl, sk_ws, e, st);
+    if (a->act == SL_ACT_GELU) return run_tiled<T, SL_ACT_GELU>(p, pl, sk_ws, e, st);
+    return run_tiled<T, SL_ACT_SILU_MUL>(p, pl, sk_ws, e, st);
   }
-  sl_set_error("sl_gemm: unknown act %d", a->act);
-  return SL_ERR_ARG;
-}
-
-// true when a plain (M, N, K) product of this dtype is served by one of the LDS-DMA tiled kernels, whose rows epilogue carries the
-// LayerNorm fold (ln_* / stats_out)
-// shapes for which the training tapes may hand a product its post-ops (train_tape.hip fuse_ok): the tiled kernels' row range, whole K slabs
-bool sl_gemm_post_ok(int64_t M, int N, int K, int dtype) {
-  return sl_family_rows((int)(M > 0x7fffffff ? 0x7fffffff : M)) > 64 && M > 64 && N % 16 == 0 && K % (dtype == SL_F32 ? 32 : 64) == 0 && sl_env().disable_glds == 0;
-}
-
-bool sl_gemm_rows_epilogue_ok(int M, int N, int K, int dtype) {
-  // any row count: a product that carries ln_* / stats_out is kept on the tiled kernels even below 65 rows (gemm_typed), so that the fold is a
-  // property of the MODEL — a short utterance encoded alone takes the same epilogues, hence the same bits, as inside a batch
-  if (!sl_is16(dtype) || M <= 0 || (N & 63) || sl_env().disable_glds != 0 || sl_env().direct_epilogue != 0) return false;
-  return K % (TROWB / 2) == 0;
+  if (dry) return 0;
+  switch (a->act) {
+    case SL_ACT_NONE: return launch_skinny<T, SL_ACT_NONE>(p, sx, a->batch, packed, e, st);
+    case SL_ACT_GELU: return launch_skinny<T, SL_ACT_GELU>(p, sx, a->batch, packed, e, st);
+    case SL_ACT_SILU_MUL: return launch_skinny<T, SL_ACT_SILU_MUL>(p, sx, a->batch, packed, e, st);
+    default: return launch_skinny<T, SL_ACT_ROPE_KV>(p, sx, a->batch, packed, e, st);
+  }
 }
 
 int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st) {
   SL_CHECK_ARG(a != nullptr, "sl_gemm: null args");
-  g_disable_glds = sl_env().disable_glds;   // 1: register staging, 2: glds with compiler-visible LDS reads
+  const SlEnv& e = sl_env();      // ONE snapshot of the tuning table per product: a concurrent sl_tuning_reload() cannot split a plan
   SL_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0 && a->batch > 0, "sl_gemm: bad shape M=%d N=%d K=%d batch=%d", a->M, a->N, a->K, a->batch);
   SL_CHECK_ARG(a->dtype == SL_F32 || sl_is16(a->dtype), "sl_gemm: bad dtype %d", a->dtype);
   const int vec = a->dtype == SL_F32 ? 4 : 8;
@@ -1042,21 +1062,16 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
     SL_CHECK_ARG(a->ldw % vec == 0 && a->strideW % vec == 0, "sl_gemm: ldw/strideW must keep rows 16-byte aligned");
   }
   if (a->act == SL_ACT_SILU_MUL) SL_CHECK_ARG(a->N % 32 == 0, "sl_gemm: SILU_MUL needs N %% 32 == 0 (16-row gate/up blocks)");
-  GemmP p;
+  GemmP p = {};
   p.A = a->A; p.lda = a->lda; p.sA = a->strideA;
   p.W = a->W; p.ldw = a->ldw; p.sW = a->strideW;
   p.C = a->C; p.ldc = a->ldc; p.sC = a->strideC;
   p.bias = a->bias; p.sBias = a->strideBias;
   p.res = a->residual; p.ldr = a->ldr; p.sR = a->strideR;
   p.M = a->M; p.N = a->N; p.K = a->K; p.out_f32 = a->out_f32;
-  p.tiles_m = p.tiles_n = 0;
-  p.ta = p.tw = 0; p.aux = nullptr; p.res_f32 = 0; p.grp = nullptr; p.w_mod = 1; p.cx = p.rx = p.wx = 0; p.grp_ext = 0; p.grp_kslab = 0;
-  p.post = 0; p.drop_thr24 = 0; p.drop_scale = 1.f; p.drop_seed = 0; p.drop_ld = 0; p.post_in = nullptr; p.post_ld = 0; p.colsum = nullptr; p.defer = nullptr;
-  p.krun = 0; p.stamp = nullptr; p.amax_val = nullptr; p.amax_idx = nullptr; p.ln_mr = nullptr; p.ln_u = nullptr; p.ln_c = nullptr; p.stats_out = nullptr;
-  const int direct_epi = sl_env().direct_epilogue;
-  p.direct_epi = direct_epi;
-  const int gm_env = sl_env().gemm_gm;
-  p.gm = gm_env;
+  p.w_mod = 1; p.drop_scale = 1.f;
+  p.direct_epi = e.direct_epilogue;
+  p.gm = e.gemm_gm;
   if (ex) {
     // fp16 is an inference dtype: the training-tape features of sl_gemm_ex are built for fp32 / bf16 only
     SL_CHECK_ARG(a->dtype != SL_F16 || !(ex->trans_a || ex->trans_w || ex->post_op || ex->colsum_out || ex->aux_out),
@@ -1071,7 +1086,7 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
     SL_CHECK_ARG(!(p.ta || p.tw) || a->w_layout == SL_W_ROWMAJOR, "sl_gemm_ex: transposed operands need row-major storage");
     if (ex->ln_mr || ex->ln_u || ex->ln_c || ex->stats_out) {
       // both sides of the LayerNorm fold live in the rows epilogue of the LDS-DMA tiled kernels (bf16, 4-column vectors)
-      SL_CHECK_ARG(sl_gemm_rows_epilogue_ok(a->M, a->N, a->K, a->dtype) && a->batch == 1 && !ex->groups && !ex->trans_a && !ex->trans_w && !ex->aux_out &&
+      SL_CHECK_ARG(rows_epilogue_ok(e, a->M, a->N, a->K, a->dtype) && a->batch == 1 && !ex->groups && !ex->trans_a && !ex->trans_w && !ex->aux_out &&
                        a->act != SL_ACT_SILU_MUL && a->w_layout == SL_W_ROWMAJOR && a->ldc % 4 == 0 && ((uintptr_t)a->C & 7) == 0 &&
                        (!a->residual || (a->ldr % 4 == 0 && ((uintptr_t)a->residual & 7) == 0)),
                    "sl_gemm_ex: ln_* / stats_out need a plain bf16 row-major product the LDS-DMA tiled kernels take (M=%d N=%d K=%d), 4-element aligned rows", a->M, a->N, a->K);
@@ -1082,7 +1097,7 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
     if (ex->colsum_out && ex->trans_a && ex->trans_w && !ex->post_op) {
       // the bias gradient riding on the weight-gradient product: colsum_out (M) += sum over K of A-stored[k][m] — the token-major kernel only
       p.colsum = ex->colsum_out;
-      SL_CHECK_ARG(a->dtype == SL_BF16 && tt_ok<bf16_t>(p, a->batch) && a->act == SL_ACT_NONE,
+      SL_CHECK_ARG(tt_ok(p, a->batch, a->dtype, e) && a->act == SL_ACT_NONE,
                    "sl_gemm_ex: colsum_out with trans_a + trans_w needs the token-major weight-gradient kernel (bf16, M and N multiples of 128, K >= 128, 8-element aligned rows; sl_gemm_tt_ok)");
     } else if (ex->post_op || ex->colsum_out) {
       SL_CHECK_ARG(ex->post_op >= SL_POST_NONE && ex->post_op <= SL_POST_SILU_MUL_BWD, "sl_gemm_ex: unknown post_op %d", ex->post_op);
@@ -1114,7 +1129,7 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
     }
   }
   SL_CHECK_ARG(p.amax_val || a->C, "sl_gemm: null C");
-  if (sl_env().gemm_log)     // SL_GEMM_LOG=1: one line per product on stderr (tools/kd_gemm_shapes.py turns a KD window's lines into a per-shape table)
+  if (e.gemm_log)     // SL_GEMM_LOG: one line per product on stderr (tools/kd_gemm_shapes.py turns a KD window's lines into a per-shape table)
     fprintf(stderr, "SLGEMM M=%d N=%d K=%d batch=%d act=%d ta=%d tw=%d res=%d resf32=%d outf32=%d aux=%d grp=%d bias=%d packed=%d dt=%d\n", a->M, a->N, a->K, a->batch, a->act,
             p.ta, p.tw, a->residual != nullptr, p.res_f32, a->out_f32, p.aux != nullptr, p.grp ? (p.grp_ext ? 2 : 1) : 0, a->bias != nullptr, a->w_layout == SL_W_PACKED, a->dtype);
   SkinnyX sx;
@@ -1131,28 +1146,28 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
                  "sl_gemm: ROPE_KV epilogue needs the sl_gemm_fused tables");
     SL_CHECK_ARG(a->N == (fx->n_heads + 2 * fx->n_kv_heads) * 128 && a->batch == 1, "sl_gemm: ROPE_KV expects N = (n_heads + 2 n_kv) * 128");
   }
-  // packed weights with more than g_stream_min_m rows: LDS-staged streaming kernel (gemm_stream.hip)
-  if (a->w_layout == SL_W_PACKED && sl_family_rows(a->M) > stream_min_m() && a->batch == 1 && !ex && a->act != SL_ACT_GELU &&
-      a->K % (a->dtype == SL_F32 ? 32 : 64) == 0)
-    return sl_gemm_stream_launch(p, sx, a->dtype, a->act, fx ? fx->split_ws : nullptr, fx ? fx->split_ws_bytes : 0, st);
+  // packed weights with more than SL_STREAM_MIN_M rows: LDS-staged streaming kernel (gemm_stream.hip)
+  if (a->w_layout == SL_W_PACKED && sl_family_rows(a->M) > e.stream_min_m && a->batch == 1 && !ex && a->act != SL_ACT_GELU &&
+      a->K % slab_elems(a->dtype) == 0)
+    return e.gemm_log == 2 ? 0 : sl_gemm_stream_launch(p, sx, a->dtype, a->act, fx ? fx->split_ws : nullptr, fx ? fx->split_ws_bytes : 0, st);
   SL_CHECK_ARG(a->w_layout != SL_W_PACKED || sl_family_rows(a->M) <= 64, "sl_gemm: packed weights with M=%d > 64 need batch 1 and K %% 64 == 0", a->M);
-  SL_CHECK_ARG(!sx.rstd_in && !sx.rstd_out && !sx.norm_out, "sl_gemm: rstd_in / rstd_out / norm_out are features of the streaming path (M > %d rows, packed weights)", stream_min_m());
+  SL_CHECK_ARG(!sx.rstd_in && !sx.rstd_out && !sx.norm_out, "sl_gemm: rstd_in / rstd_out / norm_out are features of the streaming path (M > %d rows, packed weights)", e.stream_min_m);
   void* sk_ws = ex ? ex->sk_ws : nullptr;
   const size_t sk_ws_bytes = ex ? ex->sk_ws_bytes : 0;
   SL_CHECK_ARG(!sk_ws || ((uintptr_t)sk_ws & 15) == 0, "sl_gemm_ex: sk_ws must be 16-byte aligned");
-  if (a->dtype == SL_F32) return gemm_typed<float>(a, p, sx, st, sk_ws, sk_ws_bytes);
-  if (a->dtype == SL_F16) return gemm_typed<f16_t>(a, p, sx, st, sk_ws, sk_ws_bytes);
-  return gemm_typed<bf16_t>(a, p, sx, st, sk_ws, sk_ws_bytes);
+  if (a->dtype == SL_F32) return gemm_typed<float>(a, p, sx, st, sk_ws, sk_ws_bytes, e);
+  if (a->dtype == SL_F16) return gemm_typed<f16_t>(a, p, sx, st, sk_ws, sk_ws_bytes, e);
+  return gemm_typed<bf16_t>(a, p, sx, st, sk_ws, sk_ws_bytes, e);
 }
 
 extern "C" int32_t sl_gemm_split_count(int32_t M, int32_t N, int32_t K, int32_t dtype) {
   M = sl_family_rows(M);
-  if (M <= stream_min_m() || M <= 0 || N <= 0 || K <= 0 || K % (dtype == SL_F32 ? 32 : 64) != 0) return 1;
+  if (M <= sl_env().stream_min_m || M <= 0 || N <= 0 || K <= 0 || K % (dtype == SL_F32 ? 32 : 64) != 0) return 1;
   return sl_gemm_stream_splits(M, N, K, dtype);
 }
 
 extern "C" size_t sl_gemm_split_workspace_bytes(int32_t M, int32_t N, int32_t K, int32_t dtype) {
-  if (sl_family_rows(M) <= stream_min_m() || M <= 0 || N <= 0 || K <= 0) return 0;
+  if (sl_family_rows(M) <= sl_env().stream_min_m || M <= 0 || N <= 0 || K <= 0) return 0;
   return sl_gemm_stream_ws_bytes(M, N, K, dtype);
 }
 

@@ -17,7 +17,7 @@
 //   * the slab's eight DMA requests BETWEEN the MFMAs instead of in a burst behind the barrier (SL_GLDS_RING=204)      -> 757-778
 //   * those requests spread over two 16-MFMA phases, one per four MFMAs (A half / W half in different iterations)      -> 802-857
 // which is the L2 -> CU fetch bound of a 128^2 tile (32 KiB per slab at ~31 B/clk).  Three stages (SL_GLDS_RING=3): 623.
-// launch_tiled (gemm.hip) takes it for whole-slab, untransposed, ungrouped bf16 products of <= 256 tiles (SL_GLDS_RING=0: off; more tiles run in two
+// plan_tiled (gemm.hip) takes it for whole-slab, untransposed, ungrouped bf16 products of <= 256 tiles (SL_GLDS_RING=0: off; more tiles run in two
 // rounds and lose to the two-stage kernel, profiles/r06_ap).
 #include <atomic>
 #include <type_traits>
@@ -60,21 +60,8 @@ __global__ __launch_bounds__(256, 1) void gemm_tiled_ring_kernel(GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int r = lane & 15, q = lane >> 4;
-  const int nt = p.tiles_m * p.tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int qn = nt >> 3, rn = nt & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
-  }
   int bm, bn;   // 8-row patches of tiles per XCD (as gemm_tiled_glds_kernel)
-  {
-    constexpr int GM = 8;
-    const int per = GM * p.tiles_n, grp = bid / per, first = grp * GM;
-    const int gsz = (p.tiles_m - first) < GM ? (p.tiles_m - first) : GM;
-    const int in = bid - grp * per;
-    bm = first + in % gsz;
-    bn = in / gsz;
-  }
+  tile_patch_coords(xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n), p.tiles_m, p.tiles_n, 8, bm, bn);
   const int z = blockIdx.y;
   int64_t a_off; int wz;
   if (!resolve_group(p, z, bm, a_off, wz)) return;
@@ -112,7 +99,7 @@ __global__ __launch_bounds__(256, 1) void gemm_tiled_ring_kernel(GemmP p) {
   };
 
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (SPLIT) {      // slabs 0, 1 and the A half of slab 2 (nkt >= 4: launch_tiled admits the ring from 8 slabs)
+  if constexpr (SPLIT) {      // slabs 0, 1 and the A half of slab 2 (nkt >= 4: plan_tiled admits the ring from 8 slabs)
     issue(0); issue(1);
 #pragma unroll
     for (int i = 0; i < 4; ++i) __builtin_amdgcn_global_load_lds((glb_ptr_t)(ga[i] + 2 * BK), (lds_ptr_t)(smem + 2 * STAGE + wave_lds + i * 4096), 16, 0, 0);

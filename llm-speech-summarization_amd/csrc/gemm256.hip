@@ -42,23 +42,9 @@ __global__ __launch_bounds__(512, 1) void gemm_tiled256_kernel(GemmP p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
   const int r = lane & 15, q = lane >> 4;
-  const int nt = p.tiles_m * p.tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int qn = nt >> 3, rn = nt & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
-  }
-  // blocks that run together on an XCD (consecutive ids) cover an 8 x 4 patch of tiles, so they share A and W slabs in
-  // that XCD's L2 (walking M only shares W: 33 slab streams per 32 blocks from beyond L2 instead of 12)
+  // blocks that run together on an XCD (consecutive ids) cover a patch of p.gm tile rows (gemm_internal.h tile_patch_coords)
   int bm, bn;
-  {
-    const int GM = p.gm;
-    const int per = GM * p.tiles_n, grp = bid / per, first = grp * GM;
-    const int gsz = (p.tiles_m - first) < GM ? (p.tiles_m - first) : GM;
-    const int in = bid - grp * per;
-    bm = first + in % gsz;
-    bn = in / gsz;
-  }
+  tile_patch_coords(xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n), p.tiles_m, p.tiles_n, p.gm, bm, bn);
   const int z = blockIdx.y;
   int64_t a_off; int wz;
   if (!resolve_group(p, z, bm, a_off, wz, XBM)) return;
@@ -146,7 +132,7 @@ __global__ __launch_bounds__(512, 1) void gemm_tiled256_kernel(GemmP p) {
   if constexpr (SW) {
     const int rb0 = bm * XBM + wm * 128, cb0 = bn * XBN + wn * 64;
     const float2* mrl = mr_s + wm * 128;
-    const bool res = p.res != nullptr, ln = p.ln_mr != nullptr, st = p.stats_out != nullptr;    // launch_tiled admits these five forms only
+    const bool res = p.res != nullptr, ln = p.ln_mr != nullptr, st = p.stats_out != nullptr;    // plan_tiled (gemm.hip) admits these five forms only
     if (p.aux) tile_epilogue_sw<T, ACT, EPI_AUX>(p, acc, rb0, cb0, lane, z, wz, mrl);
     else if (ln) tile_epilogue_sw<T, ACT, EPI_LN>(p, acc, rb0, cb0, lane, z, wz, mrl);
     else if (st) tile_epilogue_sw<T, ACT, EPI_RES | EPI_STATS>(p, acc, rb0, cb0, lane, z, wz, mrl);
@@ -350,20 +336,6 @@ __device__ __forceinline__ void t256_stage_ptrs(const GemmP& p, const T* A, cons
   }
 }
 
-// tile index (after the XCD remap) -> tile coordinates: XCD patches of GM tile rows (see gemm_tiled256_kernel)
-__device__ __forceinline__ void t256_tile_coords(const GemmP& p, int v, int& bm, int& bn) {
-  const int GM = p.gm;
-  const int per = GM * p.tiles_n, grp = v / per, first = grp * GM;
-  const int gsz = (p.tiles_m - first) < GM ? (p.tiles_m - first) : GM;
-  const int in = v - grp * per;
-  bm = first + in % gsz;
-  bn = in / gsz;
-}
-__device__ __forceinline__ int xcd_remap(int bid, int n) {      // bijective: the blocks of one XCD (bid % 8 equal) get consecutive indices
-  const int qn = n >> 3, rn = n & 7, xcd = bid & 7, idx = bid >> 3;
-  return (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
-}
-
 template <typename T, int ACT, bool SW, bool POSTS = false>
 __device__ __forceinline__ void t256_epilogue(const GemmP& p, f32x4 (&acc)[8][4], int bm, int bn, int wave, int lane, int z, int wz, unsigned char* smem,
                                               float2* mr_s) {
@@ -371,10 +343,10 @@ __device__ __forceinline__ void t256_epilogue(const GemmP& p, f32x4 (&acc)[8][4]
   if constexpr (SW) {
     const int rb0_ = bm * XBM + wm * 128, cb0 = bn * XBN + wn * 64;
     const float2* mrl = mr_s + wm * 128;
-    const bool res = p.res != nullptr, ln = p.ln_mr != nullptr, st = p.stats_out != nullptr;    // launch_tiled admits these five forms only
+    const bool res = p.res != nullptr, ln = p.ln_mr != nullptr, st = p.stats_out != nullptr;    // plan_tiled (gemm.hip) admits these five forms only
     bool done = false;
     if constexpr (POSTS) {
-     if (p.post) {         // launch_tiled admits exactly these post-op forms on the swapped-operand kernels (the phased kernel only)
+     if (p.post) {         // plan_tiled admits exactly these post-op forms on the swapped-operand kernels (the phased kernel only)
       done = true;
       if constexpr (ACT == SL_ACT_GELU) {
         tile_epilogue_sw<T, ACT, EPI_AUX | EPI_DROP>(p, acc, rb0_, cb0, lane, z, wz, mrl);        // FFN1 forward: mid = dropout(gelu(pre)), pre kept
@@ -417,7 +389,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tiled256p_kernel(GemmP p) {
     if ((wave & 3) == 0 && lane == 0) ((uint32_t*)mr_s)[(wave >> 2) * 32] = (uint32_t)__builtin_amdgcn_s_memtime();
   }
   int bm, bn;
-  t256_tile_coords(p, xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n), bm, bn);
+  tile_patch_coords(xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n), p.tiles_m, p.tiles_n, p.gm, bm, bn);
   const int z = blockIdx.y;
   int64_t a_off; int wz;
   if (!resolve_group(p, z, bm, a_off, wz, XBM)) return;
@@ -497,7 +469,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tiled256sk_kernel(GemmP p, unsign
     const int64_t t0 = (int64_t)tile * nkt;
     const int s1 = (int)(u_hi - t0), s0 = (int)((u_lo > t0 ? u_lo : t0) - t0);
     int bm, bn;
-    t256_tile_coords(p, tile, bm, bn);               // unit order = the XCD-patch tile order: the blocks of one XCD (consecutive vb) work on neighbouring tiles
+    tile_patch_coords(tile, p.tiles_m, p.tiles_n, p.gm, bm, bn);               // unit order = the XCD-patch tile order: the blocks of one XCD (consecutive vb) work on neighbouring tiles
     const T* gp[4][2];
     t256_stage_ptrs<T, SW>(p, A, W, bm, bn, tid, gp);
     f32x4 acc[8][4];

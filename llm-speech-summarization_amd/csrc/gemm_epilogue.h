@@ -393,7 +393,7 @@ __device__ __forceinline__ void tile_epilogue_rows_impl(const GemmP& p, f32x4 (&
   }
 }
 
-// POSTS: this kernel may be handed products with training-tape post-ops (launch_tiled routes them to the LDS-DMA 128-tile kernel and the
+// POSTS: this kernel may be handed products with training-tape post-ops (gemm.hip plan_tiled routes them to the LDS-DMA 128-tile kernel and the
 // phased 256-tile kernel only — the other kernels do not carry those instantiations: compile time)
 template <typename T, int ACT, int MT, bool POSTS = false>
 __device__ __forceinline__ bool tile_epilogue_rows(const GemmP& p, f32x4 (&acc)[MT][4], int row_base, int col_base, int lane, int z, int wz, float* wsm,

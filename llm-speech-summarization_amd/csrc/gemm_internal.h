@@ -1,4 +1,4 @@
-// gemm_internal.h — declarations shared by the GEMM translation units (gemm.hip, gemm_stream.hip).
+// gemm_internal.h — declarations shared by the GEMM translation units (gemm*.hip), and what runtime.hip / train_tape.hip ask gemm.hip about shapes.
 #pragma once
 #include "common.h"
 
@@ -57,6 +57,22 @@ __device__ __forceinline__ bool resolve_group(GemmP& p, int z, int bm, int64_t& 
     if (bm * tile_rows >= p.M) return false;
   }
   return true;
+}
+
+// XCD-aware tile order, shared by every tiled kernel.  Block ids go round-robin over the 8 XCDs, so the blocks of one XCD (bid % 8 equal)
+// get consecutive indices (bijective remap of n blocks, guide §5 T1) ...
+__device__ __forceinline__ int xcd_remap(int bid, int n) {
+  const int qn = n >> 3, rn = n & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
+}
+// ... and consecutive indices walk patches of `gm` tile rows (the last patch may be lower), M first: blocks that run together on an XCD
+// share A and W slabs in that XCD's L2 (walking M only shares W: 33 slab streams per 32 blocks from beyond L2 instead of 12)
+__device__ __forceinline__ void tile_patch_coords(int v, int tiles_m, int tiles_n, int gm, int& bm, int& bn) {
+  const int per = gm * tiles_n, grp = v / per, first = grp * gm;
+  const int gsz = (tiles_m - first) < gm ? (tiles_m - first) : gm;
+  const int in = v - grp * per;
+  bm = first + in % gsz;
+  bn = in / gsz;
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -139,8 +155,14 @@ int sl_gemm256_launch(const GemmP& p, int kind, dim3 grid, void* sk_ws, hipStrea
 // gemm128.hip: the 128-tile kernel with a ring of `stages` K slabs (3 or 4), one block per CU; whole-slab untransposed ungrouped 2-byte products
 template <typename T, int ACT>
 int sl_gemm128_ring_launch(const GemmP& p, int stages, dim3 grid, hipStream_t st);
-// gemm_tt.hip: the weight-gradient kernel on token-major operands, grid (tiles, K runs)
-int sl_gemm_tt_kernel_launch(const GemmP& p, int nt, int S, int slabs_per_run, hipStream_t st, int batch = 1);
+// gemm_tt.hip: the weight-gradient kernel on token-major operands in the form the plan chose (gemm.hip plan_tiled): grid (tiles, K runs), or
+// (tiles, 1, batch) for SL_TT_BATCHED
+enum : int { SL_TT_TWO_STAGE = 0, SL_TT_RING = 1, SL_TT_BATCHED = 2 };
+int sl_gemm_tt_kernel_launch(const GemmP& p, int form, dim3 grid, int slabs_per_run, hipStream_t st);
+
+// gemm.hip: shapes whose products the training tapes may hand post-ops (train_tape.hip fuse_ok) / the LayerNorm fold (runtime.hip)
+bool sl_gemm_post_ok(int64_t M, int N, int K, int dtype);
+bool sl_gemm_rows_epilogue_ok(int M, int N, int K, int dtype);
 
 // decode-side fused inputs of the weight-streaming kernels (sl_gemm_fused on the device side)
 struct SkinnyX {

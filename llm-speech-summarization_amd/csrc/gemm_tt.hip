@@ -40,12 +40,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tiled_tt_kernel(GemmP p, int slab
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int r = lane & 15, q = lane >> 4;
-  const int nt = p.tiles_m * p.tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int qn = nt >> 3, rn = nt & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
-  }
+  const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
   const int bm = bid % p.tiles_m, bn = bid / p.tiles_m;
   // blockIdx.y = K run (split-K); blockIdx.z = batch index (round 6: the positional conv's weight gradient is 16 groups of 64 output rows per
   // utterance — batched launches have one K run, and `z` below indexes C / residual by the batch strides)
@@ -203,12 +198,7 @@ __global__ __launch_bounds__(256, 1) void gemm_tiled_tt_ring_kernel(GemmP p, int
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int r = lane & 15, q = lane >> 4;
-  const int nt = p.tiles_m * p.tiles_n;
-  int bid = blockIdx.x;
-  {
-    const int qn = nt >> 3, rn = nt & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + idx;
-  }
+  const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
   const int bm = bid % p.tiles_m, bn = bid / p.tiles_m;
   const int z = blockIdx.y;
   const int nkt_all = (p.K + BK - 1) / BK;
@@ -371,14 +361,9 @@ __global__ __launch_bounds__(256, 1) void gemm_tiled_tt_ring_kernel(GemmP p, int
   tile_epilogue<T, ACT>(pe, acc, bm, bn, wm, wn, q, r, z, 0);
 }
 
-// launch of the kernel above (gemm.hip launch_tt decides the K runs and issues the reduce pass): grid (tiles, runs)
-int sl_gemm_tt_kernel_launch(const GemmP& p, int nt, int S, int slabs_per_run, hipStream_t st, int batch) {
-  if (batch > 1) {        // batched (one K run): the two-stage kernel, batch index on blockIdx.z
-    hipLaunchKernelGGL((gemm_tiled_tt_kernel<SL_ACT_NONE>), dim3(nt, 1, batch), dim3(256), 0, st, p, slabs_per_run);
-    SL_CHECK_LAUNCH("gemm_tiled_tt(batch)");
-    return 0;
-  }
-  if (sl_env().glds_ring && sl_env().tt_ring && (int64_t)nt * S <= 256 && slabs_per_run >= 8) {       // at most one block per CU: the ring form
+// launch of the kernels above in the form gemm.hip's plan chose (plan_tiled decides the K runs and the form, run_tiled issues the reduce pass)
+int sl_gemm_tt_kernel_launch(const GemmP& p, int form, dim3 grid, int slabs_per_run, hipStream_t st) {
+  if (form == SL_TT_RING) {       // at most one block per CU
     constexpr int LDS_BYTES = 4 * 2 * 64 * 256;
     static std::atomic<uint64_t> attr_set{0};   // one bit per device: the opt-in to > 64 KiB of dynamic LDS is per device
     int devid = 0;
@@ -387,11 +372,11 @@ int sl_gemm_tt_kernel_launch(const GemmP& p, int nt, int S, int slabs_per_run, h
       SL_HIP(hipFuncSetAttribute((const void*)gemm_tiled_tt_ring_kernel<SL_ACT_NONE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
       if (devid >= 0 && devid < 64) attr_set.fetch_or(1ull << devid, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL((gemm_tiled_tt_ring_kernel<SL_ACT_NONE>), dim3(nt, S), dim3(256), LDS_BYTES, st, p, slabs_per_run);
+    hipLaunchKernelGGL((gemm_tiled_tt_ring_kernel<SL_ACT_NONE>), grid, dim3(256), LDS_BYTES, st, p, slabs_per_run);
     SL_CHECK_LAUNCH("gemm_tiled_tt_ring");
     return 0;
   }
-  hipLaunchKernelGGL((gemm_tiled_tt_kernel<SL_ACT_NONE>), dim3(nt, S), dim3(256), 0, st, p, slabs_per_run);
-  SL_CHECK_LAUNCH("gemm_tiled_tt");
+  hipLaunchKernelGGL((gemm_tiled_tt_kernel<SL_ACT_NONE>), grid, dim3(256), 0, st, p, slabs_per_run);      // SL_TT_BATCHED: one K run, batch index on blockIdx.z
+  SL_CHECK_LAUNCH(form == SL_TT_BATCHED ? "gemm_tiled_tt(batch)" : "gemm_tiled_tt");
   return 0;
 }

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gemm_internal.h"
 
 int sl_attn_decode_impl(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, const int32_t* ctx_len,
                         int ctx_add, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx, float scale, int32_t dtype,
@@ -26,7 +27,6 @@ int sl_attn_decode_split_impl(const void* q, int64_t q_stride, const void* k_cac
 size_t sl_attn_decode_split_ws(int B, int n_heads, int n_kv, int max_ctx);
 int sl_rmsnorm_rstd_impl(const void* x, void* y, const void* w, float* rstd_out, int64_t rows, int32_t cols, float eps, int32_t dtype, hipStream_t st);
 int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st);
-bool sl_gemm_rows_epilogue_ok(int M, int N, int K, int dtype);
 
 namespace {
 

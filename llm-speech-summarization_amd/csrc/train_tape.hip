@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.h"
+#include "gemm_internal.h"
 
 // train_ops.hip: norm backward with the residual branch's gradient added in the same pass (dx = backward(dy) + add)
 // ... and, optionally, dropout(dx) as a second output (dx_drop: the incoming gradient of the sublayer below) / a second joining gradient (add2)
