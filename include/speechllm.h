@@ -107,7 +107,7 @@ typedef struct {
   const float* rope_cos; const float* rope_sin;
   const int32_t* tok_pos; const int32_t* tok_seq;
   void* k_cache; void* v_cache;
-  int32_t n_heads, n_kv_heads, max_ctx, reserved;
+  int32_t n_heads, n_kv_heads, max_ctx, reserved;   /* reserved: the caches' K/V format (SL_KV_MODEL_DTYPE / SL_KV_FP8_E4M3, see sl_kv_cache) */
   /* optional scratch for K-split partial sums (M > 16 rows against few weight rows cannot fill 256 CUs
    * otherwise): sl_gemm_split_workspace_bytes(M, N, K, dtype) bytes, or NULL to disable the split.
    * Its first 8192 bytes are arrival counters for the optional in-kernel reduce (SL_STREAM_FIXUP=1: above 384 rows the
@@ -346,6 +346,20 @@ int sl_attn_dropout_bwd(const void* p, void* p_dropped, float* d_p, int64_t n_ma
 int sl_rope_kv_append(void* qkv, void* k_cache, void* v_cache, const int32_t* tok_seq, const int32_t* tok_pos,
                       const float* cos, const float* sin, int64_t n_tok, int32_t n_heads, int32_t n_kv,
                       int32_t D, int32_t max_ctx, int32_t dtype, sl_stream stream);
+/* K/V cache formats (sl_kv_cache.reserved, sl_gemm_fused.reserved, the kv_format argument of the *_ex entries):
+ *   SL_KV_MODEL_DTYPE — rows of D elements in the model dtype;
+ *   SL_KV_FP8_E4M3    — rows of D bytes, OCP e4m3fn, unscaled: a value is first rounded to the model dtype (what the 16-bit cache
+ *                       would hold), clamped to +-448 and rounded to nearest even, so no byte is ever 0x7F / 0xFF (NaN) and
+ *                       reading a byte back into bf16 / fp16 is exact.  Built for SL_BF16 / SL_F16 and head_dim 128: SL_F32 or
+ *                       another head_dim is SL_ERR_UNSUPPORTED; any other format code is SL_ERR_ARG. */
+#define SL_KV_MODEL_DTYPE 0
+#define SL_KV_FP8_E4M3 1
+/* sl_rope_kv_append with the cache format chosen by the caller.  kv_format = SL_KV_MODEL_DTYPE: exactly sl_rope_kv_append.
+ * SL_KV_FP8_E4M3: k, v go to the cache as e4m3 bytes AND the rotated k rows are written back into qkv in place (as q is), so that
+ * a prefill can attend the unquantised keys straight from qkv. */
+int sl_rope_kv_append_ex(void* qkv, void* k_cache, void* v_cache, const int32_t* tok_seq, const int32_t* tok_pos,
+                         const float* cos, const float* sin, int64_t n_tok, int32_t n_heads, int32_t n_kv,
+                         int32_t D, int32_t max_ctx, int32_t dtype, int32_t kv_format, sl_stream stream);
 
 /* One-token GQA attention against the KV cache (decode; hf:...llama.py:191-213 with q_len 1).
  *   q: row b of (B, n_heads*D) with row stride q_stride;  ctx_len[b] keys are attended (the
@@ -362,6 +376,12 @@ size_t sl_attn_decode_workspace_bytes(int32_t B, int32_t n_heads, int32_t n_kv, 
 int sl_attn_decode_split(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out,
                          void* workspace, const int32_t* ctx_len, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D,
                          int32_t max_ctx, float scale, int32_t dtype, sl_stream stream);
+/* sl_attn_decode_split on a cache of either format.  shared_prefix = P: positions [0, P) are read from slot 0 for every sequence
+ * (sl_kv_cache.shared_prefix; the single-pass form honours it in both formats, the split forms on e4m3 rows).  kv_format =
+ * SL_KV_MODEL_DTYPE and P = 0: exactly sl_attn_decode_split. */
+int sl_attn_decode_split_ex(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out,
+                            void* workspace, const int32_t* ctx_len, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D,
+                            int32_t max_ctx, float scale, int32_t dtype, int32_t kv_format, int32_t shared_prefix, sl_stream stream);
 
 /* Greedy token selection (hf:generation/utils.py:2894,2925-2936): argmax over fp32 logits (lowest index
  * on ties), pad finished rows, EOS check, append to out_ids[b][gen_count[b]], advance gen_count and
@@ -596,14 +616,20 @@ typedef struct {
 } sl_llama_model;
 
 typedef struct {
-  void* k_cache; void* v_cache;  /* (n_layers, slots, n_kv, max_ctx, D) each */
+  void* k_cache; void* v_cache;  /* (n_layers, slots, n_kv, max_ctx, D) each: elements of the model dtype, or bytes (reserved = SL_KV_FP8_E4M3) */
   int32_t slots, max_ctx;
   /* shared_prefix = P > 0 is the caller's promise that the first P prompt positions of EVERY sequence of a generate call carry the
    * same input rows (one prompt template in front of the audio, ref:inference.py:95-113 builds it per call): prefill then leaves
    * bit-identical K/V rows at positions [0, P) of every slot, and the batched decode attention reads those positions from slot 0
    * (out of L2 instead of once per sequence from HBM).  0 = no promise.  P <= every prompt length (checked). */
-  int32_t shared_prefix, reserved;
+  int32_t shared_prefix, reserved;       /* reserved: the K/V format, SL_KV_MODEL_DTYPE (0) or SL_KV_FP8_E4M3 (1) */
 } sl_kv_cache;
+/* bytes of ONE of the two caches (k_cache or v_cache) for `slots` x `max_ctx` positions in the given format; 0 on a bad argument */
+size_t sl_kv_cache_bytes(const sl_llama_model* m, int32_t slots, int32_t max_ctx, int32_t kv_format);
+/* The SL_KV_FP8_E4M3 quantiser on HOST memory (no GPU needed): out[i] = the byte the kernels store for the value x[i] (already
+ * rounded to the model dtype by the caller).  The kernels and this entry run the same routine; it exists so that the format can be
+ * checked exhaustively without a device. */
+int sl_kv_quantize_e4m3_host(const float* x, uint8_t* out, int64_t n);
 
 /* LlamaModel.forward over packed prompt embeddings + last-token logits
  * (hf:...llama.py:367-417 + ref:model/audio_llama.py:67 with logits for the last position only).

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = (os.environ.get("SL_LIB_PATH") if os.environ.get("SL_DEV") == "1" else None) or os.path.join(_HERE, "libspeechllm.so")
 
 SL_F32, SL_BF16, SL_F16 = 0, 1, 2
+KV_MODEL_DTYPE, KV_FP8_E4M3 = 0, 1      # speechllm.h SL_KV_*: the K/V cache format (sl_kv_cache.reserved, sl_gemm_fused.reserved)
 ACT_NONE, ACT_GELU, ACT_SILU_MUL, ACT_ROPE_KV = 0, 1, 2, 3
 POST_NONE, POST_DROPOUT, POST_GELU_BWD, POST_SILU_MUL_BWD = 0, 1, 2, 3      # sl_gemm_ex_args.post_op
 W_ROWMAJOR, W_PACKED = 0, 1
@@ -239,6 +240,10 @@ _PROTOS = {
     "sl_attn_fwd": (c_i32, [C.POINTER(AttnArgs), c_vp]),
     "sl_attn_bwd": (c_i32, [C.POINTER(AttnBwdArgs), c_vp]),
     "sl_rope_kv_append": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "sl_rope_kv_append_ex": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "sl_attn_decode_split_ex": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_i32, c_vp]),
+    "sl_kv_quantize_e4m3_host": (c_i32, [c_vp, c_vp, c_i64]),
+    "sl_kv_cache_bytes": (c_sz, [C.POINTER(LlamaModel), c_i32, c_i32, c_i32]),
     "sl_attn_decode": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp]),
     "sl_greedy_select_partial": (c_i32, [c_vp, c_vp, c_i32, c_i32, C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "sl_greedy_select": (c_i32, [c_vp, c_i32, c_i32, C.POINTER(c_i32), c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
@@ -310,6 +315,18 @@ def dtype_code(dt: torch.dtype) -> int:
     if dt == torch.float16:
         return SL_F16
     raise SpeechLLMError(f"unsupported dtype {dt}: the HIP path computes in float32, bfloat16 or float16")
+
+
+def kv_format_code(kv_cache_dtype) -> int:
+    """`kv_cache_dtype` of the Python surface -> SL_KV_*: None (the model dtype), "fp8" or torch.float8_e4m3fn (OCP e4m3, unscaled)."""
+    if kv_cache_dtype is None:
+        return KV_MODEL_DTYPE
+    if isinstance(kv_cache_dtype, str):
+        if kv_cache_dtype == "fp8":
+            return KV_FP8_E4M3
+    elif kv_cache_dtype == torch.float8_e4m3fn:
+        return KV_FP8_E4M3
+    raise SpeechLLMError(f"unsupported kv_cache_dtype {kv_cache_dtype!r}: None (the model dtype), 'fp8' or torch.float8_e4m3fn")
 
 
 def is16(dt: torch.dtype) -> bool:

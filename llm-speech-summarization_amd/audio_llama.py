@@ -44,10 +44,15 @@ class _EmbedTokens:
 
 class AudioLlamaForCausalLM:
     def __init__(self, arch: LlamaArch, state_dict: Dict[str, torch.Tensor], torch_dtype: torch.dtype = torch.bfloat16,
-                 device=None, max_ctx: int = 2048, max_batch: int = 16, pack_decode: bool = True):
+                 device=None, max_ctx: int = 2048, max_batch: int = 16, pack_decode: bool = True, kv_cache_dtype=None):
         # float16 computes in fp16 (the reference's torch_dtype=float16, ref:inference.py:47-51); bfloat16 in bf16; float32 is the
         # exact parity mode.  Logits are fp32 in every mode.
         L.dtype_code(torch_dtype)    # raises for anything else
+        # kv_cache_dtype: None = K/V rows in the model dtype; "fp8" / torch.float8_e4m3fn = one OCP e4m3 byte per element (half the
+        # bytes the decode attention reads and half the cache; 16-bit models only, results differ from the 16-bit cache's)
+        self.kv_format = L.kv_format_code(kv_cache_dtype)
+        if self.kv_format == L.KV_FP8_E4M3 and not L.is16(torch_dtype):
+            raise L.SpeechLLMError("kv_cache_dtype='fp8' needs a bfloat16 or float16 model: float32 is the parity mode and keeps its K/V cache in float32")
         self.arch = arch
         self.dtype = torch_dtype
         self.config = SimpleNamespace(vocab_size=arch.vocab_size, hidden_size=arch.hidden_size,
@@ -119,6 +124,15 @@ class AudioLlamaForCausalLM:
             self._sd = None  # device copy is the only copy from here on (6.4 GB bf16 for Llama-3.2-3B)
         return self
 
+    def set_kv_cache_dtype(self, kv_cache_dtype) -> None:
+        """Switch the K/V cache format (None / "fp8" / torch.float8_e4m3fn); the cache buffers of the other format are released."""
+        fmt = L.kv_format_code(kv_cache_dtype)
+        if fmt == L.KV_FP8_E4M3 and not L.is16(self.dtype):
+            raise L.SpeechLLMError("kv_cache_dtype='fp8' needs a bfloat16 or float16 model")
+        if fmt != self.kv_format:
+            self._kv = None
+            self.kv_format = fmt
+
     def _dev(self) -> LlamaDeviceWeights:
         if self._w is None:
             raise L.SpeechLLMError("LLM weights are not on the GPU: call .to('cuda') — the hot path is HIP-only")
@@ -130,13 +144,19 @@ class AudioLlamaForCausalLM:
         if self._kv is None or self._kv[0].shape[1] < slots or self._kv[0].shape[3] != self.max_ctx:
             self._kv = None        # release the smaller cache BEFORE the larger one is allocated (2 048 slots x 448 positions of Llama-3.2-3B: 105 GB)
             shape = (a.num_hidden_layers, slots, a.num_key_value_heads, self.max_ctx, a.head_dim)
-            k = torch.zeros(shape, device=self.device, dtype=self.dtype)
-            v = torch.zeros(shape, device=self.device, dtype=self.dtype)
+            kv_dtype = self.dtype
+            if self.kv_format == L.KV_FP8_E4M3:      # e4m3 rows: byte buffers of exactly sl_kv_cache_bytes (the library refuses what it has not built)
+                kv_dtype = torch.uint8
+                nbytes = ops.kv_cache_bytes(self._dev().struct, slots, self.max_ctx, self.kv_format)
+                assert nbytes == shape[0] * shape[1] * shape[2] * shape[3] * shape[4], (nbytes, shape)
+            k = torch.zeros(shape, device=self.device, dtype=kv_dtype)
+            v = torch.zeros(shape, device=self.device, dtype=kv_dtype)
             self._kv = (k, v)
         k, v = self._kv
         kv = L.KVCache()
         kv.k_cache, kv.v_cache, kv.slots, kv.max_ctx = k.data_ptr(), v.data_ptr(), k.shape[1], self.max_ctx
         kv.shared_prefix = int(shared_prefix)
+        kv.reserved = self.kv_format                 # sl_kv_cache.reserved: the K/V format
         return kv
 
     def _workspace(self, nbytes: int) -> torch.Tensor:

@@ -46,6 +46,16 @@ def from_dict(d: dict) -> AttrDict:
 _RUNTIME_DTYPES = {"fp32": "float32", "bf16": "bfloat16", "fp16": "float16"}
 
 
+def runtime_kv_dtype(config):
+    """The K/V cache format a config's `runtime.kv_dtype` names: `model` (default: rows in the model dtype) -> None, `fp8` -> "fp8"
+    (OCP e4m3 rows, 16-bit models only) — the value the `kv_cache_dtype` keyword of the model classes takes."""
+    rt = config.get("runtime", {}) if hasattr(config, "get") else {}
+    name = str((rt or {}).get("kv_dtype", "model"))
+    if name not in ("model", "fp8"):
+        raise ValueError(f"runtime.kv_dtype: {name!r} is not one of ['fp8', 'model']")
+    return "fp8" if name == "fp8" else None
+
+
 def runtime_dtype(config) -> "torch.dtype":
     """The compute dtype a config's `runtime.dtype` names (default bf16): fp32 (exact-fp32 parity mode), bf16, or fp16
     (inference only, the reference's torch_dtype=float16 regime; training rejects it)."""

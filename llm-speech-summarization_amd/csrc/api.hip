@@ -20,6 +20,14 @@ extern "C" const char* sl_last_error(void) { return g_err; }
 
 extern "C" int sl_version(void) { return SL_ABI_VERSION; }   // 7: sl_gemm_ex_args.post_op / drop_* / post_in / colsum_out (training-tape epilogue fusions), sl_comm_world asks RCCL; 6: sl_comm_abort, SL_MAX_DECODE_BATCH 2048, sl_gemm_fused.norm_out / norm_gain (grew that struct in round 4), sl_generate_opts (compaction); 5: sl_kv_cache.shared_prefix; 4: sl_gemm_ex_args.sk_ws / sk_ws_bytes, sl_gemm_streamk_workspace_bytes; 3: sl_gemm_ex_args.amax_*, sl_greedy_select_partial, sl_adamw_step, sl_layernorm_bwd_ws, sl_decode_graph_cache_clear
 
+// the e4m3 quantiser of the fp8 K/V cache, run on the host: sl_q8_e4m3 (common.h) is one __host__ __device__ routine, so what this
+// returns is what the kernels store (tests/test_kv8_host_cpu.py holds it against torch for every bf16 and fp16 value)
+extern "C" int sl_kv_quantize_e4m3_host(const float* x, uint8_t* out, int64_t n) {
+  SL_CHECK_ARG(x != nullptr && out != nullptr && n >= 0, "sl_kv_quantize_e4m3_host: bad arguments");
+  for (int64_t i = 0; i < n; ++i) out[i] = (uint8_t)sl_q8_e4m3(x[i]);
+  return 0;
+}
+
 extern "C" int sl_device_arch(char* buf, int n) {
   SL_CHECK_ARG(buf != nullptr && n > 0, "sl_device_arch: bad buffer");
   int dev = 0;

@@ -87,6 +87,36 @@ int main() {
   EXPECT_ARG_ERROR(sl_attn_bwd(&ab, nullptr));
   EXPECT_ARG_ERROR(sl_attn_decode(nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 1.f, SL_BF16, nullptr));
   EXPECT(sl_attn_decode_workspace_bytes(512, 24, 8, 448) > 0, "decode attention workspace");
+  {  // K/V cache formats: an unknown code, e4m3 rows with fp32, e4m3 rows with head_dim 64 (pointers are never dereferenced)
+    void* fk = (void*)(uintptr_t)(1 << 20);
+    const int32_t* fi = (const int32_t*)fk;
+    const float* ff = (const float*)fk;
+    EXPECT_ARG_ERROR(sl_rope_kv_append_ex(fk, fk, fk, fi, fi, ff, ff, 4, 4, 2, 128, 64, SL_BF16, 2, nullptr));
+    EXPECT_ARG_ERROR(sl_rope_kv_append_ex(fk, fk, fk, fi, fi, ff, ff, 4, 4, 2, 128, 64, SL_F32, SL_KV_FP8_E4M3, nullptr));
+    EXPECT_ARG_ERROR(sl_rope_kv_append_ex(fk, fk, fk, fi, fi, ff, ff, 4, 4, 2, 64, 64, SL_F16, SL_KV_FP8_E4M3, nullptr));
+    EXPECT_ARG_ERROR(sl_attn_decode_split_ex(fk, 512, fk, fk, fk, fk, fi, 2, 4, 2, 128, 64, 0.1f, SL_BF16, 2, 0, nullptr));
+    EXPECT_ARG_ERROR(sl_attn_decode_split_ex(fk, 512, fk, fk, fk, fk, fi, 2, 4, 2, 128, 64, 0.1f, SL_F32, SL_KV_FP8_E4M3, 0, nullptr));
+    EXPECT_ARG_ERROR(sl_attn_decode_split_ex(fk, 512, fk, fk, fk, fk, fi, 2, 4, 2, 64, 64, 0.1f, SL_BF16, SL_KV_FP8_E4M3, 0, nullptr));
+    EXPECT_ARG_ERROR(sl_attn_decode_split_ex(fk, 512, fk, fk, fk, fk, fi, 2, 4, 2, 128, 64, 0.1f, SL_BF16, SL_KV_FP8_E4M3, 65, nullptr));   // shared_prefix > max_ctx
+    sl_llama_layer kl[2];
+    memset(kl, 0, sizeof(kl));
+    sl_llama_model km;
+    memset(&km, 0, sizeof(km));
+    km.dtype = SL_BF16; km.hidden = 256; km.n_layers = 2; km.n_heads = 4; km.n_kv_heads = 2; km.head_dim = 128; km.ffn = 512; km.vocab = 1000;
+    km.layers = kl;
+    EXPECT(sl_kv_cache_bytes(&km, 3, 448, SL_KV_FP8_E4M3) == (size_t)2 * 3 * 2 * 448 * 128, "e4m3 cache bytes");
+    EXPECT(sl_kv_cache_bytes(&km, 3, 448, SL_KV_MODEL_DTYPE) == (size_t)2 * 2 * 3 * 2 * 448 * 128, "16-bit cache bytes");
+    EXPECT(sl_kv_cache_bytes(&km, 3, 448, 2) == 0 && sl_last_error()[0] != 0, "unknown format: 0 bytes and a message");
+    km.dtype = SL_F32;
+    EXPECT(sl_kv_cache_bytes(&km, 3, 448, SL_KV_FP8_E4M3) == 0, "e4m3 with fp32: 0 bytes");
+    // the quantiser on the host: ties to even, the subnormal grid, the clamp, signed zero; never 0x7F / 0xFF
+    const float qx[] = {0.f, -0.f, 1.f, -1.f, 448.f, 449.f, 60000.f, -1e30f, 0.001953125f, 0.0009765625f, 0.0029296875f, 17.f, 19.f, 0.015625f, 432.f, 1.0625f, 1.1875f};
+    const uint8_t qw[] = {0x00, 0x80, 0x38, 0xB8, 0x7E, 0x7E, 0x7E, 0xFE, 0x01, 0x00, 0x02, 0x58, 0x5A, 0x08, 0x7E, 0x38, 0x3A};
+    uint8_t qo[sizeof(qx) / sizeof(qx[0])];
+    EXPECT(sl_kv_quantize_e4m3_host(qx, qo, (int64_t)(sizeof(qx) / sizeof(qx[0]))) == 0, "quantiser runs on the host");
+    for (size_t i = 0; i < sizeof(qx) / sizeof(qx[0]); ++i) EXPECT(qo[i] == qw[i], "e4m3 byte of a known value");
+    EXPECT_ARG_ERROR(sl_kv_quantize_e4m3_host(nullptr, qo, 1));
+  }
 
   // ---- norms / element-wise / losses
   EXPECT_ARG_ERROR(sl_layernorm(nullptr, nullptr, nullptr, nullptr, 4, 1024, 1e-5f, 0, SL_BF16, nullptr));

@@ -166,6 +166,44 @@ template <> struct Vec16<f16_t> {
 };
 
 // ----------------------------------------------------------------------------------------------
+// fp8 K/V cache rows (SL_KV_FP8_E4M3: OCP e4m3fn, unscaled).
+// sl_q8_e4m3: fp32 -> byte.  |x| >= 448 (inf and NaN included) gives the largest finite value, so 0x7F / 0xFF are never
+// produced; below that, round to nearest even on the 20 dropped mantissa bits; below 2^-6 the subnormal grid (multiples of
+// 2^-9) through one fp32 add, whose own rounding is the tie rule.  Integer and fp32-add arithmetic only: the same bits on the
+// host and on the device, whatever the hardware conversion does with saturation and subnormals.  The callers pass a value
+// already rounded to the model dtype, so the byte is quantise(what the 16-bit cache would hold).
+// ----------------------------------------------------------------------------------------------
+__host__ __device__ inline uint32_t sl_q8_e4m3(float x) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, x);
+  const uint32_t sign = (u >> 24) & 0x80u;
+  uint32_t a = u & 0x7fffffffu;
+  if (a >= 0x43E00000u) return sign | 0x7Eu;                                   // 448.0f and above
+  if (a < 0x3C800000u)                                                          // below 2^-6: ulp(2^14) = 2^-9
+    return sign | (__builtin_bit_cast(uint32_t, __builtin_bit_cast(float, a) + 16384.0f) - 0x46800000u);
+  a += 0x7FFFFu + ((a >> 20) & 1u);
+  return sign | ((a - 0x3C000000u) >> 20);                                      // exponent bias 127 -> 7
+}
+// 4 / 8 values -> 4 / 8 consecutive bytes
+__device__ __forceinline__ uint32_t sl_q8x4(float a, float b, float c, float d) {
+  return sl_q8_e4m3(a) | (sl_q8_e4m3(b) << 8) | (sl_q8_e4m3(c) << 16) | (sl_q8_e4m3(d) << 24);
+}
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
+// 8 e4m3 bytes -> 8 elements of T (every finite e4m3 value is exact in bf16 and in fp16): four v_cvt_scalef32_pk_*_fp8 at scale 1
+template <typename T> __device__ __forceinline__ u32x4_t sl_dq8x8(u32x2_t w);
+template <> __device__ __forceinline__ u32x4_t sl_dq8x8<bf16_t>(u32x2_t w) {
+  return u32x4_t{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.x, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.x, 1.0f, true)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.y, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w.y, 1.0f, true))};
+}
+template <> __device__ __forceinline__ u32x4_t sl_dq8x8<f16_t>(u32x2_t w) {
+  return u32x4_t{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w.x, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w.x, 1.0f, true)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w.y, 1.0f, false)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w.y, 1.0f, true))};
+}
+
+// ----------------------------------------------------------------------------------------------
 // MFMA 16x16 tile step, dtype-generic.  One "k-step" consumes 64 bytes of K per operand row:
 //   bf16: 32 k  -> one v_mfma_f32_16x16x32_bf16
 //   fp16: 32 k  -> one v_mfma_f32_16x16x32_f16 (same operand / accumulator layout, same cycles)
@@ -294,6 +332,25 @@ static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b;
 static inline size_t sl_dtype_size(int dtype) { return dtype == SL_F32 ? 4 : 2; }
 // a 16-bit storage type (bf16 or fp16): both run the same kernel families
 static inline bool sl_is16(int dtype) { return dtype == SL_BF16 || dtype == SL_F16; }
+// K/V cache format of an entry point (speechllm.h SL_KV_*): unknown codes are SL_ERR_ARG; e4m3 rows are built for the 16-bit
+// model dtypes and head_dim 128 only (SL_ERR_UNSUPPORTED otherwise).  0 = fine.
+static inline int sl_kv_format_check(const char* who, int kv_format, int dtype, int head_dim) {
+  if (kv_format != SL_KV_MODEL_DTYPE && kv_format != SL_KV_FP8_E4M3) {
+    sl_set_error("%s: unknown K/V cache format %d (0 = model dtype, 1 = fp8 e4m3)", who, kv_format);
+    return SL_ERR_ARG;
+  }
+  if (kv_format == SL_KV_FP8_E4M3 && !sl_is16(dtype)) {
+    sl_set_error("%s: the fp8 K/V cache is built for bf16 / fp16 models, not dtype %d (float32 is the parity mode)", who, dtype);
+    return SL_ERR_UNSUPPORTED;
+  }
+  if (kv_format == SL_KV_FP8_E4M3 && head_dim != 128) {
+    sl_set_error("%s: the fp8 K/V cache is built for head_dim 128, not %d", who, head_dim);
+    return SL_ERR_UNSUPPORTED;
+  }
+  return 0;
+}
+// bytes of one K/V element in the cache
+static inline size_t sl_kv_elem_size(int kv_format, int dtype) { return kv_format == SL_KV_FP8_E4M3 ? 1 : sl_dtype_size(dtype); }
 
 // ----------------------------------------------------------------------------------------------
 // tuning switches: environment variables read ONCE (first use) into this table, never on a dispatch path;

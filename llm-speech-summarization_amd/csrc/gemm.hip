@@ -541,13 +541,13 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
             T* dst = (T*)Cb + (int64_t)m * p.ldc + hh * 128 + d;
             dst[0] = from_f32<T>(o1); dst[64] = from_f32<T>(o2);
           } else {
-            T* dst = (T*)sx.kc + (((int64_t)sx.seq[m] * sx.nkv + (hh - sx.nh)) * sx.max_ctx + pos) * 128 + d;
-            dst[0] = from_f32<T>(o1); dst[64] = from_f32<T>(o2);
+            const int64_t at = (((int64_t)sx.seq[m] * sx.nkv + (hh - sx.nh)) * sx.max_ctx + pos) * 128 + d;
+            kv_store<T>(sx.kc, at, o1, sx.kv8); kv_store<T>(sx.kc, at + 64, o2, sx.kv8);
           }
         } else {  // v rows are in natural order: fragments 2j, 2j+1
           const int d = (gf & 7) * 16 + n;
-          T* dst = (T*)sx.vc + (((int64_t)sx.seq[m] * sx.nkv + (hh - sx.nh - sx.nkv)) * sx.max_ctx + pos) * 128 + d;
-          dst[0] = from_f32<T>(a); dst[16] = from_f32<T>(b);
+          const int64_t at = (((int64_t)sx.seq[m] * sx.nkv + (hh - sx.nh - sx.nkv)) * sx.max_ctx + pos) * 128 + d;
+          kv_store<T>(sx.vc, at, a, sx.kv8); kv_store<T>(sx.vc, at + 16, b, sx.kv8);
         }
       }
     }
@@ -1145,6 +1145,8 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
     SL_CHECK_ARG(fx && fx->rope_cos && fx->rope_sin && fx->tok_pos && fx->tok_seq && fx->k_cache && fx->v_cache,
                  "sl_gemm: ROPE_KV epilogue needs the sl_gemm_fused tables");
     SL_CHECK_ARG(a->N == (fx->n_heads + 2 * fx->n_kv_heads) * 128 && a->batch == 1, "sl_gemm: ROPE_KV expects N = (n_heads + 2 n_kv) * 128");
+    SL_TRY(sl_kv_format_check("sl_gemm (ROPE_KV)", fx->reserved, a->dtype, 128));     // sl_gemm_fused.reserved: the caches' K/V format
+    sx.kv8 = fx->reserved == SL_KV_FP8_E4M3;
   }
   // packed weights with more than SL_STREAM_MIN_M rows: LDS-staged streaming kernel (gemm_stream.hip)
   if (a->w_layout == SL_W_PACKED && sl_family_rows(a->M) > e.stream_min_m && a->batch == 1 && !ex && a->act != SL_ACT_GELU &&

@@ -171,11 +171,26 @@ struct SkinnyX {
   void* kc; void* vc;                      // this layer's caches (slots, n_kv, max_ctx, 128)
   int nh, nkv, max_ctx, fuse_rms;
   float eps;
+  int kv8;                // ROPE_KV: kc / vc hold e4m3 bytes (sl_gemm_fused.reserved = SL_KV_FP8_E4M3); uniform over the launch.  Sits in
+                          // what was padding in front of the next pointer: no other member moves
   const float* rstd_in;   // per-row RMSNorm scale computed by the producer of A (replaces the in-kernel statistics)
   float* rstd_out;        // K-split reduce kernel: also emit rsqrt(mean(out_row^2) + eps) of the rows it stores
   void* norm_out;         // ... and the normalised rows themselves: gain * round(row * rstd), row stride N (sl_gemm_fused.norm_out)
   const void* norm_gain;
 };
+// gemm_stream.hip instantiates the e4m3 form of the ROPE_KV epilogue under an act code of its own (template parameter: the
+// 16-bit instances are the code they were); never seen outside the library
+constexpr int SL_ACT_ROPE_KV8 = 64 + SL_ACT_ROPE_KV;
+constexpr bool sl_act_is_rope_kv(int act) { return act == SL_ACT_ROPE_KV || act == SL_ACT_ROPE_KV8; }
+// one K / V element of the ROPE_KV epilogue: rounded to T as the 16-bit cache holds it, then (kv8) quantised from that value
+template <typename T>
+__device__ __forceinline__ void kv_store(void* cache, int64_t at, float v, int kv8) {
+  const T t = from_f32<T>(v);
+  if constexpr (sizeof(T) == 2) {
+    if (kv8) { ((uint8_t*)cache)[at] = (uint8_t)sl_q8_e4m3(to_f32(t)); return; }
+  }
+  ((T*)cache)[at] = t;
+}
 
 // gemm_stream.hip: packed-weight streaming GEMM for 16 < M <= 256 (large-batch decode)
 int sl_gemm_stream_launch(GemmP& p, const SkinnyX& sx, int dtype, int act, void* split_ws, size_t split_ws_bytes, hipStream_t st);

@@ -86,6 +86,38 @@ __device__ __forceinline__ void stream_epilogue4(const GemmP& p, const SkinnyX& 
         dst[d + 16] = from_f32<T>(b[i]);
       }
     }
+  } else if constexpr (ACT == SL_ACT_ROPE_KV8) {
+    // the ROPE_KV branch with K / V stored as e4m3 bytes (kv_store: rounded to T first, quantised from that value); q as before
+    if (gf * 16 >= p.N) return;
+    const int hh = gf >> 3, j = (gf & 7) >> 1;
+    const int pos = sx.pos[m];
+    if (hh < sx.nh) {
+      T* dst = (T*)p.C + (int64_t)m * p.ldc + hh * 128;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int d = j * 16 + n4 + i;
+        const float c = sx.cos[(int64_t)pos * 64 + d], s = sx.sin[(int64_t)pos * 64 + d];
+        dst[d] = from_f32<T>(a[i] * c - b[i] * s);
+        dst[d + 64] = from_f32<T>(b[i] * c + a[i] * s);
+      }
+    } else if (hh < sx.nh + sx.nkv) {
+      const int64_t row = (((int64_t)sx.seq[m] * sx.nkv + (hh - sx.nh)) * sx.max_ctx + pos) * 128;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int d = j * 16 + n4 + i;
+        const float c = sx.cos[(int64_t)pos * 64 + d], s = sx.sin[(int64_t)pos * 64 + d];
+        kv_store<T>(sx.kc, row + d, a[i] * c - b[i] * s, 1);
+        kv_store<T>(sx.kc, row + d + 64, b[i] * c + a[i] * s, 1);
+      }
+    } else {
+      const int64_t row = (((int64_t)sx.seq[m] * sx.nkv + (hh - sx.nh - sx.nkv)) * sx.max_ctx + pos) * 128;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int d = (gf & 7) * 16 + n4 + i;
+        kv_store<T>(sx.vc, row + d, a[i], 1);
+        kv_store<T>(sx.vc, row + d + 16, b[i], 1);
+      }
+    }
   } else {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -104,7 +136,7 @@ __device__ __forceinline__ void stream_epilogue4(const GemmP& p, const SkinnyX& 
 template <typename T, int MT, int ACT, int RF>
 __device__ __forceinline__ void stream_finish(const GemmP& p, const SkinnyX& sx, const StreamX& s, f32x4 (&acc)[RF][MT], const float (&ssum)[MT],
                                               bool fuse, int m0, int sp, int fi0, int nfrag, bool writes_ss, int q, int r) {
-  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || ACT == SL_ACT_ROPE_KV);
+  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || sl_act_is_rope_kv(ACT));
   if (s.splits > 1) {
 #pragma unroll
     for (int t = 0; t < MT; ++t) {
@@ -149,7 +181,7 @@ template <typename T, int MT, int ACT, int RF, int NWV, int D, int NL, bool FUSE
 __global__ __launch_bounds__(64 * (NWV + NL)) void gemm_stream_kernel(GemmP p, SkinnyX sx, StreamX s) {
   constexpr int VEC = Vec16<T>::VEC;
   constexpr int KSTEP = MMA<T>::KSTEP;
-  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || ACT == SL_ACT_ROPE_KV);
+  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || sl_act_is_rope_kv(ACT));
   static_assert(!PAIRS || RF % 2 == 0, "pair epilogues need an even number of fragments");
   static_assert(MT % NL == 0 && MT / NL <= 8, "a loader wave stages at most 128 rows");
   constexpr int MTL = MT / NL;                // row tiles per loader wave (NL of them: one wave's LDS-DMA stream tops out at ~25 GB/s)
@@ -630,7 +662,7 @@ __device__ __forceinline__ void reduce_sum_splits(const float* rec, int64_t spli
 // one thread per (row, fragment or fragment pair, 4-column group)
 template <typename T, int ACT>
 __global__ __launch_bounds__(256) void gemm_stream_reduce_kernel(GemmP p, SkinnyX sx, StreamX s) {
-  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || ACT == SL_ACT_ROPE_KV);
+  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || sl_act_is_rope_kv(ACT));
   const int nfrag = (p.N + 15) >> 4;
   const int nunits = PAIRS ? (nfrag + 1) / 2 : nfrag;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -940,7 +972,7 @@ size_t sl_gemm_stream_ws_bytes(int M, int N, int K, int dtype) {
 template <typename T, int ACT>
 static int launch_stream_reduce(GemmP& p, const SkinnyX& sx, const StreamX& s, hipStream_t st) {
   if (s.splits <= 1) return 0;
-  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || ACT == SL_ACT_ROPE_KV);
+  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || sl_act_is_rope_kv(ACT));
   const int nfrag = (p.N + 15) / 16;
   const int64_t nunits = PAIRS ? (nfrag + 1) / 2 : nfrag;
   const int64_t threads = (int64_t)p.M * nunits * 4;
@@ -1014,7 +1046,9 @@ static int stream_typed(GemmP& p, const SkinnyX& sx, int act, const StreamX& s, 
   switch (act) {
     case SL_ACT_NONE: return launch_stream<T, SL_ACT_NONE>(p, sx, s, c, st);
     case SL_ACT_SILU_MUL: return launch_stream<T, SL_ACT_SILU_MUL>(p, sx, s, c, st);
-    case SL_ACT_ROPE_KV: return launch_stream<T, SL_ACT_ROPE_KV>(p, sx, s, c, st);
+    case SL_ACT_ROPE_KV:
+      if constexpr (sizeof(T) == 2) { if (sx.kv8) return launch_stream<T, SL_ACT_ROPE_KV8>(p, sx, s, c, st); }
+      return launch_stream<T, SL_ACT_ROPE_KV>(p, sx, s, c, st);
   }
   sl_set_error("sl_gemm: packed weights are not built with act %d for M > 16 streaming", act);
   return SL_ERR_UNSUPPORTED;
@@ -1050,7 +1084,9 @@ template <typename T>
 static int launch_stream_wide(GemmP& p, const SkinnyX& sx, int act, const StreamX& s, hipStream_t st) {
   switch (act) {
     case SL_ACT_SILU_MUL: return launch_stream_wide_act<T, SL_ACT_SILU_MUL>(p, sx, s, st);
-    case SL_ACT_ROPE_KV: return launch_stream_wide_act<T, SL_ACT_ROPE_KV>(p, sx, s, st);
+    case SL_ACT_ROPE_KV:
+      if constexpr (sizeof(T) == 2) { if (sx.kv8) return launch_stream_wide_act<T, SL_ACT_ROPE_KV8>(p, sx, s, st); }
+      return launch_stream_wide_act<T, SL_ACT_ROPE_KV>(p, sx, s, st);
     default: return launch_stream_wide_act<T, SL_ACT_NONE>(p, sx, s, st);
   }
 }

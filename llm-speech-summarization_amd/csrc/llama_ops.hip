@@ -2,6 +2,8 @@
 // attention against the cache, greedy token selection.  All HBM/latency-bound; 16-byte accesses, fp32 math.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 // ----------------------------------------------------------------------------------------------
@@ -37,8 +39,11 @@ extern "C" int sl_embed_gather(const void* table, const int32_t* ids, void* out,
 // RoPE + KV append.  One thread owns chunk j of the first half of a head and the matching chunk of the
 // second half (rotate_half pairs d with d + D/2).
 // ----------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void rope_kv_append_kernel(T* __restrict__ qkv, T* __restrict__ kc, T* __restrict__ vc,
+// KV8 (SL_KV_FP8_E4M3): the caches hold one e4m3 byte per element, quantised from the value rounded to T (sl_q8_e4m3), and the
+// rotated K rows also go back into qkv in place, where the fp8-mode prefill attention reads them unquantised.
+template <typename T, bool KV8 = false>
+__global__ __launch_bounds__(256) void rope_kv_append_kernel(T* __restrict__ qkv, std::conditional_t<KV8, uint8_t, T>* __restrict__ kc,
+                                                             std::conditional_t<KV8, uint8_t, T>* __restrict__ vc,
                                                              const int32_t* __restrict__ tok_seq, const int32_t* __restrict__ tok_pos,
                                                              const float* __restrict__ cosT, const float* __restrict__ sinT, int64_t n_tok,
                                                              int nh, int nkv, int D, int max_ctx) {
@@ -73,11 +78,44 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(T* __restrict__ qkv
     } else {
       const bool isk = h < nh + nkv;
       const int kvh = isk ? h - nh : h - nh - nkv;
-      T* dst = (isk ? kc : vc) + (((int64_t)tok_seq[t] * nkv + kvh) * max_ctx + pos) * D + j * VEC;
-      *(uint4*)dst = u1;
-      *(uint4*)(dst + half) = u2;
+      auto* dst = (isk ? kc : vc) + (((int64_t)tok_seq[t] * nkv + kvh) * max_ctx + pos) * D + j * VEC;
+      if constexpr (KV8) {
+        static_assert(sizeof(T) == 2, "e4m3 K/V rows are built for the 16-bit types");
+        if (isk) {
+          *(uint4*)src = u1;
+          *(uint4*)(src + half) = u2;
+        }
+        float f1[VEC], f2[VEC];
+        Vec16<T>::unpack(u1, f1);
+        Vec16<T>::unpack(u2, f2);
+        *(uint2*)dst = make_uint2(sl_q8x4(f1[0], f1[1], f1[2], f1[3]), sl_q8x4(f1[4], f1[5], f1[6], f1[7]));
+        *(uint2*)(dst + half) = make_uint2(sl_q8x4(f2[0], f2[1], f2[2], f2[3]), sl_q8x4(f2[4], f2[5], f2[6], f2[7]));
+      } else {
+        *(uint4*)dst = u1;
+        *(uint4*)(dst + half) = u2;
+      }
     }
   }
+}
+
+extern "C" int sl_rope_kv_append_ex(void* qkv, void* k_cache, void* v_cache, const int32_t* tok_seq, const int32_t* tok_pos,
+                                    const float* cos, const float* sin, int64_t n_tok, int32_t n_heads, int32_t n_kv, int32_t D,
+                                    int32_t max_ctx, int32_t dtype, int32_t kv_format, sl_stream stream) {
+  if (kv_format == SL_KV_MODEL_DTYPE)
+    return sl_rope_kv_append(qkv, k_cache, v_cache, tok_seq, tok_pos, cos, sin, n_tok, n_heads, n_kv, D, max_ctx, dtype, stream);
+  SL_CHECK_ARG(qkv && k_cache && v_cache && tok_seq && tok_pos && cos && sin, "sl_rope_kv_append_ex: null pointer");
+  SL_TRY(sl_kv_format_check("sl_rope_kv_append_ex", kv_format, dtype, D));
+  if (n_tok == 0) return 0;
+  const int64_t total = n_tok * (n_heads + 2 * n_kv) * (D / 2 / 8);
+  const unsigned grid = (unsigned)(ceil_div64(total, 256) < 8192 ? ceil_div64(total, 256) : 8192);
+  if (dtype == SL_BF16)
+    hipLaunchKernelGGL((rope_kv_append_kernel<bf16_t, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (bf16_t*)qkv, (uint8_t*)k_cache,
+                       (uint8_t*)v_cache, tok_seq, tok_pos, cos, sin, n_tok, n_heads, n_kv, D, max_ctx);
+  else
+    hipLaunchKernelGGL((rope_kv_append_kernel<f16_t, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (f16_t*)qkv, (uint8_t*)k_cache,
+                       (uint8_t*)v_cache, tok_seq, tok_pos, cos, sin, n_tok, n_heads, n_kv, D, max_ctx);
+  SL_CHECK_LAUNCH("rope_kv_append_fp8");
+  return 0;
 }
 
 extern "C" int sl_rope_kv_append(void* qkv, void* k_cache, void* v_cache, const int32_t* tok_seq, const int32_t* tok_pos,
@@ -634,7 +672,6 @@ extern "C" int sl_pack_weight(const void* src, int64_t ld_src, void* dst, int32_
 //   was 20 % slower than split + merge at B = 128 and 256: the serial chunk chain exposes three barriers per 32 KiB.)
 // ----------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* lds_ptr3_t;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 // K / V cache rows are read exactly once per decode step (one block per sequence and kv head): non-temporal loads keep them from
 // displacing what other kernels re-read in L2 / the Infinity Cache and land sooner (MI355X_MICROARCH.md, nt-weights).  Measured
 // (tools/time_decode_attn.py, bf16, 8 kv heads, profiles/r03_l_attn_nt.txt): 1 024 sequences x 264 keys 194.1 -> 178.3 us
@@ -645,9 +682,24 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
 #endif
 #if SL_KV_NT
 #define SL_KV_LOAD(ptr) __builtin_nontemporal_load((const u32x4_t*)(ptr))
+#define SL_KV_LOAD8(ptr) __builtin_nontemporal_load((const u32x2_t*)(ptr))
 #else
 #define SL_KV_LOAD(ptr) (*(const u32x4_t*)(ptr))
+#define SL_KV_LOAD8(ptr) (*(const u32x2_t*)(ptr))
 #endif
+// e4m3 K/V rows (KVT = uint8_t; 16-bit T only): a thread's 8-element chunk of a row is 8 bytes instead of 16, held as loaded and
+// widened to T (exactly: sl_dq8x8) where the 16-bit kernels copy their registers to LDS.  Everything behind that copy — tile
+// images, MFMA steps, softmax, records — is the 16-bit kernel's.
+template <typename T, typename KVT> struct KvRow {
+  using raw_t = u32x4_t;
+  static __device__ __forceinline__ raw_t load(const KVT* p) { return SL_KV_LOAD(p); }
+  static __device__ __forceinline__ u32x4_t widen(const raw_t& r) { return r; }
+};
+template <typename T> struct KvRow<T, uint8_t> {
+  using raw_t = u32x2_t;
+  static __device__ __forceinline__ raw_t load(const uint8_t* p) { return SL_KV_LOAD8(p); }
+  static __device__ __forceinline__ u32x4_t widen(const raw_t& r) { return sl_dq8x8<T>(r); }
+};
 // floats per partial record (REP x 128 outputs, REP maxima, REP sums), rounded up to whole 128-byte lines so that the records of
 // different (sequence, kv head, split) blocks never share a line (the in-launch merge hands them between workgroups with sc1 stores)
 constexpr int split_record_floats(int rep) { return (rep * 128 + 2 * rep + 31) / 32 * 32; }
@@ -718,12 +770,17 @@ __device__ __forceinline__ void split_arrive_and_merge(float* __restrict__ part,
   }
 }
 
-template <typename T, int REP, int KS>
-__global__ __launch_bounds__(256) void attn_decode_split_kernel(const T* __restrict__ q, int64_t q_stride, const T* __restrict__ kc,
-                                                                const T* __restrict__ vc, float* __restrict__ part,
+// KVT = uint8_t: e4m3 rows (KvRow).  Those instances also read positions below shared_prefix from slot 0, as the single-pass form
+// does; the 16-bit instances ignore shared_prefix as before (every slot holds the prefix rows there, so the results agree).
+template <typename T, int REP, int KS, typename KVT = T>
+__global__ __launch_bounds__(256) void attn_decode_split_kernel(const T* __restrict__ q, int64_t q_stride, const KVT* __restrict__ kc,
+                                                                const KVT* __restrict__ vc, float* __restrict__ part,
                                                                 const int32_t* __restrict__ ctx_len, int ctx_add, int nkv, int max_ctx,
-                                                                float scale, int32_t* __restrict__ cnt, T* __restrict__ out) {
+                                                                float scale, int32_t* __restrict__ cnt, T* __restrict__ out, int shared_prefix) {
   constexpr int D = 128;
+  constexpr bool KV8 = !std::is_same_v<KVT, T>;
+  static_assert(!KV8 || sizeof(T) == 2, "e4m3 K/V rows are built for the 16-bit types");
+  using Row = KvRow<T, KVT>;
   constexpr int VEC = Vec16<T>::VEC;
   constexpr int EPL = D / 16, CPLN = EPL / VEC;
   constexpr int PSTRIDE = split_record_floats(REP);  // floats per partial record
@@ -749,27 +806,29 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const T* __restr
     return;
   }
   const int nk = (n_keys - k0) < KS ? (n_keys - k0) : KS;
-  const T* kbase = kc + (((int64_t)b * nkv + kvh) * max_ctx + k0) * D;
-  const T* vbase = vc + (((int64_t)b * nkv + kvh) * max_ctx + k0) * D;
+  const KVT* kbase = kc + (((int64_t)b * nkv + kvh) * max_ctx + k0) * D;
+  const KVT* vbase = vc + (((int64_t)b * nkv + kvh) * max_ctx + k0) * D;
+  const KVT* kbase0 = kc + ((int64_t)kvh * max_ctx + k0) * D;   // slot 0 (KV8: positions below shared_prefix)
+  const KVT* vbase0 = vc + ((int64_t)kvh * max_ctx + k0) * D;
 
   // phase 1: scores; every K and V row of the split is requested up front (16-byte chunks, 256-byte rows coalesced)
-  u32x4_t kraw[NPS][CPLN];   // ext-vector type: HIP's uint4 struct copies to LDS went through scratch
+  typename Row::raw_t kraw[NPS][CPLN];   // ext-vector type: HIP's uint4 struct copies to LDS went through scratch
 #pragma unroll
   for (int ps = 0; ps < NPS; ++ps) {
     int key = ps * 16 + wave * 4 + grp;
     key = key < nk ? key : nk - 1;
 #pragma unroll
-    for (int c = 0; c < CPLN; ++c) kraw[ps][c] = SL_KV_LOAD(kbase + (int64_t)key * D + gl * EPL + c * VEC);
+    for (int c = 0; c < CPLN; ++c) kraw[ps][c] = Row::load(((KV8 && k0 + key < shared_prefix) ? kbase0 : kbase) + (int64_t)key * D + gl * EPL + c * VEC);
   }
   // V rows for phase 3 are requested now: their HBM latency hides behind the score / softmax phases
   const int kg = tid >> 4, dc = tid & 15;
-  u32x4_t vraw[NPS][CPLN];
+  typename Row::raw_t vraw[NPS][CPLN];
 #pragma unroll
   for (int ps = 0; ps < NPS; ++ps) {
     int key = kg + 16 * ps;
     key = key < nk ? key : nk - 1;
 #pragma unroll
-    for (int c = 0; c < CPLN; ++c) vraw[ps][c] = SL_KV_LOAD(vbase + (int64_t)key * D + dc * EPL + c * VEC);
+    for (int c = 0; c < CPLN; ++c) vraw[ps][c] = Row::load(((KV8 && k0 + key < shared_prefix) ? vbase0 : vbase) + (int64_t)key * D + dc * EPL + c * VEC);
   }
   if constexpr (MFMA_QK) {
     // S[head][key] = Q . K^T on the matrix core: A = the REP query heads of this kv head (rows REP..15 zero), B = 16 keys
@@ -782,7 +841,7 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const T* __restr
 #pragma unroll
     for (int ps = 0; ps < NPS; ++ps) {
       const int kl = ps * 16 + wave * 4 + grp;
-      *(u32x4_t*)(un + kl * 256 + ((gl ^ (kl & 15)) << 4)) = kraw[ps][0];
+      *(u32x4_t*)(un + kl * 256 + ((gl ^ (kl & 15)) << 4)) = Row::widen(kraw[ps][0]);
     }
     __syncthreads();
     constexpr int NF = KS / 64;
@@ -814,7 +873,10 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const T* __restr
       const int key = ps * 16 + wave * 4 + grp;
       float kf[EPL];
 #pragma unroll
-      for (int c = 0; c < CPLN; ++c) Vec16<T>::unpack(make_uint4(kraw[ps][c].x, kraw[ps][c].y, kraw[ps][c].z, kraw[ps][c].w), &kf[c * VEC]);
+      for (int c = 0; c < CPLN; ++c) {
+        const u32x4_t kr = Row::widen(kraw[ps][c]);
+        Vec16<T>::unpack(make_uint4(kr.x, kr.y, kr.z, kr.w), &kf[c * VEC]);
+      }
 #pragma unroll
       for (int h = 0; h < REP; ++h) {
         float d = 0.f;
@@ -851,7 +913,7 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const T* __restr
     for (int o = tid; o < (16 - REP) * (KS / 8); o += 256)   // zero the padding rows of P (heads REP..15)
       *(uint4*)(pt + (REP + o / (KS / 8)) * PROW + (o % (KS / 8)) * 16) = make_uint4(0, 0, 0, 0);
 #pragma unroll
-    for (int ps = 0; ps < NPS; ++ps) *(u32x4_t*)(un + voff(kg + 16 * ps, dc)) = vraw[ps][0];   // K tile is dead: scores are in sc
+    for (int ps = 0; ps < NPS; ++ps) *(u32x4_t*)(un + voff(kg + 16 * ps, dc)) = Row::widen(vraw[ps][0]);   // K tile is dead: scores are in sc
     __syncthreads();
     const int r = lane & 15, q4 = lane >> 4, qq = r >> 2, pp = r & 3;
     const uint32_t ub = (uint32_t)(uintptr_t)(lds_ptr3_t)un;
@@ -890,7 +952,10 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const T* __restr
       const int key = kg + 16 * ps;
       float vf[EPL];
 #pragma unroll
-      for (int c = 0; c < CPLN; ++c) Vec16<T>::unpack(make_uint4(vraw[ps][c].x, vraw[ps][c].y, vraw[ps][c].z, vraw[ps][c].w), &vf[c * VEC]);
+      for (int c = 0; c < CPLN; ++c) {
+        const u32x4_t vr = Row::widen(vraw[ps][c]);
+        Vec16<T>::unpack(make_uint4(vr.x, vr.y, vr.z, vr.w), &vf[c * VEC]);
+      }
 #pragma unroll
       for (int h = 0; h < REP; ++h) {
         const float p = sc[h][key];  // 0 for keys past nk
@@ -926,9 +991,10 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const T* __restr
 // small enough to sit on a CU BESIDE a 256 x 256 GEMM block of another stream (130 of the 160 KiB of LDS, half the register file):
 // the HBM-bound attention of one in-flight batch can then run under the matrix-core-bound encode / prefill of the other
 // (SL_ATTN_DECODE_KS=64; DESIGN §8.10 has what it measured).
-template <typename T, int REP, bool PREFETCH, int KS_ = 128>
-__global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restrict__ q, int64_t q_stride, const T* __restrict__ kc,
-                                                               const T* __restrict__ vc, T* __restrict__ out,
+// KVT = uint8_t: e4m3 rows (KvRow): 8-byte loads, the K / V registers hold half the dwords, the LDS images are unchanged.
+template <typename T, int REP, bool PREFETCH, int KS_ = 128, typename KVT = T>
+__global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restrict__ q, int64_t q_stride, const KVT* __restrict__ kc,
+                                                               const KVT* __restrict__ vc, T* __restrict__ out,
                                                                const int32_t* __restrict__ ctx_len, int ctx_add, int nh, int nkv, int max_ctx,
                                                                float scale, int shared_prefix) {
   static_assert(sizeof(T) == 2, "the single-pass form is built for the 16-bit types (bf16 / fp16)");
@@ -944,14 +1010,15 @@ __global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restri
   const int kg = tid >> 4, dc = tid & 15;
   const int r = lane & 15, q4 = lane >> 4, qq = r >> 2, pp = r & 3;
   const int n_keys = ctx_len[b] + ctx_add;
-  const T* kbase = kc + ((int64_t)b * nkv + kvh) * max_ctx * D;
-  const T* vbase = vc + ((int64_t)b * nkv + kvh) * max_ctx * D;
+  using Row = KvRow<T, KVT>;
+  const KVT* kbase = kc + ((int64_t)b * nkv + kvh) * max_ctx * D;
+  const KVT* vbase = vc + ((int64_t)b * nkv + kvh) * max_ctx * D;
   // positions below shared_prefix hold the same rows in every slot (the caller's promise: one prompt prefix for the whole batch);
   // every block reads them from slot 0, so they come out of L2 instead of HBM.  Measured (tools/time_decode_step.py 1024 with
   // SHARED_PREFIX=9, three A/B rounds on one box, profiles/r04_w_shared_prefix.txt): decode step 11.08 -> 10.82 ms; the same rows
   // through plain (not non-temporal) loads behind a per-load branch: 11.30 ms, slower than no sharing.
-  const T* kbase0 = kc + (int64_t)kvh * max_ctx * D;
-  const T* vbase0 = vc + (int64_t)kvh * max_ctx * D;
+  const KVT* kbase0 = kc + (int64_t)kvh * max_ctx * D;
+  const KVT* vbase0 = vc + (int64_t)kvh * max_ctx * D;
   auto voff = [](int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); };
 
   uint4 qf[4];
@@ -961,19 +1028,19 @@ __global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restri
   for (int o = tid; o < (16 - REP) * (KS / 8); o += 256)   // padding rows of P (heads REP..15) stay zero
     *(uint4*)(pt + (REP + o / (KS / 8)) * PROW + (o % (KS / 8)) * 16) = make_uint4(0, 0, 0, 0);
 
-  u32x4_t kraw[PREFETCH ? 2 : 1][NPS], vraw[PREFETCH ? 2 : 1][NPS];
+  typename Row::raw_t kraw[PREFETCH ? 2 : 1][NPS], vraw[PREFETCH ? 2 : 1][NPS];
   auto fetch_k = [&](int buf, int k0) {   // rows past the context are clamped (their scores are masked)
 #pragma unroll
     for (int ps = 0; ps < NPS; ++ps) {
       int key = k0 + ps * 16 + wave * 4 + grp; key = key < n_keys ? key : n_keys - 1;
-      kraw[buf][ps] = SL_KV_LOAD((key < shared_prefix ? kbase0 : kbase) + (int64_t)key * D + gl * 8);
+      kraw[buf][ps] = Row::load((key < shared_prefix ? kbase0 : kbase) + (int64_t)key * D + gl * 8);
     }
   };
   auto fetch_v = [&](int buf, int k0) {
 #pragma unroll
     for (int ps = 0; ps < NPS; ++ps) {
       int key = k0 + kg + 16 * ps; key = key < n_keys ? key : n_keys - 1;
-      vraw[buf][ps] = SL_KV_LOAD((key < shared_prefix ? vbase0 : vbase) + (int64_t)key * D + dc * 8);
+      vraw[buf][ps] = Row::load((key < shared_prefix ? vbase0 : vbase) + (int64_t)key * D + dc * 8);
     }
   };
   auto fetch = [&](int buf, int k0) { fetch_k(buf, k0); fetch_v(buf, k0); };
@@ -996,7 +1063,7 @@ __global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restri
 #pragma unroll
       for (int ps = 0; ps < NPS; ++ps) {
         const int kl = ps * 16 + wave * 4 + grp;
-        *(u32x4_t*)(un + kl * 256 + ((gl ^ (kl & 15)) << 4)) = kraw[u][ps];
+        *(u32x4_t*)(un + kl * 256 + ((gl ^ (kl & 15)) << 4)) = Row::widen(kraw[u][ps]);
       }
       if constexpr (!PREFETCH) fetch_v(0, k0);   // K registers are free again: V rows fly under the score / softmax phases
       __syncthreads();
@@ -1030,7 +1097,7 @@ __global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restri
       }
       // V tile over the (dead) K tile
 #pragma unroll
-      for (int ps = 0; ps < NPS; ++ps) *(u32x4_t*)(un + voff(kg + 16 * ps, dc)) = vraw[u][ps];
+      for (int ps = 0; ps < NPS; ++ps) *(u32x4_t*)(un + voff(kg + 16 * ps, dc)) = Row::widen(vraw[u][ps]);
       __syncthreads();
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -1099,10 +1166,11 @@ int sl_attn_decode_split_zero_counters(void* workspace, int B, int n_heads, int 
   return 0;
 }
 
-template <typename T, int REP>
+template <typename T, int REP, typename KVT = T>
 static int launch_attn_decode_split(const void* q, int64_t q_stride, const void* kc, const void* vc, void* out, float* part,
                                     const int32_t* ctx_len, int ctx_add, int B, int nh, int nkv, int max_ctx, float scale, hipStream_t st,
                                     int32_t* cnt, int shared_prefix) {
+  constexpr bool KV8 = !std::is_same_v<KVT, T>;
   if constexpr (sizeof(T) == 2) {
     const int64_t full_min = sl_env().attn_full_min;   // tuning switch: (sequence, kv head) pairs from which the single-pass form runs; measured faster than split + merge from B = 4 up (9.1 vs 11.4 us), 97 vs 127 us at B = 512
     // ... except long caches at batches that leave the chip under-filled: a block of the single-pass form walks its whole context in
@@ -1113,7 +1181,10 @@ static int launch_attn_decode_split(const void* q, int64_t q_stride, const void*
     const int64_t Bf = sl_family_rows(B);              // the form follows the pinned family's rows (common.h sl_family_rows)
     const bool long_thin = max_ctx >= 1024 && Bf * nkv < 768;
     if (Bf * nkv >= full_min && !long_thin && !sl_env().attn_force_split) {
-      if (sl_env().attn_decode_ks == 65)        // 64-key chunks with the NEXT chunk's K / V rows held in a second register set (twice the bytes in flight per block)
+      if constexpr (KV8)     // e4m3 rows: the 128-key form only (SL_ATTN_DECODE_KS is a 16-bit experiment)
+        hipLaunchKernelGGL((attn_decode_full_kernel<T, REP, false, 128, KVT>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride, (const KVT*)kc,
+                           (const KVT*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
+      else if (sl_env().attn_decode_ks == 65)        // 64-key chunks with the NEXT chunk's K / V rows held in a second register set (twice the bytes in flight per block)
         hipLaunchKernelGGL((attn_decode_full_kernel<T, REP, true, 64>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride, (const T*)kc,
                            (const T*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
       else if (sl_env().attn_decode_ks == 64)
@@ -1129,12 +1200,12 @@ static int launch_attn_decode_split(const void* q, int64_t q_stride, const void*
   int nsplit;
   if ((int64_t)sl_family_rows(B) * nkv >= 512) {
     nsplit = (max_ctx + 127) / 128;
-    hipLaunchKernelGGL((attn_decode_split_kernel<T, REP, 128>), dim3(nkv, B, nsplit), dim3(256), 0, st, (const T*)q, q_stride, (const T*)kc,
-                       (const T*)vc, part, ctx_len, ctx_add, nkv, max_ctx, scale, cnt, (T*)out);
+    hipLaunchKernelGGL((attn_decode_split_kernel<T, REP, 128, KVT>), dim3(nkv, B, nsplit), dim3(256), 0, st, (const T*)q, q_stride, (const KVT*)kc,
+                       (const KVT*)vc, part, ctx_len, ctx_add, nkv, max_ctx, scale, cnt, (T*)out, shared_prefix);
   } else {
     nsplit = (max_ctx + DSPLIT - 1) / DSPLIT;
-    hipLaunchKernelGGL((attn_decode_split_kernel<T, REP, DSPLIT>), dim3(nkv, B, nsplit), dim3(256), 0, st, (const T*)q, q_stride, (const T*)kc,
-                       (const T*)vc, part, ctx_len, ctx_add, nkv, max_ctx, scale, cnt, (T*)out);
+    hipLaunchKernelGGL((attn_decode_split_kernel<T, REP, DSPLIT, KVT>), dim3(nkv, B, nsplit), dim3(256), 0, st, (const T*)q, q_stride, (const KVT*)kc,
+                       (const KVT*)vc, part, ctx_len, ctx_add, nkv, max_ctx, scale, cnt, (T*)out, shared_prefix);
   }
   SL_CHECK_LAUNCH("attn_decode_split");
   if (cnt) return 0;   // the last block of every (sequence, kv head) merged its records
@@ -1147,8 +1218,9 @@ static int launch_attn_decode_split(const void* q, int64_t q_stride, const void*
 // (sl_attn_decode_split_zero_counters) on this stream; 2 = the same, zeroing them here first (one memset per call)
 int sl_attn_decode_split_impl(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, void* workspace,
                               const int32_t* ctx_len, int ctx_add, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx,
-                              float scale, int32_t dtype, hipStream_t st, int counters, int shared_prefix) {
+                              float scale, int32_t dtype, hipStream_t st, int counters, int shared_prefix, int kv_format) {
   SL_CHECK_ARG(q && k_cache && v_cache && out && workspace && ctx_len && B > 0, "sl_attn_decode_split: bad arguments");
+  SL_TRY(sl_kv_format_check("sl_attn_decode_split", kv_format, dtype, D));
   SL_CHECK_ARG(D == 128, "sl_attn_decode_split: head_dim %d not built (128)", D);
   SL_CHECK_ARG(n_kv > 0 && n_heads % n_kv == 0, "sl_attn_decode_split: n_heads %% n_kv != 0");
   SL_CHECK_ARG(shared_prefix >= 0 && shared_prefix <= max_ctx, "sl_attn_decode_split: shared_prefix %d outside [0, max_ctx=%d]", shared_prefix, max_ctx);
@@ -1164,6 +1236,18 @@ int sl_attn_decode_split_impl(const void* q, int64_t q_stride, const void* k_cac
   if (mode == 0 || (mode < 0 && (int64_t)sl_family_rows(B) * n_kv > 32)) counters = 0;
   int32_t* cnt = counters ? (int32_t*)((unsigned char*)workspace + attn_split_records_bytes(B, n_heads, n_kv, max_ctx)) : nullptr;
   if (counters == 2) SL_TRY(sl_attn_decode_split_zero_counters(workspace, B, n_heads, n_kv, max_ctx, st));
+#define SL_ATTN8_CASE(T_, R_) \
+  case R_: return launch_attn_decode_split<T_, R_, uint8_t>(q, q_stride, k_cache, v_cache, out, part, ctx_len, ctx_add, B, n_heads, n_kv, max_ctx, scale, st, cnt, shared_prefix)
+  if (kv_format == SL_KV_FP8_E4M3) {
+    if (dtype == SL_BF16) {
+      switch (rep) { SL_ATTN8_CASE(bf16_t, 1); SL_ATTN8_CASE(bf16_t, 2); SL_ATTN8_CASE(bf16_t, 3); SL_ATTN8_CASE(bf16_t, 4); default: break; }
+    } else {
+      switch (rep) { SL_ATTN8_CASE(f16_t, 1); SL_ATTN8_CASE(f16_t, 2); SL_ATTN8_CASE(f16_t, 3); SL_ATTN8_CASE(f16_t, 4); default: break; }
+    }
+    sl_set_error("sl_attn_decode_split: n_heads/n_kv=%d not built (1..4)", rep);
+    return SL_ERR_UNSUPPORTED;
+  }
+#undef SL_ATTN8_CASE
   SL_DISPATCH_DTYPE_INF(dtype, T, {
     switch (rep) {
       case 1: return launch_attn_decode_split<T, 1>(q, q_stride, k_cache, v_cache, out, part, ctx_len, ctx_add, B, n_heads, n_kv, max_ctx, scale, st, cnt, shared_prefix);
@@ -1183,5 +1267,12 @@ extern "C" int sl_attn_decode_split(const void* q, int64_t q_stride, const void*
                                     const int32_t* ctx_len, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx, float scale,
                                     int32_t dtype, sl_stream stream) {
   return sl_attn_decode_split_impl(q, q_stride, k_cache, v_cache, out, workspace, ctx_len, 0, B, n_heads, n_kv, D, max_ctx, scale, dtype,
-                                   (hipStream_t)stream, 2, 0);
+                                   (hipStream_t)stream, 2, 0, SL_KV_MODEL_DTYPE);
+}
+
+extern "C" int sl_attn_decode_split_ex(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, void* workspace,
+                                       const int32_t* ctx_len, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx, float scale,
+                                       int32_t dtype, int32_t kv_format, int32_t shared_prefix, sl_stream stream) {
+  return sl_attn_decode_split_impl(q, q_stride, k_cache, v_cache, out, workspace, ctx_len, 0, B, n_heads, n_kv, D, max_ctx, scale, dtype,
+                                   (hipStream_t)stream, 2, shared_prefix, kv_format);
 }

@@ -23,7 +23,7 @@ int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float tempe
 int sl_attn_decode_split_zero_counters(void* workspace, int B, int n_heads, int n_kv, int max_ctx, hipStream_t st);
 int sl_attn_decode_split_impl(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, void* workspace,
                               const int32_t* ctx_len, int ctx_add, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx,
-                              float scale, int32_t dtype, hipStream_t st, int counters, int shared_prefix);
+                              float scale, int32_t dtype, hipStream_t st, int counters, int shared_prefix, int kv_format);
 size_t sl_attn_decode_split_ws(int B, int n_heads, int n_kv, int max_ctx);
 int sl_rmsnorm_rstd_impl(const void* x, void* y, const void* w, float* rstd_out, int64_t rows, int32_t cols, float eps, int32_t dtype, hipStream_t st);
 int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st);
@@ -472,6 +472,7 @@ extern "C" size_t sl_llama_workspace_bytes(const sl_llama_model* m, int64_t n_to
 
 static int llama_check(const sl_llama_model* m, const sl_kv_cache* kv) {
   SL_CHECK_ARG(m && kv && m->layers && m->embed && m->lm_head && m->final_norm && m->rope_cos && m->rope_sin, "llama: null model field");
+  if (kv->reserved != SL_KV_MODEL_DTYPE) SL_TRY(sl_kv_format_check("llama (sl_kv_cache.reserved)", kv->reserved, m->dtype, m->head_dim));
   SL_CHECK_ARG(m->head_dim == 128, "llama: head_dim %d not built (128)", m->head_dim);
   SL_CHECK_ARG(kv->k_cache && kv->v_cache && kv->slots > 0 && kv->max_ctx > 0, "llama: bad kv cache");
   SL_CHECK_ARG(kv->shared_prefix >= 0 && kv->shared_prefix <= kv->max_ctx, "llama: kv cache shared_prefix %d outside [0, max_ctx=%d]", kv->shared_prefix, kv->max_ctx);
@@ -479,8 +480,16 @@ static int llama_check(const sl_llama_model* m, const sl_kv_cache* kv) {
   return 0;
 }
 
+// K / V rows are head_dim elements of the cache's own element size: 1 byte in the e4m3 format, the model dtype's otherwise
+static inline size_t kv_elem_bytes(const sl_llama_model* m, const sl_kv_cache* kv) { return sl_kv_elem_size(kv->reserved, m->dtype); }
 static inline size_t kv_layer_bytes(const sl_llama_model* m, const sl_kv_cache* kv) {
-  return (size_t)kv->slots * m->n_kv_heads * kv->max_ctx * m->head_dim * sl_dtype_size(m->dtype);
+  return (size_t)kv->slots * m->n_kv_heads * kv->max_ctx * m->head_dim * kv_elem_bytes(m, kv);
+}
+
+extern "C" size_t sl_kv_cache_bytes(const sl_llama_model* m, int32_t slots, int32_t max_ctx, int32_t kv_format) {
+  if (!m || slots <= 0 || max_ctx <= 0 || m->n_layers <= 0) { sl_set_error("sl_kv_cache_bytes: bad arguments"); return 0; }
+  if (sl_kv_format_check("sl_kv_cache_bytes", kv_format, m->dtype, m->head_dim) != 0) return 0;
+  return (size_t)m->n_layers * slots * m->n_kv_heads * max_ctx * m->head_dim * sl_kv_elem_size(kv_format, m->dtype);
 }
 
 // ---- shared prompt prefix in prefill (sl_kv_cache.shared_prefix = P): the P rows every sequence opens with are computed once ----
@@ -606,7 +615,7 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     memset(&fx, 0, sizeof(fx));
     fx.fuse_rms = m->dec_fused_norm; fx.rms_eps = m->rms_eps;
     fx.rope_cos = m->rope_cos; fx.rope_sin = m->rope_sin; fx.tok_pos = ctx_len_dev; fx.tok_seq = w.tok_seq;
-    fx.k_cache = kc; fx.v_cache = vc; fx.n_heads = nh; fx.n_kv_heads = nkv; fx.max_ctx = kv->max_ctx;
+    fx.k_cache = kc; fx.v_cache = vc; fx.n_heads = nh; fx.n_kv_heads = nkv; fx.max_ctx = kv->max_ctx; fx.reserved = kv->reserved;
     // small-batch graphs: the prefetch branch runs two matrices ahead of the chain (DecodePrefetch): released where a consumer is launched
     DecodePrefetch* pf = g_prefetch;
     const size_t esz = sl_dtype_size(dt);
@@ -620,7 +629,7 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     // that the gain-folded products stay on the 256 x 128 streaming blocks instead of taking the statistics per block themselves
     if (rstd_pass) { SL_TRY(sl_rmsnorm_rstd_impl(x, nullptr, nullptr, w.rstd_b, n, H, m->rms_eps, dt, st)); rstd_qkv = w.rstd_b; }
     SL_TRY(dec_gemm(m, w, a_in, H, L.wqkv_dec, w.qkv, (int64_t)nh * D, nullptr, (int)n, qkv_w, H, SL_ACT_ROPE_KV, 0, &fx, st, rstd_qkv));
-    SL_TRY(sl_attn_decode_split_impl(w.qkv, (int64_t)nh * D, kc, vc, w.att, w.part, ctx_len_dev, 1, (int)n, nh, nkv, D, kv->max_ctx, scale, dt, st, 1, kv->shared_prefix));
+    SL_TRY(sl_attn_decode_split_impl(w.qkv, (int64_t)nh * D, kc, vc, w.att, w.part, ctx_len_dev, 1, (int)n, nh, nkv, D, kv->max_ctx, scale, dt, st, 1, kv->shared_prefix, kv->reserved));
     // Above ~900 rows gate/up runs on the row-major 256 x 256 tiles (the prefill kernel): at 1 024 rows it is 4 x 64 = 256 tiles, one per
     // CU, 78-81 us against 99 us on the 256 x 128 streaming block (tools/time_decode_tiled.py; in the graph: profiles/r04_l_*).  Its input
     // must then be normalised: the o projection's reduce pass, which already forms each row's RMSNorm scale, writes the normalised rows
@@ -661,14 +670,14 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
   }
   SL_TRY(sl_rmsnorm(x, w.h, L.norm1, n, H, m->rms_eps, dt, (sl_stream)st));
   SL_TRY(gemm(dt, w.h, H, L.wqkv, H, w.qkv, qkv_w, nullptr, nullptr, 0, (int)n, qkv_w, H, SL_ACT_NONE, 0, st));
-  SL_TRY(sl_rope_kv_append(w.qkv, kc, vc, w.tok_seq, decode ? ctx_len_dev : w.tok_pos, m->rope_cos, m->rope_sin, n, nh, nkv, D, kv->max_ctx,
-                           dt, (sl_stream)st));
+  SL_TRY(sl_rope_kv_append_ex(w.qkv, kc, vc, w.tok_seq, decode ? ctx_len_dev : w.tok_pos, m->rope_cos, m->rope_sin, n, nh, nkv, D, kv->max_ctx,
+                              dt, kv->reserved, (sl_stream)st));
   if (decode) {
-    SL_TRY(sl_attn_decode_split_impl(w.qkv, qkv_w, kc, vc, w.att, w.part, ctx_len_dev, 1, (int)n, nh, nkv, D, kv->max_ctx, scale, dt, st, 1, kv->shared_prefix));
+    SL_TRY(sl_attn_decode_split_impl(w.qkv, qkv_w, kc, vc, w.att, w.part, ctx_len_dev, 1, (int)n, nh, nkv, D, kv->max_ctx, scale, dt, st, 1, kv->shared_prefix, kv->reserved));
   } else {
-    if (prefix_bcast > 0 && bcast_slots > 1) {
-      const int row_vec = (int)(D * sl_dtype_size(dt) / 16);
-      SL_CHECK_ARG(row_vec <= 32 && (D * sl_dtype_size(dt)) % 16 == 0, "llama: shared prefix broadcast needs K / V rows of <= 512 bytes");
+    if (prefix_bcast > 0 && bcast_slots > 1) {     // (not reached with e4m3 rows: sl_llama_prefill switches the dedupe off there; the row size is the cache's all the same)
+      const int row_vec = (int)(D * kv_elem_bytes(m, kv) / 16);
+      SL_CHECK_ARG(row_vec <= 32 && (D * kv_elem_bytes(m, kv)) % 16 == 0, "llama: shared prefix broadcast needs K / V rows of <= 512 bytes");
       hipLaunchKernelGGL(kv_prefix_broadcast_kernel, dim3(prefix_bcast, nkv, bcast_slots - 1), dim3(64), 0, st, (uint4*)kc, (uint4*)vc, nkv, kv->max_ctx, row_vec);
       SL_CHECK_LAUNCH("kv_prefix_broadcast");
     }
@@ -679,6 +688,14 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     a.v = vc; a.v_row_stride = D; a.v_head_stride = (int64_t)kv->max_ctx * D;
     a.out = w.att; a.o_row_stride = (int64_t)nh * D; a.o_head_stride = D;
     a.cu_q = w.cu; a.cu_k = w.cuk; a.klen = w.klen;
+    if (kv->reserved == SL_KV_FP8_E4M3) {
+      // e4m3 cache: the prompt attends the unquantised keys — the rotated K rows sl_rope_kv_append_ex left in qkv and the V rows beside
+      // them (same values, same key order as the 16-bit cache gives: the prefill logits are those of the 16-bit mode, bit for bit)
+      const size_t esz = sl_dtype_size(dt);
+      a.k = bptr(w.qkv) + (size_t)nh * D * esz; a.k_row_stride = qkv_w; a.k_head_stride = D;
+      a.v = bptr(w.qkv) + (size_t)(nh + nkv) * D * esz; a.v_row_stride = qkv_w; a.v_head_stride = D;
+      a.cu_k = w.cu;
+    }
     a.nseq = nseq; a.max_qlen = max_qlen; a.n_heads = nh; a.n_kv_heads = nkv; a.head_dim = D; a.causal = 1; a.dtype = dt; a.scale = scale;
     SL_TRY(sl_attn_fwd(&a, (sl_stream)st));
   }
@@ -722,7 +739,9 @@ extern "C" int sl_llama_prefill(const sl_llama_model* m, const sl_kv_cache* kv, 
   // queries attend [prefix + tail] keys of their own slot (causal with klen > qlen).  Every row-wise product, RoPE at the row's own
   // position and attention over the same keys in the same order give the bits the unshared pass gives (asserted on the cache and the
   // logits).  Not with hidden_taps (they are per row of the caller's layout) or when a sequence is nothing but the prefix.
-  int P = (kv->shared_prefix > 0 && nseq > 1 && !hidden_taps && sl_env().prefill_share_prefix) ? kv->shared_prefix : 0;
+  // Not with e4m3 rows either: that prefill reads K / V from its own qkv rows, not from the cache, so there is nothing to broadcast
+  // (decode still reads the positions below shared_prefix from slot 0).
+  int P = (kv->shared_prefix > 0 && nseq > 1 && !hidden_taps && sl_env().prefill_share_prefix && kv->reserved != SL_KV_FP8_E4M3) ? kv->shared_prefix : 0;
   for (int s = 0; s < nseq; ++s) {
     const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
     SL_CHECK_ARG(len > 0 && len <= kv->max_ctx, "sl_llama_prefill: sequence %d length %d outside (0, max_ctx=%d]", s, len, kv->max_ctx);
@@ -1070,7 +1089,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
     key.model = m; key.layers = m->layers; key.w0 = m->n_layers > 0 ? m->layers[0].wqkv_dec : nullptr; key.lm = m->lm_head_dec ? m->lm_head_dec : m->lm_head;
     key.embed = m->embed; key.kc = kv->k_cache; key.vc = kv->v_cache; key.ws = workspace; key.ws_bytes = workspace_bytes;
     key.B = B; key.B0 = B0; key.max_new = max_new_tokens; key.use_eos = use_eos; key.n_eos = n_eos; key.pad = pad_id; key.max_ctx = kv->max_ctx;
-    key.slots = kv->slots; key.shared_prefix = kv->shared_prefix; key.dtype = m->dtype; key.n_layers = m->n_layers; key.vocab = m->vocab; key.fused = m->dec_fused_norm | (sl_env().decode_tiled << 8) | ((sl_env().attn_decode_ks & 127) << 9) | ((pin_rows ? 1 : 0) << 16) | ((sl_env().decode_prefetch ? 1 : 0) << 17);   // + the switch that shapes the captured launches
+    key.slots = kv->slots; key.shared_prefix = kv->shared_prefix; key.dtype = m->dtype; key.n_layers = m->n_layers; key.vocab = m->vocab; key.fused = m->dec_fused_norm | (sl_env().decode_tiled << 8) | ((sl_env().attn_decode_ks & 127) << 9) | ((pin_rows ? 1 : 0) << 16) | ((sl_env().decode_prefetch ? 1 : 0) << 17) | ((kv->reserved & 3) << 18);   // + the switch that shapes the captured launches
     key.limits = row_limit_arg ? 1 : 0;
     key.content = model_content_hash(m);
     SL_HIP(hipGetDevice(&key.device));
@@ -1180,7 +1199,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
         ++hole;
       }
       if (!moves.empty()) {
-        const int row_vec = (int)(m->head_dim * sl_dtype_size(m->dtype) / 16);
+        const int row_vec = (int)(m->head_dim * kv_elem_bytes(m, kv) / 16);
         KvMove* mv_dev = (KvMove*)logits;         // the logits buffer is idle between steps (>= B0 * vocab floats)
         SL_CHECK_ARG(moves.size() * sizeof(KvMove) <= (size_t)B0 * m->vocab * sizeof(float), "sl_generate: move list does not fit");
         SL_HIP(hipMemcpyAsync(mv_dev, moves.data(), moves.size() * sizeof(KvMove), hipMemcpyHostToDevice, st));

@@ -237,6 +237,13 @@ def rope_kv_append(qkv, k_cache, v_cache, tok_seq, tok_pos, cos, sin, n_heads, n
             "sl_rope_kv_append")
 
 
+def rope_kv_append_ex(qkv, k_cache, v_cache, tok_seq, tok_pos, cos, sin, n_heads, n_kv, D, max_ctx, kv_format: int = L.KV_MODEL_DTYPE) -> None:
+    """sl_rope_kv_append with the cache format given: KV_FP8_E4M3 writes e4m3 bytes (uint8 caches) and the rotated K rows back into qkv."""
+    L.check(L.lib().sl_rope_kv_append_ex(L.ptr(qkv), L.ptr(k_cache), L.ptr(v_cache), L.ptr(tok_seq), L.ptr(tok_pos), L.ptr(cos), L.ptr(sin),
+                                         qkv.shape[0], n_heads, n_kv, D, max_ctx, L.dtype_code(qkv.dtype), int(kv_format), L.stream_ptr()),
+            "sl_rope_kv_append_ex")
+
+
 def attn_decode(q, q_stride, k_cache, v_cache, ctx_len, n_heads, n_kv, D, max_ctx, scale) -> torch.Tensor:
     B = ctx_len.shape[0]
     out = torch.empty((B, n_heads * D), device=q.device, dtype=q.dtype)
@@ -320,6 +327,7 @@ def gemm_decode(A: torch.Tensor, Wp: torch.Tensor, N: int, *, residual=None, act
         f.rope_cos, f.rope_sin, f.tok_pos, f.tok_seq = L.ptr(rope["cos"]), L.ptr(rope["sin"]), L.ptr(rope["pos"]), L.ptr(rope["seq"])
         f.k_cache, f.v_cache = L.ptr(rope["k_cache"]), L.ptr(rope["v_cache"])
         f.n_heads, f.n_kv_heads, f.max_ctx = rope["n_heads"], rope["n_kv"], rope["max_ctx"]
+        f.reserved = int(rope.get("kv_format", L.KV_MODEL_DTYPE))      # the caches' K/V format (sl_gemm_fused.reserved)
     if split_k:
         need = int(L.lib().sl_gemm_split_workspace_bytes(M, N, K, a.dtype))
         if need > 0:
@@ -349,6 +357,28 @@ def attn_decode_split(q, q_stride, k_cache, v_cache, ctx_len, n_heads, n_kv, D, 
     L.check(L.lib().sl_attn_decode_split(L.ptr(q), q_stride, L.ptr(k_cache), L.ptr(v_cache), L.ptr(out), L.ptr(ws), L.ptr(ctx_len), B,
                                          n_heads, n_kv, D, max_ctx, scale, L.dtype_code(q.dtype), L.stream_ptr()), "sl_attn_decode_split")
     return out
+
+
+def attn_decode_split_ex(q, q_stride, k_cache, v_cache, ctx_len, n_heads, n_kv, D, max_ctx, scale, kv_format: int = L.KV_MODEL_DTYPE,
+                         shared_prefix: int = 0, out=None, ws=None) -> torch.Tensor:
+    """attn_decode_split on a cache of either format (KV_FP8_E4M3: uint8 caches of e4m3 rows); positions below shared_prefix come from slot 0."""
+    B = ctx_len.shape[0]
+    if out is None:
+        out = torch.empty((B, n_heads * D), device=q.device, dtype=q.dtype)
+    if ws is None:
+        ws = torch.empty(int(L.lib().sl_attn_decode_workspace_bytes(B, n_heads, n_kv, max_ctx)), dtype=torch.uint8, device=q.device)
+    L.check(L.lib().sl_attn_decode_split_ex(L.ptr(q), q_stride, L.ptr(k_cache), L.ptr(v_cache), L.ptr(out), L.ptr(ws), L.ptr(ctx_len), B,
+                                            n_heads, n_kv, D, max_ctx, scale, L.dtype_code(q.dtype), int(kv_format), int(shared_prefix),
+                                            L.stream_ptr()), "sl_attn_decode_split_ex")
+    return out
+
+
+def kv_cache_bytes(model_struct, slots: int, max_ctx: int, kv_format: int = L.KV_MODEL_DTYPE) -> int:
+    """Bytes of ONE of the two caches (sl_kv_cache_bytes); raises where the library refuses the combination."""
+    n = int(L.lib().sl_kv_cache_bytes(C.byref(model_struct), int(slots), int(max_ctx), int(kv_format)))
+    if n == 0:
+        L.check(-1, "sl_kv_cache_bytes")
+    return n
 
 
 # ---------------------------------------------------------------------------------------------
