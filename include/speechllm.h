@@ -49,6 +49,7 @@ enum sl_status {
 };
 enum sl_act { SL_ACT_NONE = 0, SL_ACT_GELU = 1, SL_ACT_SILU_MUL = 2, SL_ACT_ROPE_KV = 3 };
 enum sl_w_layout { SL_W_ROWMAJOR = 0, SL_W_PACKED = 1 };
+#define SL_W_PACKED_E4M3 2                       /* sl_gemm_args.w_layout: an e4m3 weight image (sl_pack_weight_e4m3) */
 
 const char* sl_last_error(void);       /* thread-local, never NULL */
 #define SL_ABI_VERSION 7
@@ -91,6 +92,27 @@ int sl_gemm(const sl_gemm_args* a, sl_stream stream);
  *   (+25..45 % HBM throughput over 16 x 64-byte row segments, tools/tune_skinny.hip).  K %% KSTEP == 0.
  *   dst holds ceil(N/16)*16*K elements.  Pass it to sl_gemm with w_layout = SL_W_PACKED. */
 int sl_pack_weight(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype, sl_stream stream);
+
+/* Weight-only fp8 for the decode step of small batches: the "e4m3 weight image" of a bf16 / fp16 weight W (N, K), K % 64 == 0,
+ * Np = ceil(N/16)*16.  One fp32 scale per output row, s[n] = max_k |W[n][k]| / 448 (a correctly rounded division; 1 for an all-zero
+ * row and for the padding rows n >= N), and one OCP e4m3fn byte per element, b[n][k] = q8(float(W[n][k]) / s[n]) with the K/V
+ * cache's quantiser (round to nearest even, saturating at +-448: no byte is 0x7F / 0xFF); padding rows are zero bytes.  Bytes are
+ * fragment-major over PAIRS of 32-wide MFMA k-steps, so a lane load is still 16 bytes and a wave load 1 KiB contiguous:
+ *   img[f][j][lane][0..7]  = b[16 f + (lane & 15)][64 j + 8 (lane >> 4) + e]
+ *   img[f][j][lane][8..15] = b[16 f + (lane & 15)][64 j + 32 + 8 (lane >> 4) + e],      f < Np/16, j < K/64
+ * and the Np scales follow the bytes in the same buffer, at byte offset Np*K: one pointer names a whole weight.
+ *   sl_w8_image_bytes       Np*K + 4*Np; 0 on a bad argument (N <= 0, K <= 0, K % 64 != 0)
+ *   sl_pack_weight_e4m3     src (N, K) row stride ld_src on the device -> dst (16-byte aligned, sl_w8_image_bytes) on the device
+ *   sl_pack_weight_e4m3_host the same routine on host memory (no GPU needed)
+ *   sl_w8_max_rows          largest row count the e4m3 skinny kernels take (the packed skinny range: SL_STREAM_MIN_M, 26 by default)
+ * SL_F32 is SL_ERR_UNSUPPORTED, K % 64 != 0 is SL_ERR_ARG.  sl_gemm / sl_gemm_fused_decode take the image with
+ * w_layout = SL_W_PACKED_E4M3 for up to sl_w8_max_rows() rows (more: SL_ERR_UNSUPPORTED, nothing is launched): activations, the
+ * accumulation and the output stay as they are; the fp32 sum of output row n is multiplied by s[n] before bias, the fuse_rms row
+ * factor and the pair epilogues.  fuse_rms may take rstd_in here.  GELU, batches, transposes and groups are not built. */
+size_t sl_w8_image_bytes(int32_t N, int32_t K);
+int sl_pack_weight_e4m3(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype, sl_stream stream);
+int sl_pack_weight_e4m3_host(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype);
+int32_t sl_w8_max_rows(void);
 
 /* Decode-only fusions on top of sl_gemm (packed weights; M <= 16 rows run the skinny kernel, more rows the
  * LDS-staged streaming kernel of gemm_stream.hip):
@@ -612,8 +634,15 @@ typedef struct {
   const float *rope_cos, *rope_sin;      /* (rope_len, head_dim/2) */
   const sl_llama_layer* layers;          /* host array */
   const void* lm_head_dec;               /* packed (gain-folded if dec_fused_norm) or NULL */
+  /* reserved: the format of the five *_dec weights (wqkv_dec / wo_dec / wgu_dec / wdown_dec of every layer, lm_head_dec).
+   * SL_WDEC_E4M3: they are e4m3 weight images (sl_pack_weight_e4m3) of the same rows, in the same order and with the same gain fold,
+   * as the 16-bit decode copies; dec_fused_norm must be 1.  The decode step then runs the skinny structure on
+   * w_layout = SL_W_PACKED_E4M3 with the unfused lm_head + sl_greedy_select, for up to sl_w8_max_rows() rows: more rows, SL_F32 or a
+   * reduction length that is no multiple of 64 are SL_ERR_UNSUPPORTED before any launch.  Prefill ignores the field. */
   int32_t dec_fused_norm, reserved;
 } sl_llama_model;
+#define SL_WDEC_MODEL_DTYPE 0
+#define SL_WDEC_E4M3        1
 
 typedef struct {
   void* k_cache; void* v_cache;  /* (n_layers, slots, n_kv, max_ctx, D) each: elements of the model dtype, or bytes (reserved = SL_KV_FP8_E4M3) */

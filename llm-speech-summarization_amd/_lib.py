@@ -20,7 +20,8 @@ SL_F32, SL_BF16, SL_F16 = 0, 1, 2
 KV_MODEL_DTYPE, KV_FP8_E4M3 = 0, 1      # speechllm.h SL_KV_*: the K/V cache format (sl_kv_cache.reserved, sl_gemm_fused.reserved)
 ACT_NONE, ACT_GELU, ACT_SILU_MUL, ACT_ROPE_KV = 0, 1, 2, 3
 POST_NONE, POST_DROPOUT, POST_GELU_BWD, POST_SILU_MUL_BWD = 0, 1, 2, 3      # sl_gemm_ex_args.post_op
-W_ROWMAJOR, W_PACKED = 0, 1
+W_ROWMAJOR, W_PACKED, W_PACKED_E4M3 = 0, 1, 2     # W_PACKED_E4M3: an e4m3 weight image (sl_pack_weight_e4m3)
+WDEC_MODEL_DTYPE, WDEC_E4M3 = 0, 1          # speechllm.h SL_WDEC_*: the format of a model's decode weights (sl_llama_model.reserved)
 COMM_ID_BYTES = 128          # SL_COMM_ID_BYTES = sizeof(ncclUniqueId)
 MAX_DECODE_BATCH = 2048      # SL_MAX_DECODE_BATCH: sequences per generate call / rows per decode step
 
@@ -187,6 +188,10 @@ _PROTOS = {
     "sl_comm_rank": (c_i32, [c_vp]),
     "sl_comm_world": (c_i32, [c_vp]),
     "sl_pack_weight": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "sl_w8_image_bytes": (c_sz, [c_i32, c_i32]),
+    "sl_pack_weight_e4m3": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "sl_pack_weight_e4m3_host": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32]),
+    "sl_w8_max_rows": (c_i32, []),
     "sl_gemm_fused_decode": (c_i32, [C.POINTER(GemmArgs), C.POINTER(GemmFused), c_vp]),
     "sl_gemm_split_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "sl_gemm_split_count": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
@@ -327,6 +332,19 @@ def kv_format_code(kv_cache_dtype) -> int:
     elif kv_cache_dtype == torch.float8_e4m3fn:
         return KV_FP8_E4M3
     raise SpeechLLMError(f"unsupported kv_cache_dtype {kv_cache_dtype!r}: None (the model dtype), 'fp8' or torch.float8_e4m3fn")
+
+
+def weight_format_code(weight_dtype) -> int:
+    """`weight_dtype` of the Python surface -> SL_WDEC_*: None (decode weights in the model dtype), "fp8" or torch.float8_e4m3fn (e4m3
+    weight images with one fp32 scale per output row, for decode steps of up to sl_w8_max_rows() rows)."""
+    if weight_dtype is None:
+        return WDEC_MODEL_DTYPE
+    if isinstance(weight_dtype, str):
+        if weight_dtype == "fp8":
+            return WDEC_E4M3
+    elif weight_dtype == torch.float8_e4m3fn:
+        return WDEC_E4M3
+    raise SpeechLLMError(f"unsupported weight_dtype {weight_dtype!r}: None (the model dtype), 'fp8' or torch.float8_e4m3fn")
 
 
 def is16(dt: torch.dtype) -> bool:

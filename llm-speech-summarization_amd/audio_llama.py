@@ -44,7 +44,7 @@ class _EmbedTokens:
 
 class AudioLlamaForCausalLM:
     def __init__(self, arch: LlamaArch, state_dict: Dict[str, torch.Tensor], torch_dtype: torch.dtype = torch.bfloat16,
-                 device=None, max_ctx: int = 2048, max_batch: int = 16, pack_decode: bool = True, kv_cache_dtype=None):
+                 device=None, max_ctx: int = 2048, max_batch: int = 16, pack_decode: bool = True, kv_cache_dtype=None, weight_dtype=None):
         # float16 computes in fp16 (the reference's torch_dtype=float16, ref:inference.py:47-51); bfloat16 in bf16; float32 is the
         # exact parity mode.  Logits are fp32 in every mode.
         L.dtype_code(torch_dtype)    # raises for anything else
@@ -55,6 +55,12 @@ class AudioLlamaForCausalLM:
             raise L.SpeechLLMError("kv_cache_dtype='fp8' needs a bfloat16 or float16 model: float32 is the parity mode and keeps its K/V cache in float32")
         self.arch = arch
         self.dtype = torch_dtype
+        self.pack_decode = pack_decode
+        # weight_dtype: None = decode weights in the model dtype; "fp8" / torch.float8_e4m3fn = decode steps of up to sl_w8_max_rows() rows read e4m3
+        # weight images (one byte per element, one fp32 scale per output row: half the bytes a small batch streams per token); larger batches
+        # and prefill keep the 16-bit weights.  16-bit models only; results differ from the 16-bit weights' (e4m3_dequantised_state_dict).
+        self.weight_format = L.WDEC_MODEL_DTYPE
+        self.set_weight_dtype(weight_dtype)
         self.config = SimpleNamespace(vocab_size=arch.vocab_size, hidden_size=arch.hidden_size,
                                       num_hidden_layers=arch.num_hidden_layers, eos_token_id=list(arch.eos_token_ids),
                                       pad_token_id=arch.pad_token_id, use_return_dict=True)
@@ -121,6 +127,8 @@ class AudioLlamaForCausalLM:
             self._w = LlamaDeviceWeights(self.arch, self._sd, self.device, self.dtype, rope_len=max(self.max_ctx, 64))
             if self.pack_decode:
                 self._w.build_decode_weights()
+            if self.weight_format == L.WDEC_E4M3:
+                self._w.build_decode_weights_e4m3()
             self._sd = None  # device copy is the only copy from here on (6.4 GB bf16 for Llama-3.2-3B)
         return self
 
@@ -132,6 +140,31 @@ class AudioLlamaForCausalLM:
         if fmt != self.kv_format:
             self._kv = None
             self.kv_format = fmt
+
+    def set_weight_dtype(self, weight_dtype) -> None:
+        """Switch the decode-weight format (None / "fp8" / torch.float8_e4m3fn).  The e4m3 images are built on first use and kept; which
+        struct a call runs is decided per call (_struct_for), and a decode graph captured for one struct is never replayed for the other."""
+        fmt = L.weight_format_code(weight_dtype)
+        if fmt == L.WDEC_E4M3:
+            if not L.is16(self.dtype):
+                raise L.SpeechLLMError("weight_dtype='fp8' needs a bfloat16 or float16 model: float32 is the parity mode and keeps its weights in float32")
+            if not self.pack_decode:
+                raise L.SpeechLLMError("weight_dtype='fp8' needs pack_decode=True: the e4m3 weights are decode copies beside the packed 16-bit ones")
+            a = self.arch
+            ks = dict(hidden_size=a.hidden_size, attention_width=a.num_attention_heads * a.head_dim, intermediate_size=a.intermediate_size)
+            bad = {n: k for n, k in ks.items() if k % 64}
+            if bad:
+                raise L.SpeechLLMError(f"weight_dtype='fp8' needs every reduction length to be a multiple of 64, not {bad}")
+            if getattr(self, "_w", None) is not None:
+                self._w.build_decode_weights_e4m3()
+        self.weight_format = fmt
+
+    def _struct_for(self, B: int):
+        """(model struct, its name) for a call of B sequences: the e4m3 struct when the option is on and the batch is within its range"""
+        w = self._dev()
+        if self.weight_format == L.WDEC_E4M3 and B <= L.lib().sl_w8_max_rows():
+            return w.struct_e4m3, "e4m3"
+        return w.struct, "16-bit" if L.is16(self.dtype) else "float32"
 
     def _dev(self) -> LlamaDeviceWeights:
         if self._w is None:
@@ -194,11 +227,12 @@ class AudioLlamaForCausalLM:
         for n in lens:
             cu.append(cu[-1] + n)
         cu_c = (C.c_int32 * (B + 1))(*cu)
-        ws = self._workspace(lib.sl_llama_workspace_bytes(C.byref(w.struct), n_tok, B))
+        struct, _ = self._struct_for(B)      # prefill reads the row-major set of either struct: the same bits
+        ws = self._workspace(lib.sl_llama_workspace_bytes(C.byref(struct), n_tok, B))
         last_logits = torch.empty((B, a.vocab_size), device=self.device, dtype=torch.float32)
         ctx = torch.empty(B, device=self.device, dtype=torch.int32)
         taps = torch.empty((a.num_hidden_layers + 1, n_tok, a.hidden_size), device=self.device, dtype=self.dtype)
-        L.check(lib.sl_llama_prefill(C.byref(w.struct), C.byref(kv), x.data_ptr(), cu_c, B, last_logits.data_ptr(), ctx.data_ptr(),
+        L.check(lib.sl_llama_prefill(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, last_logits.data_ptr(), ctx.data_ptr(),
                                      taps.data_ptr(), ws.data_ptr(), ws.numel(), L.stream_ptr()), "sl_llama_prefill")
         # all-position logits from the post-norm hidden state (ref:model/audio_llama.py:67 with num_logits_to_keep=0)
         logits_packed = ops.gemm(taps[-1], w.lm_head, out_f32=True)
@@ -292,11 +326,12 @@ class AudioLlamaForCausalLM:
             o.sample, o.temperature, o.top_k, o.top_p = 1, float(sample["temperature"]), int(sample["top_k"]), float(sample["top_p"])
             o.seed = int(sample["seed"]) & 0xFFFFFFFFFFFFFFFF
         st = L.GenerateStats()
-        ws = self._workspace(lib.sl_generate_workspace_bytes(C.byref(w.struct), x.shape[0], B, max_new_tokens))
-        L.check(lib.sl_generate(C.byref(w.struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+        struct, fmt_name = self._struct_for(B)
+        ws = self._workspace(lib.sl_generate_workspace_bytes(C.byref(struct), x.shape[0], B, max_new_tokens))
+        L.check(lib.sl_generate(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
                                 L.stream_ptr()), "sl_generate")
         self.last_timings_ms = (st.prefill_ms, st.decode_ms)
         self.last_generate_stats = {"rows": B, "n_steps": int(st.n_steps), "decode_launches": int(st.decode_launches), "compactions": int(st.compactions),
-                                    "final_rows": int(st.final_rows), "row_steps": int(st.row_steps)}
+                                    "final_rows": int(st.final_rows), "row_steps": int(st.row_steps), "weight_format": fmt_name}
         ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B, max_new_tokens)
         return ids, int(st.n_steps)

@@ -56,6 +56,17 @@ def runtime_kv_dtype(config):
     return "fp8" if name == "fp8" else None
 
 
+def runtime_weight_dtype(config):
+    """The decode-weight format a config's `runtime.weight_dtype` names: `model` (default: the model dtype) -> None, `fp8` -> "fp8"
+    (e4m3 weight images for decode steps of small batches, 16-bit models only) — the value the `weight_dtype` keyword of the model
+    classes takes."""
+    rt = config.get("runtime", {}) if hasattr(config, "get") else {}
+    name = str((rt or {}).get("weight_dtype", "model"))
+    if name not in ("model", "fp8"):
+        raise ValueError(f"runtime.weight_dtype: {name!r} is not one of ['fp8', 'model']")
+    return "fp8" if name == "fp8" else None
+
+
 def runtime_dtype(config) -> "torch.dtype":
     """The compute dtype a config's `runtime.dtype` names (default bf16): fp32 (exact-fp32 parity mode), bf16, or fp16
     (inference only, the reference's torch_dtype=float16 regime; training rejects it)."""

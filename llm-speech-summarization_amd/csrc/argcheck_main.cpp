@@ -117,6 +117,38 @@ int main() {
     for (size_t i = 0; i < sizeof(qx) / sizeof(qx[0]); ++i) EXPECT(qo[i] == qw[i], "e4m3 byte of a known value");
     EXPECT_ARG_ERROR(sl_kv_quantize_e4m3_host(nullptr, qo, 1));
   }
+  {   // e4m3 weight images: the host packer under the sanitizers on a (40, 192) bf16 weight read with a row stride of 200 out of an
+      // exactly-sized allocation into an exactly-sized image (a read or write past either end is a report), and the refusals
+    const int N = 40, K = 192, ld = 200;
+    const size_t bytes = sl_w8_image_bytes(N, K);
+    EXPECT(bytes == (size_t)48 * 192 + 4 * 48, "e4m3 image bytes");
+    EXPECT(sl_w8_image_bytes(N, 96) == 0 && sl_w8_image_bytes(0, 64) == 0, "e4m3 image bytes of a bad shape");
+    uint16_t* src = (uint16_t*)malloc(((size_t)(N - 1) * ld + K) * sizeof(uint16_t));
+    unsigned char* img = (unsigned char*)aligned_alloc(16, (bytes + 15) / 16 * 16);
+    for (int n = 0; n < N; ++n)
+      for (int k = 0; k < K; ++k) src[(size_t)n * ld + k] = n == 7 ? 0 : (uint16_t)(0x3C00 + ((n * 131 + k * 17) & 0x3FF) + ((k & 1) << 15));   // bf16 bits, row 7 all zero
+    EXPECT(sl_pack_weight_e4m3_host(src, ld, img, N, K, SL_BF16) == 0, "host packer runs");
+    const float* sc = (const float*)(img + (size_t)48 * K);
+    EXPECT(sc[7] == 1.0f && sc[40] == 1.0f && sc[47] == 1.0f && sc[0] > 0.f, "scales: 1 for the zero row and the padding rows");
+    bool nan_byte = false, pad_zero = true;
+    for (size_t i = 0; i < (size_t)48 * K; ++i) nan_byte = nan_byte || (img[i] & 0x7F) == 0x7F;
+    for (int j = 0; j < K / 64; ++j)
+      for (int lane = 0; lane < 64; ++lane)
+        if ((lane & 15) >= 8)
+          for (int e = 0; e < 16; ++e) pad_zero = pad_zero && img[(((size_t)2 * (K / 64) + j) * 64 + lane) * 16 + e] == 0;      // fragment 2: rows 40..47
+    EXPECT(!nan_byte && pad_zero, "no 0x7F / 0xFF byte; padding rows are zero bytes");
+    EXPECT(sl_pack_weight_e4m3_host(src, ld, img, N, K, SL_F32) == SL_ERR_UNSUPPORTED, "e4m3 image of a float32 weight");
+    EXPECT_ARG_ERROR(sl_pack_weight_e4m3_host(src, ld, img, N, 96, SL_BF16));
+    EXPECT_ARG_ERROR(sl_pack_weight_e4m3(src, ld, img, N, 96, SL_F16, nullptr));
+    EXPECT(sl_w8_max_rows() == 26, "the e4m3 skinny range");
+    sl_gemm_args wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.A = img; wa.W = img; wa.C = img; wa.lda = wa.ldw = 256; wa.ldc = 256; wa.M = 27; wa.N = 256; wa.K = 256; wa.batch = 1; wa.dtype = SL_BF16; wa.w_layout = SL_W_PACKED_E4M3;
+    EXPECT(sl_gemm(&wa, nullptr) == SL_ERR_UNSUPPORTED, "e4m3 layout above sl_w8_max_rows()");
+    wa.w_layout = 3;
+    EXPECT_ARG_ERROR(sl_gemm(&wa, nullptr));
+    free(src); free(img);
+  }
 
   // ---- norms / element-wise / losses
   EXPECT_ARG_ERROR(sl_layernorm(nullptr, nullptr, nullptr, nullptr, 4, 1024, 1e-5f, 0, SL_BF16, nullptr));

@@ -204,6 +204,36 @@ template <> __device__ __forceinline__ u32x4_t sl_dq8x8<f16_t>(u32x2_t w) {
 }
 
 // ----------------------------------------------------------------------------------------------
+// e4m3 weight images (speechllm.h sl_pack_weight_e4m3): the routines the device packer and the host entry both run.
+// Values come in as the 16 raw bits of a bf16 / fp16 element; every step is an exact conversion, a comparison or ONE fp32 division,
+// so host and device give the same scale and the same bytes.
+// ----------------------------------------------------------------------------------------------
+__host__ __device__ inline float sl_w8_elem_f32(uint16_t bits, int dtype) {
+  if (dtype == SL_BF16) return __builtin_bit_cast(float, (uint32_t)bits << 16);
+  return (float)__builtin_bit_cast(_Float16, bits);
+}
+// max |W[row][k]| over k = k0, k0 + kstride, ... < K (NaN elements are skipped by the comparison)
+__host__ __device__ inline float sl_w8_absmax(const uint16_t* row, int K, int dtype, int k0, int kstride) {
+  float m = 0.f;
+  for (int k = k0; k < K; k += kstride) {
+    const float a = __builtin_fabsf(sl_w8_elem_f32(row[k], dtype));
+    m = a > m ? a : m;
+  }
+  return m;
+}
+__host__ __device__ inline float sl_w8_scale(float amax) { return amax == 0.f ? 1.0f : amax / 448.0f; }
+// the 16-byte chunk (fragment f, pair step j, lane) of the image: two runs of 8 bytes, 32 columns apart
+__host__ __device__ inline void sl_w8_chunk(const uint16_t* src, int64_t ld, const float* scales, int N, int dtype, int64_t f, int j, int lane, uint32_t out[4]) {
+  const int64_t row = f * 16 + (lane & 15);
+  out[0] = out[1] = out[2] = out[3] = 0u;
+  if (row >= N) return;
+  const float s = scales[row];
+  const uint16_t* p = src + row * ld + (int64_t)j * 64 + 8 * (lane >> 4);
+  for (int h = 0; h < 2; ++h)
+    for (int e = 0; e < 8; ++e) out[2 * h + (e >> 2)] |= sl_q8_e4m3(sl_w8_elem_f32(p[32 * h + e], dtype) / s) << (8 * (e & 3));
+}
+
+// ----------------------------------------------------------------------------------------------
 // MFMA 16x16 tile step, dtype-generic.  One "k-step" consumes 64 bytes of K per operand row:
 //   bf16: 32 k  -> one v_mfma_f32_16x16x32_bf16
 //   fp16: 32 k  -> one v_mfma_f32_16x16x32_f16 (same operand / accumulator layout, same cycles)

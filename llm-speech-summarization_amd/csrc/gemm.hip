@@ -355,10 +355,22 @@ __global__ __launch_bounds__(256, 2) void gemm_tiled_glds_kernel(GemmP p) {
 //   pairs = the two rotate_half halves of a head; q is written rotated, k/v go straight into the cache).
 //   fuse_rms: the RMSNorm gain is pre-folded into W and the per-row rsqrt(mean(x^2)+eps) is computed
 //   from the x fragments the block loads anyway, then applied to the accumulators.
+//   W8 (PACKED, 16-bit T, MT 1 / 2): W is an e4m3 weight image (speechllm.h sl_pack_weight_e4m3).  The fragment-major layout is the
+//   same with PAIRS of k-steps as its unit: one 16-byte non-temporal load per lane and fragment carries the A fragments of two
+//   consecutive 32-wide k-steps (8 bytes each), two exact conversions (sl_dq8x8: 4 v_cvt_scalef32_pk_*_fp8 each) make them 16-bit,
+//   two MFMAs take them against the two x fragments of the 128-byte x step.  The accumulation is therefore the 16-bit kernel's on the
+//   dequantised bytes; the per-row scale s[n] (fp32, behind the bytes) multiplies the fp32 sum of row n AFTER the cross-wave
+//   reduction — once per output instead of once per element, and exact with respect to the reference q(A) . dq(b)^T * s — and BEFORE
+//   bias, the fuse_rms row factor and the pair epilogues, where each row of a pair takes its own scale.  The block reads its RB scales
+//   once, into LDS, under the main loop.  Per KiB of bytes a wave issues 8 conversions + 2 MFMAs (the guides give no issue cost for
+//   v_cvt_scalef32_pk_*: taken as a plain to transcendental VALU slot, 4-8 cycles, that is 50-80 cycles per KiB per wave against the
+//   ~320 cycles per SIMD one KiB of HBM traffic is worth at 8 TB/s over 256 CUs): the loop stays load-bound, so the loads-in-flight
+//   structure (U steps, all loads issued before the first conversion) is carried over from the 16-bit kernel as it is.
 // ----------------------------------------------------------------------------------------------
 
-template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false>
+template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false, bool W8 = false>
 __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX sx) {
+  static_assert(!W8 || (PACKED && !KCONT && sizeof(T) == 2 && MT <= 2), "e4m3 weight images: packed layout, bf16 / fp16, up to 32 rows");
   constexpr int VEC = Vec16<T>::VEC;
   constexpr int KSTEP = MMA<T>::KSTEP;
   constexpr int RB = 16 * RF;
@@ -366,12 +378,13 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
   static_assert(!PAIRS || RF % 2 == 0, "pair epilogues need an even number of fragments");
   __shared__ float red[NW][RB][MT * 16 + 1];
   __shared__ float red_ss[NW][4][MT * 16];
+  __shared__ float wsc[W8 ? RB : 1];   // W8: the scales of the block's weight rows
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, q = lane >> 4;
   const int z = blockIdx.y;
   const int n0 = blockIdx.x * RB;
-  const int nks_full = p.K / KSTEP;  // full 64-byte steps
+  const int nks_full = W8 ? p.K / (2 * KSTEP) : p.K / KSTEP;  // full 64-byte steps of W (W8: 64 bytes = a pair of k-steps, 128 bytes of x)
 
   const T* A = (const T*)p.A + (int64_t)z * p.sA;
   const T* W = (const T*)p.W + (int64_t)z * p.sW;
@@ -410,6 +423,12 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
     for (int f = 0; f < RF; ++f) acc[f][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const bool fuse = sx.fuse_rms != 0;
+  if constexpr (W8) {
+    // rows past N inside the last fragment are padding rows of the image (scale 1); fragments past the last one repeat it, as wp does
+    const int np = ((p.N + 15) >> 4) << 4;
+    const float* scales = (const float*)((const unsigned char*)p.W + (int64_t)np * p.K);
+    if (tid < RB) wsc[tid] = scales[n0 + tid < np ? n0 + tid : np - 16 + (tid & 15)];
+  }
 
   auto sumsq = [&](const uint4& u, float& s) {
     float e[VEC];
@@ -429,6 +448,53 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
     ks = wave;
     kend = nks_full;
   }
+  if constexpr (W8) {
+    constexpr int XSTEP = 2 * KSTEP;      // x elements per pair step
+    auto pair = [&](const uint4& w8, const uint4 (&x0)[MT], const uint4 (&x1)[MT], int f) {
+      const uint4 a0 = as_uint4(sl_dq8x8<T>(u32x2_t{w8.x, w8.y})), a1 = as_uint4(sl_dq8x8<T>(u32x2_t{w8.z, w8.w}));
+#pragma unroll
+      for (int t = 0; t < MT; ++t) { MMA<T>::step(acc[f][t], a0, x0[t]); MMA<T>::step(acc[f][t], a1, x1[t]); }
+    };
+    for (; ks + (U - 1) * KSTR < kend; ks += U * KSTR) {
+      uint4 fw[U][RF], fx0[U][MT], fx1[U][MT];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t kk = ks + u * KSTR;
+#pragma unroll
+        for (int f = 0; f < RF; ++f) fw[u][f] = ld_nt16(wp[f] + kk * wstep);
+#pragma unroll
+        for (int t = 0; t < MT; ++t) {
+          fx0[u][t] = *(const uint4*)(xp[t] + kk * XSTEP);
+          fx1[u][t] = *(const uint4*)(xp[t] + kk * XSTEP + KSTEP);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+#pragma unroll
+        for (int f = 0; f < RF; ++f) pair(fw[u][f], fx0[u], fx1[u], f);
+        if (fuse) {
+#pragma unroll
+          for (int t = 0; t < MT; ++t) { sumsq(fx0[u][t], ss[t]); sumsq(fx1[u][t], ss[t]); }
+        }
+      }
+    }
+    for (; ks < kend; ks += KSTR) {
+      uint4 fw[RF], fx0[MT], fx1[MT];
+#pragma unroll
+      for (int f = 0; f < RF; ++f) fw[f] = ld_nt16(wp[f] + (int64_t)ks * wstep);
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        fx0[t] = *(const uint4*)(xp[t] + (int64_t)ks * XSTEP);
+        fx1[t] = *(const uint4*)(xp[t] + (int64_t)ks * XSTEP + KSTEP);
+      }
+#pragma unroll
+      for (int f = 0; f < RF; ++f) pair(fw[f], fx0, fx1, f);
+      if (fuse) {
+#pragma unroll
+        for (int t = 0; t < MT; ++t) { sumsq(fx0[t], ss[t]); sumsq(fx1[t], ss[t]); }
+      }
+    }
+  } else {
   for (; ks + (U - 1) * KSTR < kend; ks += U * KSTR) {
     uint4 fw[U][RF], fx[U][MT];
 #pragma unroll
@@ -465,6 +531,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
 #pragma unroll
       for (int t = 0; t < MT; ++t) sumsq(fx[t], ss[t]);
     }
+  }
   }
   if constexpr (!PACKED) {
     // K tail (K % KSTEP != 0): one predicated step, taken by the wave whose turn it is
@@ -505,6 +572,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
   const void* Rb = p.res ? (const void*)((const T*)p.res + (int64_t)z * p.sR) : nullptr;
   auto row_scale = [&](int m) -> float {
     if (!fuse) return 1.0f;
+    if constexpr (W8) {
+      if (sx.rstd_in) return sx.rstd_in[m];
+    }
     float s = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) s += red_ss[w][0][m] + red_ss[w][1][m] + red_ss[w][2][m] + red_ss[w][3][m];
@@ -514,6 +584,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) v += red[w][n][m];
+    if constexpr (W8) v *= wsc[n];      // the weight row's scale: on the reduced fp32 sum, before bias / row factor / pair epilogue
     return v;
   };
 
@@ -949,10 +1020,10 @@ static int run_tiled(const GemmP& p0, const TiledPlan& pl, void* sk_ws, const Sl
   return 0;
 }
 
-template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false>
+template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false, bool W8 = false>
 static int launch_skinny_cfg(GemmP& p, const SkinnyX& sx, int batch, hipStream_t st) {
   dim3 grid((p.N + 16 * RF - 1) / (16 * RF), batch);
-  hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, ACT, RF, NW, U, PACKED, KCONT>), grid, dim3(NW * 64), 0, st, p, sx);
+  hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, ACT, RF, NW, U, PACKED, KCONT, W8>), grid, dim3(NW * 64), 0, st, p, sx);
   SL_CHECK_LAUNCH("gemm_skinny");
   return 0;
 }
@@ -993,6 +1064,44 @@ static int launch_skinny_mt(GemmP& p, const SkinnyX& sx, int batch, const SlEnv&
     if constexpr (!PAIRS) return launch_skinny_cfg<T, MT, ACT, 1, 16, 2, PACKED>(p, sx, batch, st);
   }
   return 0;
+}
+
+// e4m3 weight images (W8): the (fragments, waves) structures of the 16-bit table above, re-derived for PAIR steps — a load is still 16 bytes per
+// lane, but K / 64 of them cover a row where the 16-bit kernel has K / 32, so every trip count halves (K = 3 072: 48 pair steps; 8 192: 128).
+//   * fragments x waves are CARRIED OVER UNMEASURED: they set the block count and the bytes in flight per CU, which do not depend on what a byte
+//     means.  Whether fewer waves would now do (o at M <= 8: 3 pair steps per wave of 16) has not been measured.
+//   * the unroll U is chosen so that a wave's share of the pair steps, pw = K / 64 / NW, splits evenly — the rule the 16-bit o / down structures
+//     follow (gemm.hip above: 6 = 2 x 3, 16 = 4 x 4): 4 where pw % 4 == 0, else 3 where pw % 3 == 0, else 4 with the remainder in the tail loop
+//     (2 in place of 4 for the one structure of 1 024 threads per block that holds two fragments and two x tiles).
+//     K = 3 072: gate/up, lm_head 4 x 4 waves, pw 12 -> U 4; qkv 2 x 8, pw 6 -> U 3; o 1 x 16, pw 3 -> U 3; down (8 192) 1 x 16, pw 8 -> U 4.
+//     Also unmeasured.
+// Any (NW, U) is correct for any K / 64 >= 1: the unrolled loop takes a wave's steps ks, ks + NW, ... only while U of them remain, the tail loop
+// takes the rest one at a time — with fewer pair steps than waves (K = 192 under 16 waves) the unrolled loop runs for no wave and the tail loop
+// gives the first K / 64 waves one step each (tests/test_w8_gpu.py runs K = 64, 192, 1 088, 3 072, 4 480, 8 192).
+template <typename T, int MT, int ACT, int RF, int NW, int UA = 4>
+static int launch_skinny_w8_u(GemmP& p, const SkinnyX& sx, hipStream_t st) {
+  const int pw = p.K / 64 / NW;
+  if (pw % UA != 0 && pw % 3 == 0) return launch_skinny_cfg<T, MT, ACT, RF, NW, 3, true, false, true>(p, sx, 1, st);
+  return launch_skinny_cfg<T, MT, ACT, RF, NW, UA, true, false, true>(p, sx, 1, st);
+}
+template <typename T, int MT, int ACT>
+static int launch_skinny_w8_mt(GemmP& p, const SkinnyX& sx, hipStream_t st) {
+  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || ACT == SL_ACT_ROPE_KV);
+  const int nfrag = (p.N + 15) / 16;
+  if (nfrag >= 1024) return launch_skinny_w8_u<T, MT, ACT, MT == 1 ? 4 : 2, MT == 1 ? 4 : 8>(p, sx, st);
+  // 17..32 rows, 2 fragments x 16 waves: 1 024 threads leave 128 registers, which 4 steps of loads in flight do not fit (the compiler spills): 2, or 3
+  if (nfrag >= 256 || PAIRS) return launch_skinny_w8_u<T, MT, ACT, 2, MT == 1 ? 8 : 16, MT == 1 ? 4 : 2>(p, sx, st);
+  if constexpr (!PAIRS) return launch_skinny_w8_u<T, MT, ACT, 1, 16>(p, sx, st);
+  return 0;
+}
+template <typename T>
+static int launch_skinny_w8(GemmP& p, const SkinnyX& sx, int act, hipStream_t st) {
+  const bool mt1 = sl_family_rows(p.M) <= 16;
+  switch (act) {
+    case SL_ACT_NONE: return mt1 ? launch_skinny_w8_mt<T, 1, SL_ACT_NONE>(p, sx, st) : launch_skinny_w8_mt<T, 2, SL_ACT_NONE>(p, sx, st);
+    case SL_ACT_SILU_MUL: return mt1 ? launch_skinny_w8_mt<T, 1, SL_ACT_SILU_MUL>(p, sx, st) : launch_skinny_w8_mt<T, 2, SL_ACT_SILU_MUL>(p, sx, st);
+    default: return mt1 ? launch_skinny_w8_mt<T, 1, SL_ACT_ROPE_KV>(p, sx, st) : launch_skinny_w8_mt<T, 2, SL_ACT_ROPE_KV>(p, sx, st);
+  }
 }
 
 template <typename T, int ACT>
@@ -1055,7 +1164,20 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
   SL_CHECK_ARG(both_t || a->K % vec == 0, "sl_gemm: K=%d must be a multiple of %d", a->K, vec);
   SL_CHECK_ARG(a->lda % vec == 0 && a->strideA % vec == 0, "sl_gemm: lda/strideA must keep rows 16-byte aligned");
   SL_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->W & 15) == 0, "sl_gemm: A and W must be 16-byte aligned");
-  if (a->w_layout == SL_W_PACKED) {
+  const bool w8 = a->w_layout == SL_W_PACKED_E4M3;
+  if (w8) {
+    // an e4m3 weight image: the skinny kernels' W8 form only — refused before any device work where that form is not built
+    if (a->dtype == SL_F32) {
+      sl_set_error("sl_gemm: e4m3 weight images (w_layout %d) are built for bf16 / fp16, not float32 (the parity mode)", a->w_layout);
+      return SL_ERR_UNSUPPORTED;
+    }
+    SL_CHECK_ARG(a->K % 64 == 0, "sl_gemm: e4m3 weight images need K %% 64 == 0 (K=%d)", a->K);
+    SL_CHECK_ARG(a->batch == 1 && !ex && a->act != SL_ACT_GELU, "sl_gemm: e4m3 weight images take one plain product (batch 1, no sl_gemm_ex features, no GELU)");
+    if (sl_family_rows(a->M) > sl_w8_max_rows()) {
+      sl_set_error("sl_gemm: e4m3 weight images are built for the skinny kernels, up to sl_w8_max_rows() = %d rows (M=%d)", sl_w8_max_rows(), sl_family_rows(a->M));
+      return SL_ERR_UNSUPPORTED;
+    }
+  } else if (a->w_layout == SL_W_PACKED) {
     SL_CHECK_ARG(a->K % (4 * vec) == 0, "sl_gemm: packed weights need K %% %d == 0", 4 * vec);
   } else {
     SL_CHECK_ARG(a->w_layout == SL_W_ROWMAJOR, "sl_gemm: unknown w_layout %d", a->w_layout);
@@ -1153,6 +1275,12 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
       a->K % slab_elems(a->dtype) == 0)
     return e.gemm_log == 2 ? 0 : sl_gemm_stream_launch(p, sx, a->dtype, a->act, fx ? fx->split_ws : nullptr, fx ? fx->split_ws_bytes : 0, st);
   SL_CHECK_ARG(a->w_layout != SL_W_PACKED || sl_family_rows(a->M) <= 64, "sl_gemm: packed weights with M=%d > 64 need batch 1 and K %% 64 == 0", a->M);
+  if (w8) {
+    SL_CHECK_ARG(a->act >= SL_ACT_NONE && a->act <= SL_ACT_ROPE_KV, "sl_gemm: unknown act %d", a->act);
+    SL_CHECK_ARG(!sx.rstd_out && !sx.norm_out && (!sx.rstd_in || sx.fuse_rms), "sl_gemm: e4m3 weight images take rstd_in (with fuse_rms) but not rstd_out / norm_out");
+    if (e.gemm_log == 2) return 0;
+    return a->dtype == SL_F16 ? launch_skinny_w8<f16_t>(p, sx, a->act, st) : launch_skinny_w8<bf16_t>(p, sx, a->act, st);
+  }
   SL_CHECK_ARG(!sx.rstd_in && !sx.rstd_out && !sx.norm_out, "sl_gemm: rstd_in / rstd_out / norm_out are features of the streaming path (M > %d rows, packed weights)", e.stream_min_m);
   void* sk_ws = ex ? ex->sk_ws : nullptr;
   const size_t sk_ws_bytes = ex ? ex->sk_ws_bytes : 0;

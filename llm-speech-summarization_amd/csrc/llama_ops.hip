@@ -664,6 +664,79 @@ extern "C" int sl_pack_weight(const void* src, int64_t ld_src, void* dst, int32_
 }
 
 // ----------------------------------------------------------------------------------------------
+// e4m3 weight images (speechllm.h sl_pack_weight_e4m3): scales first (one wave per row: a maximum does not depend on the order it
+// is taken in), then one thread per 16-byte chunk.  Both kernels and the host entry run the routines of common.h.
+// ----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void w8_scales_kernel(const uint16_t* __restrict__ src, int64_t ld, float* __restrict__ scales, int N, int Np, int K, int dtype) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= Np) return;
+  const float m = wave_max(row < N ? sl_w8_absmax(src + (int64_t)row * ld, K, dtype, lane, 64) : 0.f);
+  if (lane == 0) scales[row] = sl_w8_scale(m);
+}
+__global__ __launch_bounds__(256) void w8_pack_kernel(const uint16_t* __restrict__ src, int64_t ld, const float* __restrict__ scales, uint4* __restrict__ dst, int N,
+                                                      int Np, int K, int dtype) {
+  const int nkp = K / 64;
+  const int64_t total = (int64_t)(Np / 16) * nkp * 64;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t fj = i >> 6;
+    uint32_t o[4];
+    sl_w8_chunk(src, ld, scales, N, dtype, fj / nkp, (int)(fj % nkp), (int)(i & 63), o);
+    dst[i] = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+static int w8_pack_check(const char* who, const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype) {
+  SL_CHECK_ARG(src && dst && N > 0 && K > 0, "%s: bad arguments", who);
+  if (dtype == SL_F32) {
+    sl_set_error("%s: e4m3 weight images are built for bf16 / fp16 weights, not float32 (the parity mode)", who);
+    return SL_ERR_UNSUPPORTED;
+  }
+  SL_CHECK_ARG(sl_is16(dtype), "%s: unknown dtype %d", who, dtype);
+  SL_CHECK_ARG(K % 64 == 0, "%s: K=%d must be a multiple of 64 (pairs of 32-wide k-steps)", who, K);
+  SL_CHECK_ARG(ld_src >= K, "%s: ld_src=%lld < K=%d", who, (long long)ld_src, K);
+  SL_CHECK_ARG(((uintptr_t)dst & 15) == 0 && ((uintptr_t)src & 1) == 0, "%s: dst must be 16-byte aligned", who);
+  return 0;
+}
+
+extern "C" size_t sl_w8_image_bytes(int32_t N, int32_t K) {
+  if (N <= 0 || K <= 0 || K % 64 != 0) { sl_set_error("sl_w8_image_bytes: N=%d K=%d (K must be a positive multiple of 64)", N, K); return 0; }
+  const size_t Np = ((size_t)N + 15) / 16 * 16;
+  return Np * (size_t)K + 4 * Np;
+}
+
+extern "C" int32_t sl_w8_max_rows(void) {
+  const int r = sl_env().stream_min_m;      // the packed skinny range; the e4m3 kernels are built for MT 1 and 2 (<= 32 rows)
+  return r < 32 ? r : 32;
+}
+
+extern "C" int sl_pack_weight_e4m3_host(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype) {
+  SL_TRY(w8_pack_check("sl_pack_weight_e4m3_host", src, ld_src, dst, N, K, dtype));
+  const int64_t Np = ((int64_t)N + 15) / 16 * 16;
+  const int nkp = K / 64;
+  const uint16_t* s = (const uint16_t*)src;
+  float* scales = (float*)((unsigned char*)dst + Np * K);
+  for (int64_t n = 0; n < Np; ++n) scales[n] = sl_w8_scale(n < N ? sl_w8_absmax(s + n * ld_src, K, dtype, 0, 1) : 0.f);
+  uint32_t* out = (uint32_t*)dst;
+  for (int64_t f = 0; f < Np / 16; ++f)
+    for (int j = 0; j < nkp; ++j)
+      for (int lane = 0; lane < 64; ++lane) sl_w8_chunk(s, ld_src, scales, N, dtype, f, j, lane, out + ((f * nkp + j) * 64 + lane) * 4);
+  return 0;
+}
+
+extern "C" int sl_pack_weight_e4m3(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype, sl_stream stream) {
+  SL_TRY(w8_pack_check("sl_pack_weight_e4m3", src, ld_src, dst, N, K, dtype));
+  const int Np = (N + 15) / 16 * 16;
+  float* scales = (float*)((unsigned char*)dst + (int64_t)Np * K);
+  hipLaunchKernelGGL(w8_scales_kernel, dim3((Np + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src, ld_src, scales, N, Np, K, dtype);
+  SL_CHECK_LAUNCH("w8_scales");
+  const int64_t total = (int64_t)(Np / 16) * (K / 64) * 64;
+  const unsigned grid = (unsigned)(ceil_div64(total, 256) < 16384 ? ceil_div64(total, 256) : 16384);
+  hipLaunchKernelGGL(w8_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src, ld_src, scales, (uint4*)dst, N, Np, K, dtype);
+  SL_CHECK_LAUNCH("w8_pack");
+  return 0;
+}
+
+// ----------------------------------------------------------------------------------------------
 // Flash-decoding: one-token attention split over the context so that small batches still fill the chip.
 //   grid (kv head, sequence, split); each block owns 64 keys: scores -> local softmax -> partial P.V,
 //   and leaves (O[REP][128], m[REP], l[REP]) in fp32; a second tiny kernel merges the splits.

@@ -480,6 +480,33 @@ static int llama_check(const sl_llama_model* m, const sl_kv_cache* kv) {
   return 0;
 }
 
+// sl_llama_model.reserved, the format of the decode weights (speechllm.h SL_WDEC_*), against what a decode step of `rows` rows can run: checked by
+// every entry that decodes, before any launch.  An e4m3 model decodes on the skinny kernels' W8 form only.
+static int llama_wdec_check(const char* who, const sl_llama_model* m, int rows) {
+  if (m->reserved == SL_WDEC_MODEL_DTYPE) return 0;
+  SL_CHECK_ARG(m->reserved == SL_WDEC_E4M3, "%s: unknown decode-weight format %d (sl_llama_model.reserved: 0 = model dtype, 1 = e4m3 weight images)", who, m->reserved);
+  if (m->dtype == SL_F32) {
+    sl_set_error("%s: e4m3 decode weights are built for bf16 / fp16 models, not float32 (the parity mode)", who);
+    return SL_ERR_UNSUPPORTED;
+  }
+  SL_CHECK_ARG(m->dec_fused_norm == 1 && m->lm_head_dec, "%s: e4m3 decode weights need dec_fused_norm = 1 and lm_head_dec", who);
+  for (int l = 0; l < m->n_layers; ++l) {
+    const sl_llama_layer& L = m->layers[l];
+    SL_CHECK_ARG(L.wqkv_dec && L.wo_dec && L.wgu_dec && L.wdown_dec, "%s: e4m3 decode weights: layer %d has a null *_dec image", who, l);
+  }
+  const int ks[3] = {m->hidden, m->n_heads * m->head_dim, m->ffn};
+  for (int k : ks)
+    if (k % 64 != 0) {
+      sl_set_error("%s: e4m3 decode weights need every reduction length to be a multiple of 64 (hidden=%d, n_heads*head_dim=%d, ffn=%d)", who, ks[0], ks[1], ks[2]);
+      return SL_ERR_UNSUPPORTED;
+    }
+  if (sl_family_rows(rows) > sl_w8_max_rows()) {
+    sl_set_error("%s: e4m3 decode weights run up to sl_w8_max_rows() = %d rows per decode step, not %d (use the 16-bit decode copies)", who, sl_w8_max_rows(), sl_family_rows(rows));
+    return SL_ERR_UNSUPPORTED;
+  }
+  return 0;
+}
+
 // K / V rows are head_dim elements of the cache's own element size: 1 byte in the e4m3 format, the model dtype's otherwise
 static inline size_t kv_elem_bytes(const sl_llama_model* m, const sl_kv_cache* kv) { return sl_kv_elem_size(kv->reserved, m->dtype); }
 static inline size_t kv_layer_bytes(const sl_llama_model* m, const sl_kv_cache* kv) {
@@ -586,7 +613,8 @@ static int dec_gemm(const sl_llama_model* m, const LlamaWs& w, const void* A, in
   sl_gemm_args a;
   memset(&a, 0, sizeof(a));
   a.A = A; a.lda = lda; a.W = Wp; a.ldw = K; a.C = C; a.ldc = ldc; a.residual = res; a.ldr = ldc;
-  a.M = M; a.N = N; a.K = K; a.batch = 1; a.dtype = m->dtype; a.act = act; a.out_f32 = out_f32; a.w_layout = SL_W_PACKED;
+  a.M = M; a.N = N; a.K = K; a.batch = 1; a.dtype = m->dtype; a.act = act; a.out_f32 = out_f32;
+  a.w_layout = m->reserved == SL_WDEC_E4M3 ? SL_W_PACKED_E4M3 : SL_W_PACKED;      // sl_llama_model.reserved: the format of the *_dec weights
   return sl_gemm_impl(&a, fx, nullptr, st);
 }
 
@@ -619,7 +647,9 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     // small-batch graphs: the prefetch branch runs two matrices ahead of the chain (DecodePrefetch): released where a consumer is launched
     DecodePrefetch* pf = g_prefetch;
     const size_t esz = sl_dtype_size(dt);
-    const size_t b_qkv = (size_t)qkv_w * H * esz, b_o = (size_t)H * nh * D * esz, b_gu = (size_t)2 * m->ffn * H * esz, b_down = (size_t)H * m->ffn * esz;
+    const bool w8 = m->reserved == SL_WDEC_E4M3;      // e4m3 weight images: bytes + scales
+    const size_t b_qkv = w8 ? sl_w8_image_bytes(qkv_w, H) : (size_t)qkv_w * H * esz, b_o = w8 ? sl_w8_image_bytes(H, nh * D) : (size_t)H * nh * D * esz,
+                 b_gu = w8 ? sl_w8_image_bytes(2 * m->ffn, H) : (size_t)2 * m->ffn * H * esz, b_down = w8 ? sl_w8_image_bytes(H, m->ffn) : (size_t)H * m->ffn * esz;
     const sl_llama_layer* Ln = (l + 1 < m->n_layers) ? &m->layers[l + 1] : nullptr;
     if (pf && l == 0) { SL_TRY(pf->ahead(L.wqkv_dec, b_qkv)); SL_TRY(pf->ahead(L.wo_dec, b_o)); }
     if (pf) SL_TRY(pf->ahead(L.wgu_dec, b_gu));                       // ... while qkv, attention and o run
@@ -882,6 +912,7 @@ extern "C" int sl_llama_decode_step(const sl_llama_model* m, const sl_kv_cache* 
                                     int32_t B, float* logits, void* workspace, size_t workspace_bytes, sl_stream stream) {
   SL_TRY(llama_check(m, kv));
   SL_CHECK_ARG(next_ids_dev && ctx_len_dev && logits && workspace && B > 0 && B <= kv->slots && B <= SL_MAX_DECODE_BATCH, "sl_llama_decode_step: bad arguments (B<=%d)", SL_MAX_DECODE_BATCH);
+  SL_TRY(llama_wdec_check("sl_llama_decode_step", m, B));
   hipStream_t st = (hipStream_t)stream;
   LlamaWs w;
   Carver c(workspace, workspace_bytes);
@@ -1006,6 +1037,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   const int use_eos = (o->use_eos || o->row_limits_host) ? 1 : 0;       // per-row budgets finish rows the way EOS does
   SL_CHECK_ARG(x && cu_seqlens_host && out_ids_host && workspace && nseq > 0 && nseq <= SL_MAX_DECODE_BATCH && max_new_tokens > 0,
                "sl_generate: bad arguments (nseq<=%d)", SL_MAX_DECODE_BATCH);
+  SL_TRY(llama_wdec_check("sl_generate", m, nseq));      // compaction only moves down the row ladder: a call that starts within the e4m3 range stays within it
   SL_CHECK_ARG(n_eos >= 0 && n_eos <= 8 && (n_eos == 0 || eos_ids_host != nullptr), "sl_generate: 0..8 eos ids");
   SampleOpts smp_s{o->temperature, o->top_k, o->top_p, o->seed};
   const SampleOpts* smp = o->sample ? &smp_s : nullptr;
@@ -1089,7 +1121,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
     key.model = m; key.layers = m->layers; key.w0 = m->n_layers > 0 ? m->layers[0].wqkv_dec : nullptr; key.lm = m->lm_head_dec ? m->lm_head_dec : m->lm_head;
     key.embed = m->embed; key.kc = kv->k_cache; key.vc = kv->v_cache; key.ws = workspace; key.ws_bytes = workspace_bytes;
     key.B = B; key.B0 = B0; key.max_new = max_new_tokens; key.use_eos = use_eos; key.n_eos = n_eos; key.pad = pad_id; key.max_ctx = kv->max_ctx;
-    key.slots = kv->slots; key.shared_prefix = kv->shared_prefix; key.dtype = m->dtype; key.n_layers = m->n_layers; key.vocab = m->vocab; key.fused = m->dec_fused_norm | (sl_env().decode_tiled << 8) | ((sl_env().attn_decode_ks & 127) << 9) | ((pin_rows ? 1 : 0) << 16) | ((sl_env().decode_prefetch ? 1 : 0) << 17) | ((kv->reserved & 3) << 18);   // + the switch that shapes the captured launches
+    key.slots = kv->slots; key.shared_prefix = kv->shared_prefix; key.dtype = m->dtype; key.n_layers = m->n_layers; key.vocab = m->vocab; key.fused = m->dec_fused_norm | (sl_env().decode_tiled << 8) | ((sl_env().attn_decode_ks & 127) << 9) | ((pin_rows ? 1 : 0) << 16) | ((sl_env().decode_prefetch ? 1 : 0) << 17) | ((kv->reserved & 3) << 18) | ((m->reserved & 3) << 20);   // + the switch that shapes the captured launches
     key.limits = row_limit_arg ? 1 : 0;
     key.content = model_content_hash(m);
     SL_HIP(hipGetDevice(&key.device));

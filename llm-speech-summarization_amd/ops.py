@@ -297,12 +297,45 @@ def pack_weight(W: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def w8_image_bytes(N: int, K: int) -> int:
+    n = int(L.lib().sl_w8_image_bytes(N, K))
+    if n == 0:
+        L.check(-1, "sl_w8_image_bytes")
+    return n
+
+
+def pack_weight_e4m3(W: torch.Tensor) -> torch.Tensor:
+    """(N, K) bf16 / fp16 weight (row stride W.stride(0)) -> its e4m3 weight image (sl_pack_weight_e4m3): a uint8 buffer of
+    sl_w8_image_bytes(N, K) holding the fragment-major bytes and, behind them, one fp32 scale per (padded) output row.  On the GPU
+    through the device packer, on the CPU through the host entry: the same routine, the same bytes."""
+    n, k = W.shape
+    if W.stride(1) != 1:
+        raise L.SpeechLLMError("pack_weight_e4m3: rows must be contiguous")
+    out = torch.empty(w8_image_bytes(n, k), device=W.device, dtype=torch.uint8)
+    if W.is_cuda:
+        L.check(L.lib().sl_pack_weight_e4m3(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype), L.stream_ptr()), "sl_pack_weight_e4m3")
+    else:
+        L.check(L.lib().sl_pack_weight_e4m3_host(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype)), "sl_pack_weight_e4m3_host")
+    return out
+
+
+def w8_image_parts(img: torch.Tensor, N: int, K: int):
+    """An e4m3 weight image -> (bytes (Np, K) uint8 in natural row / column order, scales (Np,) fp32); Np = ceil(N/16)*16."""
+    Np = (N + 15) // 16 * 16
+    b = img[:Np * K].view(Np // 16, K // 64, 4, 16, 2, 8)                # [f][j][lane >> 4][lane & 15][half][e]
+    b = b.permute(0, 3, 1, 4, 2, 5).reshape(Np, K)                      # row 16 f + (lane & 15), column 64 j + 32 half + 8 (lane >> 4) + e
+    s = img[Np * K:Np * K + 4 * Np].clone().view(torch.float32)
+    return b, s
+
+
 def gemm_decode(A: torch.Tensor, Wp: torch.Tensor, N: int, *, residual=None, act: int = L.ACT_NONE, out_f32: bool = False,
                 fuse_rms: bool = False, eps: float = 1e-5, rope=None, out: Optional[torch.Tensor] = None,
                 split_k: bool = True, rstd_in: Optional[torch.Tensor] = None, rstd_out: Optional[torch.Tensor] = None,
-                norm_out: Optional[torch.Tensor] = None, norm_gain: Optional[torch.Tensor] = None) -> torch.Tensor:
+                norm_out: Optional[torch.Tensor] = None, norm_gain: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+                w_layout: int = L.W_PACKED) -> torch.Tensor:
     """Decode GEMM on packed weights.  rope = dict(cos, sin, pos, seq, k_cache, v_cache, n_heads, n_kv, max_ctx) for ACT_ROPE_KV.
-    split_k: hand the kernel a scratch buffer so that row counts > 64 may split K over blocks (gemm_stream.hip)."""
+    split_k: hand the kernel a scratch buffer so that row counts > 64 may split K over blocks (gemm_stream.hip).
+    w_layout = W_PACKED_E4M3: Wp is an e4m3 weight image (pack_weight_e4m3), for up to sl_w8_max_rows() rows."""
     M, K = A.shape
     if act == L.ACT_SILU_MUL:
         n_out = N // 2
@@ -318,7 +351,8 @@ def gemm_decode(A: torch.Tensor, Wp: torch.Tensor, N: int, *, residual=None, act
     a.C, a.ldc = L.ptr(out), out.stride(0)
     a.residual, a.ldr = L.ptr(residual), (residual.stride(0) if residual is not None else 0)
     a.M, a.N, a.K, a.batch = M, N, K, 1
-    a.dtype, a.act, a.out_f32, a.w_layout = L.dtype_code(A.dtype), act, int(out_f32), L.W_PACKED
+    a.bias = L.ptr(bias)
+    a.dtype, a.act, a.out_f32, a.w_layout = L.dtype_code(A.dtype), act, int(out_f32), int(w_layout)
     f = L.GemmFused()
     f.fuse_rms, f.rms_eps = int(fuse_rms), eps
     f.rstd_in, f.rstd_out = L.ptr(rstd_in), L.ptr(rstd_out)

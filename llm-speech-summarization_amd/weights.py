@@ -549,35 +549,137 @@ class LlamaDeviceWeights:
             self._keep.append(out)
             return out
 
-        def fold(w: torch.Tensor, gain: torch.Tensor) -> torch.Tensor:
-            return (w.float() * gain.float()[None, :]).to(dt) if fuse_norm else w
-
-        blk = torch.arange(16, device=dev_)
-        head_perm = torch.cat([torch.cat([blk + 16 * j, blk + 64 + 16 * j]) for j in range(4)])  # [0:16],[64:80],[16:32],...
-        perm = torch.cat([head_perm + 128 * h for h in range(nh + nkv)] + [torch.arange((nh + nkv) * 128, (nh + 2 * nkv) * 128, device=dev_)])
-        by_ptr = {t.data_ptr(): t for t in self._keep}
         self.dec_wgu: List[torch.Tensor] = []
         for li in range(a.num_hidden_layers):
             lay = self._layers[li]
-            wqkv, wo, wgu, wdown = by_ptr[lay.wqkv], by_ptr[lay.wo], by_ptr[lay.wgu], by_ptr[lay.wdown]
-            n1, n2 = by_ptr[lay.norm1], by_ptr[lay.norm2]
-            lay.wqkv_dec = pack(fold(wqkv, n1)[perm]).data_ptr()
+            wqkv, wo, wgu, wdown = self._decode_sources(li, fuse_norm)
+            lay.wqkv_dec = pack(wqkv).data_ptr()
             lay.wo_dec = pack(wo).data_ptr()
-            wgu_p = pack(fold(wgu, n2))
+            wgu_p = pack(wgu)
             self.dec_wgu.append(wgu_p)
             lay.wgu_dec = wgu_p.data_ptr()
             lay.wdown_dec = pack(wdown).data_ptr()
-        self.struct.lm_head_dec = pack(fold(self.lm_head, by_ptr[self.struct.final_norm])).data_ptr()
+        self.struct.lm_head_dec = pack(self._decode_sources(-1, fuse_norm)).data_ptr()
         self.struct.dec_fused_norm = int(bool(fuse_norm))
         torch.cuda.synchronize(dev_)
         self.decode_packed = True
 
+    def _rope_perm(self) -> torch.Tensor:
+        """row order of wqkv_dec: q / k heads in 16-row blocks alternating the two rotate_half halves, v rows as they are"""
+        a, dev_ = self.arch, self.device
+        nh, nkv = a.num_attention_heads, a.num_key_value_heads
+        blk = torch.arange(16, device=dev_)
+        head_perm = torch.cat([torch.cat([blk + 16 * j, blk + 64 + 16 * j]) for j in range(4)])  # [0:16],[64:80],[16:32],...
+        return torch.cat([head_perm + 128 * h for h in range(nh + nkv)] + [torch.arange((nh + nkv) * 128, (nh + 2 * nkv) * 128, device=dev_)])
+
+    def _decode_sources(self, li: int, fuse_norm: bool):
+        """The tensors a decode copy is packed from — layer li: (wqkv gain-folded and permuted, wo, wgu gain-folded, wdown); li = -1: the
+        gain-folded lm_head.  One place, so that the 16-bit copies and the e4m3 images hold the same rows in the same order."""
+        dt = self.dtype
+        by_ptr = {t.data_ptr(): t for t in self._keep}
+
+        def fold(w: torch.Tensor, gain: torch.Tensor) -> torch.Tensor:
+            return (w.float() * gain.float()[None, :]).to(dt) if fuse_norm else w
+
+        if li < 0:
+            return fold(self.lm_head, by_ptr[self.struct.final_norm])
+        lay = self._layers[li]
+        wqkv, wo, wgu, wdown = by_ptr[lay.wqkv], by_ptr[lay.wo], by_ptr[lay.wgu], by_ptr[lay.wdown]
+        return fold(wqkv, by_ptr[lay.norm1])[self._rope_perm()], wo, fold(wgu, by_ptr[lay.norm2]), wdown
+
+    # -- opt-in fp8 decode weights (include/speechllm.h: e4m3 weight images, SL_WDEC_E4M3) -----------------------------------------
+    def w8_shapes(self):
+        """(N, K) of the five decode products: qkv, o, gate/up, down (per layer) and lm_head"""
+        a = self.arch
+        H, D, nh, nkv, F_ = a.hidden_size, a.head_dim, a.num_attention_heads, a.num_key_value_heads, a.intermediate_size
+        return dict(qkv=((nh + 2 * nkv) * D, H), o=(H, nh * D), gu=(2 * F_, H), down=(H, F_), lm_head=(a.vocab_size, H))
+
+    def e4m3_supported(self) -> Optional[str]:
+        """None, or why this model cannot take e4m3 decode weights"""
+        if not L.is16(self.dtype):
+            return "fp8 decode weights need a bfloat16 or float16 model: float32 is the parity mode"
+        bad = {n: k for n, (_, k) in self.w8_shapes().items() if k % 64}
+        if bad:
+            return f"fp8 decode weights need every reduction length to be a multiple of 64, not {bad}"
+        return None
+
+    def build_decode_weights_e4m3(self) -> None:
+        """Third copy of the decode matrices: e4m3 weight images (sl_pack_weight_e4m3: one byte per element, one fp32 scale per output row)
+        of the same folded, permuted, interleaved tensors build_decode_weights packs, and a second sl_llama_model struct
+        (`struct_e4m3`) that differs from `struct` in the five *_dec pointers and `reserved` = SL_WDEC_E4M3 only.  The 16-bit decode
+        copies stay for batches above sl_w8_max_rows(); the images cost about half a copy of the weights more."""
+        if getattr(self, "struct_e4m3", None) is not None:
+            return
+        why = self.e4m3_supported()
+        if why:
+            raise L.SpeechLLMError(why)
+        self.build_decode_weights()
+        if not self.decode_packed or not self.struct.dec_fused_norm:
+            raise L.SpeechLLMError("fp8 decode weights need the packed, gain-folded decode copies (build_decode_weights with fuse_norm)")
+        from . import ops
+        a = self.arch
+        m = L.LlamaModel()
+        C.memmove(C.byref(m), C.byref(self.struct), C.sizeof(L.LlamaModel))
+        layers = (L.LlamaLayer * a.num_hidden_layers)()
+        C.memmove(layers, self._layers, C.sizeof(layers))
+        self.w8_images: List[Dict[str, torch.Tensor]] = []
+        for li in range(a.num_hidden_layers):
+            imgs = {n: ops.pack_weight_e4m3(t.contiguous()) for n, t in zip(("qkv", "o", "gu", "down"), self._decode_sources(li, True))}
+            self.w8_images.append(imgs)
+            lay = layers[li]
+            lay.wqkv_dec, lay.wo_dec, lay.wgu_dec, lay.wdown_dec = (imgs[n].data_ptr() for n in ("qkv", "o", "gu", "down"))
+        self.w8_lm_head = ops.pack_weight_e4m3(self._decode_sources(-1, True).contiguous())
+        m.lm_head_dec = self.w8_lm_head.data_ptr()
+        m.layers = C.cast(layers, C.POINTER(L.LlamaLayer))
+        m.reserved = L.WDEC_E4M3
+        torch.cuda.synchronize(self.device)
+        self._layers_e4m3 = layers
+        self.struct_e4m3 = m
+
+    def e4m3_dequantised_state_dict(self) -> Dict[str, torch.Tensor]:
+        """HF-keyed fp32 CPU state dict of the model the e4m3 decode step computes: the seven projections of every layer and
+        lm_head.weight are the dequantised images (byte value x s[n], formed in fp64, stored as fp32) in natural row order (q / k rows
+        un-permuted, gate / up de-interleaved); the norm gains folded into them are 1.  For tests and for scoring the quantised model
+        offline."""
+        if getattr(self, "struct_e4m3", None) is None:
+            raise L.SpeechLLMError("e4m3_dequantised_state_dict: call build_decode_weights_e4m3 first")
+        from . import ops
+        a = self.arch
+        H, D, nh, nkv, F_ = a.hidden_size, a.head_dim, a.num_attention_heads, a.num_key_value_heads, a.intermediate_size
+        shapes = self.w8_shapes()
+
+        def dq(img: torch.Tensor, name: str) -> torch.Tensor:
+            n, k = shapes[name]
+            b, s = ops.w8_image_parts(img.cpu(), n, k)
+            return (b.contiguous().view(torch.float8_e4m3fn).double() * s.double()[:, None])[:n].float()
+
+        perm = self._rope_perm().cpu()
+        ones = torch.ones(H, dtype=torch.float32)
+        sd = {"model.embed_tokens.weight": self.embed.float().cpu(), "model.norm.weight": ones.clone(), "lm_head.weight": dq(self.w8_lm_head, "lm_head")}
+        for li, imgs in enumerate(self.w8_images):
+            p = f"model.layers.{li}."
+            qkv = torch.empty(shapes["qkv"], dtype=torch.float32)
+            qkv[perm] = dq(imgs["qkv"], "qkv")
+            sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.v_proj.weight"] = \
+                (t.contiguous() for t in qkv.split([nh * D, nkv * D, nkv * D], 0))
+            sd[p + "self_attn.o_proj.weight"] = dq(imgs["o"], "o")
+            gu = dq(imgs["gu"], "gu").view(F_ // 16, 2, 16, H)
+            sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"] = gu[:, 0].reshape(F_, H).contiguous(), gu[:, 1].reshape(F_, H).contiguous()
+            sd[p + "mlp.down_proj.weight"] = dq(imgs["down"], "down")
+            sd[p + "input_layernorm.weight"], sd[p + "post_attention_layernorm.weight"] = ones.clone(), ones.clone()
+        return sd
+
     def n_params(self) -> int:
         return sum(t.numel() for t in self._keep if t.dtype == self.dtype)
 
-    def weight_bytes_per_token(self) -> int:
-        """Bytes of weights one decode step streams: every layer matrix + final norm + lm_head."""
+    def weight_bytes_per_token(self, fmt=None) -> int:
+        """Bytes of weights one decode step streams: every layer matrix + final norm + lm_head.  fmt = "fp8" / torch.float8_e4m3fn: the
+        e4m3 weight images instead (bytes and scales; the norm gains are folded in and not read)."""
         a = self.arch
+        if L.weight_format_code(fmt) == L.WDEC_E4M3:
+            sh = self.w8_shapes()
+            img = lambda n: ((sh[n][0] + 15) // 16 * 16) * (sh[n][1] + 4)
+            return a.num_hidden_layers * sum(img(n) for n in ("qkv", "o", "gu", "down")) + img("lm_head")
         per_layer = (a.num_attention_heads + 2 * a.num_key_value_heads) * a.head_dim * a.hidden_size \
             + a.num_attention_heads * a.head_dim * a.hidden_size + 3 * a.intermediate_size * a.hidden_size + 2 * a.hidden_size
         total = per_layer * a.num_hidden_layers + a.hidden_size + a.vocab_size * a.hidden_size
