@@ -762,6 +762,74 @@ int sl_sample_generate(const sl_llama_model* m, const sl_kv_cache* kv, void* x, 
                        int32_t check_every, float temperature, int32_t top_k, float top_p, uint64_t seed, int32_t* out_ids_host,
                        int32_t* n_steps_host, float* timings_ms_host, void* workspace, size_t workspace_bytes, sl_stream stream);
 
+/* Beam search (hf:generation/utils.py _beam_search with do_sample = False, prompts given as embeddings: decoder_prompt_len = 0,
+ * max_length = max_new_tokens; additive to ABI 7).  K = num_beams, E = the EOS ids in use, M = max(2, 1 + E) * K candidates per step.
+ * Per sequence: K running beams (token histories + scores, initialised to [0, -1e9, ...]), a finished set of K hypotheses (scores
+ * initialised to -1e9, flags, lengths) and `open` (HF's is_early_stop_heuristic_unsatisfied).  Step t (0-based):
+ *   1. acc[j][v] = log_softmax(logits of beam j)[v] + running_score[j]            (only beam 0 exists at t = 0)
+ *   2. candidates = the M largest acc over (j, v): larger value first, then lower flat index j * V + v
+ *   3. hit[c] = candidate c's token is an EOS id, or t + 1 == max_new_tokens
+ *   4. next running beams = the first K, in candidate order, of score + (hit ? -1e9 : 0); their source beams re-order the K/V cache
+ *   5. finished set = top-K of [old K | M candidates], concatenation order on ties; a candidate's score is score / (t+1)^length_penalty,
+ *      with -1e9 added once for each of: all K flags set and early_stopping == 1; !open; c >= K or !hit[c]
+ *   6. open &= running_score[0] / L^length_penalty > worst;  L = max_new_tokens if early_stopping == 2 and length_penalty > 0, else t + 1;
+ *      worst = min(finished scores) if all K flags are set, else -1e9
+ *   7. the sequence is done when !open, or early_stopping == 1 and all K flags are set, or t + 1 == max_new_tokens.
+ * All score arithmetic is fp32; (t+1)^length_penalty is formed in double on the host and rounded once (sl_beam_state.len_pen).
+ * Decode rows: row s * K + j is beam j of sequence s and owns cache slot s * K + j, during and after the call.  Each prompt is
+ * prefilled ONCE (into slot s * K) and its K/V rows are copied to the K - 1 sibling slots.  There is no compaction: a done sequence
+ * keeps its rows, its finished set frozen by the rules above, until every sequence is done (checked every `check_every` steps).
+ * LIMITS (SL_ERR_ARG / SL_ERR_UNSUPPORTED before any launch): 1 <= num_beams <= 8; M <= 64 and M <= vocab; nseq * num_beams <=
+ * SL_MAX_DECODE_BATCH and <= kv->slots; 1 <= num_return_sequences <= num_beams; length_penalty finite; prompt + max_new_tokens <= max_ctx;
+ * e4m3 decode weights up to sl_w8_max_rows() rows, counted as nseq * num_beams. */
+typedef struct {
+  const int32_t* eos_ids_host;     /* n_eos ids (<= 8) */
+  int32_t n_eos, pad_id, use_eos, max_new_tokens, check_every;
+  int32_t num_beams, num_return_sequences;
+  int32_t early_stopping;          /* 0 = False, 1 = True, 2 = "never" */
+  float length_penalty;
+} sl_beam_opts;
+/* Device state of sl_beam_step; R = nseq * num_beams rows, all arrays caller-owned.  Initial values: run_score [0, -1e9, ...] per
+ * sequence, fin_score -1e9, fin_flag / fin_len / seq_done / step 0, open 1, ctx_len = the prompt lengths; fin_score must stay
+ * sorted (descending) per sequence, as the kernel leaves it. */
+typedef struct {
+  float* run_score;       /* (R) */
+  int32_t* next_ids;      /* (R) token each row feeds to the next decode step */
+  int32_t* src_row;       /* (R) global row index of the beam a row continues (the cache re-ordering of the step) */
+  int32_t* ctx_len;       /* (R) advanced by one per step, except by the first */
+  int32_t* hist[2];       /* two (R, max_new_tokens) token histories: step t reads hist[t & 1] and writes hist[(t + 1) & 1] */
+  float* fin_score;       /* (R) */
+  int32_t* fin_ids;       /* (R, max_new_tokens) */
+  int32_t* fin_flag;      /* (R) */
+  int32_t* fin_len;       /* (R) */
+  int32_t* open;          /* (nseq) */
+  int32_t* seq_done;      /* (nseq) */
+  int32_t* step;          /* (nseq) t of the next step; advanced by the kernel (a step with t >= max_new_tokens does nothing) */
+  const float* len_pen;   /* (max_new_tokens) len_pen[t] = (float)pow((double)(t + 1), length_penalty) */
+} sl_beam_state;
+size_t sl_beam_generate_workspace_bytes(const sl_llama_model* m, int64_t n_tok, int32_t nseq, const sl_kv_cache* kv, const sl_beam_opts* opts);
+/* out_ids_host (nseq, R, max_new_tokens): hypothesis r of sequence s, pad_id past its length (an EOS that ended it is included);
+ * out_scores_host / out_lens_host (nseq, R).  stats (may be NULL): n_steps = steps run, decode_launches = replays of the captured
+ * step (decode on nseq * K rows -> top-M per row -> beam step -> cache gather -> scatter), cached per thread like sl_generate's. */
+int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                     const sl_beam_opts* opts, int32_t* out_ids_host, float* out_scores_host, int32_t* out_lens_host,
+                     sl_generate_stats* stats, void* workspace, size_t workspace_bytes, sl_stream stream);
+/* Kernel-level entries (the tests, callers with their own loop).
+ * sl_beam_topk: per row of fp32 logits (rows, V) the M (<= 64, <= V) largest log_softmax(row) + row_score[row] (row_score NULL: 0) with
+ *   their tokens, in the order of step 2; NaN logits count as -inf.  cand_score / cand_token: (rows, M).
+ * sl_beam_step: steps 2-7 for nseq sequences from the rows' lists.  first != 0: step 0 — sequence s has ONE list, at list row s
+ *   (the prefill logits), and ctx_len is not advanced; otherwise list row s * K + j belongs to beam j.
+ * sl_kv_beam_reorder: for every row with src_row[row] != row, positions [prompt_len[row], ctx_len[row]) (at most max_span of them) of
+ *   slot src_row[row] replace those of slot row in every layer and KV head, in two launches through `staging`
+ *   (sl_kv_beam_staging_bytes = 2 * rows * n_layers * n_kv_heads * max_span * bytes of one K row).  Either K/V format. */
+int sl_beam_topk(const float* logits, int32_t rows, int32_t V, const float* row_score, int32_t M, float* cand_score, int32_t* cand_token,
+                 sl_stream stream);
+int sl_beam_step(const sl_beam_state* state, const float* cand_score, const int32_t* cand_token, int32_t nseq, int32_t num_beams, int32_t M,
+                 int32_t first, const sl_beam_opts* opts, sl_stream stream);
+size_t sl_kv_beam_staging_bytes(const sl_kv_cache* kv, const sl_llama_model* m, int32_t rows, int32_t max_span);
+int sl_kv_beam_reorder(const sl_kv_cache* kv, const sl_llama_model* m, const int32_t* src_row_dev, const int32_t* prompt_len_dev,
+                       const int32_t* ctx_len_dev, int32_t rows, int32_t max_span, void* staging, size_t staging_bytes, sl_stream stream);
+
 /* ---------------------------------------------------------------------------------------------
  * KD step, layer stacks (C++ host runtime of the training tape: one call issues the launches of a whole stack of layers
  * over a packed ragged batch; ref:trainer.py:270-384 runs the same arithmetic through autograd, one utterance at a time).

@@ -169,6 +169,25 @@ class GenerateStats(C.Structure):
                 ("prefill_ms", c_f32), ("decode_ms", c_f32)]
 
 
+class BeamOpts(C.Structure):
+    _fields_ = [("eos_ids_host", C.POINTER(c_i32)), ("n_eos", c_i32), ("pad_id", c_i32), ("use_eos", c_i32), ("max_new_tokens", c_i32),
+                ("check_every", c_i32), ("num_beams", c_i32), ("num_return_sequences", c_i32), ("early_stopping", c_i32), ("length_penalty", c_f32)]
+
+
+class BeamState(C.Structure):
+    _fields_ = [("run_score", c_vp), ("next_ids", c_vp), ("src_row", c_vp), ("ctx_len", c_vp), ("hist", c_vp * 2), ("fin_score", c_vp),
+                ("fin_ids", c_vp), ("fin_flag", c_vp), ("fin_len", c_vp), ("open", c_vp), ("seq_done", c_vp), ("step", c_vp), ("len_pen", c_vp)]
+
+
+EARLY_STOPPING = {False: 0, True: 1, "never": 2}      # sl_beam_opts.early_stopping
+
+
+def early_stopping_code(v) -> int:
+    if isinstance(v, (bool, str)) and v in EARLY_STOPPING:
+        return EARLY_STOPPING[v]
+    raise SpeechLLMError(f"early_stopping must be False, True or 'never', not {v!r}")
+
+
 _PROTOS = {
     "sl_last_error": (C.c_char_p, []),
     "sl_version": (c_i32, []),
@@ -280,6 +299,13 @@ _PROTOS = {
                                  c_i32, c_vp, c_vp]),
     "sl_sample_generate": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, c_i32, C.POINTER(c_i32), c_i32, c_i32, c_i32,
                                    c_i32, c_f32, c_i32, c_f32, C.c_uint64, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_f32), c_vp, c_sz, c_vp]),
+    "sl_beam_generate_workspace_bytes": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, C.POINTER(KVCache), C.POINTER(BeamOpts)]),
+    "sl_beam_generate": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(BeamOpts), C.POINTER(c_i32),
+                                 C.POINTER(c_f32), C.POINTER(c_i32), C.POINTER(GenerateStats), c_vp, c_sz, c_vp]),
+    "sl_beam_topk": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sl_beam_step": (c_i32, [C.POINTER(BeamState), c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, C.POINTER(BeamOpts), c_vp]),
+    "sl_kv_beam_staging_bytes": (c_sz, [C.POINTER(KVCache), C.POINTER(LlamaModel), c_i32, c_i32]),
+    "sl_kv_beam_reorder": (c_i32, [C.POINTER(KVCache), C.POINTER(LlamaModel), c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_sz, c_vp]),
     "sl_greedy_generate": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, c_i32,
                                    C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32),
                                    C.POINTER(c_f32), c_vp, c_sz, c_vp]),

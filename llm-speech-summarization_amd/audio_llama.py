@@ -68,7 +68,8 @@ class AudioLlamaForCausalLM:
         # do_sample, so a hub generation_config.json decides; from_pretrained keeps that file's sampling parameters here and its
         # do_sample flag under `hub_do_sample`, but sampling is only used when a caller sets do_sample=True).
         self.generation_config = SimpleNamespace(eos_token_id=list(arch.eos_token_ids), pad_token_id=arch.pad_token_id,
-                                                 do_sample=False, temperature=1.0, top_k=50, top_p=1.0, hub_do_sample=None)
+                                                 do_sample=False, temperature=1.0, top_k=50, top_p=1.0, hub_do_sample=None,
+                                                 num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1)
         self.sample_seed = 0
         self._sd = state_dict
         self.device = torch.device("cpu")
@@ -79,6 +80,8 @@ class AudioLlamaForCausalLM:
         self.model = SimpleNamespace(embed_tokens=_EmbedTokens(self))
         self.last_timings_ms = None
         self.last_generate_stats = None
+        self.last_beam_scores = None       # beam search: (B * num_return_sequences) float32 sequences_scores of the last call
+        self.last_beam_lengths = None      # ... and the hypotheses' lengths (an EOS that ended one is counted)
         if device is not None:
             self.to(device)
 
@@ -262,7 +265,21 @@ class AudioLlamaForCausalLM:
     # -- generation -----------------------------------------------------------------------------
     def generate(self, input_ids=None, inputs_embeds=None, max_new_tokens: int = 256, attention_mask=None, use_eos: bool = True,
                  do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None,
-                 top_p: Optional[float] = None, seed: Optional[int] = None, **unused) -> torch.Tensor:
+                 top_p: Optional[float] = None, seed: Optional[int] = None, num_beams: Optional[int] = None,
+                 length_penalty: Optional[float] = None, early_stopping=None, num_return_sequences: Optional[int] = None,
+                 **unused) -> torch.Tensor:
+        """num_beams > 1: beam search (hf:generation/utils.py _beam_search, sl_beam_generate) -> (B * num_return_sequences, n_cols),
+        n_cols the longest returned hypothesis; `last_beam_scores` / `last_beam_lengths` hold HF's sequences_scores and the lengths."""
+        g = self.generation_config
+        K = int(g.num_beams if num_beams is None else num_beams)
+        R = int(g.num_return_sequences if num_return_sequences is None else num_return_sequences)
+        sampling = bool(g.do_sample if do_sample is None else do_sample)
+        if K < 1:
+            raise L.SpeechLLMError(f"num_beams={K}: must be >= 1")
+        if K > 1 and sampling:
+            raise L.SpeechLLMError("num_beams > 1 with do_sample=True (beam sampling) is not built: use beam search or sampling")
+        if R > K or R < 1:
+            raise L.SpeechLLMError(f"num_return_sequences={R} outside [1, num_beams={K}]" + (" (sampling several sequences per prompt is not built)" if K == 1 else ""))
         w = self._dev()
         a = self.arch
         if inputs_embeds is None:
@@ -271,9 +288,13 @@ class AudioLlamaForCausalLM:
             inputs_embeds = self.model.embed_tokens(input_ids)
         x, lens = self._pack(inputs_embeds.to(self.dtype) if torch.is_tensor(inputs_embeds) else [e.to(self.dtype) for e in inputs_embeds],
                              attention_mask)
-        g = self.generation_config
+        if K > 1:
+            beams = dict(num_beams=K, num_return_sequences=R, length_penalty=float(g.length_penalty if length_penalty is None else length_penalty),
+                         early_stopping=g.early_stopping if early_stopping is None else early_stopping)
+            ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, beams=beams)
+            return ids[:, :n_cols].to(torch.int64)
         sample = None
-        if (g.do_sample if do_sample is None else do_sample):
+        if sampling:
             # hf:generation/utils.py logits warpers: temperature, top-k (HF default 50), top-p, then one draw per row
             if seed is None:
                 seed, self.sample_seed = self.sample_seed, self.sample_seed + 1
@@ -283,18 +304,28 @@ class AudioLlamaForCausalLM:
         return ids[:, :n_cols].to(torch.int64)
 
     def generate_packed(self, x: torch.Tensor, lens: Sequence[int], max_new_tokens: int, use_eos: bool = True, sample: Optional[dict] = None,
-                        shared_prefix: int = 0, row_limits: Optional[Sequence[int]] = None, compact: bool = True, check_every: int = 4):
+                        shared_prefix: int = 0, row_limits: Optional[Sequence[int]] = None, compact: bool = True, check_every: int = 4,
+                        beams: Optional[dict] = None):
         """x: packed prompt embeddings (sum S_i, h) on the GPU (overwritten).  Returns (int32 (B, max_new) host tensor, n_cols).
         shared_prefix = P: the caller's promise that the first P rows of every sequence are the same rows (one prompt template in
         front of the audio, ref:inference.py:95-113) — the batched decode attention then reads those P cache positions from slot 0
         (sl_kv_cache.shared_prefix); ids and logits are bit for bit those of P = 0.
         row_limits: one token budget per sequence (a per-request max_new_tokens; the row then finishes like a row that emitted EOS).
         compact: with EOS / budgets on, the batch is compacted as its rows finish (sl_generate_opts.compact) — the decode step then
-        costs what the LIVE rows cost; per-sequence results are those of the uncompacted batch (`last_generate_stats` has the counts)."""
+        costs what the LIVE rows cost; per-sequence results are those of the uncompacted batch (`last_generate_stats` has the counts).
+        beams: dict(num_beams=K, length_penalty=1.0, early_stopping=False, num_return_sequences=1) -> beam search (sl_beam_generate) on
+        B * K decode rows: returns (int32 (B * R, max_new) ids, the longest hypothesis' length) and sets `last_beam_scores` /
+        `last_beam_lengths`; not with row_limits or sampling; `compact` is ignored (done sequences keep their rows)."""
         w = self._dev()
         a = self.arch
         lib = L.lib()
         B = len(lens)
+        if beams is not None:
+            if row_limits is not None:
+                raise L.SpeechLLMError("row_limits and beams together are not built: a beam search has one max_new_tokens for the call")
+            if sample is not None:
+                raise L.SpeechLLMError("sampling and beams together (beam sampling) are not built")
+            return self._beam_packed(x, lens, max_new_tokens, use_eos, shared_prefix, check_every, beams)
         if B > L.MAX_DECODE_BATCH:
             raise L.SpeechLLMError(f"{B} sequences in one generate call; the library takes {L.MAX_DECODE_BATCH} (split the batch: sequences are independent)")
         if max(lens) + max_new_tokens > self.max_ctx:
@@ -335,3 +366,55 @@ class AudioLlamaForCausalLM:
                                     "final_rows": int(st.final_rows), "row_steps": int(st.row_steps), "weight_format": fmt_name}
         ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B, max_new_tokens)
         return ids, int(st.n_steps)
+
+    def _beam_packed(self, x, lens, max_new_tokens, use_eos, shared_prefix, check_every, beams):
+        lib = L.lib()
+        B = len(lens)
+        unknown = set(beams) - {"num_beams", "length_penalty", "early_stopping", "num_return_sequences"}
+        if unknown:
+            raise L.SpeechLLMError(f"beams: unknown keys {sorted(unknown)}")
+        K, R = int(beams.get("num_beams", 1)), int(beams.get("num_return_sequences", 1))
+        if not 1 <= K <= 8:
+            raise L.SpeechLLMError(f"num_beams={K} outside [1, 8]")
+        if not 1 <= R <= K:
+            raise L.SpeechLLMError(f"num_return_sequences={R} outside [1, num_beams={K}]")
+        if B * K > L.MAX_DECODE_BATCH:
+            raise L.SpeechLLMError(f"{B} sequences x {K} beams = {B * K} decode rows; the library takes {L.MAX_DECODE_BATCH} (split the batch)")
+        if max(lens) + max_new_tokens > self.max_ctx:
+            raise L.SpeechLLMError(f"prompt ({max(lens)}) + max_new_tokens ({max_new_tokens}) exceeds max_ctx={self.max_ctx}")
+        if not 0 <= shared_prefix <= min(lens):
+            raise L.SpeechLLMError(f"shared_prefix={shared_prefix} outside [0, shortest prompt={min(lens)}]")
+        kv = self._kv_cache(B * K, shared_prefix)
+        cu = [0]
+        for n in lens:
+            cu.append(cu[-1] + int(n))
+        cu_c = (C.c_int32 * (B + 1))(*cu)
+        gen = self.generation_config
+        eos = list(gen.eos_token_id) if isinstance(gen.eos_token_id, (list, tuple)) else ([] if gen.eos_token_id is None else [gen.eos_token_id])
+        use_eos = bool(use_eos and len(eos) > 0)
+        pad = gen.pad_token_id if gen.pad_token_id is not None else (eos[0] if eos else 0)
+        eos_c = (C.c_int32 * max(1, len(eos)))(*eos)
+        o = L.BeamOpts()
+        o.eos_ids_host, o.n_eos, o.pad_id, o.use_eos = eos_c, len(eos), int(pad), int(use_eos)
+        o.max_new_tokens, o.check_every = int(max_new_tokens), int(check_every)
+        o.num_beams, o.num_return_sequences = K, R
+        o.early_stopping = L.early_stopping_code(beams.get("early_stopping", False))
+        o.length_penalty = float(beams.get("length_penalty", 1.0))
+        out = (C.c_int32 * (B * R * max_new_tokens))()
+        scores = (C.c_float * (B * R))()
+        lengths = (C.c_int32 * (B * R))()
+        st = L.GenerateStats()
+        struct, fmt_name = self._struct_for(B * K)
+        nbytes = lib.sl_beam_generate_workspace_bytes(C.byref(struct), x.shape[0], B, C.byref(kv), C.byref(o))
+        if nbytes == 0:
+            L.check(-1, "sl_beam_generate_workspace_bytes")
+        ws = self._workspace(nbytes)
+        L.check(lib.sl_beam_generate(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, scores, lengths, C.byref(st), ws.data_ptr(),
+                                     ws.numel(), L.stream_ptr()), "sl_beam_generate")
+        self.last_timings_ms = (st.prefill_ms, st.decode_ms)
+        self.last_generate_stats = {"rows": B * K, "n_steps": int(st.n_steps), "decode_launches": int(st.decode_launches), "compactions": 0,
+                                    "final_rows": int(st.final_rows), "row_steps": int(st.row_steps), "weight_format": fmt_name, "num_beams": K}
+        self.last_beam_scores = torch.frombuffer(scores, dtype=torch.float32).clone()
+        self.last_beam_lengths = torch.frombuffer(lengths, dtype=torch.int32).clone()
+        ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B * R, max_new_tokens)
+        return ids, int(self.last_beam_lengths.max())

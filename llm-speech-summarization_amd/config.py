@@ -77,3 +77,22 @@ def runtime_dtype(config) -> "torch.dtype":
     if name not in _RUNTIME_DTYPES:
         raise ValueError(f"runtime.dtype: {name!r} is not one of {sorted(_RUNTIME_DTYPES)}")
     return getattr(torch, _RUNTIME_DTYPES[name])
+
+
+def runtime_beams(config):
+    """The beam-search options a config's `runtime` section names: optional `num_beams` (default 1 = greedy), `length_penalty` (1.0) and
+    `early_stopping` (false / true / "never") -> None for greedy, else the dict the `beams` keyword of generate_packed takes."""
+    rt = config.get("runtime", {}) if hasattr(config, "get") else {}
+    rt = rt or {}
+    k = rt.get("num_beams", 1)
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 8:
+        raise ValueError(f"runtime.num_beams: {k!r} is not an integer in [1, 8]")
+    lp = rt.get("length_penalty", 1.0)
+    if isinstance(lp, bool) or not isinstance(lp, (int, float)) or lp != lp or lp in (float("inf"), float("-inf")):
+        raise ValueError(f"runtime.length_penalty: {lp!r} is not a finite number")
+    es = rt.get("early_stopping", False)
+    if not (isinstance(es, bool) or es == "never"):
+        raise ValueError(f"runtime.early_stopping: {es!r} is not one of [False, True, 'never']")
+    if k == 1:
+        return None
+    return dict(num_beams=int(k), length_penalty=float(lp), early_stopping=es, num_return_sequences=1)

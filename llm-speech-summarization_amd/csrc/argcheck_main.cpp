@@ -338,6 +338,35 @@ int main() {
     EXPECT(sl_allreduce_sum(nullptr, id, 4, SL_F32, nullptr) == SL_ERR_ARG, "sl_allreduce_sum(no communicator)");
     EXPECT(sl_comm_destroy(nullptr) == 0 && sl_comm_rank(nullptr) == -1 && sl_comm_world(nullptr) == -1, "sl_comm_destroy(null) is a no-op");
   }
+  {   // beam search: every limit is answered before any launch, and the workspace arithmetic runs under the sanitizers
+    sl_llama_model bm;
+    memset(&bm, 0, sizeof(bm));
+    bm.dtype = SL_BF16; bm.hidden = 3072; bm.n_layers = 28; bm.n_heads = 24; bm.n_kv_heads = 8; bm.head_dim = 128; bm.ffn = 8192; bm.vocab = 128256; bm.rope_len = 448;
+    sl_kv_cache bkv;
+    memset(&bkv, 0, sizeof(bkv));
+    bkv.slots = 1024; bkv.max_ctx = 448;
+    const int32_t eos[3] = {1, 2, 3};
+    sl_beam_opts bo;
+    memset(&bo, 0, sizeof(bo));
+    bo.eos_ids_host = eos; bo.n_eos = 3; bo.use_eos = 1; bo.max_new_tokens = 256; bo.num_beams = 4; bo.num_return_sequences = 1; bo.length_penalty = 1.0f;
+    const size_t need = sl_beam_generate_workspace_bytes(&bm, 137 * 256, 256, &bkv, &bo);
+    const size_t stage = sl_kv_beam_staging_bytes(&bkv, &bm, 1024, 256);
+    EXPECT(stage == (size_t)2 * 1024 * 28 * 8 * 256 * 128 * 2 && need > stage, "beam workspace holds the staging area");
+    bo.num_beams = 9;
+    EXPECT(sl_beam_generate_workspace_bytes(&bm, 137, 1, &bkv, &bo) == 0 && sl_last_error()[0] != 0, "num_beams 9");
+    EXPECT_ARG_ERROR(sl_beam_generate(&bm, &bkv, nullptr, nullptr, 1, &bo, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
+    bo.num_beams = 8; bo.n_eos = 8;                                                                            // M = 72 > 64
+    EXPECT(sl_beam_generate(&bm, &bkv, nullptr, nullptr, 1, &bo, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr) == SL_ERR_UNSUPPORTED, "M > 64");
+    bo.n_eos = 3; bo.num_return_sequences = 9;
+    EXPECT_ARG_ERROR(sl_beam_generate(&bm, &bkv, nullptr, nullptr, 1, &bo, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
+    bo.num_return_sequences = 1;
+    EXPECT_ARG_ERROR(sl_beam_generate(&bm, &bkv, nullptr, nullptr, 129, &bo, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr));      // 1 032 rows > 1 024 slots
+    EXPECT_ARG_ERROR(sl_beam_topk((const float*)ws, 4, 100, nullptr, 65, (float*)ws, (int32_t*)ws, nullptr));
+    sl_beam_state bs;
+    memset(&bs, 0, sizeof(bs));
+    EXPECT_ARG_ERROR(sl_beam_step(&bs, (const float*)ws, (const int32_t*)ws, 2, 8, 32, 0, &bo, nullptr));     // null state fields
+    EXPECT_ARG_ERROR(sl_kv_beam_reorder(&bkv, &bm, (const int32_t*)ws, (const int32_t*)ws, (const int32_t*)ws, 8, 16, ws, 16, nullptr));   // null cache
+  }
   if (g_fail == 0) printf("argcheck ok\n");
   return g_fail == 0 ? 0 : 1;
 }

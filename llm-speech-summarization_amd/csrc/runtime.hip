@@ -1,6 +1,7 @@
 // runtime.hip — C++ host runtime above the kernels: HuBERT encoder forward over a batch of utterances,
 // Llama prefill / decode step / greedy generation (decode step captured once into a hipGraph and
 // replayed, all per-step state lives on the device).  Workspace is carved from one caller-owned buffer.
+#include <cmath>
 #include <vector>
 
 #include "common.h"
@@ -748,11 +749,14 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
   return 0;
 }
 
-extern "C" int sl_llama_prefill(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
-                                float* logits, int32_t* ctx_len_dev, void* hidden_taps, void* workspace, size_t workspace_bytes,
-                                sl_stream stream) {
+// slot_stride: sequence s is written to cache slot s * slot_stride (1 for every public caller; the beam search prefills each prompt once,
+// into the slot of its first beam — without the shared-prefix dedupe, whose broadcast assumes consecutive slots)
+static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                              float* logits, int32_t* ctx_len_dev, void* hidden_taps, void* workspace, size_t workspace_bytes,
+                              sl_stream stream, int slot_stride) {
   SL_TRY(llama_check(m, kv));
-  SL_CHECK_ARG(x && cu_seqlens_host && logits && ctx_len_dev && workspace && nseq > 0 && nseq <= kv->slots, "sl_llama_prefill: bad arguments");
+  SL_CHECK_ARG(x && cu_seqlens_host && logits && ctx_len_dev && workspace && nseq > 0 && slot_stride >= 1 && (int64_t)nseq * slot_stride <= kv->slots,
+               "sl_llama_prefill: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n_tok = cu_seqlens_host[nseq];
   const int dt = m->dtype, H = m->hidden;
@@ -771,7 +775,7 @@ extern "C" int sl_llama_prefill(const sl_llama_model* m, const sl_kv_cache* kv, 
   // logits).  Not with hidden_taps (they are per row of the caller's layout) or when a sequence is nothing but the prefix.
   // Not with e4m3 rows either: that prefill reads K / V from its own qkv rows, not from the cache, so there is nothing to broadcast
   // (decode still reads the positions below shared_prefix from slot 0).
-  int P = (kv->shared_prefix > 0 && nseq > 1 && !hidden_taps && sl_env().prefill_share_prefix && kv->reserved != SL_KV_FP8_E4M3) ? kv->shared_prefix : 0;
+  int P = (kv->shared_prefix > 0 && nseq > 1 && !hidden_taps && sl_env().prefill_share_prefix && kv->reserved != SL_KV_FP8_E4M3 && slot_stride == 1) ? kv->shared_prefix : 0;
   for (int s = 0; s < nseq; ++s) {
     const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
     SL_CHECK_ARG(len > 0 && len <= kv->max_ctx, "sl_llama_prefill: sequence %d length %d outside (0, max_ctx=%d]", s, len, kv->max_ctx);
@@ -807,8 +811,8 @@ extern "C" int sl_llama_prefill(const sl_llama_model* m, const sl_kv_cache* kv, 
   } else {
     for (int s = 0; s < nseq; ++s) {
       const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
-      for (int t = 0; t < len; ++t) { tseq[cu_seqlens_host[s] + t] = s; tpos[cu_seqlens_host[s] + t] = t; }
-      cuk[s] = s * m->n_kv_heads * kv->max_ctx;  // first cache row of the sequence (rows of D elements, head-major inside)
+      for (int t = 0; t < len; ++t) { tseq[cu_seqlens_host[s] + t] = s * slot_stride; tpos[cu_seqlens_host[s] + t] = t; }
+      cuk[s] = s * slot_stride * m->n_kv_heads * kv->max_ctx;  // first cache row of the sequence (rows of D elements, head-major inside)
       kl[s] = len; ctx[s] = len;
       cuq[s] = cu_seqlens_host[s];
       last_row[s] = cu_seqlens_host[s + 1] - 1;
@@ -841,6 +845,12 @@ extern "C" int sl_llama_prefill(const sl_llama_model* m, const sl_kv_cache* kv, 
   SL_TRY(sl_rmsnorm(w.last, w.last, m->final_norm, nseq, H, m->rms_eps, dt, stream));
   SL_TRY(gemm(dt, w.last, H, m->lm_head, H, logits, m->vocab, nullptr, nullptr, 0, nseq, m->vocab, H, SL_ACT_NONE, 1, st));
   return 0;
+}
+
+extern "C" int sl_llama_prefill(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                                float* logits, int32_t* ctx_len_dev, void* hidden_taps, void* workspace, size_t workspace_bytes,
+                                sl_stream stream) {
+  return llama_prefill_impl(m, kv, x, cu_seqlens_host, nseq, logits, ctx_len_dev, hidden_taps, workspace, workspace_bytes, stream, 1);
 }
 
 // decode-step state carved from the tail of the workspace by sl_greedy_generate, or supplied by the caller
@@ -940,6 +950,8 @@ struct DecodeGraphKey {
   int sample, top_k;
   float temperature, top_p;
   uint64_t seed;
+  int beam_k, beam_m, beam_es;     // beam search (0 in every other graph: a beam graph and a greedy graph never share a key)
+  float beam_lp;
 };
 struct DecodeGraphEntry { DecodeGraphKey key; hipGraph_t graph; hipGraphExec_t exec; uint64_t stamp; };
 static thread_local std::vector<DecodeGraphEntry> g_graphs;
@@ -1319,4 +1331,240 @@ extern "C" int sl_sample_generate(const sl_llama_model* m, const sl_kv_cache* kv
   o.max_new_tokens = max_new_tokens; o.eos_ids_host = eos_ids_host; o.n_eos = n_eos; o.pad_id = pad_id; o.use_eos = use_eos; o.check_every = check_every;
   o.sample = 1; o.temperature = temperature; o.top_k = top_k; o.top_p = top_p; o.seed = seed;
   return generate_compat(m, kv, x, cu_seqlens_host, nseq, o, out_ids_host, n_steps_host, timings_ms_host, workspace, workspace_bytes, stream);
+}
+
+// ================================================================================================
+// Beam search (speechllm.h sl_beam_generate; kernels in beam.hip)
+// ================================================================================================
+int sl_beam_topk_impl(const float* logits, int32_t rows, int32_t V, const float* row_score, int32_t M, float* cand_score, int32_t* cand_token,
+                      hipStream_t st);
+int sl_beam_step_impl(const sl_beam_state* s, const float* cand_score, const int32_t* cand_token, int32_t nseq, int32_t K, int32_t M, int32_t first,
+                      const sl_beam_opts* o, hipStream_t st);
+int sl_beam_m(int num_beams, int n_eos);
+size_t sl_kv_beam_staging_bytes_impl(const sl_kv_cache* kv, const sl_llama_model* m, int32_t rows, int32_t max_span);
+int sl_kv_beam_reorder_impl(const sl_kv_cache* kv, const sl_llama_model* m, const int32_t* src_row, const int32_t* prompt_len, const int32_t* ctx_len,
+                            int32_t rows, int32_t max_span, void* staging, size_t staging_bytes, hipStream_t st);
+
+struct BeamWs {
+  float *logits, *cand_score, *zero_score, *len_pen;
+  void* xdec;
+  int32_t *cand_token, *prompt_len;
+  KvMove* moves;
+  sl_beam_state st;
+  void* staging;
+  size_t staging_bytes;
+  void* scratch;
+  size_t scratch_off;
+};
+
+// generation state first, then the staging area of the cache re-ordering, then the prefill / decode scratch
+static size_t beam_carve(const sl_llama_model* m, const sl_kv_cache* kv, int64_t n_tok, int nseq, int K, int M, int max_new, void* base, size_t cap, BeamWs& b) {
+  const size_t R = (size_t)nseq * K;
+  Carver c(base, cap);
+  b.logits = (float*)c.take(R * m->vocab * sizeof(float));
+  b.xdec = c.take(R * m->hidden * sl_dtype_size(m->dtype));
+  b.cand_score = (float*)c.take(R * M * sizeof(float));
+  b.cand_token = (int32_t*)c.take(R * M * sizeof(int32_t));
+  b.zero_score = (float*)c.take((size_t)nseq * sizeof(float));
+  b.len_pen = (float*)c.take((size_t)max_new * sizeof(float));
+  b.prompt_len = (int32_t*)c.take(R * sizeof(int32_t));
+  b.moves = (KvMove*)c.take(R * sizeof(KvMove));
+  b.st.run_score = (float*)c.take(R * sizeof(float));
+  b.st.next_ids = (int32_t*)c.take(R * sizeof(int32_t));
+  b.st.src_row = (int32_t*)c.take(R * sizeof(int32_t));
+  b.st.ctx_len = (int32_t*)c.take(R * sizeof(int32_t));
+  b.st.hist[0] = (int32_t*)c.take(R * max_new * sizeof(int32_t));
+  b.st.hist[1] = (int32_t*)c.take(R * max_new * sizeof(int32_t));
+  b.st.fin_score = (float*)c.take(R * sizeof(float));
+  b.st.fin_ids = (int32_t*)c.take(R * max_new * sizeof(int32_t));
+  b.st.fin_flag = (int32_t*)c.take(R * sizeof(int32_t));
+  b.st.fin_len = (int32_t*)c.take(R * sizeof(int32_t));
+  b.st.open = (int32_t*)c.take((size_t)nseq * sizeof(int32_t));
+  b.st.seq_done = (int32_t*)c.take((size_t)nseq * sizeof(int32_t));
+  b.st.step = (int32_t*)c.take((size_t)nseq * sizeof(int32_t));
+  b.st.len_pen = b.len_pen;
+  b.staging_bytes = K > 1 ? sl_kv_beam_staging_bytes_impl(kv, m, (int)R, max_new) : 0;
+  b.staging = c.take(b.staging_bytes);
+  c.take(0);
+  b.scratch_off = c.off;
+  b.scratch = base ? (unsigned char*)base + c.off : nullptr;
+  LlamaWs w;
+  return c.off + llama_carve(m, n_tok > (int64_t)R ? n_tok : (int64_t)R, (int)R, nullptr, 0, w) + 256;
+}
+
+// every limit of sl_beam_generate, before any launch (also what sl_beam_generate_workspace_bytes refuses)
+static int beam_check(const char* who, const sl_llama_model* m, const sl_kv_cache* kv, int nseq, const sl_beam_opts* o, int* M_out) {
+  SL_CHECK_ARG(m && kv && o, "%s: null model, cache or options", who);
+  SL_CHECK_ARG(o->num_beams >= 1 && o->num_beams <= 8, "%s: num_beams %d outside [1, 8]", who, o->num_beams);
+  const int n_eos = o->use_eos ? o->n_eos : 0;
+  SL_CHECK_ARG(n_eos >= 0 && n_eos <= 8 && (n_eos == 0 || o->eos_ids_host != nullptr), "%s: 0..8 eos ids", who);
+  const int M = sl_beam_m(o->num_beams, n_eos);
+  if (M > 64) {
+    sl_set_error("%s: max(2, 1 + n_eos) * num_beams = %d candidates per step, the kernels keep 64 (num_beams %d, %d eos ids)", who, M, o->num_beams, n_eos);
+    return SL_ERR_UNSUPPORTED;
+  }
+  SL_CHECK_ARG(M <= m->vocab, "%s: %d candidates per step exceed the vocabulary (%d)", who, M, m->vocab);
+  SL_CHECK_ARG(nseq > 0 && (int64_t)nseq * o->num_beams <= SL_MAX_DECODE_BATCH, "%s: nseq * num_beams = %lld rows outside (0, %d]", who,
+               (long long)nseq * o->num_beams, SL_MAX_DECODE_BATCH);
+  SL_CHECK_ARG((int64_t)nseq * o->num_beams <= kv->slots, "%s: nseq * num_beams = %lld rows need as many cache slots (kv->slots = %d)", who,
+               (long long)nseq * o->num_beams, kv->slots);
+  SL_CHECK_ARG(o->num_return_sequences >= 1 && o->num_return_sequences <= o->num_beams, "%s: num_return_sequences %d outside [1, num_beams = %d]", who,
+               o->num_return_sequences, o->num_beams);
+  SL_CHECK_ARG(std::isfinite(o->length_penalty), "%s: length_penalty must be finite", who);
+  SL_CHECK_ARG(o->early_stopping >= 0 && o->early_stopping <= 2, "%s: early_stopping %d (0 = False, 1 = True, 2 = \"never\")", who, o->early_stopping);
+  SL_CHECK_ARG(o->max_new_tokens > 0 && o->max_new_tokens <= kv->max_ctx, "%s: max_new_tokens %d outside (0, max_ctx = %d]", who, o->max_new_tokens, kv->max_ctx);
+  *M_out = M;
+  return 0;
+}
+
+extern "C" size_t sl_beam_generate_workspace_bytes(const sl_llama_model* m, int64_t n_tok, int32_t nseq, const sl_kv_cache* kv, const sl_beam_opts* o) {
+  int M = 0;
+  if (beam_check("sl_beam_generate_workspace_bytes", m, kv, nseq, o, &M) != 0) return 0;
+  BeamWs b;
+  return beam_carve(m, kv, n_tok, nseq, o->num_beams, M, o->max_new_tokens, nullptr, 0, b);
+}
+
+extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                                const sl_beam_opts* o, int32_t* out_ids_host, float* out_scores_host, int32_t* out_lens_host,
+                                sl_generate_stats* stats, void* workspace, size_t workspace_bytes, sl_stream stream) {
+  int M = 0;
+  SL_TRY(beam_check("sl_beam_generate", m, kv, nseq, o, &M));
+  SL_TRY(llama_check(m, kv));
+  SL_CHECK_ARG(x && cu_seqlens_host && out_ids_host && out_scores_host && out_lens_host && workspace, "sl_beam_generate: null buffer");
+  const int K = o->num_beams, R = nseq * K, Rn = o->num_return_sequences, max_new = o->max_new_tokens;
+  const int n_eos = o->use_eos ? o->n_eos : 0;
+  SL_TRY(llama_wdec_check("sl_beam_generate", m, R));
+  for (int s = 0; s < nseq; ++s) {
+    const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
+    SL_CHECK_ARG(len > 0 && len + max_new <= kv->max_ctx, "sl_beam_generate: prompt %d (%d tokens) + %d new tokens exceeds max_ctx %d", s, len, max_new, kv->max_ctx);
+    SL_CHECK_ARG(kv->shared_prefix <= len, "sl_beam_generate: kv cache shared_prefix %d exceeds prompt %d (%d tokens)", kv->shared_prefix, s, len);
+  }
+  const int64_t n_tok = cu_seqlens_host[nseq];
+  BeamWs b;
+  const size_t need = beam_carve(m, kv, n_tok, nseq, K, M, max_new, workspace, workspace_bytes, b);
+  SL_CHECK_ARG(need <= workspace_bytes, "sl_beam_generate: workspace %zu B < required %zu B", workspace_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t scratch_bytes = workspace_bytes - b.scratch_off;
+  sl_beam_opts oo = *o;           // the options the kernels see: EOS ids only when in use
+  oo.n_eos = n_eos; oo.use_eos = n_eos > 0 ? 1 : 0;
+
+  // ---- initial state
+  std::vector<float> run0(R, -1.0e9f), fin0(R, -1.0e9f), lp(max_new);
+  std::vector<int32_t> ctx0(R), ones(nseq, 1);
+  std::vector<KvMove> moves;
+  for (int s = 0; s < nseq; ++s) {
+    const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
+    run0[(size_t)s * K] = 0.f;
+    for (int j = 0; j < K; ++j) {
+      ctx0[(size_t)s * K + j] = len;
+      if (j > 0) moves.push_back(KvMove{s * K, s * K + j, len, 0});
+    }
+  }
+  for (int t = 0; t < max_new; ++t) lp[t] = (float)pow((double)(t + 1), (double)o->length_penalty);
+  hipEvent_t ev[3];
+  for (auto& e : ev) SL_HIP(hipEventCreate(&e));
+  SL_HIP(hipEventRecord(ev[0], st));
+  // prefill: each prompt once, into the slot of its first beam (it writes nseq context lengths: overwritten below with the rows')
+  SL_TRY(llama_prefill_impl(m, kv, x, cu_seqlens_host, nseq, b.logits, b.st.ctx_len, nullptr, b.scratch, scratch_bytes, stream, K));
+  SL_HIP(hipMemcpyAsync(b.st.run_score, run0.data(), R * sizeof(float), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(b.st.fin_score, fin0.data(), R * sizeof(float), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(b.st.ctx_len, ctx0.data(), R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(b.prompt_len, ctx0.data(), R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(b.len_pen, lp.data(), max_new * sizeof(float), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(b.st.open, ones.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemsetAsync(b.zero_score, 0, nseq * sizeof(float), st));
+  SL_HIP(hipMemsetAsync(b.st.seq_done, 0, nseq * sizeof(int32_t), st));
+  SL_HIP(hipMemsetAsync(b.st.step, 0, nseq * sizeof(int32_t), st));
+  SL_HIP(hipMemsetAsync(b.st.fin_flag, 0, R * sizeof(int32_t), st));
+  SL_HIP(hipMemsetAsync(b.st.fin_len, 0, R * sizeof(int32_t), st));
+  SL_HIP(hipMemsetAsync(b.st.hist[0], 0, (size_t)R * max_new * sizeof(int32_t), st));
+  SL_HIP(hipMemsetAsync(b.st.hist[1], 0, (size_t)R * max_new * sizeof(int32_t), st));
+  SL_HIP(hipMemsetAsync(b.st.fin_ids, 0, (size_t)R * max_new * sizeof(int32_t), st));
+  if (!moves.empty()) {      // the prompt's K / V rows to the K - 1 sibling slots: sources (s * K) and destinations are disjoint
+    const int row_vec = (int)(m->head_dim * kv_elem_bytes(m, kv) / 16);
+    SL_HIP(hipMemcpyAsync(b.moves, moves.data(), moves.size() * sizeof(KvMove), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(kv_move_kernel, dim3((unsigned)moves.size(), m->n_layers * m->n_kv_heads), dim3(256), 0, st, (uint4*)kv->k_cache, (uint4*)kv->v_cache,
+                       b.moves, m->n_kv_heads, kv->slots, kv->max_ctx, row_vec);
+    SL_CHECK_LAUNCH("kv_move (beam prompt)");
+  }
+  // step 0: the prefill logits are beam 0's
+  SL_TRY(sl_beam_topk_impl(b.logits, nseq, m->vocab, b.zero_score, M, b.cand_score, b.cand_token, st));
+  SL_TRY(sl_beam_step_impl(&b.st, b.cand_score, b.cand_token, nseq, K, M, 1, &oo, st));
+  SL_HIP(hipEventRecord(ev[1], st));
+  SL_HIP(hipStreamSynchronize(st));     // the host vectors above leave scope only after their copies ran
+
+  int steps_done = 1, launches = 0;
+  std::vector<int32_t> h_done(nseq, 0);
+  if (max_new > 1) {
+    LlamaWs w;
+    llama_carve(m, R, R, b.scratch, scratch_bytes, w);
+    if (w.split && w.split_bytes >= 8192) SL_HIP(hipMemsetAsync(w.split, 0, 8192, st));
+    SL_TRY(sl_attn_decode_split_zero_counters(w.part, R, m->n_heads, m->n_kv_heads, kv->max_ctx, st));
+    hipLaunchKernelGGL(iota_kernel, dim3((R + 255) / 256), dim3(256), 0, st, w.tok_seq, R);
+    SL_CHECK_LAUNCH("iota");
+    DecodeGraphKey key;
+    memset(&key, 0, sizeof(key));
+    key.model = m; key.layers = m->layers; key.w0 = m->n_layers > 0 ? m->layers[0].wqkv_dec : nullptr; key.lm = m->lm_head_dec ? m->lm_head_dec : m->lm_head;
+    key.embed = m->embed; key.kc = kv->k_cache; key.vc = kv->v_cache; key.ws = workspace; key.ws_bytes = workspace_bytes;
+    key.B = R; key.B0 = nseq; key.max_new = max_new; key.use_eos = oo.use_eos; key.n_eos = n_eos; key.pad = o->pad_id; key.max_ctx = kv->max_ctx;
+    key.slots = kv->slots; key.shared_prefix = kv->shared_prefix; key.dtype = m->dtype; key.n_layers = m->n_layers; key.vocab = m->vocab;
+    key.fused = m->dec_fused_norm | (sl_env().decode_tiled << 8) | ((sl_env().attn_decode_ks & 127) << 9) | ((kv->reserved & 3) << 18) | ((m->reserved & 3) << 20);
+    key.content = model_content_hash(m);
+    SL_HIP(hipGetDevice(&key.device));
+    for (int i = 0; i < n_eos && i < 8; ++i) key.eos[i] = o->eos_ids_host[i];
+    key.beam_k = K; key.beam_m = M; key.beam_es = o->early_stopping; key.beam_lp = o->length_penalty;
+    hipGraphExec_t exec = decode_graph_lookup(key);
+    if (!exec) {
+      hipGraph_t graph = nullptr;
+      static thread_local hipStream_t cap_by_dev[SL_MAX_DEVICES] = {};
+      SL_CHECK_ARG(key.device >= 0 && key.device < SL_MAX_DEVICES, "sl_beam_generate: device index %d", key.device);
+      hipStream_t& cap = cap_by_dev[key.device];
+      if (!cap) SL_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
+      SL_HIP(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
+      int rc = decode_step(m, kv, b.st.next_ids, b.st.ctx_len, R, b.logits, b.xdec, w, cap, false);
+      if (rc == 0) rc = sl_beam_topk_impl(b.logits, R, m->vocab, b.st.run_score, M, b.cand_score, b.cand_token, cap);
+      if (rc == 0) rc = sl_beam_step_impl(&b.st, b.cand_score, b.cand_token, nseq, K, M, 0, &oo, cap);
+      if (rc == 0 && K > 1) rc = sl_kv_beam_reorder_impl(kv, m, b.st.src_row, b.prompt_len, b.st.ctx_len, R, max_new, b.staging, b.staging_bytes, cap);
+      hipError_t ce = hipStreamEndCapture(cap, &graph);
+      if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+      if (ce != hipSuccess) { sl_set_error("hipStreamEndCapture: %s", hipGetErrorString(ce)); return SL_ERR_LAUNCH; }
+      SL_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+      decode_graph_store(key, graph, exec);
+    }
+    const int check_every = o->check_every > 0 ? o->check_every : 16;
+    while (steps_done < max_new) {
+      SL_HIP(hipGraphLaunch(exec, st));
+      ++steps_done; ++launches;
+      if (steps_done % check_every != 0 || steps_done >= max_new) continue;
+      SL_HIP(hipMemcpyAsync(h_done.data(), b.st.seq_done, nseq * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      SL_HIP(hipStreamSynchronize(st));
+      bool all = true;
+      for (int s = 0; s < nseq; ++s) all = all && h_done[s] != 0;
+      if (all) break;
+    }
+  }
+  SL_HIP(hipEventRecord(ev[2], st));
+  std::vector<int32_t> h_ids((size_t)R * max_new), h_len(R);
+  std::vector<float> h_sc(R);
+  SL_HIP(hipMemcpyAsync(h_ids.data(), b.st.fin_ids, h_ids.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  SL_HIP(hipMemcpyAsync(h_len.data(), b.st.fin_len, R * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  SL_HIP(hipMemcpyAsync(h_sc.data(), b.st.fin_score, R * sizeof(float), hipMemcpyDeviceToHost, st));
+  SL_HIP(hipStreamSynchronize(st));
+  for (int s = 0; s < nseq; ++s)
+    for (int r = 0; r < Rn; ++r) {
+      const size_t src = (size_t)s * K + r, dst = (size_t)s * Rn + r;
+      int len = h_len[src];
+      len = len < 0 ? 0 : (len > max_new ? max_new : len);
+      for (int t = 0; t < max_new; ++t) out_ids_host[dst * max_new + t] = t < len ? h_ids[src * max_new + t] : o->pad_id;
+      out_scores_host[dst] = h_sc[src];
+      out_lens_host[dst] = len;
+    }
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+    stats->n_steps = steps_done; stats->decode_launches = launches; stats->final_rows = R; stats->row_steps = (int64_t)launches * R;
+    SL_HIP(hipEventElapsedTime(&stats->prefill_ms, ev[0], ev[1]));
+    SL_HIP(hipEventElapsedTime(&stats->decode_ms, ev[1], ev[2]));
+  }
+  for (auto& e : ev) (void)hipEventDestroy(e);
+  return 0;
 }

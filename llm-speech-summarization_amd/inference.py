@@ -65,9 +65,12 @@ class LLMSpeechTextInference():
         if llm.weight_format != L.weight_format_code(weight_dtype) and weight_dtype is not None:
             raise L.SpeechLLMError("weight_dtype differs from the decode-weight format of the llm that was passed in: construct that llm with the same weight_dtype")
         self.llm = llm.eval().to(self.device)
+        # runtime.num_beams / length_penalty / early_stopping of the config (absent in the shipped yamls: greedy) -> beam search
+        from .config import runtime_beams
+        self.beams = runtime_beams(self.config)
 
     def generate_llm_response(self, inputs_embeds, max_new_tokens=256) -> List[str]:
-        generate_ids = self.llm.generate(input_ids=None, inputs_embeds=inputs_embeds, max_new_tokens=max_new_tokens)
+        generate_ids = self.llm.generate(input_ids=None, inputs_embeds=inputs_embeds, max_new_tokens=max_new_tokens, **(self.beams or {}))
         self.last_generate_ids = generate_ids
         return self.llm_tokenizer.batch_decode(generate_ids, skip_special_tokens=True, clean_up_tokenization_spaces=True)
 
@@ -129,8 +132,9 @@ class LLMSpeechTextInference():
             return [self.generate_audio_response(a, texts[i], max_new_tokens) for i, a in enumerate(audios)]
         out: List[str] = []
         ids_all = []
-        for lo_ in range(0, n, L.MAX_DECODE_BATCH):
-            ids = self._generate_chunk(audios[lo_:lo_ + L.MAX_DECODE_BATCH], texts[lo_:lo_ + L.MAX_DECODE_BATCH], max_new_tokens)
+        chunk = L.MAX_DECODE_BATCH // (self.beams["num_beams"] if self.beams else 1)      # a generate call is sized by its decode ROWS: utterances x beams
+        for lo_ in range(0, n, chunk):
+            ids = self._generate_chunk(audios[lo_:lo_ + chunk], texts[lo_:lo_ + chunk], max_new_tokens)
             ids_all.append(ids)
             out += self.llm_tokenizer.batch_decode(ids, skip_special_tokens=True, clean_up_tokenization_spaces=True)
         # one (n, widest chunk) id matrix, pad-filled like a single HF call over the whole list would leave it
@@ -185,5 +189,5 @@ class LLMSpeechTextInference():
         shared = int(pre_e.shape[0])
         if txt_e[0] is not None and all(t_ == texts[0] for t_ in texts):
             shared += int(txt_e[0].shape[0])
-        ids, n_cols = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared)
+        ids, n_cols = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams)
         return ids[:, :n_cols].to(torch.int64)
