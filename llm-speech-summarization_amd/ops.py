@@ -136,7 +136,9 @@ def embed_gather(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
 
 
 def attn_fwd(q, k, v, out, cu_q, cu_k, klen, *, q_strides, k_strides, v_strides, o_strides, nseq, max_qlen, n_heads, n_kv_heads,
-             head_dim, causal, scale) -> torch.Tensor:
+             head_dim, causal, scale, dropout_p: float = 0.0, dropout_seed: int = 0, lse: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sl_attn_fwd on separate q / k / v / out views (strides in elements: (row, head)).  dropout_p > 0 and lse: the training-mode
+    outputs of attn_packed_qkv (lse: fp32 (query rows, n_heads), indexed by the global query row)."""
     a = L.AttnArgs()
     a.q, a.q_row_stride, a.q_head_stride = L.ptr(q), q_strides[0], q_strides[1]
     a.k, a.k_row_stride, a.k_head_stride = L.ptr(k), k_strides[0], k_strides[1]
@@ -145,8 +147,35 @@ def attn_fwd(q, k, v, out, cu_q, cu_k, klen, *, q_strides, k_strides, v_strides,
     a.cu_q, a.cu_k, a.klen = L.ptr(cu_q), L.ptr(cu_k), L.ptr(klen)
     a.nseq, a.max_qlen, a.n_heads, a.n_kv_heads = nseq, max_qlen, n_heads, n_kv_heads
     a.head_dim, a.causal, a.dtype, a.scale = head_dim, int(causal), L.dtype_code(out.dtype), scale
+    a.dropout_p, a.dropout_seed = float(dropout_p), int(dropout_seed) & 0xFFFFFFFFFFFFFFFF
+    a.lse = L.ptr(lse)
     L.check(L.lib().sl_attn_fwd(C.byref(a), L.stream_ptr()), "sl_attn_fwd")
     return out
+
+
+def attn_bwd(q, k, v, out, d_out, lse, dq, dk, dv, cu_q, cu_k, klen, *, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
+             dk_strides, dv_strides, nseq, max_qlen, max_klen, n_tok_q, n_heads, n_kv_heads, head_dim, causal, scale, dropout_p: float = 0.0,
+             dropout_seed: int = 0, delta: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sl_attn_bwd on separate views (strides in elements: (row, head)): dq / dk / dv <- the gradients of q / k / v given out, d_out and the
+    forward's lse (fp32 (n_tok_q, n_heads)).  delta: fp32 (n_tok_q, n_heads) scratch for rowsum(d_out * out), allocated if None; returned."""
+    if delta is None:
+        delta = torch.empty((n_tok_q, n_heads), device=q.device, dtype=torch.float32)
+    a = L.AttnBwdArgs()
+    a.q, a.q_row_stride, a.q_head_stride = L.ptr(q), q_strides[0], q_strides[1]
+    a.k, a.k_row_stride, a.k_head_stride = L.ptr(k), k_strides[0], k_strides[1]
+    a.v, a.v_row_stride, a.v_head_stride = L.ptr(v), v_strides[0], v_strides[1]
+    a.out, a.o_row_stride, a.o_head_stride = L.ptr(out), o_strides[0], o_strides[1]
+    a.d_out, a.do_row_stride, a.do_head_stride = L.ptr(d_out), do_strides[0], do_strides[1]
+    a.dq, a.dq_row_stride, a.dq_head_stride = L.ptr(dq), dq_strides[0], dq_strides[1]
+    a.dk, a.dk_row_stride, a.dk_head_stride = L.ptr(dk), dk_strides[0], dk_strides[1]
+    a.dv, a.dv_row_stride, a.dv_head_stride = L.ptr(dv), dv_strides[0], dv_strides[1]
+    a.lse, a.delta = L.ptr(lse), L.ptr(delta)
+    a.cu_q, a.cu_k, a.klen = L.ptr(cu_q), L.ptr(cu_k), L.ptr(klen)
+    a.n_tok_q, a.nseq, a.max_qlen, a.max_klen = n_tok_q, nseq, max_qlen, max_klen
+    a.n_heads, a.n_kv_heads, a.head_dim, a.causal, a.dtype = n_heads, n_kv_heads, head_dim, int(causal), L.dtype_code(q.dtype)
+    a.scale, a.dropout_p, a.dropout_seed = scale, float(dropout_p), int(dropout_seed) & 0xFFFFFFFFFFFFFFFF
+    L.check(L.lib().sl_attn_bwd(C.byref(a), L.stream_ptr()), "sl_attn_bwd")
+    return delta
 
 
 _SEQ_DESC = {}
@@ -199,29 +228,14 @@ def attn_packed_qkv_bwd(qkv: torch.Tensor, out: torch.Tensor, d_out: torch.Tenso
                         n_heads: int, n_kv_heads: int, head_dim: int, causal: bool, scale: float, dropout_p: float = 0.0,
                         dropout_seed: int = 0) -> torch.Tensor:
     """Flash-style backward of attn_packed_qkv (sl_attn_bwd): d_qkv (same fused layout as qkv) <- [dQ | dK | dV]."""
-    dev = qkv.device
-    cu, klen = seq_descriptors(seqlens, dev)
-    ntok, rs, D = qkv.shape[0], qkv.stride(0), head_dim
-    esz = qkv.element_size()
+    cu, klen = seq_descriptors(seqlens, qkv.device)
+    rs, drs, D = qkv.stride(0), d_qkv.stride(0), head_dim
     koff, voff = n_heads * D, (n_heads + n_kv_heads) * D
-    delta = torch.empty((ntok, n_heads), device=dev, dtype=torch.float32)
-    a = L.AttnBwdArgs()
-    a.q, a.q_row_stride, a.q_head_stride = qkv.data_ptr(), rs, D
-    a.k, a.k_row_stride, a.k_head_stride = qkv.data_ptr() + koff * esz, rs, D
-    a.v, a.v_row_stride, a.v_head_stride = qkv.data_ptr() + voff * esz, rs, D
-    a.out, a.o_row_stride, a.o_head_stride = out.data_ptr(), out.stride(0), D
-    a.d_out, a.do_row_stride, a.do_head_stride = d_out.data_ptr(), d_out.stride(0), D
-    drs = d_qkv.stride(0)
-    a.dq, a.dq_row_stride, a.dq_head_stride = d_qkv.data_ptr(), drs, D
-    a.dk, a.dk_row_stride, a.dk_head_stride = d_qkv.data_ptr() + koff * esz, drs, D
-    a.dv, a.dv_row_stride, a.dv_head_stride = d_qkv.data_ptr() + voff * esz, drs, D
-    a.lse, a.delta = lse.data_ptr(), delta.data_ptr()
-    a.cu_q, a.cu_k, a.klen = cu.data_ptr(), cu.data_ptr(), klen.data_ptr()
-    a.n_tok_q, a.nseq = ntok, len(seqlens)
-    a.max_qlen = a.max_klen = max(int(n) for n in seqlens)
-    a.n_heads, a.n_kv_heads, a.head_dim, a.causal, a.dtype = n_heads, n_kv_heads, D, int(causal), L.dtype_code(qkv.dtype)
-    a.scale, a.dropout_p, a.dropout_seed = scale, float(dropout_p), int(dropout_seed) & 0xFFFFFFFFFFFFFFFF
-    L.check(L.lib().sl_attn_bwd(C.byref(a), L.stream_ptr()), "sl_attn_bwd")
+    smax = max(int(n) for n in seqlens)
+    attn_bwd(qkv, qkv[:, koff:], qkv[:, voff:], out, d_out, lse, d_qkv, d_qkv[:, koff:], d_qkv[:, voff:], cu, cu, klen, q_strides=(rs, D),
+             k_strides=(rs, D), v_strides=(rs, D), o_strides=(out.stride(0), D), do_strides=(d_out.stride(0), D), dq_strides=(drs, D),
+             dk_strides=(drs, D), dv_strides=(drs, D), nseq=len(seqlens), max_qlen=smax, max_klen=smax, n_tok_q=qkv.shape[0], n_heads=n_heads,
+             n_kv_heads=n_kv_heads, head_dim=D, causal=causal, scale=scale, dropout_p=dropout_p, dropout_seed=dropout_seed)
     return d_qkv
 
 
@@ -546,8 +560,10 @@ def dropout(x: torch.Tensor, p: float, seed: int, residual: Optional[torch.Tenso
     return out
 
 
-def dropout_keep_mask(n: int, p: float, seed: int) -> "torch.Tensor":
-    """Host restatement of sl_dropout's mask (bool, n elements) — used by the tests' oracle to apply identical masks."""
+def dropout_keep_at(idx, p: float, seed: int) -> "torch.Tensor":
+    """Host restatement of the counter-based dropout mask (common.h dropout_keep) at arbitrary 64-bit element indices: bool, the shape
+    of idx (a numpy array or a torch tensor of non-negative integers).  sl_dropout's index is the element's offset; the attention
+    kernels' is ((query row * n_heads + head) << 16) | key."""
     import numpy as np
     m32 = np.uint64(0xFFFFFFFF)
 
@@ -559,10 +575,16 @@ def dropout_keep_mask(n: int, p: float, seed: int) -> "torch.Tensor":
         return v
 
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    i = np.arange(n, dtype=np.uint64)
+    i = (idx.cpu().numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)).astype(np.uint64)
     h = lowbias32((i & m32) ^ lowbias32((i >> np.uint64(32)) ^ np.uint64(seed & 0xFFFFFFFF)) ^ np.uint64(seed >> 32))
     thr = np.uint64(int(float(np.float32(p)) * 16777216.0))
     return torch.from_numpy((h >> np.uint64(8)) >= thr)
+
+
+def dropout_keep_mask(n: int, p: float, seed: int) -> "torch.Tensor":
+    """Host restatement of sl_dropout's mask (bool, n elements) — used by the tests' oracle to apply identical masks."""
+    import numpy as np
+    return dropout_keep_at(np.arange(n, dtype=np.uint64), p, seed)
 
 
 def silu_mul(gu):

@@ -273,9 +273,11 @@ def test_flash_attention_backward_ragged_vs_autograd(dt, seqlens, nh, nkv, D, ca
     qd, dd = qkv.to(DEV, dt), d_att.to(DEV, dt)
     lse = torch.full((N, nh), float("nan"), device=DEV)
     out = ops.attn_packed_qkv(qd, seqlens, nh, nkv, D, causal, scale, lse=lse)
-    d_qkv = torch.full_like(qd, float("nan"))
+    gbuf = torch.full((N + 4, qd.shape[1]), float("nan"), device=DEV, dtype=dt)          # two guard rows above and below the gradient
+    d_qkv = gbuf[2:N + 2]
     ops.attn_packed_qkv_bwd(qd, out, dd, lse, d_qkv, seqlens, nh, nkv, D, causal, scale)
     assert bool(torch.isfinite(d_qkv.float()).all()) and bool(torch.isfinite(lse).all())
+    assert bool(torch.isnan(gbuf[:2]).all()) and bool(torch.isnan(gbuf[N + 2:]).all()), "d_qkv written outside its rows"
     ref_out, ref_grad = _attn_autograd(qkv, d_att, seqlens, nh, nkv, D, causal, scale, dt)
     assert rel_err(out.float().cpu(), ref_out) < TOL[dt]
     # lse against the definition
@@ -306,8 +308,11 @@ def test_flash_attention_backward_with_probability_dropout(dt):
     qd, dd = qkv.to(DEV, dt), d_att.to(DEV, dt)
     lse = torch.empty((N, nh), device=DEV)
     out = ops.attn_packed_qkv(qd, seqlens, nh, nh, D, False, D ** -0.5, dropout_p=p_drop, dropout_seed=seed, lse=lse)
-    d_qkv = torch.empty_like(qd)
+    gbuf = torch.full((N + 4, qd.shape[1]), float("nan"), device=DEV, dtype=dt)          # two guard rows above and below the gradient
+    d_qkv = gbuf[2:N + 2]
     ops.attn_packed_qkv_bwd(qd, out, dd, lse, d_qkv, seqlens, nh, nh, D, False, D ** -0.5, dropout_p=p_drop, dropout_seed=seed)
+    assert bool(torch.isfinite(d_qkv.float()).all())
+    assert bool(torch.isnan(gbuf[:2]).all()) and bool(torch.isnan(gbuf[N + 2:]).all()), "d_qkv written outside its rows"
     keep = ops.dropout_keep_mask((N * nh) << 16, p_drop, seed).view(N, nh, 1 << 16)
     ref_out, ref_grad = _attn_autograd(qkv, d_att, seqlens, nh, nh, D, False, D ** -0.5, dt, keep=keep, p_drop=p_drop)
     assert rel_err(out.float().cpu(), ref_out) < TOL[dt]

@@ -464,12 +464,14 @@ def test_validate_perplexities_match_reference_fixture(tmp_path):
     assert "validation/audio_perplexity" in line and "audio_response" in line
 
 
+@pytest.mark.parametrize("B", [16, 2])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-def test_kd_window_at_benchmark_width_vs_oracle_autograd(dtype):
+def test_kd_window_at_benchmark_width_vs_oracle_autograd(dtype, B):
     """BASELINE configs[2] at the width bench.py's KD leg runs (ref:trainer.py:270-384): HuBERT-large width x 2 layers + Llama-3.2-3B
-    width x 2 layers with the full 128 256-way vocabulary, ONE accumulation window of 16 utterances (5-10 s, ragged) as a packed
-    micro-batch — the 128^2 / 256^2 GEMMs at M ~ 3 000 rows, the transposed-operand gradient products, the C++ tape, the
-    128 256-way loss kernel.  Losses and EVERY encoder parameter gradient against autograd through the CPU oracle, one utterance
+    width x 2 layers with the full 128 256-way vocabulary, ONE accumulation window of B utterances (5-10 s, ragged) as a packed
+    micro-batch — at B = 16 the 128^2 / 256^2 GEMMs at M ~ 3 000 rows, the transposed-operand gradient products, the C++ tape, the
+    128 256-way loss kernel.  B = 2 is the window one rank of an 8-rank step runs (attn_bwd_both_kernel, the ring GEMMs, no side stream),
+    with the same assertions.  Losses and EVERY encoder parameter gradient against autograd through the CPU oracle, one utterance
     at a time as the reference loops.  fp32: losses <= 1e-5 relative, gradients <= 2e-3 of each parameter's norm (measured ~1e-5);
     bf16 (same bf16-rounded weights on both sides): losses <= 2e-2, gradients <= 0.12 per parameter and <= 5e-2 over all."""
     import os
@@ -479,10 +481,9 @@ def test_kd_window_at_benchmark_width_vs_oracle_autograd(dtype):
     llm, llm_sd = make_llama(LC, 92, dtype, max_ctx=512)
     prefix, suffix = ri.synthetic_ids(9, LC.vocab_size, seed=7, bos=128000), ri.synthetic_ids(6, LC.vocab_size, seed=8, bos=128000)
     taps = (0, 1, 2)
-    tr = training.KDTrainer(kd_config(taps=taps, accum=16), enc, llm, prefix, suffix)
+    tr = training.KDTrainer(kd_config(taps=taps, accum=B), enc, llm, prefix, suffix)
     tr.optimizer_step = lambda: None
     gen = torch.Generator().manual_seed(314)
-    B = 16
     waves = [ri.synthetic_waveform(80000 + 5000 * u, seed=700 + u) for u in range(B)]        # 5.0 ... 9.7 s
     texts = [torch.randint(1, LC.vocab_size, (30 + u % 11,), generator=gen) for u in range(B)]
     resps = [torch.randint(1, LC.vocab_size, (48 + (5 * u) % 17,), generator=gen) for u in range(B)]
@@ -498,7 +499,7 @@ def test_kd_window_at_benchmark_width_vs_oracle_autograd(dtype):
     for u in range(B):
         audio = ho.audio_encoder_forward(sd, HC, waves[u][None])
         r = ko.kd_losses(lsd, LC, audio, texts[u], resps[u], prefix, suffix, connector_layers=taps, tail_logits_only=True)
-        (r["total"] / 16).backward()
+        (r["total"] / B).backward()
         ref_losses.append({k: float(v) for k, v in r.items()})
     l_tol = 1e-5 if dtype == torch.float32 else 2e-2
     for u in range(B):
