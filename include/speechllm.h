@@ -830,6 +830,49 @@ size_t sl_kv_beam_staging_bytes(const sl_kv_cache* kv, const sl_llama_model* m, 
 int sl_kv_beam_reorder(const sl_kv_cache* kv, const sl_llama_model* m, const int32_t* src_row_dev, const int32_t* prompt_len_dev,
                        const int32_t* ctx_len_dev, int32_t rows, int32_t max_span, void* staging, size_t staging_bytes, sl_stream stream);
 
+/* Logits processors (hf:generation/utils.py _get_logits_processor; classes in hf:generation/logits_process.py; additive to ABI 7): what a
+ * caller of HF's generate reaches for when an answer loops — repetition_penalty, no_repeat_ngram_size — and min_new_tokens, in HF's order,
+ * on the fp32 logits of every step, the prefill's included, before the argmax / the sampling warpers / the beam selection.
+ * A row's history is the tokens it has GENERATED: the prompt is embeddings (the reference's input_ids start empty) and is never penalised.
+ *   repetition_penalty p   every token of the history: s < 0 ? s * p : s / p, once however often it occurs (IEEE fp32 division)
+ *   no_repeat_ngram_size g with n >= g history tokens: every token that followed an occurrence of the last g - 1 tokens is set to -inf
+ *                          (g = 1: every generated token); runs after the penalty, so a ban overrides it
+ *   min_new_tokens         while n < min_new_tokens the EOS ids in use are set to -inf (nothing without EOS ids)
+ * LIMITS (SL_ERR_ARG before any launch): repetition_penalty finite and > 0; no_repeat_ngram_size >= 0; 0 <= min_new_tokens <=
+ * max_new_tokens; at most 8 EOS ids.
+ * COST: with any processor on, every step is lm_head -> fp32 logits -> sl_logits_process -> select: above 64 rows a greedy step gives up
+ * the lm_head's fused per-64-column top-1 and pays the logits round trip (2 x rows x vocab x 4 bytes, about 1 GB at 1 024 rows of
+ * Llama-3.2-3B).  With lp NULL or all three off, sl_generate_lp / sl_beam_generate_lp ARE sl_generate / sl_beam_generate: the same
+ * launches, captured graphs and bits, and the workspace sizes are the same. */
+typedef struct {
+  float repetition_penalty;      /* 1.0 = off; must be finite and > 0 */
+  int32_t no_repeat_ngram_size;  /* 0 = off */
+  int32_t min_new_tokens;        /* 0 = off; <= max_new_tokens */
+  int32_t reserved;
+} sl_logits_opts;
+/* In place on logits (rows, V), one block per row.  hist (rows, hist_ld) int32 with hist_len[row] valid entries (clamped to [0, hist_ld];
+ * ids outside [0, V) are ignored); unfinished NULL or (rows): a row with 0 is left untouched (the select kernels emit pad_id for it).
+ * log_softmax != 0: the row is first rewritten as (x - max) - log(sum exp(x - max)), NaN counted as -inf — bit for bit what sl_beam_topk
+ * forms — and sl_beam_topk_ex(is_logprob = 1) then selects from it.  scratch: rows * hist_ld floats, read and written only when
+ * repetition_penalty != 1 (may be NULL otherwise).  Deterministic: no float atomics. */
+int sl_logits_process(float* logits, int32_t rows, int32_t V, const int32_t* hist, int64_t hist_ld, const int32_t* hist_len,
+                      const int32_t* unfinished, const sl_logits_opts* lp, const int32_t* eos_ids_host, int32_t n_eos, int32_t log_softmax,
+                      float* scratch, sl_stream stream);
+/* sl_beam_topk; with is_logprob != 0 the max / log-sum-exp passes are skipped: acc = x + row_score */
+int sl_beam_topk_ex(const float* logits, int32_t rows, int32_t V, const float* row_score, int32_t M, float* cand_score, int32_t* cand_token,
+                    sl_stream stream, int32_t is_logprob);
+/* sl_generate / sl_beam_generate with the processors (lp may be NULL).  History: the row's output ids (greedy, sampling: it moves with the
+ * row when the batch is compacted) / the running beam's tokens.  The workspace grows by the penalty's scratch only when it is on. */
+size_t sl_generate_workspace_bytes_lp(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int32_t max_new_tokens, const sl_logits_opts* lp);
+int sl_generate_lp(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                   const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
+                   sl_stream stream, const sl_logits_opts* lp);
+size_t sl_beam_generate_workspace_bytes_lp(const sl_llama_model* m, int64_t n_tok, int32_t nseq, const sl_kv_cache* kv, const sl_beam_opts* opts,
+                                           const sl_logits_opts* lp);
+int sl_beam_generate_lp(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                        const sl_beam_opts* opts, int32_t* out_ids_host, float* out_scores_host, int32_t* out_lens_host,
+                        sl_generate_stats* stats, void* workspace, size_t workspace_bytes, sl_stream stream, const sl_logits_opts* lp);
+
 /* ---------------------------------------------------------------------------------------------
  * KD step, layer stacks (C++ host runtime of the training tape: one call issues the launches of a whole stack of layers
  * over a packed ragged batch; ref:trainer.py:270-384 runs the same arithmetic through autograd, one utterance at a time).

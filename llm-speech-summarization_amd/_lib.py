@@ -179,6 +179,11 @@ class BeamState(C.Structure):
                 ("fin_ids", c_vp), ("fin_flag", c_vp), ("fin_len", c_vp), ("open", c_vp), ("seq_done", c_vp), ("step", c_vp), ("len_pen", c_vp)]
 
 
+class LogitsOpts(C.Structure):
+    """sl_logits_opts: HF's logits processors of a generate call (1.0 / 0 / 0 = off)"""
+    _fields_ = [("repetition_penalty", c_f32), ("no_repeat_ngram_size", c_i32), ("min_new_tokens", c_i32), ("reserved", c_i32)]
+
+
 EARLY_STOPPING = {False: 0, True: 1, "never": 2}      # sl_beam_opts.early_stopping
 
 
@@ -306,6 +311,14 @@ _PROTOS = {
     "sl_beam_step": (c_i32, [C.POINTER(BeamState), c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, C.POINTER(BeamOpts), c_vp]),
     "sl_kv_beam_staging_bytes": (c_sz, [C.POINTER(KVCache), C.POINTER(LlamaModel), c_i32, c_i32]),
     "sl_kv_beam_reorder": (c_i32, [C.POINTER(KVCache), C.POINTER(LlamaModel), c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_sz, c_vp]),
+    "sl_logits_process": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, C.POINTER(LogitsOpts), C.POINTER(c_i32), c_i32, c_i32, c_vp, c_vp]),
+    "sl_beam_topk_ex": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32]),
+    "sl_generate_workspace_bytes_lp": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, c_i32, C.POINTER(LogitsOpts)]),
+    "sl_generate_lp": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(GenerateOpts), C.POINTER(c_i32),
+                               C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts)]),
+    "sl_beam_generate_workspace_bytes_lp": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, C.POINTER(KVCache), C.POINTER(BeamOpts), C.POINTER(LogitsOpts)]),
+    "sl_beam_generate_lp": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(BeamOpts), C.POINTER(c_i32),
+                                    C.POINTER(c_f32), C.POINTER(c_i32), C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts)]),
     "sl_greedy_generate": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, c_i32,
                                    C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32),
                                    C.POINTER(c_f32), c_vp, c_sz, c_vp]),

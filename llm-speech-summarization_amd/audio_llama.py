@@ -8,7 +8,8 @@ hf:generation/utils.py:736-744), `.eval()`, `.to(device)`, `.parameters()`.
 
 RMSNorm, RoPE, GQA attention, SwiGLU, lm_head, argmax, EOS handling and the KV cache all run in
 libspeechllm (sl_llama_prefill / sl_generate); generation is greedy by construction
-(SURVEY.md §9 Q3).  No PyTorch fallback exists.
+(SURVEY.md §9 Q3).  `generate` also takes HF's `repetition_penalty`, `no_repeat_ngram_size` and
+`min_new_tokens` (sl_logits_process, off by default).  No PyTorch fallback exists.
 """
 from __future__ import annotations
 
@@ -69,7 +70,8 @@ class AudioLlamaForCausalLM:
         # do_sample flag under `hub_do_sample`, but sampling is only used when a caller sets do_sample=True).
         self.generation_config = SimpleNamespace(eos_token_id=list(arch.eos_token_ids), pad_token_id=arch.pad_token_id,
                                                  do_sample=False, temperature=1.0, top_k=50, top_p=1.0, hub_do_sample=None,
-                                                 num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1)
+                                                 num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1,
+                                                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0)
         self.sample_seed = 0
         self._sd = state_dict
         self.device = torch.device("cpu")
@@ -267,10 +269,16 @@ class AudioLlamaForCausalLM:
                  do_sample: Optional[bool] = None, temperature: Optional[float] = None, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, seed: Optional[int] = None, num_beams: Optional[int] = None,
                  length_penalty: Optional[float] = None, early_stopping=None, num_return_sequences: Optional[int] = None,
+                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
                  **unused) -> torch.Tensor:
         """num_beams > 1: beam search (hf:generation/utils.py _beam_search, sl_beam_generate) -> (B * num_return_sequences, n_cols),
-        n_cols the longest returned hypothesis; `last_beam_scores` / `last_beam_lengths` hold HF's sequences_scores and the lengths."""
+        n_cols the longest returned hypothesis; `last_beam_scores` / `last_beam_lengths` hold HF's sequences_scores and the lengths.
+        repetition_penalty / no_repeat_ngram_size / min_new_tokens: HF's logits processors (sl_logits_process) over the GENERATED tokens, in
+        every mode; None falls back to `generation_config` (HF's defaults 1.0 / 0 / 0 = off: the call is then exactly the call without them)."""
         g = self.generation_config
+        logits = self.logits_options(g.repetition_penalty if repetition_penalty is None else repetition_penalty,
+                                     g.no_repeat_ngram_size if no_repeat_ngram_size is None else no_repeat_ngram_size,
+                                     g.min_new_tokens if min_new_tokens is None else min_new_tokens, max_new_tokens)
         K = int(g.num_beams if num_beams is None else num_beams)
         R = int(g.num_return_sequences if num_return_sequences is None else num_return_sequences)
         sampling = bool(g.do_sample if do_sample is None else do_sample)
@@ -291,7 +299,7 @@ class AudioLlamaForCausalLM:
         if K > 1:
             beams = dict(num_beams=K, num_return_sequences=R, length_penalty=float(g.length_penalty if length_penalty is None else length_penalty),
                          early_stopping=g.early_stopping if early_stopping is None else early_stopping)
-            ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, beams=beams)
+            ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, beams=beams, logits=logits)
             return ids[:, :n_cols].to(torch.int64)
         sample = None
         if sampling:
@@ -300,12 +308,44 @@ class AudioLlamaForCausalLM:
                 seed, self.sample_seed = self.sample_seed, self.sample_seed + 1
             sample = dict(temperature=float(g.temperature if temperature is None else temperature), top_k=int(g.top_k if top_k is None else top_k),
                           top_p=float(g.top_p if top_p is None else top_p), seed=int(seed))
-        ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample)
+        ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits)
         return ids[:, :n_cols].to(torch.int64)
+
+    @staticmethod
+    def logits_options(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, max_new_tokens: Optional[int] = None) -> Optional[dict]:
+        """The `logits` dict of generate_packed from HF's three keywords, None when all are off; a value outside the library's limits
+        (speechllm.h sl_logits_opts) raises."""
+        p, g, mn = repetition_penalty, no_repeat_ngram_size, min_new_tokens
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or p != p or p in (float("inf"), float("-inf")) or p <= 0:
+            raise L.SpeechLLMError(f"repetition_penalty={p!r}: must be a finite number > 0 (1.0 = off)")
+        if isinstance(g, bool) or not isinstance(g, int) or g < 0:
+            raise L.SpeechLLMError(f"no_repeat_ngram_size={g!r}: must be an integer >= 0 (0 = off)")
+        if isinstance(mn, bool) or not isinstance(mn, int) or mn < 0:
+            raise L.SpeechLLMError(f"min_new_tokens={mn!r}: must be an integer >= 0 (0 = off)")
+        if max_new_tokens is not None and mn > int(max_new_tokens):
+            raise L.SpeechLLMError(f"min_new_tokens={mn} exceeds max_new_tokens={int(max_new_tokens)}")
+        if float(p) == 1.0 and g == 0 and mn == 0:
+            return None
+        return dict(repetition_penalty=float(p), no_repeat_ngram_size=int(g), min_new_tokens=int(mn))
+
+    @classmethod
+    def _logits_struct(cls, logits: Optional[dict], max_new_tokens: int):
+        """`logits` dict -> L.LogitsOpts, or None (a NULL pointer: the library then runs exactly the call without processors)"""
+        if logits is None:
+            return None
+        unknown = set(logits) - {"repetition_penalty", "no_repeat_ngram_size", "min_new_tokens"}
+        if unknown:
+            raise L.SpeechLLMError(f"logits: unknown keys {sorted(unknown)}")
+        d = cls.logits_options(logits.get("repetition_penalty", 1.0), logits.get("no_repeat_ngram_size", 0), logits.get("min_new_tokens", 0), max_new_tokens)
+        if d is None:
+            return None
+        lp = L.LogitsOpts()
+        lp.repetition_penalty, lp.no_repeat_ngram_size, lp.min_new_tokens = d["repetition_penalty"], d["no_repeat_ngram_size"], d["min_new_tokens"]
+        return lp
 
     def generate_packed(self, x: torch.Tensor, lens: Sequence[int], max_new_tokens: int, use_eos: bool = True, sample: Optional[dict] = None,
                         shared_prefix: int = 0, row_limits: Optional[Sequence[int]] = None, compact: bool = True, check_every: int = 4,
-                        beams: Optional[dict] = None):
+                        beams: Optional[dict] = None, logits: Optional[dict] = None):
         """x: packed prompt embeddings (sum S_i, h) on the GPU (overwritten).  Returns (int32 (B, max_new) host tensor, n_cols).
         shared_prefix = P: the caller's promise that the first P rows of every sequence are the same rows (one prompt template in
         front of the audio, ref:inference.py:95-113) — the batched decode attention then reads those P cache positions from slot 0
@@ -315,7 +355,10 @@ class AudioLlamaForCausalLM:
         costs what the LIVE rows cost; per-sequence results are those of the uncompacted batch (`last_generate_stats` has the counts).
         beams: dict(num_beams=K, length_penalty=1.0, early_stopping=False, num_return_sequences=1) -> beam search (sl_beam_generate) on
         B * K decode rows: returns (int32 (B * R, max_new) ids, the longest hypothesis' length) and sets `last_beam_scores` /
-        `last_beam_lengths`; not with row_limits or sampling; `compact` is ignored (done sequences keep their rows)."""
+        `last_beam_lengths`; not with row_limits or sampling; `compact` is ignored (done sequences keep their rows).
+        logits: dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0) -> HF's logits processors over each row's generated
+        tokens (sl_generate_lp / sl_beam_generate_lp), in every mode; every step then runs the unfused lm_head -> fp32 logits -> processors
+        -> select.  None, or all three off: exactly the call without them."""
         w = self._dev()
         a = self.arch
         lib = L.lib()
@@ -325,7 +368,7 @@ class AudioLlamaForCausalLM:
                 raise L.SpeechLLMError("row_limits and beams together are not built: a beam search has one max_new_tokens for the call")
             if sample is not None:
                 raise L.SpeechLLMError("sampling and beams together (beam sampling) are not built")
-            return self._beam_packed(x, lens, max_new_tokens, use_eos, shared_prefix, check_every, beams)
+            return self._beam_packed(x, lens, max_new_tokens, use_eos, shared_prefix, check_every, beams, logits)
         if B > L.MAX_DECODE_BATCH:
             raise L.SpeechLLMError(f"{B} sequences in one generate call; the library takes {L.MAX_DECODE_BATCH} (split the batch: sequences are independent)")
         if max(lens) + max_new_tokens > self.max_ctx:
@@ -357,17 +400,19 @@ class AudioLlamaForCausalLM:
             o.sample, o.temperature, o.top_k, o.top_p = 1, float(sample["temperature"]), int(sample["top_k"]), float(sample["top_p"])
             o.seed = int(sample["seed"]) & 0xFFFFFFFFFFFFFFFF
         st = L.GenerateStats()
+        lp = self._logits_struct(logits, max_new_tokens)
+        lp_ref = C.byref(lp) if lp is not None else None
         struct, fmt_name = self._struct_for(B)
-        ws = self._workspace(lib.sl_generate_workspace_bytes(C.byref(struct), x.shape[0], B, max_new_tokens))
-        L.check(lib.sl_generate(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
-                                L.stream_ptr()), "sl_generate")
+        ws = self._workspace(lib.sl_generate_workspace_bytes_lp(C.byref(struct), x.shape[0], B, max_new_tokens, lp_ref))
+        L.check(lib.sl_generate_lp(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+                                   L.stream_ptr(), lp_ref), "sl_generate")
         self.last_timings_ms = (st.prefill_ms, st.decode_ms)
         self.last_generate_stats = {"rows": B, "n_steps": int(st.n_steps), "decode_launches": int(st.decode_launches), "compactions": int(st.compactions),
                                     "final_rows": int(st.final_rows), "row_steps": int(st.row_steps), "weight_format": fmt_name}
         ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B, max_new_tokens)
         return ids, int(st.n_steps)
 
-    def _beam_packed(self, x, lens, max_new_tokens, use_eos, shared_prefix, check_every, beams):
+    def _beam_packed(self, x, lens, max_new_tokens, use_eos, shared_prefix, check_every, beams, logits=None):
         lib = L.lib()
         B = len(lens)
         unknown = set(beams) - {"num_beams", "length_penalty", "early_stopping", "num_return_sequences"}
@@ -404,13 +449,15 @@ class AudioLlamaForCausalLM:
         scores = (C.c_float * (B * R))()
         lengths = (C.c_int32 * (B * R))()
         st = L.GenerateStats()
+        lp = self._logits_struct(logits, max_new_tokens)
+        lp_ref = C.byref(lp) if lp is not None else None
         struct, fmt_name = self._struct_for(B * K)
-        nbytes = lib.sl_beam_generate_workspace_bytes(C.byref(struct), x.shape[0], B, C.byref(kv), C.byref(o))
+        nbytes = lib.sl_beam_generate_workspace_bytes_lp(C.byref(struct), x.shape[0], B, C.byref(kv), C.byref(o), lp_ref)
         if nbytes == 0:
             L.check(-1, "sl_beam_generate_workspace_bytes")
         ws = self._workspace(nbytes)
-        L.check(lib.sl_beam_generate(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, scores, lengths, C.byref(st), ws.data_ptr(),
-                                     ws.numel(), L.stream_ptr()), "sl_beam_generate")
+        L.check(lib.sl_beam_generate_lp(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, scores, lengths, C.byref(st), ws.data_ptr(),
+                                        ws.numel(), L.stream_ptr(), lp_ref), "sl_beam_generate")
         self.last_timings_ms = (st.prefill_ms, st.decode_ms)
         self.last_generate_stats = {"rows": B * K, "n_steps": int(st.n_steps), "decode_launches": int(st.decode_launches), "compactions": 0,
                                     "final_rows": int(st.final_rows), "row_steps": int(st.row_steps), "weight_format": fmt_name, "num_beams": K}

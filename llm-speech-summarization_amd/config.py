@@ -79,6 +79,26 @@ def runtime_dtype(config) -> "torch.dtype":
     return getattr(torch, _RUNTIME_DTYPES[name])
 
 
+def runtime_logits(config):
+    """The logits processors a config's `runtime` section names: optional `repetition_penalty` (default 1.0 = off),
+    `no_repeat_ngram_size` (0 = off) and `min_new_tokens` (0 = off) -> None when all are off, else the dict the `logits` keyword of
+    generate_packed takes."""
+    rt = config.get("runtime", {}) if hasattr(config, "get") else {}
+    rt = rt or {}
+    p = rt.get("repetition_penalty", 1.0)
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or p != p or p == float("inf") or p <= 0:
+        raise ValueError(f"runtime.repetition_penalty: {p!r} is not a finite number > 0")
+    out = dict(repetition_penalty=float(p))
+    for key in ("no_repeat_ngram_size", "min_new_tokens"):
+        v = rt.get(key, 0)
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"runtime.{key}: {v!r} is not an integer >= 0")
+        out[key] = int(v)
+    if out["repetition_penalty"] == 1.0 and out["no_repeat_ngram_size"] == 0 and out["min_new_tokens"] == 0:
+        return None
+    return out
+
+
 def runtime_beams(config):
     """The beam-search options a config's `runtime` section names: optional `num_beams` (default 1 = greedy), `length_penalty` (1.0) and
     `early_stopping` (false / true / "never") -> None for greedy, else the dict the `beams` keyword of generate_packed takes."""

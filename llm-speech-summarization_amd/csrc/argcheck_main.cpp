@@ -4,6 +4,7 @@
 // host code alone — argument validation, shape / workspace arithmetic, the tuning-switch parser — before any HIP call, with
 // the right status and a non-empty error string, and without the sanitizers reporting anything.
 #include <initializer_list>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -366,6 +367,33 @@ int main() {
     memset(&bs, 0, sizeof(bs));
     EXPECT_ARG_ERROR(sl_beam_step(&bs, (const float*)ws, (const int32_t*)ws, 2, 8, 32, 0, &bo, nullptr));     // null state fields
     EXPECT_ARG_ERROR(sl_kv_beam_reorder(&bkv, &bm, (const int32_t*)ws, (const int32_t*)ws, (const int32_t*)ws, 8, 16, ws, 16, nullptr));   // null cache
+    // logits processors: options are checked before anything else; off / NULL options leave the workspace sizes alone
+    bo.num_beams = 4;
+    sl_logits_opts lp = {1.0f, 0, 0, 0};
+    EXPECT(sl_beam_generate_workspace_bytes_lp(&bm, 137 * 256, 256, &bkv, &bo, &lp) == need, "processors off: the beam workspace is unchanged");
+    EXPECT(sl_generate_workspace_bytes_lp(&bm, 137 * 256, 256, 256, nullptr) == sl_generate_workspace_bytes(&bm, 137 * 256, 256, 256), "NULL options: unchanged");
+    lp.repetition_penalty = 1.2f;
+    EXPECT(sl_generate_workspace_bytes_lp(&bm, 137 * 256, 256, 256, &lp) == sl_generate_workspace_bytes(&bm, 137 * 256, 256, 256) + (size_t)256 * 256 * 4 + 256,
+           "penalty on: + the gather scratch");
+    EXPECT(sl_beam_generate_workspace_bytes_lp(&bm, 137 * 256, 256, &bkv, &bo, &lp) > need, "penalty on: the beam workspace grows");
+    sl_generate_opts go;
+    memset(&go, 0, sizeof(go));
+    go.max_new_tokens = 16;
+    const float bad_p[4] = {0.f, -1.f, INFINITY, NAN};
+    for (float p : bad_p) {
+      lp.repetition_penalty = p;
+      EXPECT_ARG_ERROR(sl_generate_lp(nullptr, nullptr, nullptr, nullptr, 1, &go, nullptr, nullptr, nullptr, 0, nullptr, &lp));
+      EXPECT_ARG_ERROR(sl_beam_generate_lp(&bm, &bkv, nullptr, nullptr, 1, &bo, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &lp));
+      EXPECT_ARG_ERROR(sl_logits_process((float*)ws, 4, 100, (const int32_t*)ws, 8, (const int32_t*)ws, nullptr, &lp, eos, 3, 0, (float*)ws, nullptr));
+    }
+    lp.repetition_penalty = 1.2f; lp.no_repeat_ngram_size = -1;
+    EXPECT_ARG_ERROR(sl_generate_lp(nullptr, nullptr, nullptr, nullptr, 1, &go, nullptr, nullptr, nullptr, 0, nullptr, &lp));
+    lp.no_repeat_ngram_size = 2; lp.min_new_tokens = 17;                                                       // > max_new_tokens = 16
+    EXPECT_ARG_ERROR(sl_generate_lp(nullptr, nullptr, nullptr, nullptr, 1, &go, nullptr, nullptr, nullptr, 0, nullptr, &lp));
+    lp.min_new_tokens = 4;
+    EXPECT_ARG_ERROR(sl_logits_process((float*)ws, 4, 100, (const int32_t*)ws, 8, (const int32_t*)ws, nullptr, &lp, eos, 9, 0, (float*)ws, nullptr));   // 9 eos ids
+    EXPECT_ARG_ERROR(sl_logits_process((float*)ws, 4, 100, (const int32_t*)ws, 8, (const int32_t*)ws, nullptr, &lp, eos, 3, 0, nullptr, nullptr));     // no scratch
+    EXPECT_ARG_ERROR(sl_beam_topk_ex((const float*)ws, 4, 100, nullptr, 65, (float*)ws, (int32_t*)ws, nullptr, 1));
   }
   if (g_fail == 0) printf("argcheck ok\n");
   return g_fail == 0 ? 0 : 1;

@@ -1,5 +1,6 @@
 // beam.hip — beam search on the device (hf:generation/utils.py _beam_search and its helpers, restated in tests/beam_ref.py):
 //   beam_topk_kernel        one block per decode row: log-softmax + the row's running score, the row's M largest with their tokens
+//                           (is_logprob: the row already holds processed log-probabilities, logits_proc.hip; the softmax passes are skipped)
 //   beam_step_kernel        one block per sequence: merge of the K rows' lists into M candidates, next running beams, finished set,
 //                           early-stop heuristic, done flag, token histories
 //   kv_beam_gather / scatter  the K/V cache re-ordered by the chosen source beams, through a staging area (a slot is source AND destination)
@@ -20,12 +21,13 @@ constexpr int BEAM_MAX_K = 8;
 constexpr int TOPK_THREADS = 1024;
 
 // ----------------------------------------------------------------------------------------------
-// Row `b`: acc[v] = (x[v] - max) - log(sum exp(x - max)) + row_score[b]  (torch.log_softmax's form), NaN logits count as -inf.
+// Row `b`: acc[v] = (x[v] - max) - log(sum exp(x - max)) + row_score[b]  (torch.log_softmax's form), NaN logits count as -inf;
+// is_logprob: the row holds log-probabilities already, acc[v] = x[v] + row_score[b].
 // Output: the M largest acc in the order (larger value, then lower v).  The threshold is the M-th largest ord_key(acc) by a 4-pass
 // radix selection (integer LDS histograms), keys above it are collected, the equal ones in index order, the <= M survivors ranked in LDS.
 // ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_kernel(const float* __restrict__ logits, int V, const float* __restrict__ row_score, int M,
-                                                                 float* __restrict__ cand_score, int32_t* __restrict__ cand_token) {
+                                                                 float* __restrict__ cand_score, int32_t* __restrict__ cand_token, int is_logprob) {
   __shared__ float redf[16];
   __shared__ int hcnt[256];
   __shared__ uint32_t s_prefix;
@@ -33,42 +35,16 @@ __global__ __launch_bounds__(TOPK_THREADS) void beam_topk_kernel(const float* __
   __shared__ int part[TOPK_THREADS];
   __shared__ float sv[BEAM_MAX_M];
   __shared__ int si[BEAM_MAX_M];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const float* row = logits + (int64_t)b * V;
-  const bool vec = (V & 3) == 0 && (((uintptr_t)row) & 15) == 0;
-  auto clean = [](float x) { return x != x ? -INFINITY : x; };
-  // every element once, in a fixed per-thread order: 16-byte loads when the row allows them
-  auto for_each = [&](auto&& f) {
-    if (vec) {
-      const float4* r4 = (const float4*)row;
-      for (int i = tid; i < (V >> 2); i += TOPK_THREADS) {
-        const float4 q = r4[i];
-        f(4 * i, clean(q.x)); f(4 * i + 1, clean(q.y)); f(4 * i + 2, clean(q.z)); f(4 * i + 3, clean(q.w));
-      }
-    } else {
-      for (int i = tid; i < V; i += TOPK_THREADS) f(i, clean(row[i]));
-    }
-  };
-  // row maximum
-  float m = -INFINITY;
-  for_each([&](int, float x) { m = fmaxf(m, x); });
-  m = wave_max(m);
-  if (lane == 0) redf[wave] = m;
-  __syncthreads();
-  m = redf[0];
-  for (int w = 1; w < 16; ++w) m = fmaxf(m, redf[w]);
-  __syncthreads();
-  if (m == -INFINITY) m = 0.f;       // a row of nothing but -inf / NaN: every acc is -inf (not NaN)
-  // log-sum-exp: per-thread sums in index order, xor-butterfly inside the wave, the 16 waves added in order — one fixed order
-  float sum = 0.f;
-  for_each([&](int, float x) { sum += expf(x - m); });
-  sum = wave_sum(sum);
-  if (lane == 0) redf[wave] = sum;
-  __syncthreads();
-  sum = 0.f;
-  for (int w = 0; w < 16; ++w) sum += redf[w];
-  __syncthreads();
-  const float ls = logf(sum), rs = row_score ? row_score[b] : 0.f;
+  const SlRowScan<TOPK_THREADS> scan(row, V, tid);
+  auto clean = [](float x) { return SlRowScan<TOPK_THREADS>::clean(x); };
+  auto for_each = [&](auto&& f) { scan.each(f); };
+  // row maximum and log-sum-exp (common.h sl_row_max_lse, shared with logits_proc.hip); a row that already holds log-probabilities
+  // (is_logprob: sl_logits_process(log_softmax = 1) formed them, and the processors edited them) keeps its values: (x - 0) - 0 = x
+  float m = 0.f, ls = 0.f;
+  if (!is_logprob) sl_row_max_lse<TOPK_THREADS>(scan, redf, m, ls);
+  const float rs = row_score ? row_score[b] : 0.f;
   auto acc = [&](float x) { const float a = ((x - m) - ls) + rs; return a != a ? -INFINITY : a; };
 
   // radix selection of the M-th largest key
@@ -312,10 +288,10 @@ __global__ __launch_bounds__(256) void kv_beam_move_kernel(uint4* __restrict__ k
 }  // namespace
 
 int sl_beam_topk_impl(const float* logits, int32_t rows, int32_t V, const float* row_score, int32_t M, float* cand_score, int32_t* cand_token,
-                      hipStream_t st) {
+                      hipStream_t st, int is_logprob) {
   SL_CHECK_ARG(logits && cand_score && cand_token && rows > 0 && V > 0, "sl_beam_topk: bad arguments");
   SL_CHECK_ARG(M >= 1 && M <= BEAM_MAX_M && M <= V, "sl_beam_topk: M = %d outside [1, min(%d, V = %d)]", M, BEAM_MAX_M, V);
-  hipLaunchKernelGGL(beam_topk_kernel, dim3(rows), dim3(TOPK_THREADS), 0, st, logits, V, row_score, M, cand_score, cand_token);
+  hipLaunchKernelGGL(beam_topk_kernel, dim3(rows), dim3(TOPK_THREADS), 0, st, logits, V, row_score, M, cand_score, cand_token, is_logprob ? 1 : 0);
   SL_CHECK_LAUNCH("beam_topk");
   return 0;
 }
@@ -373,7 +349,12 @@ int sl_kv_beam_reorder_impl(const sl_kv_cache* kv, const sl_llama_model* m, cons
 
 extern "C" int sl_beam_topk(const float* logits, int32_t rows, int32_t V, const float* row_score, int32_t M, float* cand_score, int32_t* cand_token,
                             sl_stream stream) {
-  return sl_beam_topk_impl(logits, rows, V, row_score, M, cand_score, cand_token, (hipStream_t)stream);
+  return sl_beam_topk_impl(logits, rows, V, row_score, M, cand_score, cand_token, (hipStream_t)stream, 0);
+}
+
+extern "C" int sl_beam_topk_ex(const float* logits, int32_t rows, int32_t V, const float* row_score, int32_t M, float* cand_score, int32_t* cand_token,
+                               sl_stream stream, int32_t is_logprob) {
+  return sl_beam_topk_impl(logits, rows, V, row_score, M, cand_score, cand_token, (hipStream_t)stream, is_logprob);
 }
 
 extern "C" int sl_beam_step(const sl_beam_state* state, const float* cand_score, const int32_t* cand_token, int32_t nseq, int32_t num_beams, int32_t M,

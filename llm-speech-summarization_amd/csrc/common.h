@@ -322,6 +322,57 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// One block of THREADS threads over one row of fp32 logits: every element once, in a fixed per-thread order (16-byte loads when the row
+// allows them), NaN counted as -inf.  Shared by beam_topk_kernel (beam.hip) and logits_process_kernel (logits_proc.hip): the two form
+// the same log-softmax, bit for bit, because they walk the row and reduce through this one piece of code.
+template <int THREADS>
+struct SlRowScan {
+  const float* row;
+  int V, tid;
+  bool vec;
+  __device__ __forceinline__ SlRowScan(const float* r, int v, int t) : row(r), V(v), tid(t), vec((v & 3) == 0 && (((uintptr_t)r) & 15) == 0) {}
+  static __device__ __forceinline__ float clean(float x) { return x != x ? -INFINITY : x; }
+  template <class F>
+  __device__ __forceinline__ void each(F&& f) const {
+    if (vec) {
+      const float4* r4 = (const float4*)row;
+      for (int i = tid; i < (V >> 2); i += THREADS) {
+        const float4 q = r4[i];
+        f(4 * i, clean(q.x)); f(4 * i + 1, clean(q.y)); f(4 * i + 2, clean(q.z)); f(4 * i + 3, clean(q.w));
+      }
+    } else {
+      for (int i = tid; i < V; i += THREADS) f(i, clean(row[i]));
+    }
+  }
+};
+// Row maximum m (0 for a row of nothing but -inf / NaN, so that every x - m stays -inf and not NaN) and ls = log(sum exp(x - m)):
+// per-thread partials in index order, xor-butterfly inside the wave, the waves combined in order — one fixed order, no atomics.
+// redf: THREADS / 64 floats of LDS.  Ends with a barrier: redf may be reused at once.
+template <int THREADS>
+__device__ __forceinline__ void sl_row_max_lse(const SlRowScan<THREADS>& sc, float* redf, float& m_out, float& ls_out) {
+  constexpr int WAVES = THREADS / 64;
+  const int lane = sc.tid & 63, wave = sc.tid >> 6;
+  float m = -INFINITY;
+  sc.each([&](int, float x) { m = fmaxf(m, x); });
+  m = wave_max(m);
+  if (lane == 0) redf[wave] = m;
+  __syncthreads();
+  m = redf[0];
+  for (int w = 1; w < WAVES; ++w) m = fmaxf(m, redf[w]);
+  __syncthreads();
+  if (m == -INFINITY) m = 0.f;
+  float sum = 0.f;
+  sc.each([&](int, float x) { sum += expf(x - m); });
+  sum = wave_sum(sum);
+  if (lane == 0) redf[wave] = sum;
+  __syncthreads();
+  sum = 0.f;
+  for (int w = 0; w < WAVES; ++w) sum += redf[w];
+  __syncthreads();
+  m_out = m;
+  ls_out = logf(sum);
+}
+
 constexpr int SL_MAX_DEVICES = 64;      // per-thread, per-device helper objects (capture streams, side streams) are kept in arrays of this size
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }

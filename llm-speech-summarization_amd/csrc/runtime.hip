@@ -1,6 +1,7 @@
 // runtime.hip — C++ host runtime above the kernels: HuBERT encoder forward over a batch of utterances,
 // Llama prefill / decode step / greedy generation (decode step captured once into a hipGraph and
-// replayed, all per-step state lives on the device).  Workspace is carved from one caller-owned buffer.
+// replayed, all per-step state lives on the device; sampling, beam search and HF's logits processors — logits_proc.hip — ride the same
+// loop, the processors between the lm_head's fp32 logits and the selection).  Workspace is carved from one caller-owned buffer.
 #include <cmath>
 #include <vector>
 
@@ -20,6 +21,11 @@ int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float tempe
                           const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished,
                           int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new,
                           int32_t* choice_ws, hipStream_t st, const int32_t* row_limit, const int32_t* row_ids);
+
+int sl_logits_opts_check(const char* who, const sl_logits_opts* lp, int max_new_tokens);
+int sl_logits_process_impl(float* logits, int32_t rows, int32_t V, const int32_t* hist, const int32_t* hist_odd, int64_t hist_ld, const int32_t* hist_len,
+                           const int32_t* unfinished, const sl_logits_opts* lp, const int32_t* eos_ids_host, int32_t n_eos, int32_t log_softmax,
+                           float* scratch, hipStream_t st);
 
 int sl_attn_decode_split_zero_counters(void* workspace, int B, int n_heads, int n_kv, int max_ctx, hipStream_t st);
 int sl_attn_decode_split_impl(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, void* workspace,
@@ -952,6 +958,8 @@ struct DecodeGraphKey {
   uint64_t seed;
   int beam_k, beam_m, beam_es;     // beam search (0 in every other graph: a beam graph and a greedy graph never share a key)
   float beam_lp;
+  float lp_penalty;                // logits processors (all 0 when off: the graph without them): a changed value never replays a stale graph
+  int lp_ngram, lp_min_new;
 };
 struct DecodeGraphEntry { DecodeGraphKey key; hipGraph_t graph; hipGraphExec_t exec; uint64_t stamp; };
 static thread_local std::vector<DecodeGraphEntry> g_graphs;
@@ -998,6 +1006,28 @@ static void decode_graph_store(const DecodeGraphKey& k, hipGraph_t g, hipGraphEx
   g_graphs.push_back(DecodeGraphEntry{k, g, x, ++g_graph_clock});
 }
 
+// the logits processors a call runs: none with lp NULL or all three off (min_new_tokens acts through the EOS ids: off without any)
+struct LpPlan {
+  bool on = false, penalty = false;
+  sl_logits_opts o{1.0f, 0, 0, 0};
+};
+static LpPlan lp_plan(const sl_logits_opts* lp, int n_eos) {
+  LpPlan p;
+  if (!lp) return p;
+  p.o = *lp;
+  p.o.reserved = 0;
+  if (n_eos <= 0) p.o.min_new_tokens = 0;
+  p.penalty = p.o.repetition_penalty != 1.0f;
+  p.on = p.penalty || p.o.no_repeat_ngram_size > 0 || p.o.min_new_tokens > 0;
+  return p;
+}
+
+extern "C" size_t sl_generate_workspace_bytes_lp(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int32_t max_new_tokens, const sl_logits_opts* lp) {
+  size_t a = sl_generate_workspace_bytes(m, n_tok, nseq, max_new_tokens);
+  if (lp && lp->repetition_penalty != 1.0f) a += (size_t)nseq * max_new_tokens * sizeof(float) + 256;      // the penalty's gather scratch
+  return a;
+}
+
 extern "C" size_t sl_generate_workspace_bytes(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int32_t max_new_tokens) {
   LlamaWs w;
   size_t a = llama_carve(m, n_tok > nseq ? n_tok : nseq, nseq, nullptr, 0, w);
@@ -1040,9 +1070,10 @@ struct SampleOpts { float temperature; int top_k; float top_p; uint64_t seed; };
 
 static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
                          const sl_generate_opts* o, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
-                         sl_stream stream) {
-  SL_TRY(llama_check(m, kv));
+                         sl_stream stream, const sl_logits_opts* lp_opts = nullptr) {
   SL_CHECK_ARG(o != nullptr, "sl_generate: null options");
+  SL_TRY(sl_logits_opts_check("sl_generate", lp_opts, o->max_new_tokens));
+  SL_TRY(llama_check(m, kv));
   // use_eos = 0: the EOS ids are ignored even when the caller left them in the struct — rows then finish on their budgets only
   const int max_new_tokens = o->max_new_tokens, n_eos = o->use_eos ? o->n_eos : 0, pad_id = o->pad_id;
   const int32_t* eos_ids_host = o->eos_ids_host;
@@ -1068,8 +1099,10 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
     for (int s = 0; s < nseq; ++s)
       SL_CHECK_ARG(o->row_limits_host[s] >= 1 && o->row_limits_host[s] <= max_new_tokens, "sl_generate: row limit %d of sequence %d outside [1, max_new_tokens=%d]",
                    o->row_limits_host[s], s, max_new_tokens);
-  SL_CHECK_ARG(sl_generate_workspace_bytes(m, n_tok, nseq, max_new_tokens) <= workspace_bytes, "sl_generate: workspace %zu B < required %zu B",
-               workspace_bytes, sl_generate_workspace_bytes(m, n_tok, nseq, max_new_tokens));
+  const LpPlan lp = lp_plan(lp_opts, n_eos);
+  SL_CHECK_ARG(sl_generate_workspace_bytes_lp(m, n_tok, nseq, max_new_tokens, lp.on ? &lp.o : nullptr) <= workspace_bytes,
+               "sl_generate: workspace %zu B < required %zu B", workspace_bytes,
+               sl_generate_workspace_bytes_lp(m, n_tok, nseq, max_new_tokens, lp.on ? &lp.o : nullptr));
   // carve: generation state first, then the prefill/decode scratch
   Carver c(workspace, workspace_bytes);
   float* logits = (float*)c.take((size_t)B0 * m->vocab * sizeof(float));
@@ -1083,6 +1116,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   int32_t* choice = (int32_t*)c.take(B0 * sizeof(int32_t));      // sampling mode: the drawn token of every row
   int32_t* row_limit = (int32_t*)c.take(B0 * sizeof(int32_t));   // per-row token budgets (sl_generate_opts.row_limits_host)
   int32_t* row_id = (int32_t*)c.take(B0 * sizeof(int32_t));      // the caller's index of the sequence a row holds (rows move when the batch is compacted)
+  float* lp_scratch = lp.penalty ? (float*)c.take((size_t)B0 * max_new_tokens * sizeof(float)) : nullptr;   // carved only when on: the layout without it is unchanged
   c.take(0);
   void* scratch = bptr(workspace) + c.off;
   const size_t scratch_bytes = workspace_bytes - c.off;
@@ -1101,7 +1135,11 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   for (auto& e : ev) SL_HIP(hipEventCreate(&e));
   SL_HIP(hipEventRecord(ev[0], st));
   SL_TRY(sl_llama_prefill(m, kv, x, cu_seqlens_host, nseq, logits, ctx_len, nullptr, scratch, scratch_bytes, stream));
+  // With a processor on, every step — this first one included — is lm_head -> fp32 logits -> sl_logits_process -> select.  The history is
+  // the row's own output ids (out_ids, gen_count): both move with the row at a compaction, so nothing else does.
   auto select = [&](int B, int advance_ctx, hipStream_t s_) -> int {
+    if (lp.on)
+      SL_TRY(sl_logits_process_impl(logits, B, m->vocab, out_ids, nullptr, max_new_tokens, gen_count, unfinished, &lp.o, eos_ids_host, n_eos, 0, lp_scratch, s_));
     if (smp)
       return sl_sample_select_impl(logits, B, m->vocab, smp->temperature, smp->top_k, smp->top_p, smp->seed, eos_ids_host, n_eos, pad_id, use_eos, advance_ctx,
                                    unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new_tokens, choice, s_, row_limit_arg, row_id);
@@ -1139,6 +1177,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
     SL_HIP(hipGetDevice(&key.device));
     for (int i = 0; i < n_eos && i < 8; ++i) key.eos[i] = eos_ids_host[i];
     if (smp) { key.sample = 1; key.temperature = smp->temperature; key.top_k = smp->top_k; key.top_p = smp->top_p; key.seed = smp->seed; }
+    if (lp.on) { key.lp_penalty = lp.o.repetition_penalty; key.lp_ngram = lp.o.no_repeat_ngram_size; key.lp_min_new = lp.o.min_new_tokens; }
     hipGraphExec_t exec = decode_graph_lookup(key);
     if (!exec) {
       hipGraph_t graph = nullptr;
@@ -1150,7 +1189,8 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
       if (!cap) SL_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
       SL_HIP(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
       // greedy + a batch the tiled lm_head serves: the lm_head leaves per-group maxima, the select pass reads 1/64 of the bytes
-      const bool top1 = !smp && decode_fuses_argmax(m, B);
+      // (not with a logits processor on: it edits the fp32 logits the fused form never writes)
+      const bool top1 = !smp && !lp.on && decode_fuses_argmax(m, B);
       // small batches (the skinny kernels: every matrix read once per step by a chain of short launches): a prefetch branch beside the chain
       DecodePrefetch pf;
       static thread_local hipStream_t cap2_by_dev[SL_MAX_DEVICES] = {};
@@ -1298,7 +1338,13 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
 extern "C" int sl_generate(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
                            const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
                            sl_stream stream) {
-  return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream);
+  return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int sl_generate_lp(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                              const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
+                              sl_stream stream, const sl_logits_opts* lp) {
+  return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream, lp);
 }
 
 static int generate_compat(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq, sl_generate_opts& o,
@@ -1337,7 +1383,7 @@ extern "C" int sl_sample_generate(const sl_llama_model* m, const sl_kv_cache* kv
 // Beam search (speechllm.h sl_beam_generate; kernels in beam.hip)
 // ================================================================================================
 int sl_beam_topk_impl(const float* logits, int32_t rows, int32_t V, const float* row_score, int32_t M, float* cand_score, int32_t* cand_token,
-                      hipStream_t st);
+                      hipStream_t st, int is_logprob);
 int sl_beam_step_impl(const sl_beam_state* s, const float* cand_score, const int32_t* cand_token, int32_t nseq, int32_t K, int32_t M, int32_t first,
                       const sl_beam_opts* o, hipStream_t st);
 int sl_beam_m(int num_beams, int n_eos);
@@ -1355,10 +1401,19 @@ struct BeamWs {
   size_t staging_bytes;
   void* scratch;
   size_t scratch_off;
+  int32_t* hist_len;      // logits processors on: (R) length of every row's history (= the sequence's step), refreshed inside the captured step
+  float* lp_scratch;      // ... and the repetition penalty's gather scratch (R, max_new)
 };
 
+// hist_len[r] = step of the sequence row r belongs to (sl_beam_state.step): the running beams of a sequence all hold `step` tokens
+__global__ void beam_hist_len_kernel(const int32_t* __restrict__ step, int K, int R, int32_t* __restrict__ hist_len) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r < R) hist_len[r] = step[r / K];
+}
+
 // generation state first, then the staging area of the cache re-ordering, then the prefill / decode scratch
-static size_t beam_carve(const sl_llama_model* m, const sl_kv_cache* kv, int64_t n_tok, int nseq, int K, int M, int max_new, void* base, size_t cap, BeamWs& b) {
+static size_t beam_carve(const sl_llama_model* m, const sl_kv_cache* kv, int64_t n_tok, int nseq, int K, int M, int max_new, void* base, size_t cap, BeamWs& b,
+                         const LpPlan& lp) {
   const size_t R = (size_t)nseq * K;
   Carver c(base, cap);
   b.logits = (float*)c.take(R * m->vocab * sizeof(float));
@@ -1385,6 +1440,8 @@ static size_t beam_carve(const sl_llama_model* m, const sl_kv_cache* kv, int64_t
   b.st.len_pen = b.len_pen;
   b.staging_bytes = K > 1 ? sl_kv_beam_staging_bytes_impl(kv, m, (int)R, max_new) : 0;
   b.staging = c.take(b.staging_bytes);
+  b.hist_len = lp.on ? (int32_t*)c.take(R * sizeof(int32_t)) : nullptr;          // carved only when on: the layout without them is unchanged
+  b.lp_scratch = lp.penalty ? (float*)c.take(R * max_new * sizeof(float)) : nullptr;
   c.take(0);
   b.scratch_off = c.off;
   b.scratch = base ? (unsigned char*)base + c.off : nullptr;
@@ -1417,18 +1474,25 @@ static int beam_check(const char* who, const sl_llama_model* m, const sl_kv_cach
   return 0;
 }
 
-extern "C" size_t sl_beam_generate_workspace_bytes(const sl_llama_model* m, int64_t n_tok, int32_t nseq, const sl_kv_cache* kv, const sl_beam_opts* o) {
+extern "C" size_t sl_beam_generate_workspace_bytes_lp(const sl_llama_model* m, int64_t n_tok, int32_t nseq, const sl_kv_cache* kv, const sl_beam_opts* o,
+                                                      const sl_logits_opts* lp) {
   int M = 0;
   if (beam_check("sl_beam_generate_workspace_bytes", m, kv, nseq, o, &M) != 0) return 0;
+  if (sl_logits_opts_check("sl_beam_generate_workspace_bytes", lp, o->max_new_tokens) != 0) return 0;
   BeamWs b;
-  return beam_carve(m, kv, n_tok, nseq, o->num_beams, M, o->max_new_tokens, nullptr, 0, b);
+  return beam_carve(m, kv, n_tok, nseq, o->num_beams, M, o->max_new_tokens, nullptr, 0, b, lp_plan(lp, o->use_eos ? o->n_eos : 0));
 }
 
-extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
-                                const sl_beam_opts* o, int32_t* out_ids_host, float* out_scores_host, int32_t* out_lens_host,
-                                sl_generate_stats* stats, void* workspace, size_t workspace_bytes, sl_stream stream) {
+extern "C" size_t sl_beam_generate_workspace_bytes(const sl_llama_model* m, int64_t n_tok, int32_t nseq, const sl_kv_cache* kv, const sl_beam_opts* o) {
+  return sl_beam_generate_workspace_bytes_lp(m, n_tok, nseq, kv, o, nullptr);
+}
+
+extern "C" int sl_beam_generate_lp(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                                   const sl_beam_opts* o, int32_t* out_ids_host, float* out_scores_host, int32_t* out_lens_host,
+                                   sl_generate_stats* stats, void* workspace, size_t workspace_bytes, sl_stream stream, const sl_logits_opts* lp_opts) {
   int M = 0;
   SL_TRY(beam_check("sl_beam_generate", m, kv, nseq, o, &M));
+  SL_TRY(sl_logits_opts_check("sl_beam_generate", lp_opts, o->max_new_tokens));
   SL_TRY(llama_check(m, kv));
   SL_CHECK_ARG(x && cu_seqlens_host && out_ids_host && out_scores_host && out_lens_host && workspace, "sl_beam_generate: null buffer");
   const int K = o->num_beams, R = nseq * K, Rn = o->num_return_sequences, max_new = o->max_new_tokens;
@@ -1441,7 +1505,8 @@ extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, 
   }
   const int64_t n_tok = cu_seqlens_host[nseq];
   BeamWs b;
-  const size_t need = beam_carve(m, kv, n_tok, nseq, K, M, max_new, workspace, workspace_bytes, b);
+  const LpPlan lp = lp_plan(lp_opts, n_eos);
+  const size_t need = beam_carve(m, kv, n_tok, nseq, K, M, max_new, workspace, workspace_bytes, b, lp);
   SL_CHECK_ARG(need <= workspace_bytes, "sl_beam_generate: workspace %zu B < required %zu B", workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
   const size_t scratch_bytes = workspace_bytes - b.scratch_off;
@@ -1449,7 +1514,7 @@ extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, 
   oo.n_eos = n_eos; oo.use_eos = n_eos > 0 ? 1 : 0;
 
   // ---- initial state
-  std::vector<float> run0(R, -1.0e9f), fin0(R, -1.0e9f), lp(max_new);
+  std::vector<float> run0(R, -1.0e9f), fin0(R, -1.0e9f), lpen(max_new);
   std::vector<int32_t> ctx0(R), ones(nseq, 1);
   std::vector<KvMove> moves;
   for (int s = 0; s < nseq; ++s) {
@@ -1460,7 +1525,7 @@ extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, 
       if (j > 0) moves.push_back(KvMove{s * K, s * K + j, len, 0});
     }
   }
-  for (int t = 0; t < max_new; ++t) lp[t] = (float)pow((double)(t + 1), (double)o->length_penalty);
+  for (int t = 0; t < max_new; ++t) lpen[t] = (float)pow((double)(t + 1), (double)o->length_penalty);
   hipEvent_t ev[3];
   for (auto& e : ev) SL_HIP(hipEventCreate(&e));
   SL_HIP(hipEventRecord(ev[0], st));
@@ -1470,7 +1535,7 @@ extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, 
   SL_HIP(hipMemcpyAsync(b.st.fin_score, fin0.data(), R * sizeof(float), hipMemcpyHostToDevice, st));
   SL_HIP(hipMemcpyAsync(b.st.ctx_len, ctx0.data(), R * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipMemcpyAsync(b.prompt_len, ctx0.data(), R * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  SL_HIP(hipMemcpyAsync(b.len_pen, lp.data(), max_new * sizeof(float), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(b.len_pen, lpen.data(), max_new * sizeof(float), hipMemcpyHostToDevice, st));
   SL_HIP(hipMemcpyAsync(b.st.open, ones.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipMemsetAsync(b.zero_score, 0, nseq * sizeof(float), st));
   SL_HIP(hipMemsetAsync(b.st.seq_done, 0, nseq * sizeof(int32_t), st));
@@ -1487,8 +1552,14 @@ extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, 
                        b.moves, m->n_kv_heads, kv->slots, kv->max_ctx, row_vec);
     SL_CHECK_LAUNCH("kv_move (beam prompt)");
   }
-  // step 0: the prefill logits are beam 0's
-  SL_TRY(sl_beam_topk_impl(b.logits, nseq, m->vocab, b.zero_score, M, b.cand_score, b.cand_token, st));
+  // step 0: the prefill logits are beam 0's.  With a logits processor on, HF's order: log_softmax, the processors on the log-probabilities
+  // (every history is empty here: only min_new_tokens can act), then the running score and the selection.
+  if (lp.on) {
+    SL_HIP(hipMemsetAsync(b.hist_len, 0, (size_t)R * sizeof(int32_t), st));
+    SL_TRY(sl_logits_process_impl(b.logits, nseq, m->vocab, b.st.hist[0], b.st.hist[1], max_new, b.hist_len, nullptr, &lp.o, o->eos_ids_host, n_eos, 1,
+                                  b.lp_scratch, st));
+  }
+  SL_TRY(sl_beam_topk_impl(b.logits, nseq, m->vocab, b.zero_score, M, b.cand_score, b.cand_token, st, lp.on ? 1 : 0));
   SL_TRY(sl_beam_step_impl(&b.st, b.cand_score, b.cand_token, nseq, K, M, 1, &oo, st));
   SL_HIP(hipEventRecord(ev[1], st));
   SL_HIP(hipStreamSynchronize(st));     // the host vectors above leave scope only after their copies ran
@@ -1513,6 +1584,7 @@ extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, 
     SL_HIP(hipGetDevice(&key.device));
     for (int i = 0; i < n_eos && i < 8; ++i) key.eos[i] = o->eos_ids_host[i];
     key.beam_k = K; key.beam_m = M; key.beam_es = o->early_stopping; key.beam_lp = o->length_penalty;
+    if (lp.on) { key.lp_penalty = lp.o.repetition_penalty; key.lp_ngram = lp.o.no_repeat_ngram_size; key.lp_min_new = lp.o.min_new_tokens; }
     hipGraphExec_t exec = decode_graph_lookup(key);
     if (!exec) {
       hipGraph_t graph = nullptr;
@@ -1522,7 +1594,12 @@ extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, 
       if (!cap) SL_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
       SL_HIP(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
       int rc = decode_step(m, kv, b.st.next_ids, b.st.ctx_len, R, b.logits, b.xdec, w, cap, false);
-      if (rc == 0) rc = sl_beam_topk_impl(b.logits, R, m->vocab, b.st.run_score, M, b.cand_score, b.cand_token, cap);
+      if (rc == 0 && lp.on) {       // row s * K + j: the history of running beam j, `step` tokens long, in hist[step & 1]
+        hipLaunchKernelGGL(beam_hist_len_kernel, dim3((R + 255) / 256), dim3(256), 0, cap, b.st.step, K, R, b.hist_len);
+        rc = sl_logits_process_impl(b.logits, R, m->vocab, b.st.hist[0], b.st.hist[1], max_new, b.hist_len, nullptr, &lp.o, o->eos_ids_host, n_eos, 1,
+                                    b.lp_scratch, cap);
+      }
+      if (rc == 0) rc = sl_beam_topk_impl(b.logits, R, m->vocab, b.st.run_score, M, b.cand_score, b.cand_token, cap, lp.on ? 1 : 0);
       if (rc == 0) rc = sl_beam_step_impl(&b.st, b.cand_score, b.cand_token, nseq, K, M, 0, &oo, cap);
       if (rc == 0 && K > 1) rc = sl_kv_beam_reorder_impl(kv, m, b.st.src_row, b.prompt_len, b.st.ctx_len, R, max_new, b.staging, b.staging_bytes, cap);
       hipError_t ce = hipStreamEndCapture(cap, &graph);
@@ -1567,4 +1644,10 @@ extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, 
   }
   for (auto& e : ev) (void)hipEventDestroy(e);
   return 0;
+}
+
+extern "C" int sl_beam_generate(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                                const sl_beam_opts* o, int32_t* out_ids_host, float* out_scores_host, int32_t* out_lens_host,
+                                sl_generate_stats* stats, void* workspace, size_t workspace_bytes, sl_stream stream) {
+  return sl_beam_generate_lp(m, kv, x, cu_seqlens_host, nseq, o, out_ids_host, out_scores_host, out_lens_host, stats, workspace, workspace_bytes, stream, nullptr);
 }

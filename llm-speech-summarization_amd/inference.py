@@ -66,11 +66,22 @@ class LLMSpeechTextInference():
             raise L.SpeechLLMError("weight_dtype differs from the decode-weight format of the llm that was passed in: construct that llm with the same weight_dtype")
         self.llm = llm.eval().to(self.device)
         # runtime.num_beams / length_penalty / early_stopping of the config (absent in the shipped yamls: greedy) -> beam search
-        from .config import runtime_beams
+        from .config import runtime_beams, runtime_logits
         self.beams = runtime_beams(self.config)
+        # runtime.repetition_penalty / no_repeat_ngram_size / min_new_tokens (absent in the shipped yamls: off) -> HF's logits processors
+        self.logits = runtime_logits(self.config)
 
-    def generate_llm_response(self, inputs_embeds, max_new_tokens=256) -> List[str]:
-        generate_ids = self.llm.generate(input_ids=None, inputs_embeds=inputs_embeds, max_new_tokens=max_new_tokens, **(self.beams or {}))
+    def _logits_for(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens):
+        """the config's logits processors, each overridden by a keyword that is not None -> the keywords of llm.generate"""
+        d = dict(getattr(self, "logits", None) or {})
+        for k, v in (("repetition_penalty", repetition_penalty), ("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+            if v is not None:
+                d[k] = v
+        return d
+
+    def generate_llm_response(self, inputs_embeds, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None) -> List[str]:
+        generate_ids = self.llm.generate(input_ids=None, inputs_embeds=inputs_embeds, max_new_tokens=max_new_tokens, **(self.beams or {}),
+                                         **self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens))
         self.last_generate_ids = generate_ids
         return self.llm_tokenizer.batch_decode(generate_ids, skip_special_tokens=True, clean_up_tokenization_spaces=True)
 
@@ -81,7 +92,8 @@ class LLMSpeechTextInference():
         prompt_embeds = self.llm.model.embed_tokens(prompt_input_ids)
         return self.generate_llm_response(inputs_embeds=prompt_embeds, max_new_tokens=max_new_tokens)[0]
 
-    def generate_audio_response(self, audio, additional_text_prompt="", max_new_tokens=256) -> str:
+    def generate_audio_response(self, audio, additional_text_prompt="", max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None,
+                                min_new_tokens=None) -> str:
         audio_tensor = torch.as_tensor(audio, dtype=torch.float32).unsqueeze(0).to(self.device)
         if self.audio_encoder.downsample_method == "ctc_pool":
             # the reference calls an undefined self.get_ctc_pool_ranges here
@@ -101,7 +113,7 @@ class LLMSpeechTextInference():
         prompt_emb_sequence = merge_prompt_tokens(inputs_embeds=combined_embeds, tokenizer=self.llm_tokenizer,
                                                   embed_tokens=self.llm.model.embed_tokens, llm_type=self.llm_type,
                                                   device=self.device)
-        return self.generate_llm_response(prompt_emb_sequence, max_new_tokens)[0]
+        return self.generate_llm_response(prompt_emb_sequence, max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens)[0]
 
     def _whisper_audio_embeds(self, audio) -> torch.Tensor:
         """Whisper base (ref:config/llama3_whisper.yaml).  ref:inference.py:97-107 hands the raw waveform to the Whisper encoder,
@@ -116,7 +128,8 @@ class LLMSpeechTextInference():
         keep = max(0, min(int(padded.shape[1]), compute_num_audio_embeds(int(wave.numel()), sr=sr)))
         return padded[:, :keep]
 
-    def generate_audio_responses(self, audios, additional_text_prompts=None, max_new_tokens=256) -> List[str]:
+    def generate_audio_responses(self, audios, additional_text_prompts=None, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None,
+                                 min_new_tokens=None) -> List[str]:
         """Batched form of generate_audio_response (an extension: the reference answers one utterance per call).
         Every utterance is encoded and prefilled at its own length in ONE ragged batch — the encoder writes its embeddings
         straight into the packed prompt buffer `[prefix | text[1:] | audio | suffix[1:]]` — and decoded together, so that the
@@ -129,12 +142,14 @@ class LLMSpeechTextInference():
         if len(texts) != n:
             raise ValueError(f"{len(texts)} text prompts for {n} utterances")
         if self.audio_encoder.downsample_method != "pool":       # stack / ctc_pool: the one-utterance path (ctc_pool raises as the reference does)
-            return [self.generate_audio_response(a, texts[i], max_new_tokens) for i, a in enumerate(audios)]
+            return [self.generate_audio_response(a, texts[i], max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens)
+                    for i, a in enumerate(audios)]
         out: List[str] = []
         ids_all = []
         chunk = L.MAX_DECODE_BATCH // (self.beams["num_beams"] if self.beams else 1)      # a generate call is sized by its decode ROWS: utterances x beams
         for lo_ in range(0, n, chunk):
-            ids = self._generate_chunk(audios[lo_:lo_ + chunk], texts[lo_:lo_ + chunk], max_new_tokens)
+            ids = self._generate_chunk(audios[lo_:lo_ + chunk], texts[lo_:lo_ + chunk], max_new_tokens,
+                                       self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens))
             ids_all.append(ids)
             out += self.llm_tokenizer.batch_decode(ids, skip_special_tokens=True, clean_up_tokenization_spaces=True)
         # one (n, widest chunk) id matrix, pad-filled like a single HF call over the whole list would leave it
@@ -146,7 +161,7 @@ class LLMSpeechTextInference():
         self.last_generate_ids = torch.cat([torch.nn.functional.pad(i, (0, width - int(i.shape[1])), value=int(pad)) for i in ids_all]) if ids_all else None
         return out
 
-    def _generate_chunk(self, audios, texts, max_new_tokens) -> torch.Tensor:
+    def _generate_chunk(self, audios, texts, max_new_tokens, logits=None) -> torch.Tensor:
         """One generate call's worth of utterances -> LongTensor (n, n_cols) of new tokens."""
         from .utils import compute_num_audio_embeds, prompt_template
         n = len(audios)
@@ -189,5 +204,5 @@ class LLMSpeechTextInference():
         shared = int(pre_e.shape[0])
         if txt_e[0] is not None and all(t_ == texts[0] for t_ in texts):
             shared += int(txt_e[0].shape[0])
-        ids, n_cols = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams)
+        ids, n_cols = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None)
         return ids[:, :n_cols].to(torch.int64)
