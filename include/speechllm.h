@@ -874,6 +874,43 @@ int sl_beam_generate_lp(const sl_llama_model* m, const sl_kv_cache* kv, void* x,
                         sl_generate_stats* stats, void* workspace, size_t workspace_bytes, sl_stream stream, const sl_logits_opts* lp);
 
 /* ---------------------------------------------------------------------------------------------
+ * Token log-probabilities (HF generate(output_scores=True) + compute_transition_scores(normalize_logits=True)); additive to ABI 7.
+ * For row b and step t, with y the chosen token and s the fp32 score row the selection saw (after the logits processors, and after the
+ * temperature / top-k / top-p warpers when sampling: filtered tokens at -inf):  logprob[b][t] = log_softmax(s)[y].
+ * NaN counts as -inf, the arithmetic is fp32 in one fixed order (no float atomics); positions at or after a row's finish (pad tokens)
+ * hold 0.0f; a row whose scores have no finite maximum yields a non-finite value.
+ *
+ * sl_gemm_top1_lse: sl_gemm_ex with amax_val / amax_idx set (same argument checks, same two planes bit for bit) plus a third plane
+ * amax_sum[g * M + m] = sum over the valid columns of group g of expf(v - amax_val[g * M + m]), v the value the top-1 compared; 0 for a
+ * group whose maximum is -inf.  sl_greedy_select_partial_sc turns the three planes into the token and -log(sum_g amax_sum[g] *
+ * expf(amax_val[g] - row max)) (the chosen token is the maximum); sl_greedy_select_sc forms (best - m) - log(sum exp(x - m)) over the
+ * fp32 row, through the row reduce sl_beam_topk and sl_logits_process use; sl_sample_select_sc writes log(p_chosen / mass of the
+ * survivors), the p and the mass of its own draw.  logprob_out: (B, max_new) floats on the device, written at [b][gen_count[b]];
+ * token and bookkeeping are bit for bit those of the entries without _sc.
+ *
+ * sl_generate_sc: sl_generate_lp (lp may be NULL) + out_logprobs_host (nseq, max_new_tokens) floats; with out_logprobs_host NULL /
+ * scores 0 they ARE sl_generate_lp / sl_generate_workspace_bytes_lp: same launches, captured graphs, workspace layout and bits.
+ * The device buffer is carved behind every other piece of generation state and moves with its row when the batch is compacted.
+ * Above 64 rows a greedy step keeps the lm_head's fused top-1: the third plane sits behind the other two in the idle logits buffer. */
+int sl_gemm_top1_lse(const sl_gemm_args* args, const sl_gemm_ex_args* ex, float* amax_sum, sl_stream stream);
+int sl_greedy_select_sc(const float* logits, int32_t B, int32_t V, const int32_t* eos_ids_host, int32_t n_eos, int32_t pad_id, int32_t use_eos,
+                        int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids,
+                        int32_t max_new, float* logprob_out, sl_stream stream);
+int sl_greedy_select_partial_sc(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int32_t n_groups, int32_t B,
+                                const int32_t* eos_ids_host, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t advance_ctx,
+                                int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len, int32_t* next_ids,
+                                int32_t* out_ids, int32_t max_new, float* logprob_out, sl_stream stream);
+int sl_sample_select_sc(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                        const int32_t* eos_ids_host, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t* unfinished, int32_t* ctx_len,
+                        int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, int32_t* choice_ws,
+                        float* logprob_out, sl_stream stream);
+size_t sl_generate_workspace_bytes_sc(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int32_t max_new_tokens, const sl_logits_opts* lp,
+                                      int32_t scores);
+int sl_generate_sc(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                   const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
+                   sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host);
+
+/* ---------------------------------------------------------------------------------------------
  * KD step, layer stacks (C++ host runtime of the training tape: one call issues the launches of a whole stack of layers
  * over a packed ragged batch; ref:trainer.py:270-384 runs the same arithmetic through autograd, one utterance at a time).
  * Saved activations, hidden states and fp32 gradient accumulators are caller-owned; temporaries come from `workspace`.

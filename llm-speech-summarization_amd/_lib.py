@@ -319,6 +319,16 @@ _PROTOS = {
     "sl_beam_generate_workspace_bytes_lp": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, C.POINTER(KVCache), C.POINTER(BeamOpts), C.POINTER(LogitsOpts)]),
     "sl_beam_generate_lp": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(BeamOpts), C.POINTER(c_i32),
                                     C.POINTER(c_f32), C.POINTER(c_i32), C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts)]),
+    # token log-probabilities (additive to ABI 7)
+    "sl_gemm_top1_lse": (c_i32, [C.POINTER(GemmArgs), C.POINTER(GemmEx), c_vp, c_vp]),
+    "sl_greedy_select_sc": (c_i32, [c_vp, c_i32, c_i32, C.POINTER(c_i32), c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "sl_greedy_select_partial_sc": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_i32, c_vp, c_vp]),
+    "sl_sample_select_sc": (c_i32, [c_vp, c_i32, c_i32, c_f32, c_i32, c_f32, C.c_uint64, C.POINTER(c_i32), c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sl_generate_workspace_bytes_sc": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, c_i32, C.POINTER(LogitsOpts), c_i32]),
+    "sl_generate_sc": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(GenerateOpts), C.POINTER(c_i32),
+                               C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts), C.POINTER(c_f32)]),
     "sl_greedy_generate": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, c_i32,
                                    C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32),
                                    C.POINTER(c_f32), c_vp, c_sz, c_vp]),

@@ -26,6 +26,16 @@ from . import ops
 from .weights import KNOWN_LLAMA, LlamaArch, LlamaDeviceWeights
 
 
+class GenerateOutput:
+    """What generate(return_dict_in_generate=True) returns (HF's GenerateDecoderOnlyOutput, the fields this port fills): `sequences` (rows,
+    n_cols) int64; `token_logprobs` (rows, n_cols) float32 with output_scores=True, else None; `sequences_scores` (rows) float32 — beam
+    search: HF's sequences_scores; otherwise the sum of a row's token_logprobs when scores are on, else None."""
+    __slots__ = ("sequences", "token_logprobs", "sequences_scores")
+
+    def __init__(self, sequences, token_logprobs=None, sequences_scores=None):
+        self.sequences, self.token_logprobs, self.sequences_scores = sequences, token_logprobs, sequences_scores
+
+
 class _EmbedTokens:
     """`llm.model.embed_tokens(ids)` (ref:utils.py:63-64, ref:inference.py:85,121) as a HIP row gather."""
 
@@ -71,7 +81,8 @@ class AudioLlamaForCausalLM:
         self.generation_config = SimpleNamespace(eos_token_id=list(arch.eos_token_ids), pad_token_id=arch.pad_token_id,
                                                  do_sample=False, temperature=1.0, top_k=50, top_p=1.0, hub_do_sample=None,
                                                  num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1,
-                                                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0)
+                                                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
+                                                 return_dict_in_generate=False, output_scores=False)
         self.sample_seed = 0
         self._sd = state_dict
         self.device = torch.device("cpu")
@@ -84,6 +95,7 @@ class AudioLlamaForCausalLM:
         self.last_generate_stats = None
         self.last_beam_scores = None       # beam search: (B * num_return_sequences) float32 sequences_scores of the last call
         self.last_beam_lengths = None      # ... and the hypotheses' lengths (an EOS that ended one is counted)
+        self.last_token_logprobs = None    # output_scores=True: (B, n_cols) float32 log-probabilities of the last call's tokens
         if device is not None:
             self.to(device)
 
@@ -270,12 +282,20 @@ class AudioLlamaForCausalLM:
                  top_p: Optional[float] = None, seed: Optional[int] = None, num_beams: Optional[int] = None,
                  length_penalty: Optional[float] = None, early_stopping=None, num_return_sequences: Optional[int] = None,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
-                 **unused) -> torch.Tensor:
+                 return_dict_in_generate: Optional[bool] = None, output_scores: Optional[bool] = None, **unused):
         """num_beams > 1: beam search (hf:generation/utils.py _beam_search, sl_beam_generate) -> (B * num_return_sequences, n_cols),
         n_cols the longest returned hypothesis; `last_beam_scores` / `last_beam_lengths` hold HF's sequences_scores and the lengths.
         repetition_penalty / no_repeat_ngram_size / min_new_tokens: HF's logits processors (sl_logits_process) over the GENERATED tokens, in
-        every mode; None falls back to `generation_config` (HF's defaults 1.0 / 0 / 0 = off: the call is then exactly the call without them)."""
+        every mode; None falls back to `generation_config` (HF's defaults 1.0 / 0 / 0 = off: the call is then exactly the call without them).
+        return_dict_in_generate / output_scores (None: `generation_config`): with return_dict_in_generate a GenerateOutput(sequences,
+        token_logprobs, sequences_scores) comes back instead of the tensor.  token_logprobs (B, n_cols) float32, only with output_scores:
+        log_softmax(the scores the selection saw)[chosen token] — HF's compute_transition_scores(normalize_logits=True) — 0.0 at and after
+        a row's finish.  sequences_scores: `last_beam_scores` in beam mode, else the per-row sum of token_logprobs when scores are on.
+        output_scores without return_dict_in_generate returns the tensor and sets `last_token_logprobs`.  Beam search with output_scores
+        raises: per-token scores along beam back-pointers are not built."""
         g = self.generation_config
+        ret_dict = bool(getattr(g, "return_dict_in_generate", False) if return_dict_in_generate is None else return_dict_in_generate)
+        want_scores = bool(getattr(g, "output_scores", False) if output_scores is None else output_scores)
         logits = self.logits_options(g.repetition_penalty if repetition_penalty is None else repetition_penalty,
                                      g.no_repeat_ngram_size if no_repeat_ngram_size is None else no_repeat_ngram_size,
                                      g.min_new_tokens if min_new_tokens is None else min_new_tokens, max_new_tokens)
@@ -296,11 +316,15 @@ class AudioLlamaForCausalLM:
             inputs_embeds = self.model.embed_tokens(input_ids)
         x, lens = self._pack(inputs_embeds.to(self.dtype) if torch.is_tensor(inputs_embeds) else [e.to(self.dtype) for e in inputs_embeds],
                              attention_mask)
+        if K > 1 and want_scores:
+            raise L.SpeechLLMError("output_scores with num_beams > 1 is not built (per-token scores along beam back-pointers); sequences_scores "
+                                   "/ last_beam_scores hold the hypotheses' scores")
         if K > 1:
             beams = dict(num_beams=K, num_return_sequences=R, length_penalty=float(g.length_penalty if length_penalty is None else length_penalty),
                          early_stopping=g.early_stopping if early_stopping is None else early_stopping)
             ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, beams=beams, logits=logits)
-            return ids[:, :n_cols].to(torch.int64)
+            seqs = ids[:, :n_cols].to(torch.int64)
+            return GenerateOutput(seqs, None, self.last_beam_scores) if ret_dict else seqs
         sample = None
         if sampling:
             # hf:generation/utils.py logits warpers: temperature, top-k (HF default 50), top-p, then one draw per row
@@ -308,8 +332,14 @@ class AudioLlamaForCausalLM:
                 seed, self.sample_seed = self.sample_seed, self.sample_seed + 1
             sample = dict(temperature=float(g.temperature if temperature is None else temperature), top_k=int(g.top_k if top_k is None else top_k),
                           top_p=float(g.top_p if top_p is None else top_p), seed=int(seed))
-        ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits)
-        return ids[:, :n_cols].to(torch.int64)
+        if not want_scores:
+            ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits)
+            seqs = ids[:, :n_cols].to(torch.int64)
+            return GenerateOutput(seqs, None, None) if ret_dict else seqs
+        ids, n_cols, lps = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits, scores=True)
+        seqs, lps = ids[:, :n_cols].to(torch.int64), lps[:, :n_cols].clone()
+        self.last_token_logprobs = lps
+        return GenerateOutput(seqs, lps, lps.sum(dim=1)) if ret_dict else seqs      # pads hold 0.0: the sum runs over the row's generated length
 
     @staticmethod
     def logits_options(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, max_new_tokens: Optional[int] = None) -> Optional[dict]:
@@ -345,7 +375,7 @@ class AudioLlamaForCausalLM:
 
     def generate_packed(self, x: torch.Tensor, lens: Sequence[int], max_new_tokens: int, use_eos: bool = True, sample: Optional[dict] = None,
                         shared_prefix: int = 0, row_limits: Optional[Sequence[int]] = None, compact: bool = True, check_every: int = 4,
-                        beams: Optional[dict] = None, logits: Optional[dict] = None):
+                        beams: Optional[dict] = None, logits: Optional[dict] = None, scores: bool = False):
         """x: packed prompt embeddings (sum S_i, h) on the GPU (overwritten).  Returns (int32 (B, max_new) host tensor, n_cols).
         shared_prefix = P: the caller's promise that the first P rows of every sequence are the same rows (one prompt template in
         front of the audio, ref:inference.py:95-113) — the batched decode attention then reads those P cache positions from slot 0
@@ -358,7 +388,10 @@ class AudioLlamaForCausalLM:
         `last_beam_lengths`; not with row_limits or sampling; `compact` is ignored (done sequences keep their rows).
         logits: dict(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0) -> HF's logits processors over each row's generated
         tokens (sl_generate_lp / sl_beam_generate_lp), in every mode; every step then runs the unfused lm_head -> fp32 logits -> processors
-        -> select.  None, or all three off: exactly the call without them."""
+        -> select.  None, or all three off: exactly the call without them.
+        scores=True: returns (ids, n_cols, logprobs), logprobs a float32 (B, max_new) host tensor of the chosen tokens' log-probabilities
+        (sl_generate_sc; 0.0 at and after a row's finish); above 64 rows a greedy step keeps the fused lm_head top-1 and carries a third
+        partial.  Not with beams.  False: exactly the call without them."""
         w = self._dev()
         a = self.arch
         lib = L.lib()
@@ -368,6 +401,8 @@ class AudioLlamaForCausalLM:
                 raise L.SpeechLLMError("row_limits and beams together are not built: a beam search has one max_new_tokens for the call")
             if sample is not None:
                 raise L.SpeechLLMError("sampling and beams together (beam sampling) are not built")
+            if scores:
+                raise L.SpeechLLMError("scores and beams together are not built: last_beam_scores holds the hypotheses' scores")
             return self._beam_packed(x, lens, max_new_tokens, use_eos, shared_prefix, check_every, beams, logits)
         if B > L.MAX_DECODE_BATCH:
             raise L.SpeechLLMError(f"{B} sequences in one generate call; the library takes {L.MAX_DECODE_BATCH} (split the batch: sequences are independent)")
@@ -403,13 +438,22 @@ class AudioLlamaForCausalLM:
         lp = self._logits_struct(logits, max_new_tokens)
         lp_ref = C.byref(lp) if lp is not None else None
         struct, fmt_name = self._struct_for(B)
-        ws = self._workspace(lib.sl_generate_workspace_bytes_lp(C.byref(struct), x.shape[0], B, max_new_tokens, lp_ref))
-        L.check(lib.sl_generate_lp(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
-                                   L.stream_ptr(), lp_ref), "sl_generate")
+        lps = None
+        if scores:
+            lps = (C.c_float * (B * max_new_tokens))()
+            ws = self._workspace(lib.sl_generate_workspace_bytes_sc(C.byref(struct), x.shape[0], B, max_new_tokens, lp_ref, 1))
+            L.check(lib.sl_generate_sc(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+                                       L.stream_ptr(), lp_ref, lps), "sl_generate")
+        else:
+            ws = self._workspace(lib.sl_generate_workspace_bytes_lp(C.byref(struct), x.shape[0], B, max_new_tokens, lp_ref))
+            L.check(lib.sl_generate_lp(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+                                       L.stream_ptr(), lp_ref), "sl_generate")
         self.last_timings_ms = (st.prefill_ms, st.decode_ms)
         self.last_generate_stats = {"rows": B, "n_steps": int(st.n_steps), "decode_launches": int(st.decode_launches), "compactions": int(st.compactions),
                                     "final_rows": int(st.final_rows), "row_steps": int(st.row_steps), "weight_format": fmt_name}
         ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B, max_new_tokens)
+        if scores:
+            return ids, int(st.n_steps), torch.frombuffer(lps, dtype=torch.float32).clone().view(B, max_new_tokens)
         return ids, int(st.n_steps)
 
     def _beam_packed(self, x, lens, max_new_tokens, use_eos, shared_prefix, check_every, beams, logits=None):

@@ -395,6 +395,39 @@ int main() {
     EXPECT_ARG_ERROR(sl_logits_process((float*)ws, 4, 100, (const int32_t*)ws, 8, (const int32_t*)ws, nullptr, &lp, eos, 3, 0, nullptr, nullptr));     // no scratch
     EXPECT_ARG_ERROR(sl_beam_topk_ex((const float*)ws, 4, 100, nullptr, 65, (float*)ws, (int32_t*)ws, nullptr, 1));
   }
+  {
+    // token log-probabilities (additive to ABI 7): the third plane rides on the fused top-1 and is refused with it
+    sl_gemm_args ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.A = ws; ga.W = ws; ga.lda = 64; ga.ldw = 64; ga.M = 128; ga.N = 128; ga.K = 64; ga.batch = 1; ga.dtype = SL_BF16; ga.out_f32 = 1;
+    sl_gemm_ex_args gx;
+    memset(&gx, 0, sizeof(gx));
+    gx.w_mod = 1;
+    EXPECT_ARG_ERROR(sl_gemm_top1_lse(&ga, nullptr, (float*)ws, nullptr));                    // no ex args
+    EXPECT_ARG_ERROR(sl_gemm_top1_lse(&ga, &gx, (float*)ws, nullptr));                        // the third plane without the first two
+    gx.amax_val = (float*)ws;
+    EXPECT_ARG_ERROR(sl_gemm_top1_lse(&ga, &gx, (float*)ws, nullptr));                        // ... without amax_idx
+    gx.amax_idx = (int32_t*)ws;
+    EXPECT_ARG_ERROR(sl_gemm_top1_lse(&ga, &gx, nullptr, nullptr));                           // no third plane
+    ga.M = 64;                                                                                // M <= 64: no tiled kernel, no fused top-1
+    EXPECT_ARG_ERROR(sl_gemm_top1_lse(&ga, &gx, (float*)ws, nullptr));
+    EXPECT_ARG_ERROR(sl_greedy_select_sc(nullptr, 4, 100, eos, 3, 0, 1, ctx, ctx, ctx, ctx, ctx, out_ids, 8, (float*)ws, nullptr));
+    EXPECT_ARG_ERROR(sl_greedy_select_partial_sc((const float*)ws, (const int32_t*)ws, nullptr, 16, 128, eos, 3, 0, 1, 1, ctx, ctx, ctx, ctx, ctx, out_ids, 8,
+                                                 (float*)ws, nullptr));                     // log-probabilities without the third plane
+    EXPECT_ARG_ERROR(sl_greedy_select_partial_sc((const float*)ws, (const int32_t*)ws, (const float*)ws, 16, 128, eos, 3, 0, 1, 1, ctx, ctx, ctx, ctx, ctx, out_ids,
+                                                 8, nullptr, nullptr));                     // ... and the reverse
+    EXPECT_ARG_ERROR(sl_sample_select_sc((const float*)ws, 4, 100, 0.f, 0, 1.f, 1, eos, 3, 0, 1, ctx, ctx, ctx, ctx, ctx, out_ids, 8, ctx, (float*)ws, nullptr));   // temperature 0
+    sl_llama_model sm;
+    memset(&sm, 0, sizeof(sm));
+    sm.dtype = SL_BF16; sm.hidden = 256; sm.n_layers = 2; sm.n_heads = 2; sm.n_kv_heads = 2; sm.head_dim = 128; sm.ffn = 384; sm.vocab = 1000; sm.rope_len = 64;
+    EXPECT(sl_generate_workspace_bytes_sc(&sm, 40, 4, 16, nullptr, 0) == sl_generate_workspace_bytes(&sm, 40, 4, 16), "scores off: the workspace is unchanged");
+    EXPECT(sl_generate_workspace_bytes_sc(&sm, 40, 4, 16, nullptr, 1) == sl_generate_workspace_bytes(&sm, 40, 4, 16) + (size_t)4 * 16 * 4 + 256,
+           "scores on: + the (nseq, max_new_tokens) log-probabilities");
+    sl_generate_opts go;
+    memset(&go, 0, sizeof(go));
+    go.max_new_tokens = 16;
+    EXPECT_ARG_ERROR(sl_generate_sc(nullptr, nullptr, nullptr, nullptr, 1, &go, nullptr, nullptr, nullptr, 0, nullptr, nullptr, (float*)ws));
+  }
   if (g_fail == 0) printf("argcheck ok\n");
   return g_fail == 0 ? 0 : 1;
 }

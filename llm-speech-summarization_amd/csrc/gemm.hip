@@ -1153,7 +1153,8 @@ static int gemm_typed(const sl_gemm_args* a, GemmP& p, const SkinnyX& sx, hipStr
   }
 }
 
-int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st) {
+// amax_sum: the third plane of the fused top-1 (sl_gemm_top1_lse); NULL everywhere else
+static int gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st, float* amax_sum) {
   SL_CHECK_ARG(a != nullptr, "sl_gemm: null args");
   const SlEnv& e = sl_env();      // ONE snapshot of the tuning table per product: a concurrent sl_tuning_reload() cannot split a plan
   SL_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0 && a->batch > 0, "sl_gemm: bad shape M=%d N=%d K=%d batch=%d", a->M, a->N, a->K, a->batch);
@@ -1250,6 +1251,8 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
       p.amax_val = ex->amax_val; p.amax_idx = ex->amax_idx;
     }
   }
+  SL_CHECK_ARG(!amax_sum || p.amax_val, "sl_gemm_top1_lse: amax_sum rides on the fused top-1: amax_val and amax_idx must be set");
+  p.amax_sum = amax_sum;
   SL_CHECK_ARG(p.amax_val || a->C, "sl_gemm: null C");
   if (e.gemm_log)     // SL_GEMM_LOG: one line per product on stderr (tools/kd_gemm_shapes.py turns a KD window's lines into a per-shape table)
     fprintf(stderr, "SLGEMM M=%d N=%d K=%d batch=%d act=%d ta=%d tw=%d res=%d resf32=%d outf32=%d aux=%d grp=%d bias=%d packed=%d dt=%d\n", a->M, a->N, a->K, a->batch, a->act,
@@ -1288,6 +1291,17 @@ int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_e
   if (a->dtype == SL_F32) return gemm_typed<float>(a, p, sx, st, sk_ws, sk_ws_bytes, e);
   if (a->dtype == SL_F16) return gemm_typed<f16_t>(a, p, sx, st, sk_ws, sk_ws_bytes, e);
   return gemm_typed<bf16_t>(a, p, sx, st, sk_ws, sk_ws_bytes, e);
+}
+
+int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st) { return gemm_impl(a, fx, ex, st, nullptr); }
+
+int sl_gemm_top1_lse_impl(const sl_gemm_args* a, const sl_gemm_ex_args* ex, float* amax_sum, hipStream_t st) {
+  SL_CHECK_ARG(ex != nullptr && amax_sum != nullptr, "sl_gemm_top1_lse: null ex args or amax_sum");
+  return gemm_impl(a, nullptr, ex, st, amax_sum);
+}
+
+extern "C" int sl_gemm_top1_lse(const sl_gemm_args* a, const sl_gemm_ex_args* ex, float* amax_sum, sl_stream stream) {
+  return sl_gemm_top1_lse_impl(a, ex, amax_sum, (hipStream_t)stream);
 }
 
 extern "C" int32_t sl_gemm_split_count(int32_t M, int32_t N, int32_t K, int32_t dtype) {

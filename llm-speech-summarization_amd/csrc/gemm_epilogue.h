@@ -53,6 +53,36 @@ __device__ __forceinline__ void tile_argmax(const GemmP& p, f32x4 (&acc)[MT][NT]
         if (row < p.M) { p.amax_val[g * p.M + row] = bv[i]; p.amax_idx[g * p.M + row] = bi[i]; }
       }
     }
+    if (p.amax_sum) {
+      // third plane (token log-probabilities): sum of exp(v - group max) over the group's valid columns, v the value the
+      // compare above saw, NaN counted as -inf.  Every lane of the row group holds the group maximum after the butterfly; the lane's
+      // four fragments are added in column order, then the same 16-lane xor butterfly: one fixed order.  A group without a finite or
+      // +inf value (max -inf) leaves 0.
+      float sm[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        const int col = col_base + n * 16 + r;
+        if (col >= p.N) continue;
+        const float b = bias ? to_f32(bias[col]) : 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float v = acc[m][n][i] + b;
+          if (v == v && bv[i] != -INFINITY) sm[i] += expf(v - bv[i]);
+        }
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sm[i] += __shfl_xor(sm[i], o, 64);
+      }
+      if (r == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int row = row_base + m * 16 + 4 * q + i;
+          if (row < p.M) p.amax_sum[g * p.M + row] = sm[i];
+        }
+      }
+    }
   }
 }
 

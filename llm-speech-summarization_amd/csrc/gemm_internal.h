@@ -27,6 +27,8 @@ struct GemmP {
   float* stats_out;    // producer: per row and 64-column segment {sum, sum of squares} of the STORED (rounded) values, [row][N / 64][2]
   float* amax_val;     // fused row-wise top-1 (sl_gemm_ex_args.amax_*): per 64-column group g and row m the largest value of
   int* amax_idx;       // columns [64 g, 64 g + 64) at [g][m] and its column index; C is then not written at all
+  float* amax_sum;     // optional third plane (sl_gemm_top1_lse): sum over the group's valid columns of exp(v - group max) at [g][m], 0 for a group of
+                       // nothing but -inf / NaN; NULL: tile_argmax is the code it was
   // training-tape epilogue fusions (sl_gemm_ex_args.post_op ...): rows epilogue (generic form) / direct epilogue / split-K reduce pass
   int post;            // SL_POST_*
   uint32_t drop_thr24; // keep iff u24(hash) >= thr (0: no mask)

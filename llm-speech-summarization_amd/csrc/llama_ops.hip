@@ -278,11 +278,16 @@ extern "C" int sl_attn_decode(const void* q, int64_t q_stride, const void* k_cac
 // ----------------------------------------------------------------------------------------------
 struct EosList { int ids[8]; int n; };
 
+// SC (token log-probabilities): logprob_out[b][gen_count] = log_softmax(row)[token] through the row reduce beam search and the
+// logits processors use (common.h sl_row_max_lse), 0 for a finished row.  In sampling mode sample_rows_kernel has left the drawn token's
+// value there; the commit only zeroes it for a finished row.  SC = false is the kernel as it was.
+template <bool SC>
 __global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __restrict__ logits, int V, EosList eos, int pad_id, int use_eos,
                                                              int advance_ctx, int32_t* __restrict__ unfinished, int32_t* __restrict__ ctx_len,
                                                              int32_t* __restrict__ gen_count, int32_t* __restrict__ finish_len,
                                                              int32_t* __restrict__ next_ids, int32_t* __restrict__ out_ids, int max_new,
-                                                             const int32_t* __restrict__ forced, const int32_t* __restrict__ row_limit) {
+                                                             const int32_t* __restrict__ forced, const int32_t* __restrict__ row_limit,
+                                                             float* __restrict__ logprob_out) {
   __shared__ float smax[16];
   __shared__ int sidx[16];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -295,6 +300,9 @@ __global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __rest
       const int unf = unfinished[b];
       if (use_eos) tok = unf ? tok : pad_id;
       const int n = gen_count[b];
+      if constexpr (SC) {
+        if (use_eos && !unf && n < max_new) logprob_out[(int64_t)b * max_new + n] = 0.f;
+      }
       if (n < max_new) out_ids[(int64_t)b * max_new + n] = tok;
       gen_count[b] = n + 1;
       next_ids[b] = tok;
@@ -339,6 +347,12 @@ __global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __rest
   }
   if (lane == 0) { smax[wave] = best; sidx[wave] = bi; }
   __syncthreads();
+  float row_m = 0.f, row_ls = 0.f;
+  if constexpr (SC) {
+    __shared__ float redf[16];
+    const SlRowScan<1024> scan(row, V, tid);
+    sl_row_max_lse<1024>(scan, redf, row_m, row_ls);
+  }
   if (tid == 0) {
     for (int w = 1; w < 16; ++w)
       if (smax[w] > best || (smax[w] == best && sidx[w] < bi)) { best = smax[w]; bi = sidx[w]; }
@@ -347,6 +361,9 @@ __global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __rest
     int unf = unfinished[b];
     if (use_eos) tok = unf ? tok : pad_id;   // hf:generation/utils.py:2928-2929
     const int n = gen_count[b];
+    if constexpr (SC) {
+      if (n < max_new) logprob_out[(int64_t)b * max_new + n] = (use_eos && !unf) ? 0.f : (best - row_m) - row_ls;
+    }
     if (n < max_new) out_ids[(int64_t)b * max_new + n] = tok;
     gen_count[b] = n + 1;
     next_ids[b] = tok;
@@ -362,15 +379,20 @@ __global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __rest
 
 int sl_greedy_select_impl(const float* logits, int32_t B, int32_t V, const int32_t* eos_ids, int32_t n_eos, int32_t pad_id,
                           int32_t use_eos, int32_t advance_ctx, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count,
-                          int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit) {
+                          int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit,
+                          float* logprob_out) {
   SL_CHECK_ARG(logits && unfinished && ctx_len && gen_count && finish_len && next_ids && out_ids && B > 0 && V > 0,
                "sl_greedy_select: bad arguments");
   SL_CHECK_ARG(n_eos >= 0 && n_eos <= 8, "sl_greedy_select: at most 8 eos ids");
   EosList e;
   e.n = n_eos;
   for (int i = 0; i < 8; ++i) e.ids[i] = i < n_eos ? eos_ids[i] : -1;
-  hipLaunchKernelGGL(greedy_select_kernel, dim3(B), dim3(1024), 0, st, logits, V, e, pad_id, use_eos, advance_ctx, unfinished, ctx_len,
-                     gen_count, finish_len, next_ids, out_ids, max_new, (const int32_t*)nullptr, row_limit);
+  if (logprob_out)
+    hipLaunchKernelGGL(greedy_select_kernel<true>, dim3(B), dim3(1024), 0, st, logits, V, e, pad_id, use_eos, advance_ctx, unfinished, ctx_len,
+                       gen_count, finish_len, next_ids, out_ids, max_new, (const int32_t*)nullptr, row_limit, logprob_out);
+  else
+    hipLaunchKernelGGL(greedy_select_kernel<false>, dim3(B), dim3(1024), 0, st, logits, V, e, pad_id, use_eos, advance_ctx, unfinished, ctx_len,
+                       gen_count, finish_len, next_ids, out_ids, max_new, (const int32_t*)nullptr, row_limit, (float*)nullptr);
   SL_CHECK_LAUNCH("greedy_select");
   return 0;
 }
@@ -380,12 +402,18 @@ int sl_greedy_select_impl(const float* logits, int32_t B, int32_t V, const int32
 // flight per thread — the scan is latency-bound (2 004 groups of 8 bytes per row at vocab 128 256), not bandwidth-bound; the
 // stripes meet in LDS in stripe order and the bookkeeping of greedy_select_kernel follows.  Compare rule everywhere: larger
 // value, then lower column.
+// SC (token log-probabilities): ps holds the third plane, sum_g = sum exp(v - max_g) per group.  With the row maximum Mx (every
+// thread folds the 32 stripe maxima of its row, in stripe order) a second pass forms sum_g * exp(max_g - Mx) per stripe in group order, the
+// stripes are added in stripe order, and logprob_out[b][gen_count] = -log(total): the chosen token IS the maximum.  0 for a finished row.
+// SC = false is the kernel as it was.
+template <bool SC>
 __global__ __launch_bounds__(1024) void greedy_select_partial_kernel(const float* __restrict__ pv, const int32_t* __restrict__ pi, int n_groups, int B,
                                                                      EosList eos, int pad_id, int use_eos, int advance_ctx,
                                                                      int32_t* __restrict__ unfinished, int32_t* __restrict__ ctx_len,
                                                                      int32_t* __restrict__ gen_count, int32_t* __restrict__ finish_len,
                                                                      int32_t* __restrict__ next_ids, int32_t* __restrict__ out_ids, int max_new,
-                                                                     const int32_t* __restrict__ row_limit) {
+                                                                     const int32_t* __restrict__ row_limit, const float* __restrict__ ps,
+                                                                     float* __restrict__ logprob_out) {
   constexpr int ROWS = 32, STRIPES = 32, U = 8;
   __shared__ float sv[STRIPES][ROWS];
   __shared__ int si[STRIPES][ROWS];
@@ -413,6 +441,32 @@ __global__ __launch_bounds__(1024) void greedy_select_partial_kernel(const float
   sv[stripe][lr] = best;
   si[stripe][lr] = bi;
   __syncthreads();
+  float total = 0.f;
+  if constexpr (SC) {
+    __shared__ float ss[STRIPES][ROWS];
+    float mx = sv[0][lr];
+    for (int s2 = 1; s2 < STRIPES; ++s2) mx = fmaxf(mx, sv[s2][lr]);
+    float acc = 0.f;
+    for (int g0 = stripe; g0 < n_groups; g0 += STRIPES * U) {
+      float v[U], sg[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int g = g0 + u * STRIPES;
+        const int64_t at = (int64_t)(g < n_groups ? g : n_groups - 1) * B + bc;
+        v[u] = pv[at];
+        sg[u] = ps[at];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (g0 + u * STRIPES >= n_groups) continue;
+        if (v[u] != -INFINITY) acc += sg[u] * expf(v[u] - mx);      // a group of nothing but -inf / NaN holds sum 0 and takes no part
+      }
+    }
+    ss[stripe][lr] = acc;
+    __syncthreads();
+    if (stripe == 0)
+      for (int s2 = 0; s2 < STRIPES; ++s2) total += ss[s2][lr];
+  }
   if (stripe != 0 || b >= B) return;
   for (int s2 = 1; s2 < STRIPES; ++s2)
     if (sv[s2][lr] > best || (sv[s2][lr] == best && si[s2][lr] < bi)) { best = sv[s2][lr]; bi = si[s2][lr]; }
@@ -421,6 +475,9 @@ __global__ __launch_bounds__(1024) void greedy_select_partial_kernel(const float
   const int unf = unfinished[b];
   if (use_eos) tok = unf ? tok : pad_id;   // hf:generation/utils.py:2928-2929
   const int n = gen_count[b];
+  if constexpr (SC) {
+    if (n < max_new) logprob_out[(int64_t)b * max_new + n] = (use_eos && !unf) ? 0.f : -logf(total);
+  }
   if (n < max_new) out_ids[(int64_t)b * max_new + n] = tok;
   gen_count[b] = n + 1;
   next_ids[b] = tok;
@@ -435,15 +492,21 @@ __global__ __launch_bounds__(1024) void greedy_select_partial_kernel(const float
 
 int sl_greedy_select_partial_impl(const float* amax_val, const int32_t* amax_idx, int32_t n_groups, int32_t B, const int32_t* eos_ids, int32_t n_eos,
                                   int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count,
-                                  int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit) {
+                                  int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit,
+                                  const float* amax_sum, float* logprob_out) {
   SL_CHECK_ARG(amax_val && amax_idx && unfinished && ctx_len && gen_count && finish_len && next_ids && out_ids && B > 0 && n_groups > 0,
                "sl_greedy_select_partial: bad arguments");
   SL_CHECK_ARG(n_eos >= 0 && n_eos <= 8, "sl_greedy_select_partial: at most 8 eos ids");
+  SL_CHECK_ARG((amax_sum != nullptr) == (logprob_out != nullptr), "sl_greedy_select_partial_sc: amax_sum and logprob_out come together");
   EosList e;
   e.n = n_eos;
   for (int i = 0; i < 8; ++i) e.ids[i] = i < n_eos ? eos_ids[i] : -1;
-  hipLaunchKernelGGL(greedy_select_partial_kernel, dim3((B + 31) / 32), dim3(1024), 0, st, amax_val, amax_idx, n_groups, B, e, pad_id, use_eos, advance_ctx,
-                     unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, row_limit);
+  if (logprob_out)
+    hipLaunchKernelGGL(greedy_select_partial_kernel<true>, dim3((B + 31) / 32), dim3(1024), 0, st, amax_val, amax_idx, n_groups, B, e, pad_id, use_eos, advance_ctx,
+                       unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, row_limit, amax_sum, logprob_out);
+  else
+    hipLaunchKernelGGL(greedy_select_partial_kernel<false>, dim3((B + 31) / 32), dim3(1024), 0, st, amax_val, amax_idx, n_groups, B, e, pad_id, use_eos, advance_ctx,
+                     unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, row_limit, (const float*)nullptr, (float*)nullptr);
   SL_CHECK_LAUNCH("greedy_select_partial");
   return 0;
 }
@@ -452,7 +515,15 @@ extern "C" int sl_greedy_select_partial(const float* amax_val, const int32_t* am
                                         int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count,
                                         int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, sl_stream stream) {
   return sl_greedy_select_partial_impl(amax_val, amax_idx, n_groups, B, eos_ids, n_eos, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count,
-                                       finish_len, next_ids, out_ids, max_new, (hipStream_t)stream, nullptr);
+                                       finish_len, next_ids, out_ids, max_new, (hipStream_t)stream, nullptr, nullptr, nullptr);
+}
+
+extern "C" int sl_greedy_select_partial_sc(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int32_t n_groups, int32_t B,
+                                           const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished,
+                                           int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new,
+                                           float* logprob_out, sl_stream stream) {
+  return sl_greedy_select_partial_impl(amax_val, amax_idx, n_groups, B, eos_ids, n_eos, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count,
+                                       finish_len, next_ids, out_ids, max_new, (hipStream_t)stream, nullptr, amax_sum, logprob_out);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -471,7 +542,7 @@ __device__ __forceinline__ uint32_t ord_key(float x) {
 
 __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restrict__ logits, int V, float inv_temp, int top_k, float top_p, uint64_t seed,
                                                            const int32_t* __restrict__ gen_count, int32_t* __restrict__ choice,
-                                                           const int32_t* __restrict__ row_ids) {
+                                                           const int32_t* __restrict__ row_ids, float* __restrict__ logprob_out, int max_new) {
   __shared__ float redf[16];
   __shared__ int hcnt[256];
   __shared__ unsigned long long hmass_fx[256];   // probability mass per bin in 2^-40 fixed point: integer adds commute, so the
@@ -591,13 +662,15 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
       for (int i = 0; i < V; ++i) if (ord_key(row[i]) >= keep_key) { pick = i; break; }
     }
     choice[b] = pick < 0 ? 0 : pick;
+    // token log-probabilities: the drawn token under the renormalised survivors, log(p / z) with the p and the z of the draw
+    if (logprob_out && (int)step < max_new) logprob_out[(int64_t)b * max_new + step] = logf(prob(row[pick < 0 ? 0 : pick]) / z);
   }
 }
 
 int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
                           const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished,
                           int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new,
-                          int32_t* choice_ws, hipStream_t st, const int32_t* row_limit, const int32_t* row_ids) {
+                          int32_t* choice_ws, hipStream_t st, const int32_t* row_limit, const int32_t* row_ids, float* logprob_out) {
   SL_CHECK_ARG(logits && unfinished && ctx_len && gen_count && finish_len && next_ids && out_ids && choice_ws && B > 0 && V > 0,
                "sl_sample_select: bad arguments");
   SL_CHECK_ARG(temperature > 0.f && top_p > 0.f && top_p <= 1.0f && top_k >= 0, "sl_sample_select: need temperature > 0, 0 < top_p <= 1, top_k >= 0 (got %f, %f, %d)",
@@ -606,10 +679,15 @@ int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float tempe
   EosList e;
   e.n = n_eos;
   for (int i = 0; i < 8; ++i) e.ids[i] = i < n_eos ? eos_ids[i] : -1;
-  hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(1024), 0, st, logits, V, 1.0f / temperature, top_k, top_p, seed, gen_count, choice_ws, row_ids);
+  hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(1024), 0, st, logits, V, 1.0f / temperature, top_k, top_p, seed, gen_count, choice_ws, row_ids,
+                     logprob_out, max_new);
   SL_CHECK_LAUNCH("sample_rows");
-  hipLaunchKernelGGL(greedy_select_kernel, dim3(B), dim3(64), 0, st, logits, V, e, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count, finish_len,
-                     next_ids, out_ids, max_new, (const int32_t*)choice_ws, row_limit);
+  if (logprob_out)
+    hipLaunchKernelGGL(greedy_select_kernel<true>, dim3(B), dim3(64), 0, st, logits, V, e, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count, finish_len,
+                       next_ids, out_ids, max_new, (const int32_t*)choice_ws, row_limit, logprob_out);
+  else
+    hipLaunchKernelGGL(greedy_select_kernel<false>, dim3(B), dim3(64), 0, st, logits, V, e, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count, finish_len,
+                       next_ids, out_ids, max_new, (const int32_t*)choice_ws, row_limit, (float*)nullptr);
   SL_CHECK_LAUNCH("sample_commit");
   return 0;
 }
@@ -619,14 +697,29 @@ extern "C" int sl_sample_select(const float* logits, int32_t B, int32_t V, float
                                 int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, int32_t* choice_ws,
                                 sl_stream stream) {
   return sl_sample_select_impl(logits, B, V, temperature, top_k, top_p, seed, eos_ids, n_eos, pad_id, use_eos, 1, unfinished, ctx_len, gen_count, finish_len,
-                               next_ids, out_ids, max_new, choice_ws, (hipStream_t)stream, nullptr, nullptr);
+                               next_ids, out_ids, max_new, choice_ws, (hipStream_t)stream, nullptr, nullptr, nullptr);
+}
+
+extern "C" int sl_sample_select_sc(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                                   const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t* unfinished, int32_t* ctx_len,
+                                   int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, int32_t* choice_ws,
+                                   float* logprob_out, sl_stream stream) {
+  return sl_sample_select_impl(logits, B, V, temperature, top_k, top_p, seed, eos_ids, n_eos, pad_id, use_eos, 1, unfinished, ctx_len, gen_count, finish_len,
+                               next_ids, out_ids, max_new, choice_ws, (hipStream_t)stream, nullptr, nullptr, logprob_out);
 }
 
 extern "C" int sl_greedy_select(const float* logits, int32_t B, int32_t V, const int32_t* eos_ids, int32_t n_eos, int32_t pad_id,
                                 int32_t use_eos, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len,
                                 int32_t* next_ids, int32_t* out_ids, int32_t max_new, sl_stream stream) {
   return sl_greedy_select_impl(logits, B, V, eos_ids, n_eos, pad_id, use_eos, 1, unfinished, ctx_len, gen_count, finish_len, next_ids,
-                               out_ids, max_new, (hipStream_t)stream, nullptr);
+                               out_ids, max_new, (hipStream_t)stream, nullptr, nullptr);
+}
+
+extern "C" int sl_greedy_select_sc(const float* logits, int32_t B, int32_t V, const int32_t* eos_ids, int32_t n_eos, int32_t pad_id,
+                                   int32_t use_eos, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len,
+                                   int32_t* next_ids, int32_t* out_ids, int32_t max_new, float* logprob_out, sl_stream stream) {
+  return sl_greedy_select_impl(logits, B, V, eos_ids, n_eos, pad_id, use_eos, 1, unfinished, ctx_len, gen_count, finish_len, next_ids,
+                               out_ids, max_new, (hipStream_t)stream, nullptr, logprob_out);
 }
 
 // ----------------------------------------------------------------------------------------------

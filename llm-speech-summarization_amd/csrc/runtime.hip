@@ -13,14 +13,16 @@ int sl_attn_decode_impl(const void* q, int64_t q_stride, const void* k_cache, co
                         hipStream_t st);
 int sl_greedy_select_impl(const float* logits, int32_t B, int32_t V, const int32_t* eos_ids, int32_t n_eos, int32_t pad_id,
                           int32_t use_eos, int32_t advance_ctx, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count,
-                          int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit);
+                          int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit,
+                          float* logprob_out);
 int sl_greedy_select_partial_impl(const float* amax_val, const int32_t* amax_idx, int32_t n_groups, int32_t B, const int32_t* eos_ids, int32_t n_eos,
                                   int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count,
-                                  int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit);
+                                  int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit,
+                                  const float* amax_sum, float* logprob_out);
 int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
                           const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished,
                           int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new,
-                          int32_t* choice_ws, hipStream_t st, const int32_t* row_limit, const int32_t* row_ids);
+                          int32_t* choice_ws, hipStream_t st, const int32_t* row_limit, const int32_t* row_ids, float* logprob_out);
 
 int sl_logits_opts_check(const char* who, const sl_logits_opts* lp, int max_new_tokens);
 int sl_logits_process_impl(float* logits, int32_t rows, int32_t V, const int32_t* hist, const int32_t* hist_odd, int64_t hist_ld, const int32_t* hist_len,
@@ -34,6 +36,7 @@ int sl_attn_decode_split_impl(const void* q, int64_t q_stride, const void* k_cac
 size_t sl_attn_decode_split_ws(int B, int n_heads, int n_kv, int max_ctx);
 int sl_rmsnorm_rstd_impl(const void* x, void* y, const void* w, float* rstd_out, int64_t rows, int32_t cols, float eps, int32_t dtype, hipStream_t st);
 int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st);
+int sl_gemm_top1_lse_impl(const sl_gemm_args* a, const sl_gemm_ex_args* ex, float* amax_sum, hipStream_t st);
 
 namespace {
 
@@ -868,9 +871,10 @@ constexpr int SL_FUSED_ARGMAX_MIN_B = 256;
 static bool decode_fuses_argmax(const sl_llama_model* m, int B) { B = sl_family_rows(B); return B > 64 && !(m->lm_head_dec && B < SL_FUSED_ARGMAX_MIN_B); }
 
 // fused_top1: the caller will run sl_greedy_select_partial_impl over `logits` reinterpreted as [n_groups][B] floats followed by
-// [n_groups][B] int32 (n_groups = ceil(vocab / 64)) — only honoured where decode_fuses_argmax() says so
+// [n_groups][B] int32 (n_groups = ceil(vocab / 64)) — only honoured where decode_fuses_argmax() says so.  top1_sum (token log-probabilities):
+// a third plane of [n_groups][B] floats behind the two, the groups' sum exp(v - group max) (3 ceil(V / 64) B <= B0 V floats always holds)
 static int decode_step(const sl_llama_model* m, const sl_kv_cache* kv, const int32_t* next_ids, const int32_t* ctx_len, int B, float* logits,
-                       void* x, LlamaWs& w, hipStream_t st, bool fused_top1 = false) {
+                       void* x, LlamaWs& w, hipStream_t st, bool fused_top1 = false, bool top1_sum = false) {
   const int dt = m->dtype, H = m->hidden;
   SL_TRY(sl_embed_gather(m->embed, next_ids, x, B, H, dt, (sl_stream)st));
   // hand RMSNorm scales along the chain when every o / down projection has a reduce pass to compute them in
@@ -913,6 +917,7 @@ static int decode_step(const sl_llama_model* m, const sl_kv_cache* kv, const int
     ex.w_mod = 1;
     ex.amax_val = logits;
     ex.amax_idx = (int32_t*)(logits + ng * B);
+    if (top1_sum) return sl_gemm_top1_lse_impl(&a, &ex, logits + 2 * ng * B, st);
     return sl_gemm_impl(&a, nullptr, &ex, st);
   }
   SL_TRY(gemm(dt, w.last, H, m->lm_head, H, logits, m->vocab, nullptr, nullptr, 0, B, m->vocab, H, SL_ACT_NONE, 1, st));
@@ -960,6 +965,7 @@ struct DecodeGraphKey {
   float beam_lp;
   float lp_penalty;                // logits processors (all 0 when off: the graph without them): a changed value never replays a stale graph
   int lp_ngram, lp_min_new;
+  int scores;                      // token log-probabilities on: other select kernels, a third lm_head plane — never the graph of a call without them
 };
 struct DecodeGraphEntry { DecodeGraphKey key; hipGraph_t graph; hipGraphExec_t exec; uint64_t stamp; };
 static thread_local std::vector<DecodeGraphEntry> g_graphs;
@@ -1028,6 +1034,13 @@ extern "C" size_t sl_generate_workspace_bytes_lp(const sl_llama_model* m, int64_
   return a;
 }
 
+extern "C" size_t sl_generate_workspace_bytes_sc(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int32_t max_new_tokens, const sl_logits_opts* lp,
+                                                 int32_t scores) {
+  size_t a = sl_generate_workspace_bytes_lp(m, n_tok, nseq, max_new_tokens, lp);
+  if (scores) a += (size_t)nseq * max_new_tokens * sizeof(float) + 256;      // the (nseq, max_new_tokens) log-probabilities
+  return a;
+}
+
 extern "C" size_t sl_generate_workspace_bytes(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int32_t max_new_tokens) {
   LlamaWs w;
   size_t a = llama_carve(m, n_tok > nseq ? n_tok : nseq, nseq, nullptr, 0, w);
@@ -1070,7 +1083,7 @@ struct SampleOpts { float temperature; int top_k; float top_p; uint64_t seed; };
 
 static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
                          const sl_generate_opts* o, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
-                         sl_stream stream, const sl_logits_opts* lp_opts = nullptr) {
+                         sl_stream stream, const sl_logits_opts* lp_opts = nullptr, float* out_lp_host = nullptr) {
   SL_CHECK_ARG(o != nullptr, "sl_generate: null options");
   SL_TRY(sl_logits_opts_check("sl_generate", lp_opts, o->max_new_tokens));
   SL_TRY(llama_check(m, kv));
@@ -1100,9 +1113,10 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
       SL_CHECK_ARG(o->row_limits_host[s] >= 1 && o->row_limits_host[s] <= max_new_tokens, "sl_generate: row limit %d of sequence %d outside [1, max_new_tokens=%d]",
                    o->row_limits_host[s], s, max_new_tokens);
   const LpPlan lp = lp_plan(lp_opts, n_eos);
-  SL_CHECK_ARG(sl_generate_workspace_bytes_lp(m, n_tok, nseq, max_new_tokens, lp.on ? &lp.o : nullptr) <= workspace_bytes,
+  const int scores = out_lp_host ? 1 : 0;
+  SL_CHECK_ARG(sl_generate_workspace_bytes_sc(m, n_tok, nseq, max_new_tokens, lp.on ? &lp.o : nullptr, scores) <= workspace_bytes,
                "sl_generate: workspace %zu B < required %zu B", workspace_bytes,
-               sl_generate_workspace_bytes_lp(m, n_tok, nseq, max_new_tokens, lp.on ? &lp.o : nullptr));
+               sl_generate_workspace_bytes_sc(m, n_tok, nseq, max_new_tokens, lp.on ? &lp.o : nullptr, scores));
   // carve: generation state first, then the prefill/decode scratch
   Carver c(workspace, workspace_bytes);
   float* logits = (float*)c.take((size_t)B0 * m->vocab * sizeof(float));
@@ -1117,6 +1131,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   int32_t* row_limit = (int32_t*)c.take(B0 * sizeof(int32_t));   // per-row token budgets (sl_generate_opts.row_limits_host)
   int32_t* row_id = (int32_t*)c.take(B0 * sizeof(int32_t));      // the caller's index of the sequence a row holds (rows move when the batch is compacted)
   float* lp_scratch = lp.penalty ? (float*)c.take((size_t)B0 * max_new_tokens * sizeof(float)) : nullptr;   // carved only when on: the layout without it is unchanged
+  float* lp_out = scores ? (float*)c.take((size_t)B0 * max_new_tokens * sizeof(float)) : nullptr;   // token log-probabilities: likewise, behind everything else
   c.take(0);
   void* scratch = bptr(workspace) + c.off;
   const size_t scratch_bytes = workspace_bytes - c.off;
@@ -1130,6 +1145,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   SL_HIP(hipMemcpyAsync(row_id, orig.data(), B0 * sizeof(int32_t), hipMemcpyHostToDevice, st));
   if (o->row_limits_host) SL_HIP(hipMemcpyAsync(row_limit, o->row_limits_host, B0 * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipMemsetAsync(out_ids, 0, (size_t)B0 * max_new_tokens * sizeof(int32_t), st));
+  if (scores) SL_HIP(hipMemsetAsync(lp_out, 0, (size_t)B0 * max_new_tokens * sizeof(float), st));
 
   hipEvent_t ev[3];
   for (auto& e : ev) SL_HIP(hipEventCreate(&e));
@@ -1142,9 +1158,9 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
       SL_TRY(sl_logits_process_impl(logits, B, m->vocab, out_ids, nullptr, max_new_tokens, gen_count, unfinished, &lp.o, eos_ids_host, n_eos, 0, lp_scratch, s_));
     if (smp)
       return sl_sample_select_impl(logits, B, m->vocab, smp->temperature, smp->top_k, smp->top_p, smp->seed, eos_ids_host, n_eos, pad_id, use_eos, advance_ctx,
-                                   unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new_tokens, choice, s_, row_limit_arg, row_id);
+                                   unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new_tokens, choice, s_, row_limit_arg, row_id, lp_out);
     return sl_greedy_select_impl(logits, B, m->vocab, eos_ids_host, n_eos, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count, finish_len, next_ids,
-                                 out_ids, max_new_tokens, s_, row_limit_arg);
+                                 out_ids, max_new_tokens, s_, row_limit_arg, lp_out);
   };
   SL_TRY(select(B0, 0, st));
   SL_HIP(hipEventRecord(ev[1], st));
@@ -1178,6 +1194,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
     for (int i = 0; i < n_eos && i < 8; ++i) key.eos[i] = eos_ids_host[i];
     if (smp) { key.sample = 1; key.temperature = smp->temperature; key.top_k = smp->top_k; key.top_p = smp->top_p; key.seed = smp->seed; }
     if (lp.on) { key.lp_penalty = lp.o.repetition_penalty; key.lp_ngram = lp.o.no_repeat_ngram_size; key.lp_min_new = lp.o.min_new_tokens; }
+    key.scores = scores;
     hipGraphExec_t exec = decode_graph_lookup(key);
     if (!exec) {
       hipGraph_t graph = nullptr;
@@ -1203,14 +1220,15 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
         pf.main = cap; pf.side = cap2; pf.ev = pev; pf.sink = (uint32_t*)w.tok_pos; pf.on = true;      // (the sink is never written: see the kernel)
         g_prefetch = &pf;
       }
-      int rc = decode_step(m, kv, next_ids, ctx_len, B, logits, xdec, w, cap, top1);
+      int rc = decode_step(m, kv, next_ids, ctx_len, B, logits, xdec, w, cap, top1, top1 && scores);
       g_prefetch = nullptr;
       if (pf.on) { const int rj = pf.join(); if (rc == 0) rc = rj; }       // the branch joins the chain before the capture ends
       if (rc == 0) {
         if (top1) {
           const int ng = (m->vocab + 63) / 64;
           rc = sl_greedy_select_partial_impl(logits, (const int32_t*)(logits + (int64_t)ng * B), ng, B, eos_ids_host, n_eos, pad_id, use_eos, 1, unfinished,
-                                             ctx_len, gen_count, finish_len, next_ids, out_ids, max_new_tokens, cap, row_limit_arg);
+                                             ctx_len, gen_count, finish_len, next_ids, out_ids, max_new_tokens, cap, row_limit_arg,
+                                             scores ? logits + 2 * (int64_t)ng * B : nullptr, lp_out);
         } else {
           rc = select(B, 1, cap);
         }
@@ -1227,6 +1245,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
 
   // host copies of the per-row state, filled at a check; `done[s]`: sequence s (caller's index) has been written to out_ids_host
   std::vector<int32_t> h_unf(B0, 1), h_fin(B0, 0), h_ctx, h_cnt, h_next, h_lim, h_out;
+  std::vector<float> h_lp;         // token log-probabilities: the rows travel exactly as h_out's do
   std::vector<char> done(B0, 0);
   std::vector<int32_t> fin_of(B0, 0), unf_of(B0, 1);
   int steps_done = 1, B = B0, compactions = 0, launches = 0;
@@ -1239,6 +1258,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
       const int s = orig[r];
       if (done[s] || (only_finished && h_unf[r] != 0)) continue;
       memcpy(out_ids_host + (size_t)s * max_new_tokens, h_out.data() + (size_t)r * max_new_tokens, (size_t)max_new_tokens * sizeof(int32_t));
+      if (scores) memcpy(out_lp_host + (size_t)s * max_new_tokens, h_lp.data() + (size_t)r * max_new_tokens, (size_t)max_new_tokens * sizeof(float));
       fin_of[s] = h_fin[r]; unf_of[s] = h_unf[r];
       done[s] = 1;
     }
@@ -1269,6 +1289,10 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
       SL_HIP(hipMemcpyAsync(h_next.data(), next_ids, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
       if (row_limit_arg) SL_HIP(hipMemcpyAsync(h_lim.data(), row_limit, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
       SL_HIP(hipMemcpyAsync(h_out.data(), out_ids, (size_t)B * max_new_tokens * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      if (scores) {
+        h_lp.resize((size_t)B * max_new_tokens);
+        SL_HIP(hipMemcpyAsync(h_lp.data(), lp_out, (size_t)B * max_new_tokens * sizeof(float), hipMemcpyDeviceToHost, st));
+      }
       SL_HIP(hipStreamSynchronize(st));
       retire(true);
       std::vector<KvMove> moves;
@@ -1279,6 +1303,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
         moves.push_back(KvMove{r, hole, h_ctx[r], 0});
         h_unf[hole] = h_unf[r]; h_fin[hole] = h_fin[r]; h_ctx[hole] = h_ctx[r]; h_cnt[hole] = h_cnt[r]; h_next[hole] = h_next[r]; h_lim[hole] = h_lim[r];
         memcpy(h_out.data() + (size_t)hole * max_new_tokens, h_out.data() + (size_t)r * max_new_tokens, (size_t)max_new_tokens * sizeof(int32_t));
+        if (scores) memcpy(h_lp.data() + (size_t)hole * max_new_tokens, h_lp.data() + (size_t)r * max_new_tokens, (size_t)max_new_tokens * sizeof(float));
         orig[hole] = orig[r];
         ++hole;
       }
@@ -1300,6 +1325,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
       SL_HIP(hipMemcpyAsync(row_id, orig.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
       if (row_limit_arg) SL_HIP(hipMemcpyAsync(row_limit, h_lim.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
       SL_HIP(hipMemcpyAsync(out_ids, h_out.data(), (size_t)B * max_new_tokens * sizeof(int32_t), hipMemcpyHostToDevice, st));
+      if (scores) SL_HIP(hipMemcpyAsync(lp_out, h_lp.data(), (size_t)B * max_new_tokens * sizeof(float), hipMemcpyHostToDevice, st));
       SL_HIP(hipStreamSynchronize(st));           // the host vectors above are reused / the move list is overwritten by the next step's logits
       SL_TRY(graph_for(B, &exec));
       ++compactions;
@@ -1311,6 +1337,10 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   SL_HIP(hipMemcpyAsync(h_unf.data(), unfinished, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   SL_HIP(hipMemcpyAsync(h_fin.data(), finish_len, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   SL_HIP(hipMemcpyAsync(h_out.data(), out_ids, (size_t)B * max_new_tokens * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (scores) {
+    h_lp.resize((size_t)B * max_new_tokens);
+    SL_HIP(hipMemcpyAsync(h_lp.data(), lp_out, (size_t)B * max_new_tokens * sizeof(float), hipMemcpyDeviceToHost, st));
+  }
   SL_HIP(hipStreamSynchronize(st));
   retire(false);
   int n_cols = steps_done;
@@ -1323,7 +1353,10 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
     // batch would have (hf:generation/utils.py:2928-2929)
     for (int s = 0; s < B0; ++s)
       if (unf_of[s] == 0)
-        for (int t = fin_of[s]; t < max_new_tokens; ++t) out_ids_host[(size_t)s * max_new_tokens + t] = pad_id;
+        for (int t = fin_of[s]; t < max_new_tokens; ++t) {
+          out_ids_host[(size_t)s * max_new_tokens + t] = pad_id;
+          if (scores) out_lp_host[(size_t)s * max_new_tokens + t] = 0.f;
+        }
   }
   if (stats) {
     memset(stats, 0, sizeof(*stats));
@@ -1345,6 +1378,12 @@ extern "C" int sl_generate_lp(const sl_llama_model* m, const sl_kv_cache* kv, vo
                               const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
                               sl_stream stream, const sl_logits_opts* lp) {
   return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream, lp);
+}
+
+extern "C" int sl_generate_sc(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                              const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
+                              sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host) {
+  return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream, lp, out_logprobs_host);
 }
 
 static int generate_compat(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq, sl_generate_opts& o,

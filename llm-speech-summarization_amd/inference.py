@@ -79,9 +79,28 @@ class LLMSpeechTextInference():
                 d[k] = v
         return d
 
-    def generate_llm_response(self, inputs_embeds, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None) -> List[str]:
-        generate_ids = self.llm.generate(input_ids=None, inputs_embeds=inputs_embeds, max_new_tokens=max_new_tokens, **(self.beams or {}),
-                                         **self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens))
+    def _mean_logprobs(self, ids: torch.Tensor, logprobs: torch.Tensor) -> List[float]:
+        """One mean token log-probability per row over its generated length (up to and including the first EOS; pads hold 0.0)."""
+        e = self.llm.generation_config.eos_token_id
+        eos = list(e) if isinstance(e, (list, tuple)) else ([] if e is None else [e])
+        out = []
+        for row, lp in zip(ids.tolist(), logprobs.tolist()):
+            n = next((i + 1 for i, tok in enumerate(row) if tok in eos), len(row))
+            out.append(sum(lp[:n]) / max(n, 1))
+        return out
+
+    def generate_llm_response(self, inputs_embeds, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None,
+                              return_scores=False):
+        """return_scores=True: (texts, scores), one mean token log-probability per answer over its generated length (llm.generate with
+        output_scores; not with beam search)."""
+        kw = dict(self.beams or {}, **self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens))
+        if return_scores:
+            res = self.llm.generate(input_ids=None, inputs_embeds=inputs_embeds, max_new_tokens=max_new_tokens, return_dict_in_generate=True,
+                                    output_scores=True, **kw)
+            self.last_generate_ids = res.sequences
+            texts = self.llm_tokenizer.batch_decode(res.sequences, skip_special_tokens=True, clean_up_tokenization_spaces=True)
+            return texts, self._mean_logprobs(res.sequences, res.token_logprobs)
+        generate_ids = self.llm.generate(input_ids=None, inputs_embeds=inputs_embeds, max_new_tokens=max_new_tokens, **kw)
         self.last_generate_ids = generate_ids
         return self.llm_tokenizer.batch_decode(generate_ids, skip_special_tokens=True, clean_up_tokenization_spaces=True)
 
@@ -93,7 +112,7 @@ class LLMSpeechTextInference():
         return self.generate_llm_response(inputs_embeds=prompt_embeds, max_new_tokens=max_new_tokens)[0]
 
     def generate_audio_response(self, audio, additional_text_prompt="", max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None,
-                                min_new_tokens=None) -> str:
+                                min_new_tokens=None, return_scores=False):
         audio_tensor = torch.as_tensor(audio, dtype=torch.float32).unsqueeze(0).to(self.device)
         if self.audio_encoder.downsample_method == "ctc_pool":
             # the reference calls an undefined self.get_ctc_pool_ranges here
@@ -113,6 +132,9 @@ class LLMSpeechTextInference():
         prompt_emb_sequence = merge_prompt_tokens(inputs_embeds=combined_embeds, tokenizer=self.llm_tokenizer,
                                                   embed_tokens=self.llm.model.embed_tokens, llm_type=self.llm_type,
                                                   device=self.device)
+        if return_scores:
+            texts, scores = self.generate_llm_response(prompt_emb_sequence, max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens, True)
+            return texts[0], scores[0]
         return self.generate_llm_response(prompt_emb_sequence, max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens)[0]
 
     def _whisper_audio_embeds(self, audio) -> torch.Tensor:
@@ -129,8 +151,9 @@ class LLMSpeechTextInference():
         return padded[:, :keep]
 
     def generate_audio_responses(self, audios, additional_text_prompts=None, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None,
-                                 min_new_tokens=None) -> List[str]:
-        """Batched form of generate_audio_response (an extension: the reference answers one utterance per call).
+                                 min_new_tokens=None, return_scores=False):
+        """return_scores=True: (texts, scores), one mean token log-probability per answer; chunks are concatenated in order.
+        Batched form of generate_audio_response (an extension: the reference answers one utterance per call).
         Every utterance is encoded and prefilled at its own length in ONE ragged batch — the encoder writes its embeddings
         straight into the packed prompt buffer `[prefix | text[1:] | audio | suffix[1:]]` — and decoded together, so that the
         weights are streamed once per step for the whole batch; rows that stop early leave the batch (sl_generate's compaction).
@@ -142,14 +165,19 @@ class LLMSpeechTextInference():
         if len(texts) != n:
             raise ValueError(f"{len(texts)} text prompts for {n} utterances")
         if self.audio_encoder.downsample_method != "pool":       # stack / ctc_pool: the one-utterance path (ctc_pool raises as the reference does)
-            return [self.generate_audio_response(a, texts[i], max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens)
-                    for i, a in enumerate(audios)]
+            res = [self.generate_audio_response(a, texts[i], max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens, return_scores)
+                   for i, a in enumerate(audios)]
+            return ([r[0] for r in res], [r[1] for r in res]) if return_scores else res
         out: List[str] = []
         ids_all = []
+        scores_all: List[float] = []
         chunk = L.MAX_DECODE_BATCH // (self.beams["num_beams"] if self.beams else 1)      # a generate call is sized by its decode ROWS: utterances x beams
         for lo_ in range(0, n, chunk):
             ids = self._generate_chunk(audios[lo_:lo_ + chunk], texts[lo_:lo_ + chunk], max_new_tokens,
-                                       self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens))
+                                       self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens), return_scores)
+            if return_scores:
+                ids, lps = ids
+                scores_all += self._mean_logprobs(ids, lps)
             ids_all.append(ids)
             out += self.llm_tokenizer.batch_decode(ids, skip_special_tokens=True, clean_up_tokenization_spaces=True)
         # one (n, widest chunk) id matrix, pad-filled like a single HF call over the whole list would leave it
@@ -159,10 +187,10 @@ class LLMSpeechTextInference():
             e = self.llm.generation_config.eos_token_id
             pad = (e[0] if isinstance(e, (list, tuple)) else e) if e else 0
         self.last_generate_ids = torch.cat([torch.nn.functional.pad(i, (0, width - int(i.shape[1])), value=int(pad)) for i in ids_all]) if ids_all else None
-        return out
+        return (out, scores_all) if return_scores else out
 
-    def _generate_chunk(self, audios, texts, max_new_tokens, logits=None) -> torch.Tensor:
-        """One generate call's worth of utterances -> LongTensor (n, n_cols) of new tokens."""
+    def _generate_chunk(self, audios, texts, max_new_tokens, logits=None, scores=False):
+        """One generate call's worth of utterances -> LongTensor (n, n_cols) of new tokens (scores: and their (n, n_cols) log-probabilities)."""
         from .utils import compute_num_audio_embeds, prompt_template
         n = len(audios)
         emb = self.llm.model.embed_tokens
@@ -204,5 +232,9 @@ class LLMSpeechTextInference():
         shared = int(pre_e.shape[0])
         if txt_e[0] is not None and all(t_ == texts[0] for t_ in texts):
             shared += int(txt_e[0].shape[0])
+        if scores:
+            ids, n_cols, lps = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None,
+                                                        scores=True)
+            return ids[:, :n_cols].to(torch.int64), lps[:, :n_cols]
         ids, n_cols = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None)
         return ids[:, :n_cols].to(torch.int64)

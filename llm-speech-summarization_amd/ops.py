@@ -771,3 +771,53 @@ def sample_uniform(seed: int, row: int, step: int) -> float:
     seed &= 0xFFFFFFFFFFFFFFFF
     h = lowbias32((step & m32) ^ lowbias32((row & m32) ^ (seed & m32)) ^ (seed >> 32))
     return (h >> 8) / 16777216.0
+
+
+# ---- token log-probabilities (speechllm.h: sl_gemm_top1_lse and the _sc select entries)
+def gemm_top1_lse(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None, out=None):
+    """gemm_top1 plus the third plane: returns (val, idx, sum), each (ceil(N / 64), M); sum[g][m] = sum over group g's columns of
+    exp(v - val[g][m]).  out: optional (val, idx, sum) buffers to write into (the tests put guard bands around them)."""
+    L.require_gpu(A, "A"); L.require_gpu(W, "W")
+    M, K = A.shape
+    N = W.shape[0]
+    ng = (N + 63) // 64
+    if out is None:
+        out = (torch.empty((ng, M), device=A.device, dtype=torch.float32), torch.empty((ng, M), device=A.device, dtype=torch.int32),
+               torch.empty((ng, M), device=A.device, dtype=torch.float32))
+    val, idx, ssum = out
+    a = L.GemmArgs()
+    a.A, a.lda, a.W, a.ldw, a.C, a.ldc = L.ptr(A), A.stride(0), L.ptr(W), W.stride(0), None, N
+    a.bias = L.ptr(bias)
+    a.M, a.N, a.K, a.batch = M, N, K, 1
+    a.dtype, a.act, a.out_f32 = L.dtype_code(A.dtype), L.ACT_NONE, 1
+    ex = L.GemmEx()
+    ex.w_mod, ex.amax_val, ex.amax_idx = 1, L.ptr(val), L.ptr(idx)
+    L.check(L.lib().sl_gemm_top1_lse(C.byref(a), C.byref(ex), L.ptr(ssum), L.stream_ptr()), "sl_gemm_top1_lse")
+    return val, idx, ssum
+
+
+def greedy_select_sc(logits, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, logprobs) -> None:
+    B, V = logits.shape
+    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
+    L.check(L.lib().sl_greedy_select_sc(L.ptr(logits), B, V, eos, len(eos_ids), pad_id, int(use_eos), L.ptr(unfinished), L.ptr(ctx_len),
+                                        L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids), L.ptr(out_ids), out_ids.shape[1], L.ptr(logprobs),
+                                        L.stream_ptr()), "sl_greedy_select_sc")
+
+
+def greedy_select_partial_sc(val, idx, ssum, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, logprobs,
+                             advance_ctx=True) -> None:
+    ng, B = val.shape
+    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
+    L.check(L.lib().sl_greedy_select_partial_sc(L.ptr(val), L.ptr(idx), L.ptr(ssum), ng, B, eos, len(eos_ids), pad_id, int(use_eos), int(advance_ctx),
+                                                L.ptr(unfinished), L.ptr(ctx_len), L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids), L.ptr(out_ids),
+                                                out_ids.shape[1], L.ptr(logprobs), L.stream_ptr()), "sl_greedy_select_partial_sc")
+
+
+def sample_select_sc(logits, temperature, top_k, top_p, seed, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids,
+                     logprobs) -> None:
+    B, V = logits.shape
+    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
+    choice = torch.empty(B, dtype=torch.int32, device=logits.device)
+    L.check(L.lib().sl_sample_select_sc(L.ptr(logits), B, V, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, eos, len(eos_ids),
+                                        pad_id, int(use_eos), L.ptr(unfinished), L.ptr(ctx_len), L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids),
+                                        L.ptr(out_ids), out_ids.shape[1], L.ptr(choice), L.ptr(logprobs), L.stream_ptr()), "sl_sample_select_sc")
