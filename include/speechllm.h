@@ -510,7 +510,10 @@ int sl_softmax_bwd_var(const void* P, const float* dP, void* dS, int64_t n_mats,
 /* Losses over rows of fp32 logits; *loss += coef * sum_rows(...), d logits (+)= coef * grad (dtype T):
  *   ce:      lse(s) - s[label]                    (ref:model/audio_llama.py:72-101 with coef = w/(n-1))
  *   soft-ce: -sum softmax(t) * log_softmax(s)     (ref:utils.py:167-178 with coef = w/n)
- *   mse:     mean((a-b)^2)                        (ref:trainer.py:358-370) */
+ *   mse:     mean((a-b)^2)                        (ref:trainer.py:358-370)
+ * sl_ce_loss: every labels[r] must be in [0, V) — the kernel reads logits[r][labels[r]] unconditionally.  Its one caller hands it the
+ * response's own token ids (ref:model/audio_llama.py:84-98: labels exist for the response portion only, no ignore index reaches the
+ * loss); rows without a next-token term belong to sl_kd_logit_losses, which skips labels < 0. */
 int sl_ce_loss(const float* logits, const int32_t* labels, int64_t rows, int32_t V, float coef, float* loss, void* dlogits,
                int32_t accumulate, int32_t dtype, sl_stream stream);
 int sl_soft_ce_loss(const float* student, const float* teacher, int64_t rows, int32_t V, float coef, float* loss,
