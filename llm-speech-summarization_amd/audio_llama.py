@@ -373,6 +373,27 @@ class AudioLlamaForCausalLM:
         lp.repetition_penalty, lp.no_repeat_ngram_size, lp.min_new_tokens = d["repetition_penalty"], d["no_repeat_ngram_size"], d["min_new_tokens"]
         return lp
 
+    def _generate_preamble(self, lens, max_new_tokens, use_eos, shared_prefix):
+        """What generate_packed and _beam_packed check and build alike: the context and shared-prefix limits, then
+        (cu_seqlens, eos ids, n_eos, use_eos, pad) as the library takes them."""
+        if max(lens) + max_new_tokens > self.max_ctx:
+            raise L.SpeechLLMError(f"prompt ({max(lens)}) + max_new_tokens ({max_new_tokens}) exceeds max_ctx={self.max_ctx}")
+        if not 0 <= shared_prefix <= min(lens):
+            raise L.SpeechLLMError(f"shared_prefix={shared_prefix} outside [0, shortest prompt={min(lens)}]")
+        cu = [0]
+        for n in lens:
+            cu.append(cu[-1] + int(n))
+        cu_c = (C.c_int32 * (len(lens) + 1))(*cu)
+        gen = self.generation_config
+        eos = list(gen.eos_token_id) if isinstance(gen.eos_token_id, (list, tuple)) else ([] if gen.eos_token_id is None else [gen.eos_token_id])
+        pad = gen.pad_token_id if gen.pad_token_id is not None else (eos[0] if eos else 0)
+        return cu_c, (C.c_int32 * max(1, len(eos)))(*eos), len(eos), bool(use_eos and len(eos) > 0), pad
+
+    def _record_generate_stats(self, st, rows, fmt_name, **extra):
+        self.last_timings_ms = (st.prefill_ms, st.decode_ms)
+        self.last_generate_stats = {"rows": rows, "n_steps": int(st.n_steps), "decode_launches": int(st.decode_launches), "compactions": int(st.compactions),
+                                    "final_rows": int(st.final_rows), "row_steps": int(st.row_steps), "weight_format": fmt_name, **extra}
+
     def generate_packed(self, x: torch.Tensor, lens: Sequence[int], max_new_tokens: int, use_eos: bool = True, sample: Optional[dict] = None,
                         shared_prefix: int = 0, row_limits: Optional[Sequence[int]] = None, compact: bool = True, check_every: int = 4,
                         beams: Optional[dict] = None, logits: Optional[dict] = None, scores: bool = False):
@@ -406,24 +427,12 @@ class AudioLlamaForCausalLM:
             return self._beam_packed(x, lens, max_new_tokens, use_eos, shared_prefix, check_every, beams, logits)
         if B > L.MAX_DECODE_BATCH:
             raise L.SpeechLLMError(f"{B} sequences in one generate call; the library takes {L.MAX_DECODE_BATCH} (split the batch: sequences are independent)")
-        if max(lens) + max_new_tokens > self.max_ctx:
-            raise L.SpeechLLMError(f"prompt ({max(lens)}) + max_new_tokens ({max_new_tokens}) exceeds max_ctx={self.max_ctx}")
-        if not 0 <= shared_prefix <= min(lens):
-            raise L.SpeechLLMError(f"shared_prefix={shared_prefix} outside [0, shortest prompt={min(lens)}]")
+        cu_c, eos_c, n_eos, use_eos, pad = self._generate_preamble(lens, max_new_tokens, use_eos, shared_prefix)
         kv = self._kv_cache(B, shared_prefix)
-        cu = [0]
-        for n in lens:
-            cu.append(cu[-1] + int(n))
-        cu_c = (C.c_int32 * (B + 1))(*cu)
-        gen = self.generation_config
-        eos = list(gen.eos_token_id) if isinstance(gen.eos_token_id, (list, tuple)) else ([] if gen.eos_token_id is None else [gen.eos_token_id])
-        use_eos = bool(use_eos and len(eos) > 0)
-        pad = gen.pad_token_id if gen.pad_token_id is not None else (eos[0] if eos else 0)
-        eos_c = (C.c_int32 * max(1, len(eos)))(*eos)
         out = (C.c_int32 * (B * max_new_tokens))()
         o = L.GenerateOpts()
         # the ids are handed over as configured; with use_eos = 0 the library ignores them (rows then finish on their budgets only)
-        o.eos_ids_host, o.n_eos, o.pad_id, o.use_eos = eos_c, len(eos), int(pad), int(use_eos)
+        o.eos_ids_host, o.n_eos, o.pad_id, o.use_eos = eos_c, n_eos, int(pad), int(use_eos)
         o.max_new_tokens, o.check_every, o.compact = int(max_new_tokens), int(check_every), int(bool(compact))
         lim_c = None
         if row_limits is not None:
@@ -448,9 +457,7 @@ class AudioLlamaForCausalLM:
             ws = self._workspace(lib.sl_generate_workspace_bytes_lp(C.byref(struct), x.shape[0], B, max_new_tokens, lp_ref))
             L.check(lib.sl_generate_lp(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
                                        L.stream_ptr(), lp_ref), "sl_generate")
-        self.last_timings_ms = (st.prefill_ms, st.decode_ms)
-        self.last_generate_stats = {"rows": B, "n_steps": int(st.n_steps), "decode_launches": int(st.decode_launches), "compactions": int(st.compactions),
-                                    "final_rows": int(st.final_rows), "row_steps": int(st.row_steps), "weight_format": fmt_name}
+        self._record_generate_stats(st, B, fmt_name)
         ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B, max_new_tokens)
         if scores:
             return ids, int(st.n_steps), torch.frombuffer(lps, dtype=torch.float32).clone().view(B, max_new_tokens)
@@ -469,22 +476,10 @@ class AudioLlamaForCausalLM:
             raise L.SpeechLLMError(f"num_return_sequences={R} outside [1, num_beams={K}]")
         if B * K > L.MAX_DECODE_BATCH:
             raise L.SpeechLLMError(f"{B} sequences x {K} beams = {B * K} decode rows; the library takes {L.MAX_DECODE_BATCH} (split the batch)")
-        if max(lens) + max_new_tokens > self.max_ctx:
-            raise L.SpeechLLMError(f"prompt ({max(lens)}) + max_new_tokens ({max_new_tokens}) exceeds max_ctx={self.max_ctx}")
-        if not 0 <= shared_prefix <= min(lens):
-            raise L.SpeechLLMError(f"shared_prefix={shared_prefix} outside [0, shortest prompt={min(lens)}]")
+        cu_c, eos_c, n_eos, use_eos, pad = self._generate_preamble(lens, max_new_tokens, use_eos, shared_prefix)
         kv = self._kv_cache(B * K, shared_prefix)
-        cu = [0]
-        for n in lens:
-            cu.append(cu[-1] + int(n))
-        cu_c = (C.c_int32 * (B + 1))(*cu)
-        gen = self.generation_config
-        eos = list(gen.eos_token_id) if isinstance(gen.eos_token_id, (list, tuple)) else ([] if gen.eos_token_id is None else [gen.eos_token_id])
-        use_eos = bool(use_eos and len(eos) > 0)
-        pad = gen.pad_token_id if gen.pad_token_id is not None else (eos[0] if eos else 0)
-        eos_c = (C.c_int32 * max(1, len(eos)))(*eos)
         o = L.BeamOpts()
-        o.eos_ids_host, o.n_eos, o.pad_id, o.use_eos = eos_c, len(eos), int(pad), int(use_eos)
+        o.eos_ids_host, o.n_eos, o.pad_id, o.use_eos = eos_c, n_eos, int(pad), int(use_eos)
         o.max_new_tokens, o.check_every = int(max_new_tokens), int(check_every)
         o.num_beams, o.num_return_sequences = K, R
         o.early_stopping = L.early_stopping_code(beams.get("early_stopping", False))
@@ -502,9 +497,7 @@ class AudioLlamaForCausalLM:
         ws = self._workspace(nbytes)
         L.check(lib.sl_beam_generate_lp(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, scores, lengths, C.byref(st), ws.data_ptr(),
                                         ws.numel(), L.stream_ptr(), lp_ref), "sl_beam_generate")
-        self.last_timings_ms = (st.prefill_ms, st.decode_ms)
-        self.last_generate_stats = {"rows": B * K, "n_steps": int(st.n_steps), "decode_launches": int(st.decode_launches), "compactions": 0,
-                                    "final_rows": int(st.final_rows), "row_steps": int(st.row_steps), "weight_format": fmt_name, "num_beams": K}
+        self._record_generate_stats(st, B * K, fmt_name, num_beams=K)
         self.last_beam_scores = torch.frombuffer(scores, dtype=torch.float32).clone()
         self.last_beam_lengths = torch.frombuffer(lengths, dtype=torch.int32).clone()
         ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B * R, max_new_tokens)

@@ -24,6 +24,13 @@ static int g_fail = 0;
     EXPECT(sl_last_error()[0] != 0, #call " must leave an error message");         \
   } while (0)
 
+// ... and the message names the reason: a case refused by an EARLIER check would pass EXPECT_ARG_ERROR all the same
+#define EXPECT_ARG_ERROR_SAYS(call, needle)                                         \
+  do {                                                                              \
+    EXPECT_ARG_ERROR(call);                                                         \
+    EXPECT(strstr(sl_last_error(), needle) != nullptr, #call " must name " needle); \
+  } while (0)
+
 static void fill_hubert(sl_hubert_model* m, sl_hubert_layer* layers, int n_layers) {
   memset(m, 0, sizeof(*m));
   m->dtype = SL_BF16; m->n_conv = 7; m->hidden = 1024; m->n_layers = n_layers; m->n_heads = 16; m->ffn = 4096; m->pos_k = 128; m->pos_groups = 16;
@@ -231,6 +238,35 @@ int main() {
     EXPECT_ARG_ERROR(sl_generate(&lm, &kv, ws, cu, 1, &go, out_ids, &gs, ws, sizeof(ws), nullptr));                      // temperature 0
     go.sample = 0;
     EXPECT_ARG_ERROR(sl_generate(&lm, &kv, ws, cu, 1, &go, out_ids, &gs, ws, 64, nullptr));                              // workspace too small
+  }
+  {   // the generation loops' own limits, with a model and a cache that pass every earlier check: refused before any device call
+    sl_generate_opts go;
+    memset(&go, 0, sizeof(go));
+    sl_generate_stats gs;
+    go.max_new_tokens = 8; go.eos_ids_host = eos; go.n_eos = 3; go.pad_id = 128001; go.use_eos = 1; go.compact = 1;
+    float* lps = (float*)ws;
+    const size_t need = sl_generate_workspace_bytes_sc(&lm, 137, 1, 8, nullptr, 1);
+    EXPECT(need > 0, "generate workspace with scores");
+    EXPECT_ARG_ERROR_SAYS(sl_generate_sc(&lm, &kv, ws, cu, 1, &go, out_ids, &gs, ws, need - 1, nullptr, nullptr, lps), "workspace");       // workspace one byte short
+    go.max_new_tokens = 128;
+    EXPECT_ARG_ERROR_SAYS(sl_generate_sc(&lm, &kv, ws, cu, 1, &go, out_ids, &gs, ws, need, nullptr, nullptr, lps), "max_ctx");           // 137 + 128 > max_ctx = 256
+    go.max_new_tokens = 8;
+    int32_t lim[1] = {0};
+    go.row_limits_host = lim;
+    EXPECT_ARG_ERROR_SAYS(sl_generate_sc(&lm, &kv, ws, cu, 1, &go, out_ids, &gs, ws, need, nullptr, nullptr, lps), "row limit");           // row limit 0
+    sl_kv_cache kv4 = kv;
+    kv4.slots = 4;
+    sl_beam_opts bo;
+    memset(&bo, 0, sizeof(bo));
+    bo.eos_ids_host = eos; bo.n_eos = 3; bo.use_eos = 1; bo.max_new_tokens = 8; bo.num_beams = 2; bo.num_return_sequences = 1; bo.length_penalty = 1.0f;
+    sl_logits_opts lp = {1.2f, 0, 0, 0};
+    float sc[2];
+    int32_t ln[2];
+    const size_t bneed = sl_beam_generate_workspace_bytes_lp(&lm, 137, 1, &kv4, &bo, &lp);
+    EXPECT(bneed > 0, "beam workspace with the penalty on");
+    EXPECT_ARG_ERROR_SAYS(sl_beam_generate_lp(&lm, &kv4, ws, cu, 1, &bo, out_ids, sc, ln, &gs, ws, bneed - 1, nullptr, &lp), "workspace");   // workspace one byte short
+    bo.num_beams = 9;
+    EXPECT_ARG_ERROR_SAYS(sl_beam_generate_lp(&lm, &kv4, ws, cu, 1, &bo, out_ids, sc, ln, &gs, ws, bneed, nullptr, &lp), "num_beams");       // num_beams 9
   }
   EXPECT(sl_comm_abort(nullptr) == 0, "aborting no communicator is a no-op");
   kv.shared_prefix = -1;

@@ -524,3 +524,21 @@ struct SlFamilyPin {
   explicit SlFamilyPin(int rows) : prev(sl_family_pin(rows)) {}
   ~SlFamilyPin() { sl_family_pin(prev); }
 };
+
+// Per-row generation state a select pass reads and advances (llama_ops.hip), all device arrays of B rows unless noted: the one argument
+// of the three selects below, which the extern "C" entries and the generation loop (runtime.hip) fill.
+struct SlRowState {
+  int32_t *unfinished, *ctx_len, *gen_count, *finish_len, *next_ids;
+  int32_t* out_ids;               // (B, max_new)
+  int32_t max_new;
+  const int32_t* row_limit;       // per-row token budgets, NULL = none
+  float* logprob_out;             // (B, max_new) token log-probabilities, NULL = off
+  const int32_t* eos_ids;         // HOST, n_eos <= 8 ids
+  int32_t n_eos, pad_id, use_eos, advance_ctx;
+};
+int sl_greedy_select_impl(const float* logits, int32_t B, int32_t V, const SlRowState& rs, hipStream_t st);
+// amax_sum (the third plane) and rs.logprob_out come together
+int sl_greedy_select_partial_impl(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int32_t n_groups, int32_t B, const SlRowState& rs,
+                                  hipStream_t st);
+int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed, int32_t* choice_ws,
+                          const int32_t* row_ids, const SlRowState& rs, hipStream_t st);

@@ -278,16 +278,38 @@ extern "C" int sl_attn_decode(const void* q, int64_t q_stride, const void* k_cac
 // ----------------------------------------------------------------------------------------------
 struct EosList { int ids[8]; int n; };
 
+// The bookkeeping every select ends with, by the one thread that holds row b's token: pad for a finished row (hf:generation/utils.py:2928-2929),
+// out_ids[b][gen_count], the counters, EOS / the row's own budget (a spent budget finishes the row like an EOS), the context.
+// SC: the token's log-probability `lp` goes to logprob_out[b][gen_count], 0 for a finished row; LP = false (sampling: the draw left it there
+// already) only writes that 0.
+template <bool SC, bool LP = true>
+__device__ __forceinline__ void select_commit(const SlRowState& rs, const EosList& eos, int b, int tok, float lp = 0.f) {
+  const int unf = rs.unfinished[b];
+  if (rs.use_eos) tok = unf ? tok : rs.pad_id;
+  const int n = rs.gen_count[b];
+  if constexpr (SC) {
+    if (n < rs.max_new && (LP || (rs.use_eos && !unf))) rs.logprob_out[(int64_t)b * rs.max_new + n] = (rs.use_eos && !unf) ? 0.f : lp;
+  }
+  if (n < rs.max_new) rs.out_ids[(int64_t)b * rs.max_new + n] = tok;
+  rs.gen_count[b] = n + 1;
+  rs.next_ids[b] = tok;
+  if (rs.use_eos && unf) {
+    bool is_eos = false;
+    for (int e = 0; e < eos.n; ++e) is_eos |= (tok == eos.ids[e]);
+    if (rs.row_limit) is_eos |= (n + 1 >= rs.row_limit[b]);
+    if (is_eos) { rs.unfinished[b] = 0; rs.finish_len[b] = n + 1; }
+  }
+  if (rs.advance_ctx) rs.ctx_len[b] += 1;
+}
+
 // SC (token log-probabilities): logprob_out[b][gen_count] = log_softmax(row)[token] through the row reduce beam search and the
 // logits processors use (common.h sl_row_max_lse), 0 for a finished row.  In sampling mode sample_rows_kernel has left the drawn token's
 // value there; the commit only zeroes it for a finished row.  SC = false is the kernel as it was.
+// rs travels by value: the state pointers and scalars are the device's to read, rs.eos_ids is a HOST pointer (the ids come in `eos`) —
+// never read rs.eos_ids / rs.n_eos in device code.
 template <bool SC>
-__global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __restrict__ logits, int V, EosList eos, int pad_id, int use_eos,
-                                                             int advance_ctx, int32_t* __restrict__ unfinished, int32_t* __restrict__ ctx_len,
-                                                             int32_t* __restrict__ gen_count, int32_t* __restrict__ finish_len,
-                                                             int32_t* __restrict__ next_ids, int32_t* __restrict__ out_ids, int max_new,
-                                                             const int32_t* __restrict__ forced, const int32_t* __restrict__ row_limit,
-                                                             float* __restrict__ logprob_out) {
+__global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __restrict__ logits, int V, EosList eos, SlRowState rs,
+                                                             const int32_t* __restrict__ forced) {
   __shared__ float smax[16];
   __shared__ int sidx[16];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -295,25 +317,7 @@ __global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __rest
   float best = -INFINITY;
   int bi = 0x7fffffff;
   if (forced) {   // sampling mode: the token was drawn by sample_rows_kernel; only the bookkeeping below runs
-    if (tid == 0) {
-      int tok = forced[b];
-      const int unf = unfinished[b];
-      if (use_eos) tok = unf ? tok : pad_id;
-      const int n = gen_count[b];
-      if constexpr (SC) {
-        if (use_eos && !unf && n < max_new) logprob_out[(int64_t)b * max_new + n] = 0.f;
-      }
-      if (n < max_new) out_ids[(int64_t)b * max_new + n] = tok;
-      gen_count[b] = n + 1;
-      next_ids[b] = tok;
-      if (use_eos && unf) {
-        bool is_eos = false;
-        for (int e = 0; e < eos.n; ++e) is_eos |= (tok == eos.ids[e]);
-        if (row_limit) is_eos |= (n + 1 >= row_limit[b]);       // the row's own token budget is spent: finished like a row that emitted EOS
-        if (is_eos) { unfinished[b] = 0; finish_len[b] = n + 1; }
-      }
-      if (advance_ctx) ctx_len[b] += 1;
-    }
+    if (tid == 0) select_commit<SC, false>(rs, eos, b, forced[b]);
     return;
   }
   auto upd = [&](float v, int i) {
@@ -357,42 +361,26 @@ __global__ __launch_bounds__(1024) void greedy_select_kernel(const float* __rest
     for (int w = 1; w < 16; ++w)
       if (smax[w] > best || (smax[w] == best && sidx[w] < bi)) { best = smax[w]; bi = sidx[w]; }
     if (bi == 0x7fffffff) bi = 0;
-    int tok = bi;
-    int unf = unfinished[b];
-    if (use_eos) tok = unf ? tok : pad_id;   // hf:generation/utils.py:2928-2929
-    const int n = gen_count[b];
-    if constexpr (SC) {
-      if (n < max_new) logprob_out[(int64_t)b * max_new + n] = (use_eos && !unf) ? 0.f : (best - row_m) - row_ls;
-    }
-    if (n < max_new) out_ids[(int64_t)b * max_new + n] = tok;
-    gen_count[b] = n + 1;
-    next_ids[b] = tok;
-    if (use_eos && unf) {
-      bool is_eos = false;
-      for (int e = 0; e < eos.n; ++e) is_eos |= (tok == eos.ids[e]);
-      if (row_limit) is_eos |= (n + 1 >= row_limit[b]);
-      if (is_eos) { unfinished[b] = 0; finish_len[b] = n + 1; }
-    }
-    if (advance_ctx) ctx_len[b] += 1;
+    select_commit<SC>(rs, eos, b, bi, (best - row_m) - row_ls);
   }
 }
 
-int sl_greedy_select_impl(const float* logits, int32_t B, int32_t V, const int32_t* eos_ids, int32_t n_eos, int32_t pad_id,
-                          int32_t use_eos, int32_t advance_ctx, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count,
-                          int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit,
-                          float* logprob_out) {
-  SL_CHECK_ARG(logits && unfinished && ctx_len && gen_count && finish_len && next_ids && out_ids && B > 0 && V > 0,
-               "sl_greedy_select: bad arguments");
-  SL_CHECK_ARG(n_eos >= 0 && n_eos <= 8, "sl_greedy_select: at most 8 eos ids");
+// the state arrays every select needs, and the EOS ids as the kernels take them
+static bool row_state_ok(const SlRowState& rs) {
+  return rs.unfinished && rs.ctx_len && rs.gen_count && rs.finish_len && rs.next_ids && rs.out_ids;
+}
+static EosList eos_list(const SlRowState& rs) {
   EosList e;
-  e.n = n_eos;
-  for (int i = 0; i < 8; ++i) e.ids[i] = i < n_eos ? eos_ids[i] : -1;
-  if (logprob_out)
-    hipLaunchKernelGGL(greedy_select_kernel<true>, dim3(B), dim3(1024), 0, st, logits, V, e, pad_id, use_eos, advance_ctx, unfinished, ctx_len,
-                       gen_count, finish_len, next_ids, out_ids, max_new, (const int32_t*)nullptr, row_limit, logprob_out);
-  else
-    hipLaunchKernelGGL(greedy_select_kernel<false>, dim3(B), dim3(1024), 0, st, logits, V, e, pad_id, use_eos, advance_ctx, unfinished, ctx_len,
-                       gen_count, finish_len, next_ids, out_ids, max_new, (const int32_t*)nullptr, row_limit, (float*)nullptr);
+  e.n = rs.n_eos;
+  for (int i = 0; i < 8; ++i) e.ids[i] = i < rs.n_eos ? rs.eos_ids[i] : -1;
+  return e;
+}
+
+int sl_greedy_select_impl(const float* logits, int32_t B, int32_t V, const SlRowState& rs, hipStream_t st) {
+  SL_CHECK_ARG(logits && row_state_ok(rs) && B > 0 && V > 0, "sl_greedy_select: bad arguments");
+  SL_CHECK_ARG(rs.n_eos >= 0 && rs.n_eos <= 8, "sl_greedy_select: at most 8 eos ids");
+  auto* kern = rs.logprob_out ? greedy_select_kernel<true> : greedy_select_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(B), dim3(1024), 0, st, logits, V, eos_list(rs), rs, (const int32_t*)nullptr);
   SL_CHECK_LAUNCH("greedy_select");
   return 0;
 }
@@ -400,7 +388,7 @@ int sl_greedy_select_impl(const float* logits, int32_t B, int32_t V, const int32
 // greedy selection over the [group][B] partial maxima a fused lm_head left (gemm.hip tile_argmax): block = 32 rows x 32 group
 // stripes (a wave = two stripes of 32 consecutive rows: two 128-byte segments per load), eight groups' values and columns in
 // flight per thread — the scan is latency-bound (2 004 groups of 8 bytes per row at vocab 128 256), not bandwidth-bound; the
-// stripes meet in LDS in stripe order and the bookkeeping of greedy_select_kernel follows.  Compare rule everywhere: larger
+// stripes meet in LDS in stripe order and select_commit follows.  Compare rule everywhere: larger
 // value, then lower column.
 // SC (token log-probabilities): ps holds the third plane, sum_g = sum exp(v - max_g) per group.  With the row maximum Mx (every
 // thread folds the 32 stripe maxima of its row, in stripe order) a second pass forms sum_g * exp(max_g - Mx) per stripe in group order, the
@@ -408,12 +396,7 @@ int sl_greedy_select_impl(const float* logits, int32_t B, int32_t V, const int32
 // SC = false is the kernel as it was.
 template <bool SC>
 __global__ __launch_bounds__(1024) void greedy_select_partial_kernel(const float* __restrict__ pv, const int32_t* __restrict__ pi, int n_groups, int B,
-                                                                     EosList eos, int pad_id, int use_eos, int advance_ctx,
-                                                                     int32_t* __restrict__ unfinished, int32_t* __restrict__ ctx_len,
-                                                                     int32_t* __restrict__ gen_count, int32_t* __restrict__ finish_len,
-                                                                     int32_t* __restrict__ next_ids, int32_t* __restrict__ out_ids, int max_new,
-                                                                     const int32_t* __restrict__ row_limit, const float* __restrict__ ps,
-                                                                     float* __restrict__ logprob_out) {
+                                                                     EosList eos, SlRowState rs, const float* __restrict__ ps) {
   constexpr int ROWS = 32, STRIPES = 32, U = 8;
   __shared__ float sv[STRIPES][ROWS];
   __shared__ int si[STRIPES][ROWS];
@@ -471,42 +454,16 @@ __global__ __launch_bounds__(1024) void greedy_select_partial_kernel(const float
   for (int s2 = 1; s2 < STRIPES; ++s2)
     if (sv[s2][lr] > best || (sv[s2][lr] == best && si[s2][lr] < bi)) { best = sv[s2][lr]; bi = si[s2][lr]; }
   if (bi == 0x7fffffff) bi = 0;
-  int tok = bi;
-  const int unf = unfinished[b];
-  if (use_eos) tok = unf ? tok : pad_id;   // hf:generation/utils.py:2928-2929
-  const int n = gen_count[b];
-  if constexpr (SC) {
-    if (n < max_new) logprob_out[(int64_t)b * max_new + n] = (use_eos && !unf) ? 0.f : -logf(total);
-  }
-  if (n < max_new) out_ids[(int64_t)b * max_new + n] = tok;
-  gen_count[b] = n + 1;
-  next_ids[b] = tok;
-  if (use_eos && unf) {
-    bool is_eos = false;
-    for (int e = 0; e < eos.n; ++e) is_eos |= (tok == eos.ids[e]);
-    if (row_limit) is_eos |= (n + 1 >= row_limit[b]);
-    if (is_eos) { unfinished[b] = 0; finish_len[b] = n + 1; }
-  }
-  if (advance_ctx) ctx_len[b] += 1;
+  select_commit<SC>(rs, eos, b, bi, SC ? -logf(total) : 0.f);
 }
 
-int sl_greedy_select_partial_impl(const float* amax_val, const int32_t* amax_idx, int32_t n_groups, int32_t B, const int32_t* eos_ids, int32_t n_eos,
-                                  int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count,
-                                  int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit,
-                                  const float* amax_sum, float* logprob_out) {
-  SL_CHECK_ARG(amax_val && amax_idx && unfinished && ctx_len && gen_count && finish_len && next_ids && out_ids && B > 0 && n_groups > 0,
-               "sl_greedy_select_partial: bad arguments");
-  SL_CHECK_ARG(n_eos >= 0 && n_eos <= 8, "sl_greedy_select_partial: at most 8 eos ids");
-  SL_CHECK_ARG((amax_sum != nullptr) == (logprob_out != nullptr), "sl_greedy_select_partial_sc: amax_sum and logprob_out come together");
-  EosList e;
-  e.n = n_eos;
-  for (int i = 0; i < 8; ++i) e.ids[i] = i < n_eos ? eos_ids[i] : -1;
-  if (logprob_out)
-    hipLaunchKernelGGL(greedy_select_partial_kernel<true>, dim3((B + 31) / 32), dim3(1024), 0, st, amax_val, amax_idx, n_groups, B, e, pad_id, use_eos, advance_ctx,
-                       unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, row_limit, amax_sum, logprob_out);
-  else
-    hipLaunchKernelGGL(greedy_select_partial_kernel<false>, dim3((B + 31) / 32), dim3(1024), 0, st, amax_val, amax_idx, n_groups, B, e, pad_id, use_eos, advance_ctx,
-                     unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, row_limit, (const float*)nullptr, (float*)nullptr);
+int sl_greedy_select_partial_impl(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int32_t n_groups, int32_t B, const SlRowState& rs,
+                                  hipStream_t st) {
+  SL_CHECK_ARG(amax_val && amax_idx && row_state_ok(rs) && B > 0 && n_groups > 0, "sl_greedy_select_partial: bad arguments");
+  SL_CHECK_ARG(rs.n_eos >= 0 && rs.n_eos <= 8, "sl_greedy_select_partial: at most 8 eos ids");
+  SL_CHECK_ARG((amax_sum != nullptr) == (rs.logprob_out != nullptr), "sl_greedy_select_partial_sc: amax_sum and logprob_out come together");
+  auto* kern = rs.logprob_out ? greedy_select_partial_kernel<true> : greedy_select_partial_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((B + 31) / 32), dim3(1024), 0, st, amax_val, amax_idx, n_groups, B, eos_list(rs), rs, amax_sum);
   SL_CHECK_LAUNCH("greedy_select_partial");
   return 0;
 }
@@ -514,16 +471,16 @@ int sl_greedy_select_partial_impl(const float* amax_val, const int32_t* amax_idx
 extern "C" int sl_greedy_select_partial(const float* amax_val, const int32_t* amax_idx, int32_t n_groups, int32_t B, const int32_t* eos_ids, int32_t n_eos,
                                         int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count,
                                         int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, sl_stream stream) {
-  return sl_greedy_select_partial_impl(amax_val, amax_idx, n_groups, B, eos_ids, n_eos, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count,
-                                       finish_len, next_ids, out_ids, max_new, (hipStream_t)stream, nullptr, nullptr, nullptr);
+  const SlRowState rs{unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, nullptr, nullptr, eos_ids, n_eos, pad_id, use_eos, advance_ctx};
+  return sl_greedy_select_partial_impl(amax_val, amax_idx, nullptr, n_groups, B, rs, (hipStream_t)stream);
 }
 
 extern "C" int sl_greedy_select_partial_sc(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int32_t n_groups, int32_t B,
                                            const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished,
                                            int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new,
                                            float* logprob_out, sl_stream stream) {
-  return sl_greedy_select_partial_impl(amax_val, amax_idx, n_groups, B, eos_ids, n_eos, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count,
-                                       finish_len, next_ids, out_ids, max_new, (hipStream_t)stream, nullptr, amax_sum, logprob_out);
+  const SlRowState rs{unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, nullptr, logprob_out, eos_ids, n_eos, pad_id, use_eos, advance_ctx};
+  return sl_greedy_select_partial_impl(amax_val, amax_idx, amax_sum, n_groups, B, rs, (hipStream_t)stream);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -667,27 +624,17 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
   }
 }
 
-int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
-                          const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished,
-                          int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new,
-                          int32_t* choice_ws, hipStream_t st, const int32_t* row_limit, const int32_t* row_ids, float* logprob_out) {
-  SL_CHECK_ARG(logits && unfinished && ctx_len && gen_count && finish_len && next_ids && out_ids && choice_ws && B > 0 && V > 0,
-               "sl_sample_select: bad arguments");
+int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed, int32_t* choice_ws,
+                          const int32_t* row_ids, const SlRowState& rs, hipStream_t st) {
+  SL_CHECK_ARG(logits && row_state_ok(rs) && choice_ws && B > 0 && V > 0, "sl_sample_select: bad arguments");
   SL_CHECK_ARG(temperature > 0.f && top_p > 0.f && top_p <= 1.0f && top_k >= 0, "sl_sample_select: need temperature > 0, 0 < top_p <= 1, top_k >= 0 (got %f, %f, %d)",
                (double)temperature, (double)top_p, top_k);
-  SL_CHECK_ARG(n_eos >= 0 && n_eos <= 8, "sl_sample_select: at most 8 eos ids");
-  EosList e;
-  e.n = n_eos;
-  for (int i = 0; i < 8; ++i) e.ids[i] = i < n_eos ? eos_ids[i] : -1;
-  hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(1024), 0, st, logits, V, 1.0f / temperature, top_k, top_p, seed, gen_count, choice_ws, row_ids,
-                     logprob_out, max_new);
+  SL_CHECK_ARG(rs.n_eos >= 0 && rs.n_eos <= 8, "sl_sample_select: at most 8 eos ids");
+  hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(1024), 0, st, logits, V, 1.0f / temperature, top_k, top_p, seed, rs.gen_count, choice_ws, row_ids,
+                     rs.logprob_out, rs.max_new);
   SL_CHECK_LAUNCH("sample_rows");
-  if (logprob_out)
-    hipLaunchKernelGGL(greedy_select_kernel<true>, dim3(B), dim3(64), 0, st, logits, V, e, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count, finish_len,
-                       next_ids, out_ids, max_new, (const int32_t*)choice_ws, row_limit, logprob_out);
-  else
-    hipLaunchKernelGGL(greedy_select_kernel<false>, dim3(B), dim3(64), 0, st, logits, V, e, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count, finish_len,
-                       next_ids, out_ids, max_new, (const int32_t*)choice_ws, row_limit, (float*)nullptr);
+  auto* kern = rs.logprob_out ? greedy_select_kernel<true> : greedy_select_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(B), dim3(64), 0, st, logits, V, eos_list(rs), rs, (const int32_t*)choice_ws);
   SL_CHECK_LAUNCH("sample_commit");
   return 0;
 }
@@ -696,30 +643,30 @@ extern "C" int sl_sample_select(const float* logits, int32_t B, int32_t V, float
                                 const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t* unfinished, int32_t* ctx_len,
                                 int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, int32_t* choice_ws,
                                 sl_stream stream) {
-  return sl_sample_select_impl(logits, B, V, temperature, top_k, top_p, seed, eos_ids, n_eos, pad_id, use_eos, 1, unfinished, ctx_len, gen_count, finish_len,
-                               next_ids, out_ids, max_new, choice_ws, (hipStream_t)stream, nullptr, nullptr, nullptr);
+  const SlRowState rs{unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, nullptr, nullptr, eos_ids, n_eos, pad_id, use_eos, 1};
+  return sl_sample_select_impl(logits, B, V, temperature, top_k, top_p, seed, choice_ws, nullptr, rs, (hipStream_t)stream);
 }
 
 extern "C" int sl_sample_select_sc(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
                                    const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t* unfinished, int32_t* ctx_len,
                                    int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, int32_t* choice_ws,
                                    float* logprob_out, sl_stream stream) {
-  return sl_sample_select_impl(logits, B, V, temperature, top_k, top_p, seed, eos_ids, n_eos, pad_id, use_eos, 1, unfinished, ctx_len, gen_count, finish_len,
-                               next_ids, out_ids, max_new, choice_ws, (hipStream_t)stream, nullptr, nullptr, logprob_out);
+  const SlRowState rs{unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, nullptr, logprob_out, eos_ids, n_eos, pad_id, use_eos, 1};
+  return sl_sample_select_impl(logits, B, V, temperature, top_k, top_p, seed, choice_ws, nullptr, rs, (hipStream_t)stream);
 }
 
 extern "C" int sl_greedy_select(const float* logits, int32_t B, int32_t V, const int32_t* eos_ids, int32_t n_eos, int32_t pad_id,
                                 int32_t use_eos, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len,
                                 int32_t* next_ids, int32_t* out_ids, int32_t max_new, sl_stream stream) {
-  return sl_greedy_select_impl(logits, B, V, eos_ids, n_eos, pad_id, use_eos, 1, unfinished, ctx_len, gen_count, finish_len, next_ids,
-                               out_ids, max_new, (hipStream_t)stream, nullptr, nullptr);
+  const SlRowState rs{unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, nullptr, nullptr, eos_ids, n_eos, pad_id, use_eos, 1};
+  return sl_greedy_select_impl(logits, B, V, rs, (hipStream_t)stream);
 }
 
 extern "C" int sl_greedy_select_sc(const float* logits, int32_t B, int32_t V, const int32_t* eos_ids, int32_t n_eos, int32_t pad_id,
                                    int32_t use_eos, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len,
                                    int32_t* next_ids, int32_t* out_ids, int32_t max_new, float* logprob_out, sl_stream stream) {
-  return sl_greedy_select_impl(logits, B, V, eos_ids, n_eos, pad_id, use_eos, 1, unfinished, ctx_len, gen_count, finish_len, next_ids,
-                               out_ids, max_new, (hipStream_t)stream, nullptr, logprob_out);
+  const SlRowState rs{unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, nullptr, logprob_out, eos_ids, n_eos, pad_id, use_eos, 1};
+  return sl_greedy_select_impl(logits, B, V, rs, (hipStream_t)stream);
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 // runtime.hip — C++ host runtime above the kernels: HuBERT encoder forward over a batch of utterances,
-// Llama prefill / decode step / greedy generation (decode step captured once into a hipGraph and
-// replayed, all per-step state lives on the device; sampling, beam search and HF's logits processors — logits_proc.hip — ride the same
-// loop, the processors between the lm_head's fp32 logits and the selection).  Workspace is carved from one caller-owned buffer.
+// Llama prefill / decode step / generation.  The decode step is captured once into a hipGraph and replayed, all per-step state lives on
+// the device.  Two host loops, generate_impl (greedy / sampling, per-row budgets, compaction, token log-probabilities) and
+// sl_beam_generate_lp, share decode_graph_get — scratch reset, the one key constructor, capture, instantiate, cache — and hand it what
+// follows the lm_head as a callable; HF's logits processors (logits_proc.hip) sit between the lm_head's fp32 logits and the selection in
+// both.  generate_impl's per-row state is one RowTable.  Workspace is carved from one caller-owned buffer.
 #include <cmath>
 #include <vector>
 
@@ -11,19 +13,6 @@
 int sl_attn_decode_impl(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, const int32_t* ctx_len,
                         int ctx_add, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx, float scale, int32_t dtype,
                         hipStream_t st);
-int sl_greedy_select_impl(const float* logits, int32_t B, int32_t V, const int32_t* eos_ids, int32_t n_eos, int32_t pad_id,
-                          int32_t use_eos, int32_t advance_ctx, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count,
-                          int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit,
-                          float* logprob_out);
-int sl_greedy_select_partial_impl(const float* amax_val, const int32_t* amax_idx, int32_t n_groups, int32_t B, const int32_t* eos_ids, int32_t n_eos,
-                                  int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished, int32_t* ctx_len, int32_t* gen_count,
-                                  int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, hipStream_t st, const int32_t* row_limit,
-                                  const float* amax_sum, float* logprob_out);
-int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
-                          const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t advance_ctx, int32_t* unfinished,
-                          int32_t* ctx_len, int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new,
-                          int32_t* choice_ws, hipStream_t st, const int32_t* row_limit, const int32_t* row_ids, float* logprob_out);
-
 int sl_logits_opts_check(const char* who, const sl_logits_opts* lp, int max_new_tokens);
 int sl_logits_process_impl(float* logits, int32_t rows, int32_t V, const int32_t* hist, const int32_t* hist_odd, int64_t hist_ld, const int32_t* hist_len,
                            const int32_t* unfinished, const sl_logits_opts* lp, const int32_t* eos_ids_host, int32_t n_eos, int32_t log_softmax,
@@ -929,6 +918,16 @@ __global__ void iota_kernel(int32_t* p, int n) {
   if (i < n) p[i] = i;
 }
 
+// what a decode step expects of its scratch before its first launch, per captured graph: the K-split fix-up's counters (sl_gemm_fused.split_ws)
+// and the split attention's arrival counters (merged in-launch) at zero, tok_seq = the slot index list
+static int decode_scratch_reset(const sl_llama_model* m, const sl_kv_cache* kv, const LlamaWs& w, int rows, hipStream_t st) {
+  if (w.split && w.split_bytes >= 8192) SL_HIP(hipMemsetAsync(w.split, 0, 8192, st));
+  SL_TRY(sl_attn_decode_split_zero_counters(w.part, rows, m->n_heads, m->n_kv_heads, kv->max_ctx, st));
+  hipLaunchKernelGGL(iota_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, w.tok_seq, rows);
+  SL_CHECK_LAUNCH("iota");
+  return 0;
+}
+
 extern "C" int sl_llama_decode_step(const sl_llama_model* m, const sl_kv_cache* kv, const int32_t* next_ids_dev, const int32_t* ctx_len_dev,
                                     int32_t B, float* logits, void* workspace, size_t workspace_bytes, sl_stream stream) {
   SL_TRY(llama_check(m, kv));
@@ -943,10 +942,7 @@ extern "C" int sl_llama_decode_step(const sl_llama_model* m, const sl_kv_cache* 
   SL_CHECK_ARG(off <= workspace_bytes, "sl_llama_decode_step: workspace too small");
   const size_t need = off + llama_carve(m, B, B, bptr(workspace) + off, workspace_bytes - off, w);
   SL_CHECK_ARG(need <= workspace_bytes, "sl_llama_decode_step: workspace %zu B < required %zu B", workspace_bytes, need);
-  if (w.split && w.split_bytes >= 8192) SL_HIP(hipMemsetAsync(w.split, 0, 8192, st));   // the K-split fix-up's counters start at zero
-  SL_TRY(sl_attn_decode_split_zero_counters(w.part, B, m->n_heads, m->n_kv_heads, kv->max_ctx, st));   // ... and the split attention's arrival counters
-  hipLaunchKernelGGL(iota_kernel, dim3((B + 255) / 256), dim3(256), 0, st, w.tok_seq, B);
-  SL_CHECK_LAUNCH("iota");
+  SL_TRY(decode_scratch_reset(m, kv, w, B, st));
   return decode_step(m, kv, next_ids_dev, ctx_len_dev, B, logits, x, w, st);
 }
 
@@ -1081,6 +1077,177 @@ static int compact_rung(int n_live) {
 
 struct SampleOpts { float temperature; int top_k; float top_p; uint64_t seed; };
 
+// the three timing events of a generate call, destroyed on every way out of it
+struct Events3 {
+  hipEvent_t e[3] = {};
+  int create() { for (auto& x : e) SL_HIP(hipEventCreate(&x)); return 0; }
+  ~Events3() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// ---- the decode graph of both generation loops (sl_generate, sl_beam_generate) ----
+// What a loop knows when it asks for the captured step of B rows.  Everything the captured launches bake in is in here, and decode_graph_key
+// turns ALL of it into the cache key: a field a mode adds goes into this struct and into that one function.
+struct GraphCtx {
+  const char* who;
+  const sl_llama_model* m;
+  const sl_kv_cache* kv;
+  void *ws, *scratch;                 // the caller's workspace (its pointer stands for the layout of every state array) and the decode scratch inside it
+  size_t ws_bytes, scratch_bytes;
+  float* logits;                      // decode_step's arguments: the rows' ids and context lengths in, fp32 logits (or the top-1 planes) out
+  void* xdec;
+  const int32_t *next_ids, *ctx_len;
+  hipStream_t st;                     // the caller's stream: the scratch reset runs here, the capture on a private one
+  int B0, max_new, use_eos, n_eos, pad;
+  const int32_t* eos;                 // host
+  int pin_rows, limits, scores;       // sl_generate only: family pin of a compacting call, per-row budgets, token log-probabilities
+  const SampleOpts* smp;              // ... and sampling (NULL = greedy)
+  const LpPlan* lp;
+  int beam_k, beam_m, beam_es;        // sl_beam_generate only (0 elsewhere: a beam graph and a greedy graph never share a key)
+  float beam_lp;
+};
+
+// The capture stream of every device, per thread (a stream belongs to the device that was current when it was made), and the prefetch
+// branch's side stream and event.  At file scope, NOT inside decode_graph_get: a function template has one set of local statics per
+// specialisation, and each loop's tail is a closure type of its own.
+static thread_local hipStream_t cap_by_dev[SL_MAX_DEVICES] = {};
+static thread_local hipStream_t cap2_by_dev[SL_MAX_DEVICES] = {};
+static thread_local hipEvent_t pev_by_dev[SL_MAX_DEVICES] = {};
+
+// the ONLY writer of DecodeGraphKey's fields
+static int decode_graph_key(const GraphCtx& g, int B, DecodeGraphKey& key) {
+  const sl_llama_model* m = g.m;
+  const sl_kv_cache* kv = g.kv;
+  memset(&key, 0, sizeof(key));
+  key.model = m; key.layers = m->layers; key.w0 = m->n_layers > 0 ? m->layers[0].wqkv_dec : nullptr; key.lm = m->lm_head_dec ? m->lm_head_dec : m->lm_head;
+  key.embed = m->embed; key.kc = kv->k_cache; key.vc = kv->v_cache; key.ws = g.ws; key.ws_bytes = g.ws_bytes;
+  key.B = B; key.B0 = g.B0; key.max_new = g.max_new; key.use_eos = g.use_eos; key.n_eos = g.n_eos; key.pad = g.pad; key.max_ctx = kv->max_ctx;
+  key.slots = kv->slots; key.shared_prefix = kv->shared_prefix; key.dtype = m->dtype; key.n_layers = m->n_layers; key.vocab = m->vocab;
+  // + the switches that shape the captured launches
+  key.fused = m->dec_fused_norm | (sl_env().decode_tiled << 8) | ((sl_env().attn_decode_ks & 127) << 9) | ((g.pin_rows ? 1 : 0) << 16) |
+              ((sl_env().decode_prefetch ? 1 : 0) << 17) | ((kv->reserved & 3) << 18) | ((m->reserved & 3) << 20);
+  key.limits = g.limits;
+  key.content = model_content_hash(m);
+  SL_HIP(hipGetDevice(&key.device));
+  for (int i = 0; i < g.n_eos && i < 8; ++i) key.eos[i] = g.eos[i];
+  if (g.smp) { key.sample = 1; key.temperature = g.smp->temperature; key.top_k = g.smp->top_k; key.top_p = g.smp->top_p; key.seed = g.smp->seed; }
+  key.beam_k = g.beam_k; key.beam_m = g.beam_m; key.beam_es = g.beam_es; key.beam_lp = g.beam_lp;
+  if (g.lp->on) { key.lp_penalty = g.lp->o.repetition_penalty; key.lp_ngram = g.lp->o.no_repeat_ngram_size; key.lp_min_new = g.lp->o.min_new_tokens; }
+  key.scores = g.scores;
+  return 0;
+}
+
+// The decode step for `B` rows: captured ONCE per (model, cache, workspace, row count, mode) and kept in a small per-thread
+// cache — a second call with the same buffers (the usual case: a serving loop reusing its KV cache and workspace) replays it
+// without re-capturing.  Every pointer the captured launches were recorded with is part of the key (the state arrays and the
+// scratch layout follow from the workspace pointer, the ORIGINAL batch B0 and the row count B), so a changed buffer can never
+// replay a stale graph.  Also resets the per-graph scratch (decode_scratch_reset).
+// tail(cap, B, top1) records on the capture stream everything behind the layers' lm_head; top1: the lm_head left per-64-column
+// maxima instead of fp32 logits (greedy without a logits processor — which edits the logits the fused form never writes — at a
+// batch the tiled lm_head serves).
+template <class Tail>
+static int decode_graph_get(const GraphCtx& g, int B, Tail&& tail, hipGraphExec_t* exec_out) {
+  const sl_llama_model* m = g.m;
+  SlFamilyPin pin(g.pin_rows);
+  LlamaWs w;
+  llama_carve(m, B, B, g.scratch, g.scratch_bytes, w);
+  SL_TRY(decode_scratch_reset(m, g.kv, w, B, g.st));
+  DecodeGraphKey key;
+  SL_TRY(decode_graph_key(g, B, key));
+  hipGraphExec_t exec = decode_graph_lookup(key);
+  if (!exec) {
+    hipGraph_t graph = nullptr;
+    // Capture on a private stream (the caller's may be the legacy null stream, which cannot capture);
+    // capturing records the launches without running them, the graph is then replayed on `st`.
+    SL_CHECK_ARG(key.device >= 0 && key.device < SL_MAX_DEVICES, "%s: device index %d", g.who, key.device);
+    hipStream_t& cap = cap_by_dev[key.device];
+    if (!cap) SL_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
+    SL_HIP(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
+    const bool top1 = !g.beam_k && !g.smp && !g.lp->on && decode_fuses_argmax(m, B);
+    // small batches (the skinny kernels: every matrix read once per step by a chain of short launches): a prefetch branch beside the chain
+    DecodePrefetch pf;
+    if (!g.beam_k && sl_env().decode_prefetch && B <= sl_env().stream_min_m && m->dtype == SL_BF16) {
+      hipStream_t& cap2 = cap2_by_dev[key.device];
+      hipEvent_t& pev = pev_by_dev[key.device];
+      if (!cap2) SL_HIP(hipStreamCreateWithFlags(&cap2, hipStreamNonBlocking));
+      if (!pev) SL_HIP(hipEventCreateWithFlags(&pev, hipEventDisableTiming));
+      pf.main = cap; pf.side = cap2; pf.ev = pev; pf.sink = (uint32_t*)w.tok_pos; pf.on = true;      // (the sink is never written: see the kernel)
+      g_prefetch = &pf;
+    }
+    int rc = decode_step(m, g.kv, g.next_ids, g.ctx_len, B, g.logits, g.xdec, w, cap, top1, top1 && g.scores);
+    g_prefetch = nullptr;
+    if (pf.on) { const int rj = pf.join(); if (rc == 0) rc = rj; }       // the branch joins the chain before the capture ends
+    if (rc == 0) rc = tail(cap, B, top1);
+    const hipError_t ce = hipStreamEndCapture(cap, &graph);
+    if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (ce != hipSuccess) { sl_set_error("hipStreamEndCapture: %s", hipGetErrorString(ce)); return SL_ERR_LAUNCH; }
+    const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    if (ie != hipSuccess) (void)hipGraphDestroy(graph);
+    SL_HIP(ie);
+    decode_graph_store(key, graph, exec);
+  }
+  *exec_out = exec;
+  return 0;
+}
+
+// ---- sl_generate's per-row state: each array listed ONCE, in carve order (the workspace layout is part of the graph key through the
+// workspace pointer).  Elements are 4 bytes (int32, or float for the two log-probability arrays).  Carve, initial upload, the pulls at a
+// check / compaction / the end, the move of a row into a hole and the push back all walk this list.
+struct RowTable {
+  enum { UNF, CTX, CNT, FIN, NEXT, OUT, CHOICE, LIM, ROW, LPS, LP, NCOL };
+  // unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, the sampler's drawn tokens, row_limit, row_id (the caller's index of the
+  // sequence a row holds), the repetition penalty's gather scratch, the token log-probabilities
+  static constexpr unsigned bit(int i) { return 1u << i; }
+  static constexpr unsigned ALL = (1u << NCOL) - 1;
+  struct Col {
+    size_t row_bytes = 4;
+    bool carved = true;             // LPS / LP are carved only when on: the layout without them is unchanged
+    bool on = true;                 // state that travels with the row in THIS call (never the two scratch arrays)
+    unsigned char* dev = nullptr;
+    std::vector<unsigned char> host;
+  };
+  Col col[NCOL];
+  RowTable(int B0, int max_new, bool limits, bool penalty, bool scores) {
+    for (int i : {OUT, LPS, LP}) col[i].row_bytes = (size_t)max_new * 4;
+    col[CHOICE].on = col[LPS].on = false;
+    col[LIM].on = limits;
+    col[LPS].carved = penalty;
+    col[LP].carved = col[LP].on = scores;
+    for (auto& a : col)
+      if (a.on) a.host.assign((size_t)B0 * a.row_bytes, 0);
+  }
+  void carve(Carver& c, int B0) {
+    for (auto& a : col)
+      if (a.carved) a.dev = (unsigned char*)c.take((size_t)B0 * a.row_bytes);
+  }
+  template <class T> T* d(int i) const { return (T*)col[i].dev; }
+  template <class T> T* h(int i) { return (T*)col[i].host.data(); }
+  // rows [0, B) of the arrays in `mask` that this call carries, queued on st
+  int copy(unsigned mask, int B, hipMemcpyKind kind, hipStream_t st) {
+    for (int i = 0; i < NCOL; ++i) {
+      Col& a = col[i];
+      if (!a.on || !(mask & bit(i))) continue;
+      const bool down = kind == hipMemcpyDeviceToHost;
+      SL_HIP(hipMemcpyAsync(down ? (void*)a.host.data() : (void*)a.dev, down ? (const void*)a.dev : (const void*)a.host.data(), (size_t)B * a.row_bytes, kind, st));
+    }
+    return 0;
+  }
+  int pull(unsigned mask, int B, hipStream_t st) { return copy(mask, B, hipMemcpyDeviceToHost, st); }
+  int push(unsigned mask, int B, hipStream_t st) { return copy(mask, B, hipMemcpyHostToDevice, st); }
+  void move(int hole, int r) {
+    for (auto& a : col)
+      if (a.on) memcpy(a.host.data() + hole * a.row_bytes, a.host.data() + r * a.row_bytes, a.row_bytes);
+  }
+  // every row unfinished, nothing generated, row r holds sequence r; ctx_len and next_ids are the prefill's and the first select's to write
+  int init(const int32_t* limits, int B0, hipStream_t st) {
+    for (int b = 0; b < B0; ++b) { h<int32_t>(UNF)[b] = 1; h<int32_t>(ROW)[b] = b; }
+    if (limits) memcpy(h<int32_t>(LIM), limits, (size_t)B0 * 4);
+    SL_TRY(push(bit(UNF) | bit(CNT) | bit(FIN) | bit(LIM) | bit(ROW), B0, st));
+    for (int i : {OUT, LP})
+      if (col[i].on) SL_HIP(hipMemsetAsync(col[i].dev, 0, (size_t)B0 * col[i].row_bytes, st));
+    return 0;
+  }
+};
+
 static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
                          const sl_generate_opts* o, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
                          sl_stream stream, const sl_logits_opts* lp_opts = nullptr, float* out_lp_host = nullptr) {
@@ -1121,131 +1288,53 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   Carver c(workspace, workspace_bytes);
   float* logits = (float*)c.take((size_t)B0 * m->vocab * sizeof(float));
   void* xdec = c.take((size_t)B0 * m->hidden * sl_dtype_size(m->dtype));
-  int32_t* unfinished = (int32_t*)c.take(B0 * sizeof(int32_t));
-  int32_t* ctx_len = (int32_t*)c.take(B0 * sizeof(int32_t));
-  int32_t* gen_count = (int32_t*)c.take(B0 * sizeof(int32_t));
-  int32_t* finish_len = (int32_t*)c.take(B0 * sizeof(int32_t));
-  int32_t* next_ids = (int32_t*)c.take(B0 * sizeof(int32_t));
-  int32_t* out_ids = (int32_t*)c.take((size_t)B0 * max_new_tokens * sizeof(int32_t));
-  int32_t* choice = (int32_t*)c.take(B0 * sizeof(int32_t));      // sampling mode: the drawn token of every row
-  int32_t* row_limit = (int32_t*)c.take(B0 * sizeof(int32_t));   // per-row token budgets (sl_generate_opts.row_limits_host)
-  int32_t* row_id = (int32_t*)c.take(B0 * sizeof(int32_t));      // the caller's index of the sequence a row holds (rows move when the batch is compacted)
-  float* lp_scratch = lp.penalty ? (float*)c.take((size_t)B0 * max_new_tokens * sizeof(float)) : nullptr;   // carved only when on: the layout without it is unchanged
-  float* lp_out = scores ? (float*)c.take((size_t)B0 * max_new_tokens * sizeof(float)) : nullptr;   // token log-probabilities: likewise, behind everything else
+  using RT = RowTable;
+  RT tab(B0, max_new_tokens, o->row_limits_host != nullptr, lp.penalty, scores != 0);
+  tab.carve(c, B0);
   c.take(0);
   void* scratch = bptr(workspace) + c.off;
   const size_t scratch_bytes = workspace_bytes - c.off;
-  const int32_t* row_limit_arg = o->row_limits_host ? row_limit : nullptr;
+  SL_TRY(tab.init(o->row_limits_host, B0, st));
+  // what every select of this call reads and advances (advance_ctx: off for the prefill's token, on inside the captured step)
+  SlRowState rs{tab.d<int32_t>(RT::UNF), tab.d<int32_t>(RT::CTX), tab.d<int32_t>(RT::CNT), tab.d<int32_t>(RT::FIN), tab.d<int32_t>(RT::NEXT), tab.d<int32_t>(RT::OUT),
+                max_new_tokens, o->row_limits_host ? tab.d<int32_t>(RT::LIM) : nullptr, tab.d<float>(RT::LP), eos_ids_host, n_eos, pad_id, use_eos, 0};
 
-  std::vector<int32_t> ones(B0, 1), zeros(B0, 0), orig(B0);
-  for (int b = 0; b < B0; ++b) orig[b] = b;
-  SL_HIP(hipMemcpyAsync(unfinished, ones.data(), B0 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  SL_HIP(hipMemcpyAsync(gen_count, zeros.data(), B0 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  SL_HIP(hipMemcpyAsync(finish_len, zeros.data(), B0 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  SL_HIP(hipMemcpyAsync(row_id, orig.data(), B0 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  if (o->row_limits_host) SL_HIP(hipMemcpyAsync(row_limit, o->row_limits_host, B0 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  SL_HIP(hipMemsetAsync(out_ids, 0, (size_t)B0 * max_new_tokens * sizeof(int32_t), st));
-  if (scores) SL_HIP(hipMemsetAsync(lp_out, 0, (size_t)B0 * max_new_tokens * sizeof(float), st));
-
-  hipEvent_t ev[3];
-  for (auto& e : ev) SL_HIP(hipEventCreate(&e));
-  SL_HIP(hipEventRecord(ev[0], st));
-  SL_TRY(sl_llama_prefill(m, kv, x, cu_seqlens_host, nseq, logits, ctx_len, nullptr, scratch, scratch_bytes, stream));
+  Events3 ev;
+  SL_TRY(ev.create());
+  SL_HIP(hipEventRecord(ev.e[0], st));
+  SL_TRY(sl_llama_prefill(m, kv, x, cu_seqlens_host, nseq, logits, rs.ctx_len, nullptr, scratch, scratch_bytes, stream));
   // With a processor on, every step — this first one included — is lm_head -> fp32 logits -> sl_logits_process -> select.  The history is
   // the row's own output ids (out_ids, gen_count): both move with the row at a compaction, so nothing else does.
-  auto select = [&](int B, int advance_ctx, hipStream_t s_) -> int {
+  auto select = [&](int B, hipStream_t s_) -> int {
     if (lp.on)
-      SL_TRY(sl_logits_process_impl(logits, B, m->vocab, out_ids, nullptr, max_new_tokens, gen_count, unfinished, &lp.o, eos_ids_host, n_eos, 0, lp_scratch, s_));
+      SL_TRY(sl_logits_process_impl(logits, B, m->vocab, rs.out_ids, nullptr, max_new_tokens, rs.gen_count, rs.unfinished, &lp.o, eos_ids_host, n_eos, 0,
+                                    tab.d<float>(RT::LPS), s_));
     if (smp)
-      return sl_sample_select_impl(logits, B, m->vocab, smp->temperature, smp->top_k, smp->top_p, smp->seed, eos_ids_host, n_eos, pad_id, use_eos, advance_ctx,
-                                   unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new_tokens, choice, s_, row_limit_arg, row_id, lp_out);
-    return sl_greedy_select_impl(logits, B, m->vocab, eos_ids_host, n_eos, pad_id, use_eos, advance_ctx, unfinished, ctx_len, gen_count, finish_len, next_ids,
-                                 out_ids, max_new_tokens, s_, row_limit_arg, lp_out);
+      return sl_sample_select_impl(logits, B, m->vocab, smp->temperature, smp->top_k, smp->top_p, smp->seed, tab.d<int32_t>(RT::CHOICE), tab.d<int32_t>(RT::ROW), rs, s_);
+    return sl_greedy_select_impl(logits, B, m->vocab, rs, s_);
   };
-  SL_TRY(select(B0, 0, st));
-  SL_HIP(hipEventRecord(ev[1], st));
+  SL_TRY(select(B0, st));
+  rs.advance_ctx = 1;
+  SL_HIP(hipEventRecord(ev.e[1], st));
 
-  // The decode step for `B` rows: captured ONCE per (model, cache, workspace, row count, limits) and kept in a small per-thread
-  // cache — a second call with the same buffers (the usual case: a serving loop reusing its KV cache and workspace) replays it
-  // without re-capturing.  Every pointer the captured launches were recorded with is part of the key (the state arrays and the
-  // scratch layout follow from the workspace pointer, the ORIGINAL batch B0 and the row count B), so a changed buffer can never
-  // replay a stale graph.  Also resets the per-graph scratch (K-split counters, split-attention counters, the slot index list).
-  // A compacting generation keeps the kernel family of the batch it started with (common.h sl_family_rows): measured at full depth in bf16,
-  // 819 of 1 024 random-init sequences changed ids when each rung picked its own family (near-ties flip between the families' rounding
-  // orders) — pinned, a sequence's ids are those of the uncompacted batch, bit for bit.  SL_COMPACT_PIN=0: the old behaviour (A/B only).
-  const int pin_rows = (o->compact && use_eos && sl_env().compact_pin) ? B0 : 0;
-  auto graph_for = [&](int B, hipGraphExec_t* exec_out) -> int {
-    SlFamilyPin pin(pin_rows);
-    LlamaWs w;
-    llama_carve(m, B, B, scratch, scratch_bytes, w);
-    if (w.split && w.split_bytes >= 8192) SL_HIP(hipMemsetAsync(w.split, 0, 8192, st));   // the K-split fix-up's counters start at zero (sl_gemm_fused.split_ws)
-    SL_TRY(sl_attn_decode_split_zero_counters(w.part, B, m->n_heads, m->n_kv_heads, kv->max_ctx, st));   // split attention merges its records in-launch: arrival counters start at zero
-    hipLaunchKernelGGL(iota_kernel, dim3((B + 255) / 256), dim3(256), 0, st, w.tok_seq, B);
-    SL_CHECK_LAUNCH("iota");
-    DecodeGraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.model = m; key.layers = m->layers; key.w0 = m->n_layers > 0 ? m->layers[0].wqkv_dec : nullptr; key.lm = m->lm_head_dec ? m->lm_head_dec : m->lm_head;
-    key.embed = m->embed; key.kc = kv->k_cache; key.vc = kv->v_cache; key.ws = workspace; key.ws_bytes = workspace_bytes;
-    key.B = B; key.B0 = B0; key.max_new = max_new_tokens; key.use_eos = use_eos; key.n_eos = n_eos; key.pad = pad_id; key.max_ctx = kv->max_ctx;
-    key.slots = kv->slots; key.shared_prefix = kv->shared_prefix; key.dtype = m->dtype; key.n_layers = m->n_layers; key.vocab = m->vocab; key.fused = m->dec_fused_norm | (sl_env().decode_tiled << 8) | ((sl_env().attn_decode_ks & 127) << 9) | ((pin_rows ? 1 : 0) << 16) | ((sl_env().decode_prefetch ? 1 : 0) << 17) | ((kv->reserved & 3) << 18) | ((m->reserved & 3) << 20);   // + the switch that shapes the captured launches
-    key.limits = row_limit_arg ? 1 : 0;
-    key.content = model_content_hash(m);
-    SL_HIP(hipGetDevice(&key.device));
-    for (int i = 0; i < n_eos && i < 8; ++i) key.eos[i] = eos_ids_host[i];
-    if (smp) { key.sample = 1; key.temperature = smp->temperature; key.top_k = smp->top_k; key.top_p = smp->top_p; key.seed = smp->seed; }
-    if (lp.on) { key.lp_penalty = lp.o.repetition_penalty; key.lp_ngram = lp.o.no_repeat_ngram_size; key.lp_min_new = lp.o.min_new_tokens; }
-    key.scores = scores;
-    hipGraphExec_t exec = decode_graph_lookup(key);
-    if (!exec) {
-      hipGraph_t graph = nullptr;
-      // Capture on a private stream (the caller's may be the legacy null stream, which cannot capture);
-      // capturing records the launches without running them, the graph is then replayed on `st`.
-      static thread_local hipStream_t cap_by_dev[SL_MAX_DEVICES] = {};    // a stream belongs to the device that was current when it was made
-      SL_CHECK_ARG(key.device >= 0 && key.device < SL_MAX_DEVICES, "sl_generate: device index %d", key.device);
-      hipStream_t& cap = cap_by_dev[key.device];
-      if (!cap) SL_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-      SL_HIP(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
-      // greedy + a batch the tiled lm_head serves: the lm_head leaves per-group maxima, the select pass reads 1/64 of the bytes
-      // (not with a logits processor on: it edits the fp32 logits the fused form never writes)
-      const bool top1 = !smp && !lp.on && decode_fuses_argmax(m, B);
-      // small batches (the skinny kernels: every matrix read once per step by a chain of short launches): a prefetch branch beside the chain
-      DecodePrefetch pf;
-      static thread_local hipStream_t cap2_by_dev[SL_MAX_DEVICES] = {};
-      static thread_local hipEvent_t pev_by_dev[SL_MAX_DEVICES] = {};
-      if (sl_env().decode_prefetch && B <= sl_env().stream_min_m && m->dtype == SL_BF16) {
-        hipStream_t& cap2 = cap2_by_dev[key.device];
-        hipEvent_t& pev = pev_by_dev[key.device];
-        if (!cap2) SL_HIP(hipStreamCreateWithFlags(&cap2, hipStreamNonBlocking));
-        if (!pev) SL_HIP(hipEventCreateWithFlags(&pev, hipEventDisableTiming));
-        pf.main = cap; pf.side = cap2; pf.ev = pev; pf.sink = (uint32_t*)w.tok_pos; pf.on = true;      // (the sink is never written: see the kernel)
-        g_prefetch = &pf;
-      }
-      int rc = decode_step(m, kv, next_ids, ctx_len, B, logits, xdec, w, cap, top1, top1 && scores);
-      g_prefetch = nullptr;
-      if (pf.on) { const int rj = pf.join(); if (rc == 0) rc = rj; }       // the branch joins the chain before the capture ends
-      if (rc == 0) {
-        if (top1) {
-          const int ng = (m->vocab + 63) / 64;
-          rc = sl_greedy_select_partial_impl(logits, (const int32_t*)(logits + (int64_t)ng * B), ng, B, eos_ids_host, n_eos, pad_id, use_eos, 1, unfinished,
-                                             ctx_len, gen_count, finish_len, next_ids, out_ids, max_new_tokens, cap, row_limit_arg,
-                                             scores ? logits + 2 * (int64_t)ng * B : nullptr, lp_out);
-        } else {
-          rc = select(B, 1, cap);
-        }
-      }
-      hipError_t ce = hipStreamEndCapture(cap, &graph);
-      if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-      if (ce != hipSuccess) { sl_set_error("hipStreamEndCapture: %s", hipGetErrorString(ce)); return SL_ERR_LAUNCH; }
-      SL_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-      decode_graph_store(key, graph, exec);
-    }
-    *exec_out = exec;
-    return 0;
+  // The decode step for `B` rows comes from decode_graph_get.  A compacting generation keeps the kernel family of the batch it started with
+  // (common.h sl_family_rows): measured at full depth in bf16, 819 of 1 024 random-init sequences changed ids when each rung picked its own
+  // family (near-ties flip between the families' rounding orders) — pinned, a sequence's ids are those of the uncompacted batch, bit for bit.
+  // SL_COMPACT_PIN=0: the old behaviour (A/B only).
+  GraphCtx g{};
+  g.who = "sl_generate"; g.m = m; g.kv = kv; g.ws = workspace; g.ws_bytes = workspace_bytes; g.scratch = scratch; g.scratch_bytes = scratch_bytes;
+  g.logits = logits; g.xdec = xdec; g.next_ids = rs.next_ids; g.ctx_len = rs.ctx_len; g.st = st;
+  g.B0 = B0; g.max_new = max_new_tokens; g.use_eos = use_eos; g.n_eos = n_eos; g.pad = pad_id; g.eos = eos_ids_host; g.lp = &lp; g.smp = smp;
+  g.pin_rows = (o->compact && use_eos && sl_env().compact_pin) ? B0 : 0; g.limits = rs.row_limit ? 1 : 0; g.scores = scores;
+  // behind the lm_head: the select above, or — top1: the lm_head left per-group maxima — the pass that reads 1/64 of the bytes
+  auto tail = [&](hipStream_t cap, int B, bool top1) -> int {
+    if (!top1) return select(B, cap);
+    const int64_t ng = (m->vocab + 63) / 64;
+    return sl_greedy_select_partial_impl(logits, (const int32_t*)(logits + ng * B), scores ? logits + 2 * ng * B : nullptr, (int)ng, B, rs, cap);
   };
 
-  // host copies of the per-row state, filled at a check; `done[s]`: sequence s (caller's index) has been written to out_ids_host
-  std::vector<int32_t> h_unf(B0, 1), h_fin(B0, 0), h_ctx, h_cnt, h_next, h_lim, h_out;
-  std::vector<float> h_lp;         // token log-probabilities: the rows travel exactly as h_out's do
+  // host copies of the per-row state live in the table, filled at a check; `done[s]`: sequence s (caller's index) has been written to out_ids_host
+  int32_t *h_unf = tab.h<int32_t>(RT::UNF), *h_fin = tab.h<int32_t>(RT::FIN), *orig = tab.h<int32_t>(RT::ROW);
   std::vector<char> done(B0, 0);
   std::vector<int32_t> fin_of(B0, 0), unf_of(B0, 1);
   int steps_done = 1, B = B0, compactions = 0, launches = 0;
@@ -1257,21 +1346,21 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
     for (int r = 0; r < B; ++r) {
       const int s = orig[r];
       if (done[s] || (only_finished && h_unf[r] != 0)) continue;
-      memcpy(out_ids_host + (size_t)s * max_new_tokens, h_out.data() + (size_t)r * max_new_tokens, (size_t)max_new_tokens * sizeof(int32_t));
-      if (scores) memcpy(out_lp_host + (size_t)s * max_new_tokens, h_lp.data() + (size_t)r * max_new_tokens, (size_t)max_new_tokens * sizeof(float));
+      memcpy(out_ids_host + (size_t)s * max_new_tokens, tab.h<int32_t>(RT::OUT) + (size_t)r * max_new_tokens, (size_t)max_new_tokens * sizeof(int32_t));
+      if (scores) memcpy(out_lp_host + (size_t)s * max_new_tokens, tab.h<float>(RT::LP) + (size_t)r * max_new_tokens, (size_t)max_new_tokens * sizeof(float));
       fin_of[s] = h_fin[r]; unf_of[s] = h_unf[r];
       done[s] = 1;
     }
   };
   if (max_new_tokens > 1) {
     hipGraphExec_t exec = nullptr;
-    SL_TRY(graph_for(B, &exec));
+    SL_TRY(decode_graph_get(g, B, tail, &exec));
     const int check_every = o->check_every > 0 ? o->check_every : 16;
     while (steps_done < max_new_tokens) {
       SL_HIP(hipGraphLaunch(exec, st));
       ++steps_done; ++launches; row_steps += B;
       if (!(use_eos && (steps_done % check_every == 0) && steps_done < max_new_tokens)) continue;
-      SL_HIP(hipMemcpyAsync(h_unf.data(), unfinished, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+      SL_TRY(tab.pull(RT::bit(RT::UNF), B, st));
       SL_HIP(hipStreamSynchronize(st));
       int n_live = 0;
       for (int b = 0; b < B; ++b) n_live += (h_unf[b] != 0);
@@ -1280,19 +1369,9 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
       if (!o->compact || rung >= B) continue;
       // ---- compact: the live rows that sit at or above `rung` (the movers) take the places of finished rows below it; live rows
       // below it and the remaining finished ones (padding of the rung) stay where they are.  Finished sequences are written to the
-      // caller's buffer first.  Everything per-row moves with the row: state arrays (through the host: a few KB), output ids, and
+      // caller's buffer first.  Everything per-row moves with the row: the table's arrays (through the host: a few KB) and
       // the row's K / V slot (on the device).
-      h_ctx.resize(B); h_cnt.resize(B); h_next.resize(B); h_lim.resize(B); h_out.resize((size_t)B * max_new_tokens);
-      SL_HIP(hipMemcpyAsync(h_fin.data(), finish_len, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      SL_HIP(hipMemcpyAsync(h_ctx.data(), ctx_len, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      SL_HIP(hipMemcpyAsync(h_cnt.data(), gen_count, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      SL_HIP(hipMemcpyAsync(h_next.data(), next_ids, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      if (row_limit_arg) SL_HIP(hipMemcpyAsync(h_lim.data(), row_limit, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      SL_HIP(hipMemcpyAsync(h_out.data(), out_ids, (size_t)B * max_new_tokens * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      if (scores) {
-        h_lp.resize((size_t)B * max_new_tokens);
-        SL_HIP(hipMemcpyAsync(h_lp.data(), lp_out, (size_t)B * max_new_tokens * sizeof(float), hipMemcpyDeviceToHost, st));
-      }
+      SL_TRY(tab.pull(RT::ALL & ~(RT::bit(RT::UNF) | RT::bit(RT::ROW)), B, st));      // (unfinished is here already, the row ids are the host's to say)
       SL_HIP(hipStreamSynchronize(st));
       retire(true);
       std::vector<KvMove> moves;
@@ -1300,11 +1379,8 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
       for (int r = rung; r < B; ++r) {
         if (h_unf[r] == 0) continue;
         while (h_unf[hole] != 0) ++hole;          // exists: at most `rung` rows are live
-        moves.push_back(KvMove{r, hole, h_ctx[r], 0});
-        h_unf[hole] = h_unf[r]; h_fin[hole] = h_fin[r]; h_ctx[hole] = h_ctx[r]; h_cnt[hole] = h_cnt[r]; h_next[hole] = h_next[r]; h_lim[hole] = h_lim[r];
-        memcpy(h_out.data() + (size_t)hole * max_new_tokens, h_out.data() + (size_t)r * max_new_tokens, (size_t)max_new_tokens * sizeof(int32_t));
-        if (scores) memcpy(h_lp.data() + (size_t)hole * max_new_tokens, h_lp.data() + (size_t)r * max_new_tokens, (size_t)max_new_tokens * sizeof(float));
-        orig[hole] = orig[r];
+        moves.push_back(KvMove{r, hole, tab.h<int32_t>(RT::CTX)[r], 0});
+        tab.move(hole, r);
         ++hole;
       }
       if (!moves.empty()) {
@@ -1317,30 +1393,15 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
         SL_CHECK_LAUNCH("kv_move");
       }
       B = rung;
-      SL_HIP(hipMemcpyAsync(unfinished, h_unf.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      SL_HIP(hipMemcpyAsync(finish_len, h_fin.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      SL_HIP(hipMemcpyAsync(ctx_len, h_ctx.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      SL_HIP(hipMemcpyAsync(gen_count, h_cnt.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      SL_HIP(hipMemcpyAsync(next_ids, h_next.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      SL_HIP(hipMemcpyAsync(row_id, orig.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      if (row_limit_arg) SL_HIP(hipMemcpyAsync(row_limit, h_lim.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      SL_HIP(hipMemcpyAsync(out_ids, h_out.data(), (size_t)B * max_new_tokens * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      if (scores) SL_HIP(hipMemcpyAsync(lp_out, h_lp.data(), (size_t)B * max_new_tokens * sizeof(float), hipMemcpyHostToDevice, st));
-      SL_HIP(hipStreamSynchronize(st));           // the host vectors above are reused / the move list is overwritten by the next step's logits
-      SL_TRY(graph_for(B, &exec));
+      SL_TRY(tab.push(RT::ALL, B, st));
+      SL_HIP(hipStreamSynchronize(st));           // the host arrays above are reused / the move list is overwritten by the next step's logits
+      SL_TRY(decode_graph_get(g, B, tail, &exec));
       ++compactions;
     }
   }
-  SL_HIP(hipEventRecord(ev[2], st));
+  SL_HIP(hipEventRecord(ev.e[2], st));
   // results: queued behind the last step on the caller's stream, ONE synchronisation for the whole call (plus one per check above)
-  h_out.resize((size_t)B * max_new_tokens);
-  SL_HIP(hipMemcpyAsync(h_unf.data(), unfinished, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  SL_HIP(hipMemcpyAsync(h_fin.data(), finish_len, B * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  SL_HIP(hipMemcpyAsync(h_out.data(), out_ids, (size_t)B * max_new_tokens * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (scores) {
-    h_lp.resize((size_t)B * max_new_tokens);
-    SL_HIP(hipMemcpyAsync(h_lp.data(), lp_out, (size_t)B * max_new_tokens * sizeof(float), hipMemcpyDeviceToHost, st));
-  }
+  SL_TRY(tab.pull(RT::bit(RT::UNF) | RT::bit(RT::FIN) | RT::bit(RT::OUT) | RT::bit(RT::LP), B, st));
   SL_HIP(hipStreamSynchronize(st));
   retire(false);
   int n_cols = steps_done;
@@ -1361,10 +1422,9 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   if (stats) {
     memset(stats, 0, sizeof(*stats));
     stats->n_steps = n_cols; stats->decode_launches = launches; stats->compactions = compactions; stats->final_rows = B; stats->row_steps = row_steps;
-    SL_HIP(hipEventElapsedTime(&stats->prefill_ms, ev[0], ev[1]));
-    SL_HIP(hipEventElapsedTime(&stats->decode_ms, ev[1], ev[2]));
+    SL_HIP(hipEventElapsedTime(&stats->prefill_ms, ev.e[0], ev.e[1]));
+    SL_HIP(hipEventElapsedTime(&stats->decode_ms, ev.e[1], ev.e[2]));
   }
-  for (auto& e : ev) (void)hipEventDestroy(e);
   return 0;
 }
 
@@ -1565,9 +1625,9 @@ extern "C" int sl_beam_generate_lp(const sl_llama_model* m, const sl_kv_cache* k
     }
   }
   for (int t = 0; t < max_new; ++t) lpen[t] = (float)pow((double)(t + 1), (double)o->length_penalty);
-  hipEvent_t ev[3];
-  for (auto& e : ev) SL_HIP(hipEventCreate(&e));
-  SL_HIP(hipEventRecord(ev[0], st));
+  Events3 ev;
+  SL_TRY(ev.create());
+  SL_HIP(hipEventRecord(ev.e[0], st));
   // prefill: each prompt once, into the slot of its first beam (it writes nseq context lengths: overwritten below with the rows')
   SL_TRY(llama_prefill_impl(m, kv, x, cu_seqlens_host, nseq, b.logits, b.st.ctx_len, nullptr, b.scratch, scratch_bytes, stream, K));
   SL_HIP(hipMemcpyAsync(b.st.run_score, run0.data(), R * sizeof(float), hipMemcpyHostToDevice, st));
@@ -1600,53 +1660,31 @@ extern "C" int sl_beam_generate_lp(const sl_llama_model* m, const sl_kv_cache* k
   }
   SL_TRY(sl_beam_topk_impl(b.logits, nseq, m->vocab, b.zero_score, M, b.cand_score, b.cand_token, st, lp.on ? 1 : 0));
   SL_TRY(sl_beam_step_impl(&b.st, b.cand_score, b.cand_token, nseq, K, M, 1, &oo, st));
-  SL_HIP(hipEventRecord(ev[1], st));
+  SL_HIP(hipEventRecord(ev.e[1], st));
   SL_HIP(hipStreamSynchronize(st));     // the host vectors above leave scope only after their copies ran
 
   int steps_done = 1, launches = 0;
   std::vector<int32_t> h_done(nseq, 0);
   if (max_new > 1) {
-    LlamaWs w;
-    llama_carve(m, R, R, b.scratch, scratch_bytes, w);
-    if (w.split && w.split_bytes >= 8192) SL_HIP(hipMemsetAsync(w.split, 0, 8192, st));
-    SL_TRY(sl_attn_decode_split_zero_counters(w.part, R, m->n_heads, m->n_kv_heads, kv->max_ctx, st));
-    hipLaunchKernelGGL(iota_kernel, dim3((R + 255) / 256), dim3(256), 0, st, w.tok_seq, R);
-    SL_CHECK_LAUNCH("iota");
-    DecodeGraphKey key;
-    memset(&key, 0, sizeof(key));
-    key.model = m; key.layers = m->layers; key.w0 = m->n_layers > 0 ? m->layers[0].wqkv_dec : nullptr; key.lm = m->lm_head_dec ? m->lm_head_dec : m->lm_head;
-    key.embed = m->embed; key.kc = kv->k_cache; key.vc = kv->v_cache; key.ws = workspace; key.ws_bytes = workspace_bytes;
-    key.B = R; key.B0 = nseq; key.max_new = max_new; key.use_eos = oo.use_eos; key.n_eos = n_eos; key.pad = o->pad_id; key.max_ctx = kv->max_ctx;
-    key.slots = kv->slots; key.shared_prefix = kv->shared_prefix; key.dtype = m->dtype; key.n_layers = m->n_layers; key.vocab = m->vocab;
-    key.fused = m->dec_fused_norm | (sl_env().decode_tiled << 8) | ((sl_env().attn_decode_ks & 127) << 9) | ((kv->reserved & 3) << 18) | ((m->reserved & 3) << 20);
-    key.content = model_content_hash(m);
-    SL_HIP(hipGetDevice(&key.device));
-    for (int i = 0; i < n_eos && i < 8; ++i) key.eos[i] = o->eos_ids_host[i];
-    key.beam_k = K; key.beam_m = M; key.beam_es = o->early_stopping; key.beam_lp = o->length_penalty;
-    if (lp.on) { key.lp_penalty = lp.o.repetition_penalty; key.lp_ngram = lp.o.no_repeat_ngram_size; key.lp_min_new = lp.o.min_new_tokens; }
-    hipGraphExec_t exec = decode_graph_lookup(key);
-    if (!exec) {
-      hipGraph_t graph = nullptr;
-      static thread_local hipStream_t cap_by_dev[SL_MAX_DEVICES] = {};
-      SL_CHECK_ARG(key.device >= 0 && key.device < SL_MAX_DEVICES, "sl_beam_generate: device index %d", key.device);
-      hipStream_t& cap = cap_by_dev[key.device];
-      if (!cap) SL_HIP(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-      SL_HIP(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
-      int rc = decode_step(m, kv, b.st.next_ids, b.st.ctx_len, R, b.logits, b.xdec, w, cap, false);
-      if (rc == 0 && lp.on) {       // row s * K + j: the history of running beam j, `step` tokens long, in hist[step & 1]
+    GraphCtx g{};
+    g.who = "sl_beam_generate"; g.m = m; g.kv = kv; g.ws = workspace; g.ws_bytes = workspace_bytes; g.scratch = b.scratch; g.scratch_bytes = scratch_bytes;
+    g.logits = b.logits; g.xdec = b.xdec; g.next_ids = b.st.next_ids; g.ctx_len = b.st.ctx_len; g.st = st;
+    g.B0 = nseq; g.max_new = max_new; g.use_eos = oo.use_eos; g.n_eos = n_eos; g.pad = o->pad_id; g.eos = o->eos_ids_host; g.lp = &lp;
+    g.beam_k = K; g.beam_m = M; g.beam_es = o->early_stopping; g.beam_lp = o->length_penalty;
+    // behind the lm_head's fp32 logits: row s * K + j holds the history of running beam j, `step` tokens long, in hist[step & 1]
+    auto tail = [&](hipStream_t cap, int, bool) -> int {
+      if (lp.on) {
         hipLaunchKernelGGL(beam_hist_len_kernel, dim3((R + 255) / 256), dim3(256), 0, cap, b.st.step, K, R, b.hist_len);
-        rc = sl_logits_process_impl(b.logits, R, m->vocab, b.st.hist[0], b.st.hist[1], max_new, b.hist_len, nullptr, &lp.o, o->eos_ids_host, n_eos, 1,
-                                    b.lp_scratch, cap);
+        SL_CHECK_LAUNCH("beam_hist_len");
+        SL_TRY(sl_logits_process_impl(b.logits, R, m->vocab, b.st.hist[0], b.st.hist[1], max_new, b.hist_len, nullptr, &lp.o, o->eos_ids_host, n_eos, 1,
+                                      b.lp_scratch, cap));
       }
-      if (rc == 0) rc = sl_beam_topk_impl(b.logits, R, m->vocab, b.st.run_score, M, b.cand_score, b.cand_token, cap, lp.on ? 1 : 0);
-      if (rc == 0) rc = sl_beam_step_impl(&b.st, b.cand_score, b.cand_token, nseq, K, M, 0, &oo, cap);
-      if (rc == 0 && K > 1) rc = sl_kv_beam_reorder_impl(kv, m, b.st.src_row, b.prompt_len, b.st.ctx_len, R, max_new, b.staging, b.staging_bytes, cap);
-      hipError_t ce = hipStreamEndCapture(cap, &graph);
-      if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-      if (ce != hipSuccess) { sl_set_error("hipStreamEndCapture: %s", hipGetErrorString(ce)); return SL_ERR_LAUNCH; }
-      SL_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-      decode_graph_store(key, graph, exec);
-    }
+      SL_TRY(sl_beam_topk_impl(b.logits, R, m->vocab, b.st.run_score, M, b.cand_score, b.cand_token, cap, lp.on ? 1 : 0));
+      SL_TRY(sl_beam_step_impl(&b.st, b.cand_score, b.cand_token, nseq, K, M, 0, &oo, cap));
+      return K > 1 ? sl_kv_beam_reorder_impl(kv, m, b.st.src_row, b.prompt_len, b.st.ctx_len, R, max_new, b.staging, b.staging_bytes, cap) : 0;
+    };
+    hipGraphExec_t exec = nullptr;
+    SL_TRY(decode_graph_get(g, R, tail, &exec));
     const int check_every = o->check_every > 0 ? o->check_every : 16;
     while (steps_done < max_new) {
       SL_HIP(hipGraphLaunch(exec, st));
@@ -1659,7 +1697,7 @@ extern "C" int sl_beam_generate_lp(const sl_llama_model* m, const sl_kv_cache* k
       if (all) break;
     }
   }
-  SL_HIP(hipEventRecord(ev[2], st));
+  SL_HIP(hipEventRecord(ev.e[2], st));
   std::vector<int32_t> h_ids((size_t)R * max_new), h_len(R);
   std::vector<float> h_sc(R);
   SL_HIP(hipMemcpyAsync(h_ids.data(), b.st.fin_ids, h_ids.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1678,10 +1716,9 @@ extern "C" int sl_beam_generate_lp(const sl_llama_model* m, const sl_kv_cache* k
   if (stats) {
     memset(stats, 0, sizeof(*stats));
     stats->n_steps = steps_done; stats->decode_launches = launches; stats->final_rows = R; stats->row_steps = (int64_t)launches * R;
-    SL_HIP(hipEventElapsedTime(&stats->prefill_ms, ev[0], ev[1]));
-    SL_HIP(hipEventElapsedTime(&stats->decode_ms, ev[1], ev[2]));
+    SL_HIP(hipEventElapsedTime(&stats->prefill_ms, ev.e[0], ev.e[1]));
+    SL_HIP(hipEventElapsedTime(&stats->decode_ms, ev.e[1], ev.e[2]));
   }
-  for (auto& e : ev) (void)hipEventDestroy(e);
   return 0;
 }
 

@@ -377,3 +377,37 @@ def test_second_call_replays_the_cached_graph_and_a_greedy_call_in_between_keeps
     assert torch.equal(greedy0, greedy1) and torch.equal(greedy1, greedy2)
     assert torch.equal(ids1[:, :int(llm.last_beam_lengths.max())], t(c["ids"])[:, :int(llm.last_beam_lengths.max())].to(torch.int32))
     assert lib.sl_decode_graph_cache_clear() == 2                     # one beam graph + one greedy graph: the second calls replayed them
+
+
+def test_decode_graph_census():
+    """One graph per mode and not one more: greedy, greedy + scores, sampling, greedy + repetition penalty, beams, beams + no-repeat n-grams on
+    the same buffers each capture once (their keys differ in scores / sample / lp_* / beam_*), the second round replays all six and returns
+    what the first did.  Then a budgeted greedy call that compacts once: 3 -> 2 rows, ids those of the uncompacted call."""
+    lib = L.lib()
+    llm = _llm("tiny_gqa", 31, 1, torch.float32)
+    _set_eos(llm, TINY_LLAMA.eos_token_ids, TINY_LLAMA.pad_token_id)          # the model's own: whatever an earlier test left is not this test's
+    lens, max_new = [5, 9, 7], 6
+    x = (torch.randn(sum(lens), TINY_LLAMA.hidden_size, generator=torch.Generator().manual_seed(9)) * 0.05).to(DEV)
+    modes = [dict(), dict(scores=True), dict(sample=dict(temperature=0.8, top_k=20, top_p=0.9, seed=1234)), dict(logits=dict(repetition_penalty=1.3)),
+             dict(beams=dict(num_beams=2)), dict(beams=dict(num_beams=2), logits=dict(no_repeat_ngram_size=2))]
+
+    def run(kw):
+        r = llm.generate_packed(x.clone(), lens, max_new, use_eos=False, compact=False, **kw)
+        extra = llm.last_beam_scores.clone() if "beams" in kw else (r[2].clone() if kw.get("scores") else None)
+        return r[0].clone(), extra
+
+    for kw in modes:                                   # sizes the workspace and the cache for the largest mode: the rounds below share one buffer
+        run(kw)
+    lib.sl_decode_graph_cache_clear()
+    first = [run(kw) for kw in modes]
+    second = [run(kw) for kw in modes]
+    for kw, a, b in zip(modes, first, second):
+        assert torch.equal(a[0], b[0]), kw
+        assert (a[1] is None and b[1] is None) or torch.equal(a[1], b[1]), kw
+    assert lib.sl_decode_graph_cache_clear() == 6
+    out = {}
+    for compact in (False, True):
+        ids, n_cols = llm.generate_packed(x.clone(), lens, max_new, use_eos=True, row_limits=[2, 6, 6], check_every=2, compact=compact)
+        out[compact] = (ids.clone(), n_cols, dict(llm.last_generate_stats))
+    assert out[True][2]["compactions"] == 1 and out[True][2]["final_rows"] == 2, out[True][2]
+    assert torch.equal(out[True][0], out[False][0]) and out[True][1] == out[False][1]

@@ -133,6 +133,74 @@ def test_e4m3_decode_weight_row_limit_counts_nseq_times_num_beams():
     assert rc == -3 and b"sl_w8_max_rows" in lib.sl_last_error(), (rc, lib.sl_last_error())
 
 
+# (n_tok, nseq, max_new, penalty on, x, sl_generate_workspace_bytes_sc with scores = x, sl_beam_generate_workspace_bytes_lp with num_beams = x + 1):
+# the byte counts the library returned BEFORE the per-row state table and the shared decode-graph builder went in (fp32 model of _model(),
+# cache of 256 slots x 48).  The layout is part of the decode-graph key through the workspace pointer, so the counts are pinned, not recomputed.
+WORKSPACE_BYTES = [
+    (7, 1, 1, 0, 0, 59592, 61444),
+    (7, 1, 1, 0, 1, 59852, 77064),
+    (7, 1, 1, 1, 0, 59852, 61956),
+    (7, 1, 1, 1, 1, 60112, 77576),
+    (7, 1, 6, 0, 0, 59612, 61444),
+    (7, 1, 6, 0, 1, 59892, 118024),
+    (7, 1, 6, 1, 0, 59892, 61956),
+    (7, 1, 6, 1, 1, 60172, 118536),
+    (7, 3, 1, 0, 0, 74328, 76044),
+    (7, 3, 1, 0, 1, 74596, 122648),
+    (7, 3, 1, 1, 0, 74596, 76556),
+    (7, 3, 1, 1, 1, 74864, 123160),
+    (7, 3, 6, 0, 0, 74388, 76044),
+    (7, 3, 6, 0, 1, 74716, 245528),
+    (7, 3, 6, 1, 0, 74716, 76556),
+    (7, 3, 6, 1, 1, 75044, 246040),
+    (7, 65, 1, 0, 0, 1461192, 1466628),
+    (7, 65, 1, 0, 1, 1461708, 3450632),
+    (7, 65, 1, 1, 0, 1461708, 1467652),
+    (7, 65, 1, 1, 1, 1462224, 3452168),
+    (7, 65, 6, 0, 0, 1462492, 1470468),
+    (7, 65, 6, 0, 1, 1464308, 6120712),
+    (7, 65, 6, 1, 0, 1464308, 1472772),
+    (7, 65, 6, 1, 1, 1466124, 6124808),
+    (300, 1, 1, 0, 0, 2011848, 2013700),
+    (300, 1, 1, 0, 1, 2012108, 2029320),
+    (300, 1, 1, 1, 0, 2012108, 2014212),
+    (300, 1, 1, 1, 1, 2012368, 2029832),
+    (300, 1, 6, 0, 0, 2011868, 2013700),
+    (300, 1, 6, 0, 1, 2012148, 2070280),
+    (300, 1, 6, 1, 0, 2012148, 2014212),
+    (300, 1, 6, 1, 1, 2012428, 2070792),
+    (300, 3, 1, 0, 0, 2026584, 2028300),
+    (300, 3, 1, 0, 1, 2026852, 2074904),
+    (300, 3, 1, 1, 0, 2026852, 2028812),
+    (300, 3, 1, 1, 1, 2027120, 2075416),
+    (300, 3, 6, 0, 0, 2026644, 2028300),
+    (300, 3, 6, 0, 1, 2026972, 2197784),
+    (300, 3, 6, 1, 0, 2026972, 2028812),
+    (300, 3, 6, 1, 1, 2027300, 2198296),
+    (300, 65, 1, 0, 0, 3026888, 3032324),
+    (300, 65, 1, 0, 1, 3027404, 4583176),
+    (300, 65, 1, 1, 0, 3027404, 3033348),
+    (300, 65, 1, 1, 1, 3027920, 4584712),
+    (300, 65, 6, 0, 0, 3028188, 3036164),
+    (300, 65, 6, 0, 1, 3030004, 7253256),
+    (300, 65, 6, 1, 0, 3030004, 3038468),
+    (300, 65, 6, 1, 1, 3031820, 7257352),
+]
+
+
+def test_workspace_byte_counts_are_those_recorded_before_the_state_table():
+    lib = L.lib()
+    m, kv = _model(), _kv(slots=256, max_ctx=48)
+    pen = L.LogitsOpts()
+    pen.repetition_penalty = 1.3
+    assert len(WORKSPACE_BYTES) == 2 * 3 * 2 * 2 * 2
+    for n_tok, nseq, max_new, lp, x, gen, beam in WORKSPACE_BYTES:
+        lpr = C.byref(pen) if lp else None
+        o = _opts(K=x + 1, max_new=max_new)
+        assert lib.sl_generate_workspace_bytes_sc(C.byref(m), n_tok, nseq, max_new, lpr, x) == gen, (n_tok, nseq, max_new, lp, x)
+        assert lib.sl_beam_generate_workspace_bytes_lp(C.byref(m), n_tok, nseq, C.byref(kv), C.byref(o), lpr) == beam, (n_tok, nseq, max_new, lp, x)
+
+
 def test_kernel_level_entries_check_their_arguments_without_a_gpu():
     lib = L.lib()
     assert lib.sl_beam_topk(1, 4, 100, None, 65, 1, 1, None) == -1 and b"M = 65" in lib.sl_last_error()

@@ -363,6 +363,31 @@ def test_compacted_and_uncompacted_calls_give_the_same_log_probabilities(pack, r
         assert bool((out[True][2][r, n_:] == 0).all()) and bool((out[True][2][r, :n_] < 0).all())
 
 
+@pytest.mark.parametrize("rows", [12, 96])
+def test_one_compaction_moves_ids_and_log_probabilities_together_on_both_sides_of_the_fused_gate(rows):
+    """12 rows with the packed lm_head (row form: fp32 logits, greedy_select_kernel) and 96 without (fused top-1: three planes,
+    greedy_select_partial_kernel; the family stays pinned at 96 after the compaction).  Even rows have a budget of 3, so half the batch is
+    finished at the first check (step 4): one compaction, to the rung of rows / 2 live rows (6 and 48), in which every surviving row changes
+    its slot — out_ids and the log-probabilities travel through the same per-row table.  fp32: both equal the uncompacted call bit for bit."""
+    c = _case("ragged3")
+    llm = _llm(pack_decode=rows == 12)
+    _set_eos(llm, [])
+    x, lens, n = _tiled(c, rows)
+    max_new = 8
+    budgets = [3 if r % 2 == 0 else max_new for r in range(rows)]
+    out = {}
+    for compact in (False, True):
+        ids, n_cols, lps = llm.generate_packed(x.to(DEV), lens, max_new, row_limits=budgets, compact=compact, check_every=4, scores=True)
+        out[compact] = (ids.clone(), n_cols, lps.clone(), dict(llm.last_generate_stats))
+    assert out[True][3]["compactions"] == 1 and out[True][3]["final_rows"] == rows // 2, out[True][3]
+    assert out[False][3]["compactions"] == 0 and out[False][3]["final_rows"] == rows
+    assert out[True][1] == out[False][1] == max_new
+    assert torch.equal(out[True][0], out[False][0])
+    assert torch.equal(out[True][2].view(torch.int32), out[False][2].view(torch.int32))
+    for r, n_ in enumerate(budgets):
+        assert bool((out[True][2][r, n_:] == 0).all()) and bool((out[True][2][r, :n_] < 0).all())
+
+
 def test_scores_off_is_the_call_without_them_and_on_never_replays_the_other_graph():
     c = _case("greedy")
     lib = L.lib()
