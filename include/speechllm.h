@@ -157,6 +157,13 @@ int sl_gemm_fused_decode(const sl_gemm_args* a, const sl_gemm_fused* fx, sl_stre
  *   trans_w: W is stored as (K, N) with row stride ldw  — C = A . W-stored       (e.g. dX = dY W)
  *            transposed operands are read in 16-byte chunks along the OUTPUT index: lda/ldw must be
  *            multiples of 8 (bf16) / 4 (f32) and each stored row readable up to that multiple.
+ *            What the loader requires of lda / ldw: a chunk is loaded whole when its FIRST element lies inside
+ *            the extent, so with M (N) no multiple of the chunk, each of the K stored rows is read up to the
+ *            next multiple of 8 / 4 elements: M rounded up must fit in lda, or in the buffer behind the last
+ *            row.  The elements read behind the extent land in tile rows that no epilogue stores, so their
+ *            values never matter; rows K and beyond are never read.  A row stride below the extent
+ *            (overlapping rows: the implicit-GEMM conv windows) is allowed for W.  The token-major kernel
+ *            (both transposed, bf16, M and N multiples of 128) reads exactly M x K and N x K elements.
  *   aux_out: also store the pre-activation (after bias, before act) — what GELU's backward needs.
  *   residual_f32: with out_f32, the residual is float: C = residual + A.W^T accumulates fp32 gradients.
  *   groups / w_mod: see below. */

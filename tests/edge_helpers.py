@@ -1,6 +1,6 @@
-"""Helpers shared by the chapters of the edge suite (tests/test_kernel_edges_gpu.py, tests/test_train_edges_gpu.py): dtypes and their
-half-ulps, finite poison, the output sentinel, guarded output buffers, poisoned operand views, the per-element comparison and the
-`tuning` fixture.  A plain module, not a conftest: the test files import what they use."""
+"""Helpers shared by the chapters of the edge suite (tests/test_kernel_edges_gpu.py, tests/test_train_edges_gpu.py,
+tests/test_train_gemm_edges_gpu.py): dtypes and their half-ulps, finite poison, the output sentinel, guarded output buffers, poisoned
+operand views, the per-element comparison and the `tuning` fixture.  A plain module, not a conftest: the test files import what they use."""
 import pytest
 import torch
 
@@ -32,6 +32,11 @@ def tuning(monkeypatch):
     yield set_
     monkeypatch.undo()
     L.lib().sl_tuning_reload()
+
+
+def _set(tuning, switches):
+    for k, v in switches.items():
+        tuning(k, v)
 
 
 def _gen(seed):
@@ -100,5 +105,3 @@ def bad(got, want, tol=None, bits=False):
     i = tuple(wrong.nonzero()[0].tolist())
     worst = "" if tol is None else f", worst err/tol {float(((got.double() - want.double()).abs() / tol).max()):.3g}"
     return f"{int(wrong.sum())} of {wrong.numel()} elements wrong, first at {i}: got {float(got[i])!r} want {float(want[i])!r}{worst}"
-
-

@@ -31,7 +31,7 @@ import torch
 
 import attn_train_ref as R
 from conftest import pkg, rel_err
-from edge_helpers import (BF16, BIG, DEV, DT16, DTS, E24, F16, F32, FILL, U, _gen, bad, gauss, guarded, ints, operand, to_dt, tuning,  # noqa: F401
+from edge_helpers import (BF16, BIG, DEV, DT16, DTS, E24, F16, F32, FILL, U, _gen, _set, bad, gauss, guarded, ints, operand, to_dt, tuning,  # noqa: F401
                           untouched, vec)
 
 pytestmark = pytest.mark.gpu
@@ -186,11 +186,6 @@ def packed(M, N, K, dt, **extra):
 # ------------------------------------------------------------------------------------------------------------------------------
 # row-major GEMM
 # ------------------------------------------------------------------------------------------------------------------------------
-def _set(tuning, switches):
-    for k, v in switches.items():
-        tuning(k, v)
-
-
 @pytest.mark.parametrize("dt,M,N,K", [(dt, M, N, K) for dt in DT16 for M, N, K in [(70, 50, 72), (130, 96, 200)]] + [(F32, 70, 50, 36), (F32, 130, 96, 200)])
 def test_gemm_register_path_k_not_a_whole_slab(dt, M, N, K):
     """gemm_tiled_kernel: K that is no whole 128-byte slab (16-bit: 72, 200; fp32: 36, 200)"""
