@@ -412,6 +412,25 @@ int sl_attn_decode_split_ex(const void* q, int64_t q_stride, const void* k_cache
                             void* workspace, const int32_t* ctx_len, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D,
                             int32_t max_ctx, float scale, int32_t dtype, int32_t kv_format, int32_t shared_prefix, sl_stream stream);
 
+/* Grouped decode attention: rows that share a prompt (several sampled answers per prompt, sl_generate_n) read its K / V rows once.
+ * Row b attends positions [0, prefix_len[b]) of its record's prefix_slot and [prefix_len[b], ctx_len[b]) of slot row_slot0 + b (both
+ * slot indices into k_cache / v_cache; ctx_len[b] >= prefix_len[b], an empty tail is allowed).  A row with prefix_len 0 is in no record
+ * and attends its own slot only.  Two launches: a prefix pass, one block per (record, kv head), whose 16-row matrix-core tile carries the
+ * n_heads / n_kv query heads of up to floor(16 / (n_heads / n_kv)) sibling rows and which leaves an fp32 {O[128], max, sum} record per
+ * (row, head) in the workspace; and a tail pass, one block per (row, kv head), that starts its online softmax from that record.  No
+ * merge launch, no atomics.  The grid of the prefix pass is B records whatever the plan used (hipGraph-capturable: groups_dev is read
+ * at run time); a record with n_rows = 0 exits at once.  Rows of a record need not be adjacent.
+ * Built for SL_BF16 / SL_F16 (SL_F32: SL_ERR_UNSUPPORTED), D = 128, n_heads / n_kv in 1..4, both K / V formats.
+ * sl_attn_group_plan_host is a pure host routine (no GPU): rows with the same (prefix_slot, prefix_len > 0) share records, in row
+ * order, floor(16 / rep) rows per record; it always writes B records (the unused ones with n_rows = 0) and *n_used = the used count. */
+typedef struct { int32_t prefix_slot, prefix_len, n_rows, reserved; int32_t rows[16]; } sl_attn_group;
+int sl_attn_group_plan_host(const int32_t* prefix_slot, const int32_t* prefix_len, int32_t B, int32_t rep, sl_attn_group* out, int32_t* n_used);
+size_t sl_attn_decode_grouped_workspace_bytes(int32_t B, int32_t n_heads);
+int sl_attn_decode_grouped(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, void* workspace,
+                           const int32_t* ctx_len, const int32_t* prefix_len, const sl_attn_group* groups_dev, int32_t B,
+                           int32_t row_slot0, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx, float scale,
+                           int32_t dtype, int32_t kv_format, sl_stream stream);
+
 /* Greedy token selection (hf:generation/utils.py:2894,2925-2936): argmax over fp32 logits (lowest index
  * on ties), pad finished rows, EOS check, append to out_ids[b][gen_count[b]], advance gen_count and
  * ctx_len.  logits (B, V) float; eos_ids is a HOST array of at most 8 ids (passed by value to the
@@ -919,6 +938,25 @@ size_t sl_generate_workspace_bytes_sc(const sl_llama_model* m, int64_t n_tok, in
 int sl_generate_sc(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
                    const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
                    sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host);
+
+/* sl_generate_n: sl_generate_sc with N = num_return_sequences sampled answers per prompt (HF's do_sample = True,
+ * num_return_sequences = N).  N = 1 IS sl_generate_sc: same launches, captured graphs, workspace layout and bits.  N > 1 needs
+ * opts->sample = 1 (HF refuses greedy with several return sequences too), nseq * N <= SL_MAX_DECODE_BATCH decode rows and
+ * kv->slots >= nseq * (N + 1): the nseq prompts are prefilled ONCE into slots [0, nseq), which are never written again, and row
+ * s * N + j (answer j of prompt s) appends its own tokens to slot nseq + s * N + j.  out_ids_host / out_logprobs_host are
+ * (nseq * N, max_new_tokens), prompt-major; row_limits_host, when given, has nseq * N entries.  The draw of answer j of prompt s is
+ * that of sequence index s * N + j of an sl_generate_sc call in which every prompt is repeated N times, compacted or not.
+ * Decode attention: where the grouped kernels are built and the switch SL_GEN_GROUP_ATTN allows it (0 = never, 1 = wherever built,
+ * -1 = default rule), a row reads its prompt from the prompt slot through sl_attn_decode_grouped and its row slot holds positions
+ * >= the prompt length only; otherwise the prompt's K / V rows are copied to the N row slots once and the attention of sl_generate_sc
+ * runs on them.  sl_generate_last_attn_path(): what the calling thread's last sl_generate_n call ran — 0 = N was 1, 1 = the copy,
+ * 2 = the grouped kernels. */
+size_t sl_generate_workspace_bytes_n(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int32_t max_new_tokens, const sl_logits_opts* lp,
+                                     int32_t scores, int32_t num_return_sequences);
+int sl_generate_n(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                  const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
+                  sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host, int32_t num_return_sequences);
+int32_t sl_generate_last_attn_path(void);
 
 /* ---------------------------------------------------------------------------------------------
  * KD step, layer stacks (C++ host runtime of the training tape: one call issues the launches of a whole stack of layers

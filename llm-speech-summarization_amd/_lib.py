@@ -169,6 +169,11 @@ class GenerateStats(C.Structure):
                 ("prefill_ms", c_f32), ("decode_ms", c_f32)]
 
 
+class AttnGroup(C.Structure):
+    """sl_attn_group: rows of a decode step that read one prompt's K / V rows together (sl_attn_decode_grouped)"""
+    _fields_ = [("prefix_slot", c_i32), ("prefix_len", c_i32), ("n_rows", c_i32), ("reserved", c_i32), ("rows", c_i32 * 16)]
+
+
 class BeamOpts(C.Structure):
     _fields_ = [("eos_ids_host", C.POINTER(c_i32)), ("n_eos", c_i32), ("pad_id", c_i32), ("use_eos", c_i32), ("max_new_tokens", c_i32),
                 ("check_every", c_i32), ("num_beams", c_i32), ("num_return_sequences", c_i32), ("early_stopping", c_i32), ("length_penalty", c_f32)]
@@ -329,6 +334,14 @@ _PROTOS = {
     "sl_generate_workspace_bytes_sc": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, c_i32, C.POINTER(LogitsOpts), c_i32]),
     "sl_generate_sc": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(GenerateOpts), C.POINTER(c_i32),
                                C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts), C.POINTER(c_f32)]),
+    # several sampled answers per prompt (additive to ABI 7)
+    "sl_attn_group_plan_host": (c_i32, [C.POINTER(c_i32), C.POINTER(c_i32), c_i32, c_i32, C.POINTER(AttnGroup), C.POINTER(c_i32)]),
+    "sl_attn_decode_grouped_workspace_bytes": (c_sz, [c_i32, c_i32]),
+    "sl_attn_decode_grouped": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_i32, c_vp]),
+    "sl_generate_workspace_bytes_n": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, c_i32, C.POINTER(LogitsOpts), c_i32, c_i32]),
+    "sl_generate_n": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(GenerateOpts), C.POINTER(c_i32),
+                              C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts), C.POINTER(c_f32), c_i32]),
+    "sl_generate_last_attn_path": (c_i32, []),
     "sl_greedy_generate": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, c_i32,
                                    C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32),
                                    C.POINTER(c_f32), c_vp, c_sz, c_vp]),

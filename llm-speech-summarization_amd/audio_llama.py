@@ -283,7 +283,9 @@ class AudioLlamaForCausalLM:
                  length_penalty: Optional[float] = None, early_stopping=None, num_return_sequences: Optional[int] = None,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
                  return_dict_in_generate: Optional[bool] = None, output_scores: Optional[bool] = None, **unused):
-        """num_beams > 1: beam search (hf:generation/utils.py _beam_search, sl_beam_generate) -> (B * num_return_sequences, n_cols),
+        """do_sample=True with num_return_sequences=R > 1: R sampled answers per prompt -> (B * R, n_cols), prompt-major as HF returns them
+        (sl_generate_n: each prompt is prefilled once); greedy search with R > 1 raises, as in HF.
+        num_beams > 1: beam search (hf:generation/utils.py _beam_search, sl_beam_generate) -> (B * num_return_sequences, n_cols),
         n_cols the longest returned hypothesis; `last_beam_scores` / `last_beam_lengths` hold HF's sequences_scores and the lengths.
         repetition_penalty / no_repeat_ngram_size / min_new_tokens: HF's logits processors (sl_logits_process) over the GENERATED tokens, in
         every mode; None falls back to `generation_config` (HF's defaults 1.0 / 0 / 0 = off: the call is then exactly the call without them).
@@ -306,8 +308,8 @@ class AudioLlamaForCausalLM:
             raise L.SpeechLLMError(f"num_beams={K}: must be >= 1")
         if K > 1 and sampling:
             raise L.SpeechLLMError("num_beams > 1 with do_sample=True (beam sampling) is not built: use beam search or sampling")
-        if R > K or R < 1:
-            raise L.SpeechLLMError(f"num_return_sequences={R} outside [1, num_beams={K}]" + (" (sampling several sequences per prompt is not built)" if K == 1 else ""))
+        if R < 1 or (R > K and not (K == 1 and sampling)):
+            raise L.SpeechLLMError(f"num_return_sequences={R} outside [1, num_beams={K}]" + (" (greedy search returns one sequence per prompt: several need do_sample=True)" if K == 1 else ""))
         w = self._dev()
         a = self.arch
         if inputs_embeds is None:
@@ -333,10 +335,10 @@ class AudioLlamaForCausalLM:
             sample = dict(temperature=float(g.temperature if temperature is None else temperature), top_k=int(g.top_k if top_k is None else top_k),
                           top_p=float(g.top_p if top_p is None else top_p), seed=int(seed))
         if not want_scores:
-            ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits)
+            ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits, num_return=R)
             seqs = ids[:, :n_cols].to(torch.int64)
             return GenerateOutput(seqs, None, None) if ret_dict else seqs
-        ids, n_cols, lps = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits, scores=True)
+        ids, n_cols, lps = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits, scores=True, num_return=R)
         seqs, lps = ids[:, :n_cols].to(torch.int64), lps[:, :n_cols].clone()
         self.last_token_logprobs = lps
         return GenerateOutput(seqs, lps, lps.sum(dim=1)) if ret_dict else seqs      # pads hold 0.0: the sum runs over the row's generated length
@@ -396,7 +398,7 @@ class AudioLlamaForCausalLM:
 
     def generate_packed(self, x: torch.Tensor, lens: Sequence[int], max_new_tokens: int, use_eos: bool = True, sample: Optional[dict] = None,
                         shared_prefix: int = 0, row_limits: Optional[Sequence[int]] = None, compact: bool = True, check_every: int = 4,
-                        beams: Optional[dict] = None, logits: Optional[dict] = None, scores: bool = False):
+                        beams: Optional[dict] = None, logits: Optional[dict] = None, scores: bool = False, num_return: int = 1):
         """x: packed prompt embeddings (sum S_i, h) on the GPU (overwritten).  Returns (int32 (B, max_new) host tensor, n_cols).
         shared_prefix = P: the caller's promise that the first P rows of every sequence are the same rows (one prompt template in
         front of the audio, ref:inference.py:95-113) — the batched decode attention then reads those P cache positions from slot 0
@@ -412,7 +414,15 @@ class AudioLlamaForCausalLM:
         -> select.  None, or all three off: exactly the call without them.
         scores=True: returns (ids, n_cols, logprobs), logprobs a float32 (B, max_new) host tensor of the chosen tokens' log-probabilities
         (sl_generate_sc; 0.0 at and after a row's finish); above 64 rows a greedy step keeps the fused lm_head top-1 and carries a third
-        partial.  Not with beams.  False: exactly the call without them."""
+        partial.  Not with beams.  False: exactly the call without them.
+        num_return = R > 1 (sampling only): R answers per prompt from ONE prefill (sl_generate_n) -> (B * R, max_new) ids / logprobs,
+        prompt-major; row_limits then has B * R entries; the cache holds B prompt slots + B * R row slots.  The draws are those of a call
+        on every prompt repeated R times.  `last_generate_stats` has prefill_seqs and attn_path ("copy" / "grouped")."""
+        R = int(num_return)
+        if R < 1:
+            raise L.SpeechLLMError(f"num_return_sequences={R}: must be >= 1")
+        if R > 1 and sample is None and beams is None:
+            raise L.SpeechLLMError(f"num_return_sequences={R} with greedy search: several answers per prompt need sampling")
         w = self._dev()
         a = self.arch
         lib = L.lib()
@@ -425,10 +435,11 @@ class AudioLlamaForCausalLM:
             if scores:
                 raise L.SpeechLLMError("scores and beams together are not built: last_beam_scores holds the hypotheses' scores")
             return self._beam_packed(x, lens, max_new_tokens, use_eos, shared_prefix, check_every, beams, logits)
-        if B > L.MAX_DECODE_BATCH:
-            raise L.SpeechLLMError(f"{B} sequences in one generate call; the library takes {L.MAX_DECODE_BATCH} (split the batch: sequences are independent)")
+        if B * R > L.MAX_DECODE_BATCH:
+            raise L.SpeechLLMError(f"{B * R} sequences in one generate call; the library takes {L.MAX_DECODE_BATCH} (split the batch: sequences are independent)")
         cu_c, eos_c, n_eos, use_eos, pad = self._generate_preamble(lens, max_new_tokens, use_eos, shared_prefix)
-        kv = self._kv_cache(B, shared_prefix)
+        kv = self._kv_cache(B * (R + 1) if R > 1 else B, shared_prefix)
+        n_prompts, B = B, B * R      # B: decode rows = rows of every returned array
         out = (C.c_int32 * (B * max_new_tokens))()
         o = L.GenerateOpts()
         # the ids are handed over as configured; with use_eos = 0 the library ignores them (rows then finish on their budgets only)
@@ -448,6 +459,21 @@ class AudioLlamaForCausalLM:
         lp_ref = C.byref(lp) if lp is not None else None
         struct, fmt_name = self._struct_for(B)
         lps = None
+        if R > 1:
+            if scores:
+                lps = (C.c_float * (B * max_new_tokens))()
+            nbytes = lib.sl_generate_workspace_bytes_n(C.byref(struct), x.shape[0], n_prompts, max_new_tokens, lp_ref, int(bool(scores)), R)
+            if nbytes == 0:
+                L.check(-1, "sl_generate_workspace_bytes_n")
+            ws = self._workspace(nbytes)
+            L.check(lib.sl_generate_n(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, n_prompts, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+                                      L.stream_ptr(), lp_ref, lps, R), "sl_generate_n")
+            self._record_generate_stats(st, B, fmt_name, prefill_seqs=n_prompts, num_return_sequences=R,
+                                        attn_path={1: "copy", 2: "grouped"}[int(lib.sl_generate_last_attn_path())])
+            ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B, max_new_tokens)
+            if scores:
+                return ids, int(st.n_steps), torch.frombuffer(lps, dtype=torch.float32).clone().view(B, max_new_tokens)
+            return ids, int(st.n_steps)
         if scores:
             lps = (C.c_float * (B * max_new_tokens))()
             ws = self._workspace(lib.sl_generate_workspace_bytes_sc(C.byref(struct), x.shape[0], B, max_new_tokens, lp_ref, 1))

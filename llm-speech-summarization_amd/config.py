@@ -116,3 +116,13 @@ def runtime_beams(config):
     if k == 1:
         return None
     return dict(num_beams=int(k), length_penalty=float(lp), early_stopping=es, num_return_sequences=1)
+
+
+def runtime_num_return(config) -> int:
+    """`runtime.num_return_sequences` of a config (default 1): sampled answers per utterance; above 1 the answers are drawn with the
+    llm's generation_config temperature / top_k / top_p (greedy search has one answer per prompt)."""
+    rt = config.get("runtime", {}) if hasattr(config, "get") else {}
+    r = (rt or {}).get("num_return_sequences", 1)
+    if isinstance(r, bool) or not isinstance(r, int) or r < 1:
+        raise ValueError(f"runtime.num_return_sequences: {r!r} is not an integer >= 1")
+    return int(r)

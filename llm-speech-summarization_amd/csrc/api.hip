@@ -57,6 +57,7 @@ static const SlEnv* env_load() {
   // 26: the decode step at 17..32 sequences on either family (tools/time_decode_step.py, profiles/r04_zb_stream_min_m.txt): the skinny kernels win
   // up to 26 rows (2.34 vs 2.36 ms), the 32-row streaming blocks from 27 (2.42 vs 2.38) to 32 (2.57 vs 2.40)
   e.compact_pin = env_int("SL_COMPACT_PIN", 1);
+  e.gen_group_attn = env_int("SL_GEN_GROUP_ATTN", -1);
   e.tape_fuse = env_int("SL_TAPE_FUSE", 1);
   e.attn_bwd_kf = env_int("SL_ATTN_BWD_KF", 0);
   e.decode_prefetch = env_int("SL_DECODE_PREFETCH", 0);

@@ -456,6 +456,7 @@ struct SlEnv {
   int attn_bwd_kf;         // SL_ATTN_BWD_KF       (default 0 = by shape) 16-row fragments per wave in the attention-backward kernels: 1 / 2 force a form
   int tape_fuse;           // SL_TAPE_FUSE         (default 1) training tapes: dropout / GELU' / SwiGLU' / bias-gradient passes inside the GEMM and norm-backward kernels (0: the unfused launch sequence, A/B + parity tests)
   int compact_pin;         // SL_COMPACT_PIN       (default 1) a compacting generation keeps the kernel family of its first batch (0: each rung picks its own — A/B only)
+  int gen_group_attn;      // SL_GEN_GROUP_ATTN    sl_generate_n with several answers per prompt: 1 = decode attention reads the prompt's K / V once per group of sibling rows (sl_attn_decode_grouped) wherever built, 0 = the prompt rows are copied to every row slot, -1 (default) = by the measured rule (runtime.hip gen_group_attn_rule: 16-bit K / V rows from 256 decode rows up)
   int stream_min_m;        // SL_STREAM_MIN_M      (default 26) packed-weight products with more rows than this take the LDS-staged streaming kernels
   int disable_t256;        // SL_DISABLE_T256
   int t256_min_tiles;      // SL_T256_MIN_TILES    (default 512)

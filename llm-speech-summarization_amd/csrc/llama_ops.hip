@@ -2,7 +2,9 @@
 // attention against the cache, greedy token selection.  All HBM/latency-bound; 16-byte accesses, fp32 math.
 #include <stdlib.h>
 
+#include <map>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 
@@ -1105,11 +1107,16 @@ __global__ __launch_bounds__(256) void attn_decode_split_kernel(const T* __restr
 // the HBM-bound attention of one in-flight batch can then run under the matrix-core-bound encode / prefill of the other
 // (SL_ATTN_DECODE_KS=64; DESIGN §8.10 has what it measured).
 // KVT = uint8_t: e4m3 rows (KvRow): 8-byte loads, the K / V registers hold half the dwords, the LDS images are unchanged.
-template <typename T, int REP, bool PREFETCH, int KS_ = 128, typename KVT = T>
+// TAIL = true (sl_attn_decode_grouped's second pass; rec / prefix_len are NULL and unread otherwise): the walk starts at key prefix_len[b]
+// instead of 0, and the running maximum, sum and output start from the fp32 record {O[128], m, l} the prefix pass left for every
+// (row, head) instead of -inf / 0 / 0 — the row's prompt keys live in another slot and were folded in there.
+constexpr int GROUP_REC_FLOATS = 136;      // O[128], m, l, padded to whole 32-byte sectors
+template <typename T, int REP, bool PREFETCH, int KS_ = 128, typename KVT = T, bool TAIL = false>
 __global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restrict__ q, int64_t q_stride, const KVT* __restrict__ kc,
                                                                const KVT* __restrict__ vc, T* __restrict__ out,
                                                                const int32_t* __restrict__ ctx_len, int ctx_add, int nh, int nkv, int max_ctx,
-                                                               float scale, int shared_prefix) {
+                                                               float scale, int shared_prefix, const float* __restrict__ rec,
+                                                               const int32_t* __restrict__ prefix_len) {
   static_assert(sizeof(T) == 2, "the single-pass form is built for the 16-bit types (bf16 / fp16)");
   constexpr int D = 128, KS = KS_, NPS = KS / 16;
   static_assert(KS == 64 || KS == 128, "chunks of 64 or 128 keys");
@@ -1123,6 +1130,8 @@ __global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restri
   const int kg = tid >> 4, dc = tid & 15;
   const int r = lane & 15, q4 = lane >> 4, qq = r >> 2, pp = r & 3;
   const int n_keys = ctx_len[b] + ctx_add;
+  int k_begin = 0;
+  if constexpr (TAIL) k_begin = prefix_len[b];
   using Row = KvRow<T, KVT>;
   const KVT* kbase = kc + ((int64_t)b * nkv + kvh) * max_ctx * D;
   const KVT* vbase = vc + ((int64_t)b * nkv + kvh) * max_ctx * D;
@@ -1160,8 +1169,20 @@ __global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restri
   f32x4 oacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   float m_run = -INFINITY, l_run = 0.f;   // live in wave h (< REP), replicated over its lanes
   const uint32_t ub = (uint32_t)(uintptr_t)(lds_ptr3_t)un;
-  const int nchunk = (n_keys + KS - 1) / KS;
-  if constexpr (PREFETCH) fetch(0, 0);
+  if constexpr (TAIL) {
+    if (k_begin > 0) {
+      const float* rb = rec + ((int64_t)b * nh + kvh * REP) * GROUP_REC_FLOATS;
+      if (wave < REP) { m_run = rb[wave * GROUP_REC_FLOATS + D]; l_run = rb[wave * GROUP_REC_FLOATS + D + 1]; }
+      if (q4 == 0) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int h = 0; h < REP; ++h) oacc[j][h] = rb[h * GROUP_REC_FLOATS + (2 * wave + j) * 16 + r];
+      }
+    }
+  }
+  const int nchunk = (n_keys - k_begin + KS - 1) / KS;
+  if constexpr (PREFETCH) fetch(0, k_begin);
   for (int c0 = 0; c0 < nchunk; c0 += 2) {
 #pragma unroll
     for (int u2 = 0; u2 < 2; ++u2) {
@@ -1169,7 +1190,7 @@ __global__ __launch_bounds__(256) void attn_decode_full_kernel(const T* __restri
       const int u = PREFETCH ? u2 : 0;
       const int ci = c0 + u2;
       if (ci >= nchunk) break;
-      const int k0 = ci * KS;
+      const int k0 = k_begin + ci * KS;
       if constexpr (PREFETCH) { if (ci + 1 < nchunk) fetch(u ^ 1, k0 + KS); }
       else fetch_k(0, k0);
       // K tile -> LDS -> scores on the matrix core
@@ -1296,16 +1317,16 @@ static int launch_attn_decode_split(const void* q, int64_t q_stride, const void*
     if (Bf * nkv >= full_min && !long_thin && !sl_env().attn_force_split) {
       if constexpr (KV8)     // e4m3 rows: the 128-key form only (SL_ATTN_DECODE_KS is a 16-bit experiment)
         hipLaunchKernelGGL((attn_decode_full_kernel<T, REP, false, 128, KVT>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride, (const KVT*)kc,
-                           (const KVT*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
+                           (const KVT*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix, nullptr, nullptr);
       else if (sl_env().attn_decode_ks == 65)        // 64-key chunks with the NEXT chunk's K / V rows held in a second register set (twice the bytes in flight per block)
         hipLaunchKernelGGL((attn_decode_full_kernel<T, REP, true, 64>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride, (const T*)kc,
-                           (const T*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
+                           (const T*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix, nullptr, nullptr);
       else if (sl_env().attn_decode_ks == 64)
         hipLaunchKernelGGL((attn_decode_full_kernel<T, REP, false, 64>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride, (const T*)kc,
-                           (const T*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
+                           (const T*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix, nullptr, nullptr);
       else
         hipLaunchKernelGGL((attn_decode_full_kernel<T, REP, false>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride, (const T*)kc,
-                           (const T*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix);
+                           (const T*)vc, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, shared_prefix, nullptr, nullptr);
       SL_CHECK_LAUNCH("attn_decode_full");
       return 0;
     }
@@ -1388,4 +1409,236 @@ extern "C" int sl_attn_decode_split_ex(const void* q, int64_t q_stride, const vo
                                        int32_t dtype, int32_t kv_format, int32_t shared_prefix, sl_stream stream) {
   return sl_attn_decode_split_impl(q, q_stride, k_cache, v_cache, out, workspace, ctx_len, 0, B, n_heads, n_kv, D, max_ctx, scale, dtype,
                                    (hipStream_t)stream, 2, shared_prefix, kv_format);
+}
+
+// ----------------------------------------------------------------------------------------------
+// Grouped decode attention (speechllm.h sl_attn_decode_grouped): rows that share a prompt read its K / V once.
+// Pass 1, attn_decode_prefix_kernel: one block per (group record, kv head).  The single-pass kernel's 16-row MFMA tile carries REP live
+// rows there; here tile row t holds head t % REP of the record's sibling t / REP (up to 16 / REP siblings), so the C / D rows
+// 4 * (lane >> 4) + reg of every 16-lane group are live, each wave runs the online softmax of four tile rows, and the block walks keys
+// [0, prefix_len) of prefix_slot in 128-key chunks — the single-pass kernel's loads, LDS images and MFMA steps.  It leaves the fp32
+// record {O[128] (unnormalised), m, l} of every (row, head) in the workspace.
+// Pass 2, attn_decode_full_kernel<.., TAIL = true>: one block per (row, kv head) starts from that record and walks the row's own slot from
+// prefix_len on.  No merge launch, no atomics; a record with n_rows = 0 exits at once (the grid is B records whatever the plan used).
+// ----------------------------------------------------------------------------------------------
+template <typename T, int REP, typename KVT = T>
+__global__ __launch_bounds__(256) void attn_decode_prefix_kernel(const T* __restrict__ q, int64_t q_stride, const KVT* __restrict__ kc,
+                                                                 const KVT* __restrict__ vc, float* __restrict__ rec,
+                                                                 const sl_attn_group* __restrict__ groups, int B, int nh, int nkv, int max_ctx,
+                                                                 float scale) {
+  static_assert(sizeof(T) == 2, "the grouped form is built for the 16-bit types (bf16 / fp16)");
+  constexpr int D = 128, KS = 128, NPS = KS / 16, PROW = KS * 2 + 16, NSIB = 16 / REP;
+  __shared__ float sc[16][KS];
+  __shared__ float alpha[16];
+  __shared__ int32_t s_row[16];        // tile row -> batch row (-1: padding)
+  __shared__ __attribute__((aligned(16))) unsigned char un[KS * D * 2];   // K tile, then V tile
+  __shared__ __attribute__((aligned(16))) unsigned char pt[16 * PROW];
+  const int kvh = blockIdx.x;
+  const sl_attn_group* g = groups + blockIdx.y;
+  const int n_rows = g->n_rows < NSIB ? g->n_rows : NSIB;
+  const int n_keys = g->prefix_len < max_ctx ? g->prefix_len : max_ctx;
+  if (n_rows <= 0 || n_keys <= 0) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = lane >> 4, gl = lane & 15;
+  const int kg = tid >> 4, dc = tid & 15;
+  const int r = lane & 15, q4 = lane >> 4, qq = r >> 2, pp = r & 3;
+  using Row = KvRow<T, KVT>;
+  const KVT* kbase = kc + ((int64_t)g->prefix_slot * nkv + kvh) * max_ctx * D;
+  const KVT* vbase = vc + ((int64_t)g->prefix_slot * nkv + kvh) * max_ctx * D;
+  auto voff = [](int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); };
+  auto row_of = [&](int t) {      // batch row of tile row t; a row index outside the batch is padding
+    if (t >= n_rows * REP) return -1;
+    const int b = g->rows[t / REP];
+    return (b >= 0 && b < B) ? b : -1;
+  };
+  if (tid < 16) { s_row[tid] = row_of(tid); alpha[tid] = 1.0f; }
+  uint4 qf[4];
+  {
+    const int b = row_of(r);
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4)
+      qf[s4] = b >= 0 ? *(const uint4*)(q + (int64_t)b * q_stride + (int64_t)(kvh * REP + r % REP) * D + 32 * s4 + 8 * q4) : make_uint4(0, 0, 0, 0);
+  }
+  for (int o = tid; o < 16 * (KS / 8); o += 256)   // P rows of padding tile rows stay zero
+    *(uint4*)(pt + (o / (KS / 8)) * PROW + (o % (KS / 8)) * 16) = make_uint4(0, 0, 0, 0);
+  __syncthreads();
+  typename Row::raw_t kraw[NPS], vraw[NPS];
+  f32x4 oacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  float m_run[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, l_run[4] = {0.f, 0.f, 0.f, 0.f};   // tile rows 4 * wave + i
+  const uint32_t ub = (uint32_t)(uintptr_t)(lds_ptr3_t)un;
+  const int nchunk = (n_keys + KS - 1) / KS;
+  for (int ci = 0; ci < nchunk; ++ci) {
+    const int k0 = ci * KS;
+#pragma unroll
+    for (int ps = 0; ps < NPS; ++ps) {   // rows past the prefix are clamped (their scores are masked)
+      int key = k0 + ps * 16 + wave * 4 + grp; key = key < n_keys ? key : n_keys - 1;
+      kraw[ps] = Row::load(kbase + (int64_t)key * D + gl * 8);
+    }
+#pragma unroll
+    for (int ps = 0; ps < NPS; ++ps) {
+      const int kl = ps * 16 + wave * 4 + grp;
+      *(u32x4_t*)(un + kl * 256 + ((gl ^ (kl & 15)) << 4)) = Row::widen(kraw[ps]);
+    }
+#pragma unroll
+    for (int ps = 0; ps < NPS; ++ps) {
+      int key = k0 + kg + 16 * ps; key = key < n_keys ? key : n_keys - 1;
+      vraw[ps] = Row::load(vbase + (int64_t)key * D + dc * 8);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < KS / 64; ++n) {
+      const int rowbase = wave * (KS / 4) + n * 16;
+      f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s4 = 0; s4 < 4; ++s4) {
+        const uint4 kf = *(const uint4*)(un + (rowbase + r) * 256 + (((4 * s4 + q4) ^ r) << 4));
+        MMA<T>::step(sacc, qf[s4], kf);
+      }
+      const int key = rowbase + r;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sc[4 * q4 + e][key] = (k0 + key) < n_keys ? sacc[e] * scale : -INFINITY;
+    }
+    __syncthreads();
+    // online softmax: wave w owns tile rows 4 w .. 4 w + 3 (two keys per lane); P rounded to 16 bits as in the single-pass form
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int t = 4 * wave + i;
+      if (t >= n_rows * REP) break;
+      const float s0 = sc[t][lane], s1 = sc[t][lane + 64];
+      const float m_new = fmaxf(m_run[i], wave_max(fmaxf(s0, s1)));   // finite: key k0 is inside the prefix
+      const float p0 = __expf(s0 - m_new), p1 = __expf(s1 - m_new);
+      const float a = __expf(m_run[i] - m_new);
+      l_run[i] = l_run[i] * a + wave_sum(p0 + p1);
+      m_run[i] = m_new;
+      *(T*)(pt + t * PROW + lane * 2) = from_f32<T>(p0);
+      *(T*)(pt + t * PROW + (lane + 64) * 2) = from_f32<T>(p1);
+      if (lane == 0) alpha[t] = a;
+    }
+#pragma unroll
+    for (int ps = 0; ps < NPS; ++ps) *(u32x4_t*)(un + voff(kg + 16 * ps, dc)) = Row::widen(vraw[ps]);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int df = 2 * wave + j;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) oacc[j][e] *= alpha[4 * q4 + e];
+#pragma unroll
+      for (int ks = 0; ks < KS / 32; ++ks) {
+        const uint4 pa = *(const uint4*)(pt + r * PROW + (32 * ks + 8 * q4) * 2);
+        const int r0 = 32 * ks + 8 * q4 + qq;
+        u32x2_t lo, hi;
+        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(ub + (uint32_t)(voff(r0, 2 * df + (pp >> 1)) + 8 * (pp & 1))) : "memory");
+        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(hi) : "v"(ub + (uint32_t)(voff(r0 + 4, 2 * df + (pp >> 1)) + 8 * (pp & 1))) : "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo), "+v"(hi));
+        MMA<T>::step(oacc[j], pa, make_uint4(lo.x, lo.y, hi.x, hi.y));
+      }
+    }
+    __syncthreads();   // un / pt / sc / alpha are rewritten by the next chunk
+  }
+  // records: (m, l) from the wave that ran the row's softmax, O from every wave's two 16-dim fragments
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int t = 4 * wave + i, b = s_row[t];
+      if (b < 0) continue;
+      float* p = rec + ((int64_t)b * nh + kvh * REP + t % REP) * GROUP_REC_FLOATS;
+      p[D] = m_run[i]; p[D + 1] = l_run[i];
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int t = 4 * q4 + e, b = s_row[t];
+    if (b < 0) continue;
+    float* p = rec + ((int64_t)b * nh + kvh * REP + t % REP) * GROUP_REC_FLOATS;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) p[(2 * wave + j) * 16 + r] = oacc[j][e];
+  }
+}
+
+extern "C" int sl_attn_group_plan_host(const int32_t* prefix_slot, const int32_t* prefix_len, int32_t B, int32_t rep, sl_attn_group* out, int32_t* n_used) {
+  SL_CHECK_ARG(prefix_slot && prefix_len && out && n_used, "sl_attn_group_plan_host: null prefix_slot, prefix_len, out or n_used");
+  SL_CHECK_ARG(B > 0 && B <= SL_MAX_DECODE_BATCH, "sl_attn_group_plan_host: B %d outside (0, %d]", B, SL_MAX_DECODE_BATCH);
+  SL_CHECK_ARG(rep >= 1 && rep <= 16, "sl_attn_group_plan_host: rep %d outside [1, 16]", rep);
+  const int per = 16 / rep;
+  memset(out, 0, (size_t)B * sizeof(sl_attn_group));
+  std::map<std::pair<int32_t, int32_t>, int> open;      // (slot, len) -> its record that still has room
+  int used = 0;
+  for (int b = 0; b < B; ++b) {
+    if (prefix_len[b] <= 0) continue;
+    const auto key = std::make_pair(prefix_slot[b], prefix_len[b]);
+    auto it = open.find(key);
+    if (it == open.end() || out[it->second].n_rows == per) {
+      out[used].prefix_slot = key.first; out[used].prefix_len = key.second;
+      open[key] = used++;
+      it = open.find(key);
+    }
+    sl_attn_group& g = out[it->second];
+    g.rows[g.n_rows++] = b;
+  }
+  *n_used = used;
+  return 0;
+}
+
+extern "C" size_t sl_attn_decode_grouped_workspace_bytes(int32_t B, int32_t n_heads) {
+  if (B <= 0 || n_heads <= 0) { sl_set_error("sl_attn_decode_grouped_workspace_bytes: B=%d n_heads=%d", B, n_heads); return 0; }
+  return ((size_t)B * n_heads * GROUP_REC_FLOATS * sizeof(float) + 255) & ~(size_t)255;
+}
+
+// what the grouped kernels are built for (the generation runtime asks before it chooses the path)
+bool sl_attn_decode_grouped_built(int n_heads, int n_kv, int D, int dtype, int kv_format) {
+  return sl_is16(dtype) && D == 128 && n_kv > 0 && n_heads % n_kv == 0 && n_heads / n_kv >= 1 && n_heads / n_kv <= 4 &&
+         (kv_format == SL_KV_MODEL_DTYPE || kv_format == SL_KV_FP8_E4M3);
+}
+
+template <typename T, int REP, typename KVT>
+static int launch_attn_decode_grouped(const void* q, int64_t q_stride, const void* kc, const void* vc, void* out, float* rec, const int32_t* ctx_len,
+                                      int ctx_add, const int32_t* prefix_len, const sl_attn_group* groups, int B, int row_slot0, int nh, int nkv,
+                                      int max_ctx, float scale, hipStream_t st) {
+  hipLaunchKernelGGL((attn_decode_prefix_kernel<T, REP, KVT>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride, (const KVT*)kc, (const KVT*)vc, rec,
+                     groups, B, nh, nkv, max_ctx, scale);
+  SL_CHECK_LAUNCH("attn_decode_prefix");
+  const int64_t slot0 = (int64_t)row_slot0 * nkv * max_ctx * 128;      // the rows' own slots start here
+  hipLaunchKernelGGL((attn_decode_full_kernel<T, REP, false, 128, KVT, true>), dim3(nkv, B), dim3(256), 0, st, (const T*)q, q_stride,
+                     (const KVT*)kc + slot0, (const KVT*)vc + slot0, (T*)out, ctx_len, ctx_add, nh, nkv, max_ctx, scale, 0, rec, prefix_len);
+  SL_CHECK_LAUNCH("attn_decode_tail");
+  return 0;
+}
+
+int sl_attn_decode_grouped_impl(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, void* workspace,
+                                const int32_t* ctx_len, int ctx_add, const int32_t* prefix_len, const sl_attn_group* groups_dev, int32_t B,
+                                int32_t row_slot0, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx, float scale, int32_t dtype,
+                                int32_t kv_format, hipStream_t st) {
+  SL_CHECK_ARG(q && k_cache && v_cache && out && workspace && ctx_len && prefix_len && groups_dev, "sl_attn_decode_grouped: null q, k_cache, v_cache, out, workspace, ctx_len, prefix_len or groups_dev");
+  SL_CHECK_ARG(B > 0 && B <= SL_MAX_DECODE_BATCH, "sl_attn_decode_grouped: B %d outside (0, %d]", B, SL_MAX_DECODE_BATCH);
+  SL_CHECK_ARG(row_slot0 >= 0, "sl_attn_decode_grouped: row_slot0 %d < 0", row_slot0);
+  SL_CHECK_ARG(max_ctx > 0, "sl_attn_decode_grouped: max_ctx %d", max_ctx);
+  if (dtype == SL_F32) {
+    sl_set_error("sl_attn_decode_grouped: dtype float32 not built (bf16 / fp16; the generation runtime copies the prompt rows there)");
+    return SL_ERR_UNSUPPORTED;
+  }
+  SL_CHECK_ARG(sl_is16(dtype), "sl_attn_decode_grouped: unknown dtype %d", dtype);
+  SL_TRY(sl_kv_format_check("sl_attn_decode_grouped", kv_format, dtype, D));
+  SL_CHECK_ARG(D == 128, "sl_attn_decode_grouped: head_dim D %d not built (128)", D);
+  SL_CHECK_ARG(n_kv > 0 && n_heads % n_kv == 0, "sl_attn_decode_grouped: n_heads %% n_kv != 0");
+  const int rep = n_heads / n_kv;
+  float* rec = (float*)workspace;
+#define SL_ATTNG_CASE(T_, KVT_, R_) \
+  case R_: return launch_attn_decode_grouped<T_, R_, KVT_>(q, q_stride, k_cache, v_cache, out, rec, ctx_len, ctx_add, prefix_len, groups_dev, B, row_slot0, n_heads, n_kv, max_ctx, scale, st)
+#define SL_ATTNG_REPS(T_, KVT_) switch (rep) { SL_ATTNG_CASE(T_, KVT_, 1); SL_ATTNG_CASE(T_, KVT_, 2); SL_ATTNG_CASE(T_, KVT_, 3); SL_ATTNG_CASE(T_, KVT_, 4); default: break; }
+  if (kv_format == SL_KV_FP8_E4M3) {
+    if (dtype == SL_BF16) SL_ATTNG_REPS(bf16_t, uint8_t) else SL_ATTNG_REPS(f16_t, uint8_t)
+  } else {
+    if (dtype == SL_BF16) SL_ATTNG_REPS(bf16_t, bf16_t) else SL_ATTNG_REPS(f16_t, f16_t)
+  }
+#undef SL_ATTNG_REPS
+#undef SL_ATTNG_CASE
+  sl_set_error("sl_attn_decode_grouped: n_heads/n_kv=%d not built (1..4)", rep);
+  return SL_ERR_UNSUPPORTED;
+}
+
+extern "C" int sl_attn_decode_grouped(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, void* workspace,
+                                      const int32_t* ctx_len, const int32_t* prefix_len, const sl_attn_group* groups_dev, int32_t B,
+                                      int32_t row_slot0, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx, float scale, int32_t dtype,
+                                      int32_t kv_format, sl_stream stream) {
+  return sl_attn_decode_grouped_impl(q, q_stride, k_cache, v_cache, out, workspace, ctx_len, 0, prefix_len, groups_dev, B, row_slot0, n_heads, n_kv, D,
+                                     max_ctx, scale, dtype, kv_format, (hipStream_t)stream);
 }

@@ -23,6 +23,11 @@ int sl_attn_decode_split_impl(const void* q, int64_t q_stride, const void* k_cac
                               const int32_t* ctx_len, int ctx_add, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx,
                               float scale, int32_t dtype, hipStream_t st, int counters, int shared_prefix, int kv_format);
 size_t sl_attn_decode_split_ws(int B, int n_heads, int n_kv, int max_ctx);
+int sl_attn_decode_grouped_impl(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, void* workspace,
+                                const int32_t* ctx_len, int ctx_add, const int32_t* prefix_len, const sl_attn_group* groups_dev, int32_t B,
+                                int32_t row_slot0, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx, float scale, int32_t dtype,
+                                int32_t kv_format, hipStream_t st);
+bool sl_attn_decode_grouped_built(int n_heads, int n_kv, int D, int dtype, int kv_format);
 int sl_rmsnorm_rstd_impl(const void* x, void* y, const void* w, float* rstd_out, int64_t rows, int32_t cols, float eps, int32_t dtype, hipStream_t st);
 int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st);
 int sl_gemm_top1_lse_impl(const sl_gemm_args* a, const sl_gemm_ex_args* ex, float* amax_sum, hipStream_t st);
@@ -598,6 +603,17 @@ struct DecodePrefetch {
 };
 static thread_local DecodePrefetch* g_prefetch = nullptr;      // set by sl_generate around the capture of a small-batch decode graph
 
+// Where a decode step's rows keep their K / V (sl_generate_n with several answers per prompt; all zero for every other caller): the rows' slots
+// start at slot row_slot0 of the cache — the K / V append, the attention's "own slot" and compaction all work on the per-layer base
+// shifted by that many slots — and, with `groups` set, a row's positions below prefix_len[row] are read from its record's prompt slot
+// by the grouped attention (sl_attn_decode_grouped) instead of from a copy in its own slot.
+struct DecodeAttn {
+  int row_slot0 = 0;
+  const sl_attn_group* groups = nullptr;      // device, B records rebuilt at every compaction (NULL: the copy path)
+  const int32_t* prefix_len = nullptr;        // device, per row
+  void* gws = nullptr;                        // the grouped attention's records
+};
+
 // one decoder layer over `n` token rows; attention chosen by `decode`
 // decode GEMM on the fragment-packed weights, optionally absorbing the preceding RMSNorm / RoPE+KV-append
 static int dec_gemm(const sl_llama_model* m, const LlamaWs& w, const void* A, int64_t lda, const void* Wp, void* C, int64_t ldc, const void* res,
@@ -629,13 +645,25 @@ static int dec_gemm(const sl_llama_model* m, const LlamaWs& w, const void* A, in
 // The products stay pinned to the family of n rows, so a row goes through the kernel — and the K order — it goes through in the full pass.
 static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, void* x, int64_t n, LlamaWs& w, bool decode, int nseq,
                        int max_qlen, const int32_t* ctx_len_dev, hipStream_t st, bool rstd_chain = false, const float* rstd_qkv = nullptr,
-                       int prefix_bcast = 0, int bcast_slots = 0, bool rstd_pass = false, const int32_t* tail_rows = nullptr, int n_tail = 0) {
+                       int prefix_bcast = 0, int bcast_slots = 0, bool rstd_pass = false, const int32_t* tail_rows = nullptr, int n_tail = 0,
+                       const DecodeAttn* da = nullptr) {
   const sl_llama_layer& L = m->layers[l];
   const int dt = m->dtype, H = m->hidden, D = m->head_dim, nh = m->n_heads, nkv = m->n_kv_heads;
   const int qkv_w = (nh + 2 * nkv) * D;
   void* kc = bptr(kv->k_cache) + (size_t)l * kv_layer_bytes(m, kv);
   void* vc = bptr(kv->v_cache) + (size_t)l * kv_layer_bytes(m, kv);
+  const void *kc0 = kc, *vc0 = vc;       // slot 0 of the layer: the grouped attention's prompt slots are indexed from here
+  if (decode && da && da->row_slot0 > 0) {
+    const size_t off = (size_t)da->row_slot0 * nkv * kv->max_ctx * D * kv_elem_bytes(m, kv);
+    kc = bptr(kc) + off; vc = bptr(vc) + off;
+  }
   const float scale = 1.0f / sqrtf((float)D);
+  auto decode_attn = [&](int64_t q_stride) -> int {
+    if (da && da->groups)
+      return sl_attn_decode_grouped_impl(w.qkv, q_stride, kc0, vc0, w.att, da->gws, ctx_len_dev, 1, da->prefix_len, da->groups, (int)n, da->row_slot0, nh, nkv,
+                                         D, kv->max_ctx, scale, dt, kv->reserved, st);
+    return sl_attn_decode_split_impl(w.qkv, q_stride, kc, vc, w.att, w.part, ctx_len_dev, 1, (int)n, nh, nkv, D, kv->max_ctx, scale, dt, st, 1, kv->shared_prefix, kv->reserved);
+  };
   if (decode && L.wqkv_dec && L.wo_dec && L.wgu_dec && L.wdown_dec) {
     // 5-6 launches per layer: [norm+]qkv+rope+append | attention (split + merge) | o+res | [norm+]gate/up+silu.mul | down+res
     sl_gemm_fused fx;
@@ -658,7 +686,7 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     // that the gain-folded products stay on the 256 x 128 streaming blocks instead of taking the statistics per block themselves
     if (rstd_pass) { SL_TRY(sl_rmsnorm_rstd_impl(x, nullptr, nullptr, w.rstd_b, n, H, m->rms_eps, dt, st)); rstd_qkv = w.rstd_b; }
     SL_TRY(dec_gemm(m, w, a_in, H, L.wqkv_dec, w.qkv, (int64_t)nh * D, nullptr, (int)n, qkv_w, H, SL_ACT_ROPE_KV, 0, &fx, st, rstd_qkv));
-    SL_TRY(sl_attn_decode_split_impl(w.qkv, (int64_t)nh * D, kc, vc, w.att, w.part, ctx_len_dev, 1, (int)n, nh, nkv, D, kv->max_ctx, scale, dt, st, 1, kv->shared_prefix, kv->reserved));
+    SL_TRY(decode_attn((int64_t)nh * D));
     // Above ~900 rows gate/up runs on the row-major 256 x 256 tiles (the prefill kernel): at 1 024 rows it is 4 x 64 = 256 tiles, one per
     // CU, 78-81 us against 99 us on the 256 x 128 streaming block (tools/time_decode_tiled.py; in the graph: profiles/r04_l_*).  Its input
     // must then be normalised: the o projection's reduce pass, which already forms each row's RMSNorm scale, writes the normalised rows
@@ -702,7 +730,7 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
   SL_TRY(sl_rope_kv_append_ex(w.qkv, kc, vc, w.tok_seq, decode ? ctx_len_dev : w.tok_pos, m->rope_cos, m->rope_sin, n, nh, nkv, D, kv->max_ctx,
                               dt, kv->reserved, (sl_stream)st));
   if (decode) {
-    SL_TRY(sl_attn_decode_split_impl(w.qkv, qkv_w, kc, vc, w.att, w.part, ctx_len_dev, 1, (int)n, nh, nkv, D, kv->max_ctx, scale, dt, st, 1, kv->shared_prefix, kv->reserved));
+    SL_TRY(decode_attn(qkv_w));
   } else {
     if (prefix_bcast > 0 && bcast_slots > 1) {     // (not reached with e4m3 rows: sl_llama_prefill switches the dedupe off there; the row size is the cache's all the same)
       const int row_vec = (int)(D * kv_elem_bytes(m, kv) / 16);
@@ -863,7 +891,7 @@ static bool decode_fuses_argmax(const sl_llama_model* m, int B) { B = sl_family_
 // [n_groups][B] int32 (n_groups = ceil(vocab / 64)) — only honoured where decode_fuses_argmax() says so.  top1_sum (token log-probabilities):
 // a third plane of [n_groups][B] floats behind the two, the groups' sum exp(v - group max) (3 ceil(V / 64) B <= B0 V floats always holds)
 static int decode_step(const sl_llama_model* m, const sl_kv_cache* kv, const int32_t* next_ids, const int32_t* ctx_len, int B, float* logits,
-                       void* x, LlamaWs& w, hipStream_t st, bool fused_top1 = false, bool top1_sum = false) {
+                       void* x, LlamaWs& w, hipStream_t st, bool fused_top1 = false, bool top1_sum = false, const DecodeAttn* da = nullptr) {
   const int dt = m->dtype, H = m->hidden;
   SL_TRY(sl_embed_gather(m->embed, next_ids, x, B, H, dt, (sl_stream)st));
   // hand RMSNorm scales along the chain when every o / down projection has a reduce pass to compute them in
@@ -882,7 +910,7 @@ static int decode_step(const sl_llama_model* m, const sl_kv_cache* kv, const int
     rstd_pass = L.wqkv_dec && L.wo_dec && L.wgu_dec && L.wdown_dec;
   }
   for (int l = 0; l < m->n_layers; ++l)
-    SL_TRY(llama_layer(m, kv, l, x, B, w, true, B, 1, ctx_len, st, chain, (chain && l > 0) ? w.rstd_b : nullptr, 0, 0, rstd_pass));
+    SL_TRY(llama_layer(m, kv, l, x, B, w, true, B, 1, ctx_len, st, chain, (chain && l > 0) ? w.rstd_b : nullptr, 0, 0, rstd_pass, nullptr, 0, da));
   // lm_head: above ~256 rows the 128-tile MFMA kernel on the row-major matrix beats the streaming kernel on the packed one
   // (M=512: 439 vs 632 us; the 263 MB of fp32 logits dominate either way)
   if (m->lm_head_dec && sl_family_rows(B) < SL_FUSED_ARGMAX_MIN_B) {
@@ -962,6 +990,8 @@ struct DecodeGraphKey {
   float lp_penalty;                // logits processors (all 0 when off: the graph without them): a changed value never replays a stale graph
   int lp_ngram, lp_min_new;
   int scores;                      // token log-probabilities on: other select kernels, a third lm_head plane — never the graph of a call without them
+  int n_ret, row_slot0, grouped;   // sl_generate_n: answers per prompt (1 in every other generate graph, 0 in a beam graph), first row slot, attention path
+  const void* groups;              // ... and the device records the grouped attention reads
 };
 struct DecodeGraphEntry { DecodeGraphKey key; hipGraph_t graph; hipGraphExec_t exec; uint64_t stamp; };
 static thread_local std::vector<DecodeGraphEntry> g_graphs;
@@ -1047,9 +1077,9 @@ extern "C" size_t sl_generate_workspace_bytes(const sl_llama_model* m, int64_t n
 }
 
 // ---- compaction of a batch whose rows finish at different steps (sl_generate_opts.compact) ----
-// K / V rows [0, len) of slot `src` copied to slot `dst` in every layer: grid (pair, layer * n_kv); src >= every dst (the movers sit
-// above the rows that stay), so no block reads what another writes
-struct KvMove { int32_t src, dst, len, pad; };
+// K / V rows [first, len) of slot `src` copied to slot `dst` in every layer: grid (pair, layer * n_kv); src >= every dst (the movers sit
+// above the rows that stay), so no block reads what another writes.  first > 0: a row slot of the grouped path, which holds no prompt rows
+struct KvMove { int32_t src, dst, len, first; };
 __global__ __launch_bounds__(256) void kv_move_kernel(uint4* __restrict__ kc, uint4* __restrict__ vc, const KvMove* __restrict__ mv, int nkv, int slots,
                                                       int max_ctx, int row_vec) {
   const KvMove m = mv[blockIdx.x];
@@ -1057,7 +1087,7 @@ __global__ __launch_bounds__(256) void kv_move_kernel(uint4* __restrict__ kc, ui
   const int64_t lay = (int64_t)l * slots * nkv * max_ctx * row_vec;
   const int64_t s0 = lay + ((int64_t)m.src * nkv + h) * max_ctx * row_vec, d0 = lay + ((int64_t)m.dst * nkv + h) * max_ctx * row_vec;
   const int n = m.len * row_vec;
-  for (int i = threadIdx.x; i < n; i += 256) {
+  for (int i = m.first * row_vec + threadIdx.x; i < n; i += 256) {
     kc[d0 + i] = kc[s0 + i];
     vc[d0 + i] = vc[s0 + i];
   }
@@ -1104,6 +1134,8 @@ struct GraphCtx {
   const LpPlan* lp;
   int beam_k, beam_m, beam_es;        // sl_beam_generate only (0 elsewhere: a beam graph and a greedy graph never share a key)
   float beam_lp;
+  int n_ret;                          // sl_generate only: answers per prompt
+  const DecodeAttn* da;               // ... and, above 1, where the rows keep their K / V (NULL otherwise)
 };
 
 // The capture stream of every device, per thread (a stream belongs to the device that was current when it was made), and the prefetch
@@ -1133,6 +1165,8 @@ static int decode_graph_key(const GraphCtx& g, int B, DecodeGraphKey& key) {
   key.beam_k = g.beam_k; key.beam_m = g.beam_m; key.beam_es = g.beam_es; key.beam_lp = g.beam_lp;
   if (g.lp->on) { key.lp_penalty = g.lp->o.repetition_penalty; key.lp_ngram = g.lp->o.no_repeat_ngram_size; key.lp_min_new = g.lp->o.min_new_tokens; }
   key.scores = g.scores;
+  key.n_ret = g.n_ret;
+  if (g.da) { key.row_slot0 = g.da->row_slot0; key.grouped = g.da->groups ? 1 : 0; key.groups = g.da->groups; }
   return 0;
 }
 
@@ -1173,7 +1207,7 @@ static int decode_graph_get(const GraphCtx& g, int B, Tail&& tail, hipGraphExec_
       pf.main = cap; pf.side = cap2; pf.ev = pev; pf.sink = (uint32_t*)w.tok_pos; pf.on = true;      // (the sink is never written: see the kernel)
       g_prefetch = &pf;
     }
-    int rc = decode_step(m, g.kv, g.next_ids, g.ctx_len, B, g.logits, g.xdec, w, cap, top1, top1 && g.scores);
+    int rc = decode_step(m, g.kv, g.next_ids, g.ctx_len, B, g.logits, g.xdec, w, cap, top1, top1 && g.scores, g.da);
     g_prefetch = nullptr;
     if (pf.on) { const int rj = pf.join(); if (rc == 0) rc = rj; }       // the branch joins the chain before the capture ends
     if (rc == 0) rc = tail(cap, B, top1);
@@ -1193,9 +1227,10 @@ static int decode_graph_get(const GraphCtx& g, int B, Tail&& tail, hipGraphExec_
 // workspace pointer).  Elements are 4 bytes (int32, or float for the two log-probability arrays).  Carve, initial upload, the pulls at a
 // check / compaction / the end, the move of a row into a hole and the push back all walk this list.
 struct RowTable {
-  enum { UNF, CTX, CNT, FIN, NEXT, OUT, CHOICE, LIM, ROW, LPS, LP, NCOL };
+  enum { UNF, CTX, CNT, FIN, NEXT, OUT, CHOICE, LIM, ROW, LPS, LP, PSLOT, PLEN, NCOL };
   // unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, the sampler's drawn tokens, row_limit, row_id (the caller's index of the
-  // sequence a row holds), the repetition penalty's gather scratch, the token log-probabilities
+  // sequence a row holds), the repetition penalty's gather scratch, the token log-probabilities, and — several answers per prompt — the
+  // slot that holds the row's prompt and the positions the row reads from it (0 on the copy path: the row's own slot holds them)
   static constexpr unsigned bit(int i) { return 1u << i; }
   static constexpr unsigned ALL = (1u << NCOL) - 1;
   struct Col {
@@ -1206,12 +1241,13 @@ struct RowTable {
     std::vector<unsigned char> host;
   };
   Col col[NCOL];
-  RowTable(int B0, int max_new, bool limits, bool penalty, bool scores) {
+  RowTable(int B0, int max_new, bool limits, bool penalty, bool scores, bool prefixes) {
     for (int i : {OUT, LPS, LP}) col[i].row_bytes = (size_t)max_new * 4;
     col[CHOICE].on = col[LPS].on = false;
     col[LIM].on = limits;
     col[LPS].carved = penalty;
     col[LP].carved = col[LP].on = scores;
+    for (int i : {PSLOT, PLEN}) col[i].carved = col[i].on = prefixes;      // carved only with several answers per prompt: the layout without them is unchanged
     for (auto& a : col)
       if (a.on) a.host.assign((size_t)B0 * a.row_bytes, 0);
   }
@@ -1241,33 +1277,91 @@ struct RowTable {
   int init(const int32_t* limits, int B0, hipStream_t st) {
     for (int b = 0; b < B0; ++b) { h<int32_t>(UNF)[b] = 1; h<int32_t>(ROW)[b] = b; }
     if (limits) memcpy(h<int32_t>(LIM), limits, (size_t)B0 * 4);
-    SL_TRY(push(bit(UNF) | bit(CNT) | bit(FIN) | bit(LIM) | bit(ROW), B0, st));
+    SL_TRY(push(bit(UNF) | bit(CNT) | bit(FIN) | bit(LIM) | bit(ROW) | bit(PSLOT) | bit(PLEN), B0, st));
     for (int i : {OUT, LP})
       if (col[i].on) SL_HIP(hipMemsetAsync(col[i].dev, 0, (size_t)B0 * col[i].row_bytes, st));
     return 0;
   }
 };
 
+// fp32 logits row s of `src` (nseq rows) -> rows s * N .. s * N + N - 1 of `dst`: grid (ceil(V / 1024), nseq * N)
+__global__ __launch_bounds__(256) void logits_fanout_kernel(const float* __restrict__ src, float* __restrict__ dst, int V, int N) {
+  const int b = blockIdx.y;
+  const float* s = src + (int64_t)(b / N) * V;
+  float* d = dst + (int64_t)b * V;
+  for (int i = blockIdx.x * 1024 + threadIdx.x; i < V && i < (int)(blockIdx.x + 1) * 1024; i += 256) d[i] = s[i];
+}
+
+// SL_GEN_GROUP_ATTN = -1: where a decode step with the grouped attention was measured no slower than with the prompt rows copied to every
+// row slot (tools/bench_sample_n.py, profiles/sample_n_ab.txt; Llama-3.2-3B, bf16, 137-row prompts, N = 4): 16-bit K / V rows
+// from 256 rows up (4.87 against 4.99 ms per step at 256 rows, 11.29 against 12.04 at 1 024; 3.02 against 2.84 at 64: two launches per
+// layer against one, both launch-bound).  Never on e4m3 rows: 1.01-1.08 of the copy path's step at every row count measured — half the
+// bytes to save, the same two launches.
+static bool gen_group_attn_rule(int rows, int kv_format) { return kv_format == SL_KV_MODEL_DTYPE && rows >= 256; }
+
+// what generate_impl carves behind the row table when N > 1 (one list for the size query and the carve)
+struct SampleNWs {
+  sl_attn_group* groups;      // B0 records
+  void* gws;                  // the grouped attention's (row, head) records
+  float* logits_stage;        // the prefill's nseq logits rows, fanned out to the B0 rows' buffer
+  KvMove* fan;                // the copy path's prompt -> row slot moves
+  void carve(Carver& c, const sl_llama_model* m, int nseq, int B0) {
+    groups = (sl_attn_group*)c.take((size_t)B0 * sizeof(sl_attn_group));
+    gws = c.take(sl_attn_decode_grouped_workspace_bytes(B0, m->n_heads));
+    logits_stage = (float*)c.take((size_t)nseq * m->vocab * sizeof(float));
+    fan = (KvMove*)c.take((size_t)B0 * sizeof(KvMove));
+  }
+};
+
+static thread_local int g_last_attn_path = 0;
+extern "C" int32_t sl_generate_last_attn_path(void) { return g_last_attn_path; }
+
+extern "C" size_t sl_generate_workspace_bytes_n(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int32_t max_new_tokens, const sl_logits_opts* lp,
+                                                int32_t scores, int32_t num_return_sequences) {
+  const int N = num_return_sequences;
+  if (N == 1) return sl_generate_workspace_bytes_sc(m, n_tok, nseq, max_new_tokens, lp, scores);
+  if (!m || N < 1 || nseq <= 0 || (int64_t)nseq * N > SL_MAX_DECODE_BATCH) {
+    sl_set_error("sl_generate_workspace_bytes_n: nseq %d x num_return_sequences %d rows outside (0, %d]", nseq, N, SL_MAX_DECODE_BATCH);
+    return 0;
+  }
+  const int B0 = nseq * N;
+  size_t a = sl_generate_workspace_bytes_sc(m, n_tok, B0, max_new_tokens, lp, scores);      // every per-row piece, for B0 rows
+  a += 2 * ((size_t)B0 * sizeof(int32_t) + 256);                                                // the row table's prefix_slot / prefix_len
+  Carver c(nullptr, 0);
+  SampleNWs sw;
+  sw.carve(c, m, nseq, B0);
+  return a + c.off + 512;
+}
+
 static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
                          const sl_generate_opts* o, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
-                         sl_stream stream, const sl_logits_opts* lp_opts = nullptr, float* out_lp_host = nullptr) {
+                         sl_stream stream, const sl_logits_opts* lp_opts = nullptr, float* out_lp_host = nullptr, int N = 1) {
   SL_CHECK_ARG(o != nullptr, "sl_generate: null options");
   SL_TRY(sl_logits_opts_check("sl_generate", lp_opts, o->max_new_tokens));
   SL_TRY(llama_check(m, kv));
+  // several answers per prompt: refused before anything is launched
+  SL_CHECK_ARG(N >= 1, "sl_generate_n: num_return_sequences %d < 1", N);
+  if (N > 1) {
+    SL_CHECK_ARG(o->sample != 0, "sl_generate_n: num_return_sequences %d > 1 needs sample = 1 (greedy answers of one prompt are all the same)", N);
+    SL_CHECK_ARG(nseq > 0 && (int64_t)nseq * N <= SL_MAX_DECODE_BATCH, "sl_generate_n: nseq %d x num_return_sequences %d decode rows outside (0, %d]", nseq, N,
+                 SL_MAX_DECODE_BATCH);
+    SL_CHECK_ARG((int64_t)kv->slots >= (int64_t)nseq * (N + 1), "sl_generate_n: kv->slots %d < nseq * (num_return_sequences + 1) = %lld (nseq prompt slots + a slot per row)",
+                 kv->slots, (long long)nseq * (N + 1));
+  }
   // use_eos = 0: the EOS ids are ignored even when the caller left them in the struct — rows then finish on their budgets only
   const int max_new_tokens = o->max_new_tokens, n_eos = o->use_eos ? o->n_eos : 0, pad_id = o->pad_id;
   const int32_t* eos_ids_host = o->eos_ids_host;
   const int use_eos = (o->use_eos || o->row_limits_host) ? 1 : 0;       // per-row budgets finish rows the way EOS does
   SL_CHECK_ARG(x && cu_seqlens_host && out_ids_host && workspace && nseq > 0 && nseq <= SL_MAX_DECODE_BATCH && max_new_tokens > 0,
                "sl_generate: bad arguments (nseq<=%d)", SL_MAX_DECODE_BATCH);
-  SL_TRY(llama_wdec_check("sl_generate", m, nseq));      // compaction only moves down the row ladder: a call that starts within the e4m3 range stays within it
+  const int B0 = nseq * N;         // decode rows: row s * N + j is answer j of prompt s
+  SL_TRY(llama_wdec_check("sl_generate", m, B0));      // compaction only moves down the row ladder: a call that starts within the e4m3 range stays within it
   SL_CHECK_ARG(n_eos >= 0 && n_eos <= 8 && (n_eos == 0 || eos_ids_host != nullptr), "sl_generate: 0..8 eos ids");
   SampleOpts smp_s{o->temperature, o->top_k, o->top_p, o->seed};
   const SampleOpts* smp = o->sample ? &smp_s : nullptr;
   if (smp) SL_CHECK_ARG(smp->temperature > 0.f && smp->top_p > 0.f && smp->top_p <= 1.0f && smp->top_k >= 0, "sl_generate: sampling needs temperature > 0, 0 < top_p <= 1, top_k >= 0");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n_tok = cu_seqlens_host[nseq];
-  const int B0 = nseq;
   for (int s = 0; s < nseq; ++s)
     SL_CHECK_ARG(cu_seqlens_host[s + 1] - cu_seqlens_host[s] + max_new_tokens <= kv->max_ctx,
                  "sl_generate: prompt %d (%d tokens) + %d new tokens exceeds max_ctx %d", s,
@@ -1276,21 +1370,44 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
     SL_CHECK_ARG(kv->shared_prefix <= cu_seqlens_host[s + 1] - cu_seqlens_host[s], "sl_generate: kv cache shared_prefix %d exceeds prompt %d (%d tokens)",
                  kv->shared_prefix, s, cu_seqlens_host[s + 1] - cu_seqlens_host[s]);
   if (o->row_limits_host)
-    for (int s = 0; s < nseq; ++s)
+    for (int s = 0; s < B0; ++s)
       SL_CHECK_ARG(o->row_limits_host[s] >= 1 && o->row_limits_host[s] <= max_new_tokens, "sl_generate: row limit %d of sequence %d outside [1, max_new_tokens=%d]",
                    o->row_limits_host[s], s, max_new_tokens);
   const LpPlan lp = lp_plan(lp_opts, n_eos);
   const int scores = out_lp_host ? 1 : 0;
-  SL_CHECK_ARG(sl_generate_workspace_bytes_sc(m, n_tok, nseq, max_new_tokens, lp.on ? &lp.o : nullptr, scores) <= workspace_bytes,
+  SL_CHECK_ARG(sl_generate_workspace_bytes_n(m, n_tok, nseq, max_new_tokens, lp.on ? &lp.o : nullptr, scores, N) <= workspace_bytes,
                "sl_generate: workspace %zu B < required %zu B", workspace_bytes,
-               sl_generate_workspace_bytes_sc(m, n_tok, nseq, max_new_tokens, lp.on ? &lp.o : nullptr, scores));
+               sl_generate_workspace_bytes_n(m, n_tok, nseq, max_new_tokens, lp.on ? &lp.o : nullptr, scores, N));
+  // N > 1: prompts in slots [0, nseq), rows from slot nseq on.  Grouped: a row reads its prompt from the prompt slot; copy: from its own slot
+  DecodeAttn da;
+  da.row_slot0 = N > 1 ? nseq : 0;
+  const int rep_heads = m->n_kv_heads > 0 ? m->n_heads / m->n_kv_heads : 0;
+  const bool grouped = N > 1 && sl_attn_decode_grouped_built(m->n_heads, m->n_kv_heads, m->head_dim, m->dtype, kv->reserved) &&
+                       (sl_env().gen_group_attn == 1 || (sl_env().gen_group_attn < 0 && gen_group_attn_rule(B0, kv->reserved)));
+  g_last_attn_path = N == 1 ? 0 : (grouped ? 2 : 1);
   // carve: generation state first, then the prefill/decode scratch
   Carver c(workspace, workspace_bytes);
   float* logits = (float*)c.take((size_t)B0 * m->vocab * sizeof(float));
   void* xdec = c.take((size_t)B0 * m->hidden * sl_dtype_size(m->dtype));
   using RT = RowTable;
-  RT tab(B0, max_new_tokens, o->row_limits_host != nullptr, lp.penalty, scores != 0);
+  RT tab(B0, max_new_tokens, o->row_limits_host != nullptr, lp.penalty, scores != 0, N > 1);
   tab.carve(c, B0);
+  SampleNWs sn{};
+  std::vector<int32_t> ctx0;
+  std::vector<KvMove> fan;
+  std::vector<sl_attn_group> recs;
+  if (N > 1) {
+    sn.carve(c, m, nseq, B0);
+    ctx0.resize(B0); recs.resize(B0);
+    for (int b = 0; b < B0; ++b) {
+      const int s = b / N, len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
+      ctx0[b] = len;
+      tab.h<int32_t>(RT::PSLOT)[b] = s;
+      tab.h<int32_t>(RT::PLEN)[b] = grouped ? len : 0;
+      if (!grouped) fan.push_back(KvMove{s, nseq + b, len, 0});
+    }
+    if (grouped) { da.groups = sn.groups; da.prefix_len = tab.d<int32_t>(RT::PLEN); da.gws = sn.gws; }
+  }
   c.take(0);
   void* scratch = bptr(workspace) + c.off;
   const size_t scratch_bytes = workspace_bytes - c.off;
@@ -1302,7 +1419,25 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   Events3 ev;
   SL_TRY(ev.create());
   SL_HIP(hipEventRecord(ev.e[0], st));
-  SL_TRY(sl_llama_prefill(m, kv, x, cu_seqlens_host, nseq, logits, rs.ctx_len, nullptr, scratch, scratch_bytes, stream));
+  SL_TRY(sl_llama_prefill(m, kv, x, cu_seqlens_host, nseq, N > 1 ? sn.logits_stage : logits, rs.ctx_len, nullptr, scratch, scratch_bytes, stream));
+  const int kv_row_vec = (int)(m->head_dim * kv_elem_bytes(m, kv) / 16);
+  if (N > 1) {
+    // each prompt was prefilled once: its logits row and its length go to its N rows; then either the group records (grouped) or a
+    // copy of its K / V rows to the N row slots (sources below nseq, destinations from nseq on: disjoint)
+    hipLaunchKernelGGL(logits_fanout_kernel, dim3((m->vocab + 1023) / 1024, B0), dim3(256), 0, st, sn.logits_stage, logits, m->vocab, N);
+    SL_CHECK_LAUNCH("logits_fanout");
+    SL_HIP(hipMemcpyAsync(rs.ctx_len, ctx0.data(), (size_t)B0 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (grouped) {
+      int32_t n_used = 0;
+      SL_TRY(sl_attn_group_plan_host(tab.h<int32_t>(RT::PSLOT), tab.h<int32_t>(RT::PLEN), B0, rep_heads, recs.data(), &n_used));
+      SL_HIP(hipMemcpyAsync(sn.groups, recs.data(), (size_t)B0 * sizeof(sl_attn_group), hipMemcpyHostToDevice, st));
+    } else {
+      SL_HIP(hipMemcpyAsync(sn.fan, fan.data(), fan.size() * sizeof(KvMove), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(kv_move_kernel, dim3((unsigned)fan.size(), m->n_layers * m->n_kv_heads), dim3(256), 0, st, (uint4*)kv->k_cache, (uint4*)kv->v_cache,
+                         sn.fan, m->n_kv_heads, kv->slots, kv->max_ctx, kv_row_vec);
+      SL_CHECK_LAUNCH("kv_move (prompt fan-out)");
+    }
+  }
   // With a processor on, every step — this first one included — is lm_head -> fp32 logits -> sl_logits_process -> select.  The history is
   // the row's own output ids (out_ids, gen_count): both move with the row at a compaction, so nothing else does.
   auto select = [&](int B, hipStream_t s_) -> int {
@@ -1326,6 +1461,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   g.logits = logits; g.xdec = xdec; g.next_ids = rs.next_ids; g.ctx_len = rs.ctx_len; g.st = st;
   g.B0 = B0; g.max_new = max_new_tokens; g.use_eos = use_eos; g.n_eos = n_eos; g.pad = pad_id; g.eos = eos_ids_host; g.lp = &lp; g.smp = smp;
   g.pin_rows = (o->compact && use_eos && sl_env().compact_pin) ? B0 : 0; g.limits = rs.row_limit ? 1 : 0; g.scores = scores;
+  g.n_ret = N; g.da = N > 1 ? &da : nullptr;
   // behind the lm_head: the select above, or — top1: the lm_head left per-group maxima — the pass that reads 1/64 of the bytes
   auto tail = [&](hipStream_t cap, int B, bool top1) -> int {
     if (!top1) return select(B, cap);
@@ -1379,21 +1515,25 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
       for (int r = rung; r < B; ++r) {
         if (h_unf[r] == 0) continue;
         while (h_unf[hole] != 0) ++hole;          // exists: at most `rung` rows are live
-        moves.push_back(KvMove{r, hole, tab.h<int32_t>(RT::CTX)[r], 0});
+        moves.push_back(KvMove{da.row_slot0 + r, da.row_slot0 + hole, tab.h<int32_t>(RT::CTX)[r], N > 1 ? tab.h<int32_t>(RT::PLEN)[r] : 0});
         tab.move(hole, r);
         ++hole;
       }
       if (!moves.empty()) {
-        const int row_vec = (int)(m->head_dim * kv_elem_bytes(m, kv) / 16);
         KvMove* mv_dev = (KvMove*)logits;         // the logits buffer is idle between steps (>= B0 * vocab floats)
         SL_CHECK_ARG(moves.size() * sizeof(KvMove) <= (size_t)B0 * m->vocab * sizeof(float), "sl_generate: move list does not fit");
         SL_HIP(hipMemcpyAsync(mv_dev, moves.data(), moves.size() * sizeof(KvMove), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(kv_move_kernel, dim3((unsigned)moves.size(), m->n_layers * m->n_kv_heads), dim3(256), 0, st, (uint4*)kv->k_cache, (uint4*)kv->v_cache,
-                           mv_dev, m->n_kv_heads, kv->slots, kv->max_ctx, row_vec);
+                           mv_dev, m->n_kv_heads, kv->slots, kv->max_ctx, kv_row_vec);
         SL_CHECK_LAUNCH("kv_move");
       }
       B = rung;
       SL_TRY(tab.push(RT::ALL, B, st));
+      if (grouped) {      // the rows moved: their records are planned again over the rung's rows
+        int32_t n_used = 0;
+        SL_TRY(sl_attn_group_plan_host(tab.h<int32_t>(RT::PSLOT), tab.h<int32_t>(RT::PLEN), B, rep_heads, recs.data(), &n_used));
+        SL_HIP(hipMemcpyAsync(sn.groups, recs.data(), (size_t)B * sizeof(sl_attn_group), hipMemcpyHostToDevice, st));
+      }
       SL_HIP(hipStreamSynchronize(st));           // the host arrays above are reused / the move list is overwritten by the next step's logits
       SL_TRY(decode_graph_get(g, B, tail, &exec));
       ++compactions;
@@ -1444,6 +1584,13 @@ extern "C" int sl_generate_sc(const sl_llama_model* m, const sl_kv_cache* kv, vo
                               const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
                               sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host) {
   return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream, lp, out_logprobs_host);
+}
+
+extern "C" int sl_generate_n(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                             const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
+                             sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host, int32_t num_return_sequences) {
+  return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream, lp, out_logprobs_host,
+                       num_return_sequences);
 }
 
 static int generate_compat(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq, sl_generate_opts& o,

@@ -66,8 +66,12 @@ class LLMSpeechTextInference():
             raise L.SpeechLLMError("weight_dtype differs from the decode-weight format of the llm that was passed in: construct that llm with the same weight_dtype")
         self.llm = llm.eval().to(self.device)
         # runtime.num_beams / length_penalty / early_stopping of the config (absent in the shipped yamls: greedy) -> beam search
-        from .config import runtime_beams, runtime_logits
+        from .config import runtime_beams, runtime_logits, runtime_num_return
         self.beams = runtime_beams(self.config)
+        # runtime.num_return_sequences (absent in the shipped yamls: 1) -> that many SAMPLED answers per utterance, prompt-major
+        self.num_return_sequences = runtime_num_return(self.config)
+        if self.num_return_sequences > 1 and self.beams:
+            raise ValueError("runtime.num_return_sequences > 1 with runtime.num_beams > 1 (beam sampling) is not built")
         # runtime.repetition_penalty / no_repeat_ngram_size / min_new_tokens (absent in the shipped yamls: off) -> HF's logits processors
         self.logits = runtime_logits(self.config)
 
@@ -89,11 +93,20 @@ class LLMSpeechTextInference():
             out.append(sum(lp[:n]) / max(n, 1))
         return out
 
+    def _num_return(self, num_return_sequences) -> int:
+        r = int(getattr(self, "num_return_sequences", 1) if num_return_sequences is None else num_return_sequences)
+        if r < 1:
+            raise ValueError(f"num_return_sequences={r}: must be >= 1")
+        return r
+
     def generate_llm_response(self, inputs_embeds, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None,
-                              return_scores=False):
+                              return_scores=False, num_return_sequences=None):
         """return_scores=True: (texts, scores), one mean token log-probability per answer over its generated length (llm.generate with
-        output_scores; not with beam search)."""
+        output_scores; not with beam search).  num_return_sequences=R > 1 (None: runtime.num_return_sequences): R sampled answers per
+        prompt, prompt-major (llm.generate with do_sample=True)."""
         kw = dict(self.beams or {}, **self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens))
+        if self._num_return(num_return_sequences) > 1:
+            kw.update(do_sample=True, num_return_sequences=self._num_return(num_return_sequences))
         if return_scores:
             res = self.llm.generate(input_ids=None, inputs_embeds=inputs_embeds, max_new_tokens=max_new_tokens, return_dict_in_generate=True,
                                     output_scores=True, **kw)
@@ -112,7 +125,9 @@ class LLMSpeechTextInference():
         return self.generate_llm_response(inputs_embeds=prompt_embeds, max_new_tokens=max_new_tokens)[0]
 
     def generate_audio_response(self, audio, additional_text_prompt="", max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None,
-                                min_new_tokens=None, return_scores=False):
+                                min_new_tokens=None, return_scores=False, num_return_sequences=None):
+        """num_return_sequences=R > 1 (None: runtime.num_return_sequences): the list of R sampled answers (and, with return_scores, the
+        list of their scores) instead of one answer."""
         audio_tensor = torch.as_tensor(audio, dtype=torch.float32).unsqueeze(0).to(self.device)
         if self.audio_encoder.downsample_method == "ctc_pool":
             # the reference calls an undefined self.get_ctc_pool_ranges here (SURVEY.md §9 Q2)
@@ -132,10 +147,12 @@ class LLMSpeechTextInference():
         prompt_emb_sequence = merge_prompt_tokens(inputs_embeds=combined_embeds, tokenizer=self.llm_tokenizer,
                                                   embed_tokens=self.llm.model.embed_tokens, llm_type=self.llm_type,
                                                   device=self.device)
+        R = self._num_return(num_return_sequences)
         if return_scores:
-            texts, scores = self.generate_llm_response(prompt_emb_sequence, max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens, True)
-            return texts[0], scores[0]
-        return self.generate_llm_response(prompt_emb_sequence, max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens)[0]
+            texts, scores = self.generate_llm_response(prompt_emb_sequence, max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens, True, R)
+            return (texts, scores) if R > 1 else (texts[0], scores[0])
+        texts = self.generate_llm_response(prompt_emb_sequence, max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens, False, R)
+        return texts if R > 1 else texts[0]
 
     def _whisper_audio_embeds(self, audio) -> torch.Tensor:
         """Whisper base (ref:config/llama3_whisper.yaml).  ref:inference.py:97-107 hands the raw waveform to the Whisper encoder,
@@ -151,8 +168,10 @@ class LLMSpeechTextInference():
         return padded[:, :keep]
 
     def generate_audio_responses(self, audios, additional_text_prompts=None, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None,
-                                 min_new_tokens=None, return_scores=False):
+                                 min_new_tokens=None, return_scores=False, num_return_sequences=None):
         """return_scores=True: (texts, scores), one mean token log-probability per answer; chunks are concatenated in order.
+        num_return_sequences=R > 1 (None: runtime.num_return_sequences): R sampled answers per utterance from one prefill of each
+        (generate_packed num_return), returned prompt-major: answer j of utterance i is entry i * R + j.
         Batched form of generate_audio_response (an extension: the reference answers one utterance per call).
         Every utterance is encoded and prefilled at its own length in ONE ragged batch — the encoder writes its embeddings
         straight into the packed prompt buffer `[prefix | text[1:] | audio | suffix[1:]]` — and decoded together, so that the
@@ -164,17 +183,24 @@ class LLMSpeechTextInference():
         texts = list(additional_text_prompts) if additional_text_prompts is not None else [""] * n
         if len(texts) != n:
             raise ValueError(f"{len(texts)} text prompts for {n} utterances")
+        R = self._num_return(num_return_sequences)
+        if R > 1 and self.beams:
+            raise L.SpeechLLMError("num_return_sequences > 1 with beam search (beam sampling) is not built")
         if self.audio_encoder.downsample_method != "pool":       # stack / ctc_pool: the one-utterance path (ctc_pool raises as the reference does)
-            res = [self.generate_audio_response(a, texts[i], max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens, return_scores)
+            res = [self.generate_audio_response(a, texts[i], max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens, return_scores, R)
                    for i, a in enumerate(audios)]
+            if R > 1:      # each entry is a list of R answers (or a pair of lists): flattened prompt-major
+                return ([t for r in res for t in r[0]], [v for r in res for v in r[1]]) if return_scores else [t for r in res for t in r]
             return ([r[0] for r in res], [r[1] for r in res]) if return_scores else res
         out: List[str] = []
         ids_all = []
         scores_all: List[float] = []
-        chunk = L.MAX_DECODE_BATCH // (self.beams["num_beams"] if self.beams else 1)      # a generate call is sized by its decode ROWS: utterances x beams
+        chunk = L.MAX_DECODE_BATCH // (self.beams["num_beams"] if self.beams else R)      # a generate call is sized by its decode ROWS: utterances x beams (or answers)
+        if chunk < 1:
+            raise L.SpeechLLMError(f"num_return_sequences={R} exceeds the {L.MAX_DECODE_BATCH} decode rows of one generate call")
         for lo_ in range(0, n, chunk):
             ids = self._generate_chunk(audios[lo_:lo_ + chunk], texts[lo_:lo_ + chunk], max_new_tokens,
-                                       self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens), return_scores)
+                                       self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens), return_scores, R)
             if return_scores:
                 ids, lps = ids
                 scores_all += self._mean_logprobs(ids, lps)
@@ -189,8 +215,9 @@ class LLMSpeechTextInference():
         self.last_generate_ids = torch.cat([torch.nn.functional.pad(i, (0, width - int(i.shape[1])), value=int(pad)) for i in ids_all]) if ids_all else None
         return (out, scores_all) if return_scores else out
 
-    def _generate_chunk(self, audios, texts, max_new_tokens, logits=None, scores=False):
-        """One generate call's worth of utterances -> LongTensor (n, n_cols) of new tokens (scores: and their (n, n_cols) log-probabilities)."""
+    def _generate_chunk(self, audios, texts, max_new_tokens, logits=None, scores=False, num_return=1):
+        """One generate call's worth of utterances -> LongTensor (n, n_cols) of new tokens (scores: and their (n, n_cols) log-probabilities).
+        num_return = R > 1: (n * R, n_cols), R answers per utterance sampled with the llm's generation_config warpers."""
         from .utils import compute_num_audio_embeds, prompt_template
         n = len(audios)
         emb = self.llm.model.embed_tokens
@@ -232,9 +259,15 @@ class LLMSpeechTextInference():
         shared = int(pre_e.shape[0])
         if txt_e[0] is not None and all(t_ == texts[0] for t_ in texts):
             shared += int(txt_e[0].shape[0])
+        sample = None
+        if num_return > 1:      # several answers are sampled ones: HF's warpers as llm.generate builds them
+            g = self.llm.generation_config
+            seed, self.llm.sample_seed = self.llm.sample_seed, self.llm.sample_seed + 1
+            sample = dict(temperature=float(g.temperature), top_k=int(g.top_k), top_p=float(g.top_p), seed=int(seed))
         if scores:
             ids, n_cols, lps = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None,
-                                                        scores=True)
+                                                        scores=True, sample=sample, num_return=num_return)
             return ids[:, :n_cols].to(torch.int64), lps[:, :n_cols]
-        ids, n_cols = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None)
+        ids, n_cols = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None,
+                                               sample=sample, num_return=num_return)
         return ids[:, :n_cols].to(torch.int64)

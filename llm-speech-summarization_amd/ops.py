@@ -421,6 +421,34 @@ def attn_decode_split_ex(q, q_stride, k_cache, v_cache, ctx_len, n_heads, n_kv, 
     return out
 
 
+def attn_group_plan(prefix_slot: Sequence[int], prefix_len: Sequence[int], rep: int):
+    """sl_attn_group_plan_host (pure host): -> (list of B (prefix_slot, prefix_len, [rows]) records, n_used, the ctypes array)."""
+    B = len(prefix_slot)
+    recs = (L.AttnGroup * max(B, 1))()
+    n_used = C.c_int32(0)
+    L.check(L.lib().sl_attn_group_plan_host((C.c_int32 * max(B, 1))(*[int(v) for v in prefix_slot]), (C.c_int32 * max(B, 1))(*[int(v) for v in prefix_len]),
+                                            B, int(rep), recs, C.byref(n_used)), "sl_attn_group_plan_host")
+    out = [(int(r.prefix_slot), int(r.prefix_len), [int(r.rows[i]) for i in range(int(r.n_rows))]) for r in recs[:B]]
+    return out, int(n_used.value), recs
+
+
+def attn_decode_grouped(q, q_stride, k_cache, v_cache, ctx_len, prefix_slot: Sequence[int], prefix_len: Sequence[int], row_slot0: int, n_heads, n_kv, D,
+                        max_ctx, scale, kv_format: int = L.KV_MODEL_DTYPE, out=None) -> torch.Tensor:
+    """Decode attention of rows that share prompts (sl_attn_decode_grouped): row b attends [0, prefix_len[b]) of slot prefix_slot[b] and
+    [prefix_len[b], ctx_len[b]) of slot row_slot0 + b.  prefix_slot / prefix_len are host sequences: the records are planned here."""
+    B = ctx_len.shape[0]
+    if out is None:
+        out = torch.empty((B, n_heads * D), device=q.device, dtype=q.dtype)
+    _, _, recs = attn_group_plan(prefix_slot, prefix_len, n_heads // n_kv)
+    groups = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.int32).to(q.device)
+    plen = torch.tensor([int(v) for v in prefix_len], dtype=torch.int32).to(q.device)
+    ws = torch.empty(int(L.lib().sl_attn_decode_grouped_workspace_bytes(B, n_heads)), dtype=torch.uint8, device=q.device)
+    L.check(L.lib().sl_attn_decode_grouped(L.ptr(q), q_stride, L.ptr(k_cache), L.ptr(v_cache), L.ptr(out), L.ptr(ws), L.ptr(ctx_len), L.ptr(plen),
+                                           L.ptr(groups), B, int(row_slot0), n_heads, n_kv, D, max_ctx, scale, L.dtype_code(q.dtype), int(kv_format),
+                                           L.stream_ptr()), "sl_attn_decode_grouped")
+    return out
+
+
 def kv_cache_bytes(model_struct, slots: int, max_ctx: int, kv_format: int = L.KV_MODEL_DTYPE) -> int:
     """Bytes of ONE of the two caches (sl_kv_cache_bytes); raises where the library refuses the combination."""
     n = int(L.lib().sl_kv_cache_bytes(C.byref(model_struct), int(slots), int(max_ctx), int(kv_format)))
