@@ -297,6 +297,28 @@ int sl_posconv_stage_batch(const void* x, void* xg, const int32_t* cu, const int
 int sl_avgpool_batch(const void* x, void* y, const int32_t* cu, const int32_t* klen, const int64_t* rec, int32_t n_utt, int64_t max_P,
                      int32_t H, int32_t kernel, int32_t stride, int32_t dtype, sl_stream stream);
 
+/* The other two downsamples of the reference (ref:model/audio_encoder.py:65-85) on a packed ragged batch, one launch each, fp32 / bf16 / fp16,
+ * fp32 accumulation, 16-byte accesses (H a multiple of 4 in fp32, 8 in 16 bits), no atomics, device tables only (additive to ABI 7).
+ *   sl_segment_mean_batch (ctc_pool): ranges_dev = int64 (n_ranges, 2) records {first row, end row} in PACKED-row coordinates of x (n_rows, H);
+ *     y[r] = mean of x[first_r .. end_r) (n_ranges, H).  The rows of one range are spread over eight row slices of a block and 32-chunk tiles of H.
+ *   sl_stack_rows_batch (stack): desc_dev = n_utt int64 records {P_u, first frame row of the utterance in x, first stacked row in y, -}; stacked row p
+ *     of y (sum P_u, factor * H) is frames factor p .. factor p + factor - 1 side by side; P_u = T_u / factor (T_u % factor == 0 keeps every frame,
+ *     SURVEY.md section 9 Q5), P_u = 0 gives no rows; max_P sizes the grid (0: nothing to do).
+ * Host side of ctc_pool (no device, no stream):
+ *   sl_segment_ranges_host: utterance-relative (start, end) pairs as the dataset stores them (counts[u] of them for utterance u of frames[u] frames,
+ *     concatenated) -> packed_out records.  Each pair is clamped to the utterance the way a tensor slice clamps it (a negative position counts from the
+ *     end); a pair that is empty afterwards is SL_ERR_ARG, the message naming the utterance and the range (the reference would average nothing into a
+ *     NaN row there).
+ *   sl_segment_csr_host: the inverse index frame -> covering ranges of a packed table, in CSR form: row_ptr (n_rows + 1) is always written; cols (range
+ *     numbers, those of frame t at row_ptr[t] .. row_ptr[t + 1], in table order) when cols is not NULL and cols_cap >= row_ptr[n_rows] (the sum of the
+ *     lengths).  Ranges may overlap, repeat, be unsorted and leave gaps; one that is empty or leaves [0, n_rows) is SL_ERR_ARG. */
+int sl_segment_mean_batch(const void* x, void* y, const int64_t* ranges_dev, int64_t n_ranges, int64_t n_rows, int32_t H, int32_t dtype,
+                          sl_stream stream);
+int sl_stack_rows_batch(const void* x, void* y, const int64_t* desc_dev, int32_t n_utt, int64_t max_P, int32_t H, int32_t factor, int32_t dtype,
+                        sl_stream stream);
+int sl_segment_ranges_host(const int64_t* ranges_rel, const int32_t* counts, const int64_t* frames, int32_t n_utt, int64_t* packed_out);
+int sl_segment_csr_host(const int64_t* ranges, int64_t n_ranges, int64_t n_rows, int64_t* row_ptr, int32_t* cols, int64_t cols_cap);
+
 /* Embedding row gather (hf:...llama.py:380-381; ref:utils.py:63-64). ids int32 on device. */
 int sl_embed_gather(const void* table, const int32_t* ids, void* out, int64_t n, int32_t cols,
                     int32_t dtype, sl_stream stream);
@@ -571,6 +593,16 @@ int sl_col2im_batch(const void* dcol, void* dx, const int64_t* desc_dev, int32_t
                     int32_t dtype, sl_stream stream);
 int sl_avgpool_bwd_batch(const void* dy, void* dx, const int64_t* desc_dev, int32_t n_utt, int64_t max_T, int32_t H, int32_t kernel,
                          int32_t stride, int32_t dtype, sl_stream stream);
+/* Backward of the ctc_pool / stack downsamples (additive to ABI 7; fp32 / bf16 / fp16).  Every row of dx is written (the caller does no memset), nothing
+ * is accumulated atomically: the result is a function of the tables alone.
+ *   sl_segment_mean_bwd_batch: dx[t] = sum over the ranges r covering frame t of dy[r] / len_r, gathered through the CSR index of sl_segment_csr_host
+ *     (row_ptr_dev int64 (n_rows + 1), cols_dev int32) in table order; frames nothing covers get zeros.
+ *   sl_stack_rows_bwd_batch: desc_dev = n_utt int64 records {P_u, T_u, first stacked row in dy, first frame row in dx}; the T_u % factor cropped frames
+ *     get zeros; max_T sizes the grid. */
+int sl_segment_mean_bwd_batch(const void* dy, void* dx, const int64_t* ranges_dev, const int64_t* row_ptr_dev, const int32_t* cols_dev, int64_t n_ranges,
+                              int64_t n_rows, int32_t H, int32_t dtype, sl_stream stream);
+int sl_stack_rows_bwd_batch(const void* dy, void* dx, const int64_t* desc_dev, int32_t n_utt, int64_t max_T, int32_t H, int32_t factor, int32_t dtype,
+                            sl_stream stream);
 int sl_hubert_conv0_bwd(const float* wave, int64_t n_samples, const float* w, const float* bias, const float* gamma,
                         const float* beta, const void* dy, int32_t C, int32_t k, int32_t stride, float eps, float* dw,
                         float* dbias, float* dgamma, float* dbeta, int32_t dtype, sl_stream stream);
@@ -629,6 +661,33 @@ int sl_hubert_num_frames(const sl_hubert_model* m, int64_t n_samples);
 int sl_hubert_forward(const sl_hubert_model* m, const float* waves, const int64_t* sample_offsets_host, int32_t n_utt,
                       void* out, int64_t out_ld, const int64_t* out_row_offsets_host, void* last_hidden,
                       void* workspace, size_t workspace_bytes, sl_stream stream);
+
+/* The same forward with the `stack` or `ctc_pool` downsample (ref:model/audio_encoder.py:65-85) between the final LayerNorm and the projection (additive
+ * to ABI 7; sl_hubert_forward itself is unchanged and stays the `pool` entry).  The model's own proj_w / proj_b are not read: the projection comes with the
+ * descriptor, since its input width depends on the method.
+ *   stack: utterance u gives P_u = T_u / factor rows; the projection (llm_dim, factor * hidden) reads the frames in place (row stride factor * hidden),
+ *     no copy is made.  ctc_pool: P_u = range_counts_host[u] rows, the means of its ranges (sl_segment_mean_batch), ranges_dev holding the packed-row
+ *     records of all utterances in order (sl_segment_ranges_host); the projection is (llm_dim, hidden).
+ *   Utterance u's P_u rows go to row out_row_offsets_host[u] of out (packed if NULL), as in sl_hubert_forward.
+ * SL_ERR_ARG before any launch: a NULL descriptor / projection / table, a method other than these two, factor < 1, proj_in != factor * hidden (stack) or
+ * != hidden (ctc_pool), range counts that do not add up to n_ranges. */
+#define SL_DS_POOL 0
+#define SL_DS_STACK 1
+#define SL_DS_CTC_POOL 2
+typedef struct {
+  int32_t method;                      /* SL_DS_STACK or SL_DS_CTC_POOL */
+  int32_t factor;                      /* downsample_factor (>= 1; ctc_pool does not read it further) */
+  int32_t proj_in;                     /* input features of the projection */
+  int32_t reserved;
+  int64_t n_ranges;                    /* ctc_pool: records in ranges_dev */
+  const int64_t* ranges_dev;           /* ctc_pool: (n_ranges, 2) {first row, end row} in packed frame rows */
+  const int32_t* range_counts_host;    /* ctc_pool: n_utt counts, adding up to n_ranges */
+  const void *proj_w, *proj_b;         /* embed_projection (llm_dim, proj_in), (llm_dim) */
+} sl_downsample_desc;
+size_t sl_hubert_workspace_bytes_ds(const sl_hubert_model* m, const int64_t* sample_offsets_host, int32_t n_utt, const sl_downsample_desc* ds);
+int sl_hubert_forward_ds(const sl_hubert_model* m, const float* waves, const int64_t* sample_offsets_host, int32_t n_utt, void* out, int64_t out_ld,
+                         const int64_t* out_row_offsets_host, void* last_hidden, const sl_downsample_desc* ds, void* workspace,
+                         size_t workspace_bytes, sl_stream stream);
 
 /* Whisper path (BASELINE configs[3]; ref:model/audio_encoder.py:10-13, ref:trainer.py:168-199, 280-291).
  * sl_whisper_logmel: WhisperFeatureExtractor's torch path (hf:models/whisper/feature_extraction_whisper.py:135-168)

@@ -108,6 +108,15 @@ class HubertModel(C.Structure):
                 ("fold", C.POINTER(HubertFold))]
 
 
+class DownsampleDesc(C.Structure):
+    """sl_downsample_desc: the stack / ctc_pool head of sl_hubert_forward_ds"""
+    _fields_ = [("method", c_i32), ("factor", c_i32), ("proj_in", c_i32), ("reserved", c_i32), ("n_ranges", c_i64), ("ranges_dev", c_vp),
+                ("range_counts_host", C.POINTER(c_i32)), ("proj_w", c_vp), ("proj_b", c_vp)]
+
+
+DS_POOL, DS_STACK, DS_CTC_POOL = 0, 1, 2      # speechllm.h SL_DS_*
+
+
 class LlamaLayer(C.Structure):
     _fields_ = [(n, c_vp) for n in ("norm1", "wqkv", "wo", "norm2", "wgu", "wdown", "wqkv_dec", "wo_dec", "wgu_dec", "wdown_dec")]
 
@@ -342,6 +351,16 @@ _PROTOS = {
     "sl_generate_n": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(GenerateOpts), C.POINTER(c_i32),
                               C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts), C.POINTER(c_f32), c_i32]),
     "sl_generate_last_attn_path": (c_i32, []),
+    # stack / ctc_pool downsampling of ragged batches (additive to ABI 7)
+    "sl_segment_mean_batch": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),
+    "sl_stack_rows_batch": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_vp]),
+    "sl_segment_ranges_host": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "sl_segment_csr_host": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64]),
+    "sl_segment_mean_bwd_batch": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp]),
+    "sl_stack_rows_bwd_batch": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_vp]),
+    "sl_hubert_workspace_bytes_ds": (c_sz, [C.POINTER(HubertModel), C.POINTER(c_i64), c_i32, C.POINTER(DownsampleDesc)]),
+    "sl_hubert_forward_ds": (c_i32, [C.POINTER(HubertModel), c_vp, C.POINTER(c_i64), c_i32, c_vp, c_i64, C.POINTER(c_i64), c_vp, C.POINTER(DownsampleDesc),
+                                     c_vp, c_sz, c_vp]),
     "sl_greedy_generate": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, c_i32,
                                    C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32),
                                    C.POINTER(c_f32), c_vp, c_sz, c_vp]),

@@ -189,11 +189,16 @@ class AudioEncoder:
         return self._ws
 
     def encode_packed(self, waves: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None,
-                      out_row_offsets: Optional[Sequence[int]] = None, want_last_hidden: bool = False):
+                      out_row_offsets: Optional[Sequence[int]] = None, want_last_hidden: bool = False, ctc_pool_ranges=None,
+                      _frames_only: bool = False):
         """Encode utterances of arbitrary lengths.  Returns (out, P_list, last_hidden|None, T_list).
 
         `out` (rows, llm_dim) + `out_row_offsets` let the encoder write each utterance's embeddings
         directly at its place inside a prompt buffer (ref:utils.py:66-72 concatenation becomes a no-op).
+        All three downsample methods take ragged batches: `pool` through sl_hubert_forward, `stack` (P_u = T_u // factor) and `ctc_pool`
+        (P_u = the utterance's number of ranges; `ctc_pool_ranges`: one list of utterance-relative (start, end) per utterance, as the
+        dataset's `pool_ranges_4` holds them) through sl_hubert_forward_ds.  `_frames_only` (forward()'s one-utterance stack / ctc_pool
+        path, which composes the head on the host): stop at last_hidden.
         """
         if self.weights is None:
             raise L.SpeechLLMError("AudioEncoder weights are not on the GPU: call load_state_dict(...).to('cuda')")
@@ -210,13 +215,28 @@ class AudioEncoder:
         n_utt = len(waves)
         T = [self.arch.num_frames(n) for n in lens]
         pool = self.downsample_method == "pool"
-        P = [((t - self.pool_kernel) // self.pool_stride + 1) if pool else 0 for t in T]
+        head = pool or not _frames_only               # the library runs downsample + projection
+        ranges_dev = counts = None
+        if pool:
+            P = [(t - self.pool_kernel) // self.pool_stride + 1 for t in T]
+        elif not head:
+            P = [0] * n_utt
+        elif self.downsample_method == "stack":
+            P = [t // self.downsample_factor for t in T]
+        else:
+            if ctc_pool_ranges is None:
+                raise L.SpeechLLMError("the ctc_pool downsample needs ctc_pool_ranges: one list of (start, end) frame ranges per utterance")
+            packed, counts = ops.segment_ranges_pack(ctc_pool_ranges, T)      # clamped, offset to packed rows; refuses an empty range
+            ranges_dev = L.h2d(packed, torch.int64, self.device)
+            P = list(counts)
         last_hidden = None
-        if want_last_hidden or not pool:
+        if want_last_hidden or not head:
             last_hidden = torch.empty((sum(T), self.arch.hidden_size), device=self.device, dtype=self.dtype)
-        if pool and out is None:
-            out = torch.empty((sum(P), self.llm_dim), device=self.device, dtype=self.dtype)
-        if pool and out_row_offsets is None:
+        spare = None
+        if head and out is None:      # (at least one row allocated: a batch of utterances too short for one stacked row still hands the library a buffer)
+            spare = torch.empty((max(sum(P), 1), self.llm_dim), device=self.device, dtype=self.dtype)
+            out = spare[:sum(P)]
+        if head and out_row_offsets is None:
             out_row_offsets, acc_rows = [], 0
             for p_ in P:
                 out_row_offsets.append(acc_rows)
@@ -226,7 +246,7 @@ class AudioEncoder:
         # per 2 560 audio-seconds), and 1 024 x 10 s in one call would hold ~75 GB of it for no gain — the GEMMs of a 256-utterance
         # group already have 128 k rows.
         limit = int(getattr(self, "max_samples_per_call", 256 * 160000))
-        t_row = 0
+        t_row = r_row = 0
         start = 0
         while start < n_utt:
             end = start + 1
@@ -234,12 +254,33 @@ class AudioEncoder:
                 end += 1
             n_c = end - start
             offs_c = (C.c_int64 * (n_c + 1))(*[o - offs[start] for o in offs[start:end + 1]])
+            rows_c = (C.c_int64 * n_c)(*[int(r) for r in out_row_offsets[start:end]]) if head else None
+            lh_ptr = (last_hidden.data_ptr() + t_row * last_hidden.stride(0) * last_hidden.element_size()) if last_hidden is not None else None
+            if head and not pool:      # stack / ctc_pool: final LayerNorm -> downsample -> projection inside the library, rows written at rows_c
+                ds = L.DownsampleDesc()
+                w_ = self.weights
+                ds.factor, ds.proj_in, ds.proj_w, ds.proj_b = int(self.downsample_factor), int(w_.proj_w.shape[1]), w_.proj_w.data_ptr(), w_.proj_b.data_ptr()
+                if counts is None:
+                    ds.method = L.DS_STACK
+                else:      # this call's slice of the table, rebased to its first frame row
+                    n_r = sum(counts[start:end])
+                    cnt_c = (C.c_int32 * n_c)(*counts[start:end])
+                    tab = ranges_dev[r_row:r_row + n_r] - t_row if t_row else ranges_dev[r_row:r_row + n_r]
+                    ds.method, ds.n_ranges, ds.ranges_dev, ds.range_counts_host = L.DS_CTC_POOL, n_r, (tab.data_ptr() if n_r else None), cnt_c
+                    r_row += n_r
+                nbytes = lib.sl_hubert_workspace_bytes_ds(C.byref(m), offs_c, n_c, C.byref(ds))
+                if nbytes == 0:
+                    raise L.SpeechLLMError("sl_hubert_workspace_bytes_ds: " + lib.sl_last_error().decode())
+                ws = self._workspace(nbytes)
+                L.check(lib.sl_hubert_forward_ds(C.byref(m), flat.data_ptr() + offs[start] * 4, offs_c, n_c, L.ptr(out) or L.ptr(spare), out.stride(0), rows_c, lh_ptr,
+                                                 C.byref(ds), ws.data_ptr(), ws.numel(), L.stream_ptr()), "sl_hubert_forward_ds")
+                t_row += sum(T[start:end])
+                start = end
+                continue
             nbytes = lib.sl_hubert_workspace_bytes(C.byref(m), offs_c, n_c)
             if nbytes == 0:
                 raise L.SpeechLLMError("sl_hubert_workspace_bytes: " + lib.sl_last_error().decode())
             ws = self._workspace(nbytes)
-            rows_c = (C.c_int64 * n_c)(*[int(r) for r in out_row_offsets[start:end]]) if pool else None
-            lh_ptr = (last_hidden.data_ptr() + t_row * last_hidden.stride(0) * last_hidden.element_size()) if last_hidden is not None else None
             L.check(lib.sl_hubert_forward(C.byref(m), flat.data_ptr() + offs[start] * 4, offs_c, n_c, L.ptr(out), (out.stride(0) if out is not None else 0),
                                           rows_c, lh_ptr, ws.data_ptr(), ws.numel(), L.stream_ptr()), "sl_hubert_forward")
             t_row += sum(T[start:end])
@@ -284,7 +325,7 @@ class AudioEncoder:
                 raise L.SpeechLLMError("forward() returns a dense (B,P,C) tensor: use encode_packed for ragged batches")
             return out.view(len(waves), P[0], self.llm_dim)
         outs = []
-        _, _, hidden, T = self.encode_packed(waves, want_last_hidden=True)
+        _, _, hidden, T = self.encode_packed(waves, want_last_hidden=True, _frames_only=True)
         t0 = 0
         for t in T:
             outs.append(self._downsample_host(hidden[t0:t0 + t], ctc_pool_ranges))

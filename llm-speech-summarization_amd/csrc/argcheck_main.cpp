@@ -191,6 +191,48 @@ int main() {
   sl_hubert_model wm = hm;
   EXPECT_ARG_ERROR(sl_whisper_forward(&wm, wave, 1, ws, 3072, nullptr, nullptr, ws, sizeof(ws), nullptr));          // not a Whisper struct
 
+  // ---- stack / ctc_pool head: descriptor checks, range clamping and the inverse index are host code
+  {
+    sl_downsample_desc ds;
+    memset(&ds, 0, sizeof(ds));
+    int32_t cnt3[3] = {2, 1, 3};
+    ds.method = SL_DS_STACK; ds.factor = 4; ds.proj_in = 4 * hm.hidden; ds.proj_w = w1; ds.proj_b = w1;
+    EXPECT(sl_hubert_workspace_bytes_ds(&hm, offs, 3, &ds) > 0, "stack workspace");
+    EXPECT_ARG_ERROR(sl_hubert_forward_ds(&hm, wave, offs, 3, ws, 3072, nullptr, nullptr, nullptr, ws, sizeof(ws), nullptr));   // no descriptor
+    ds.factor = 0;
+    EXPECT_ARG_ERROR(sl_hubert_forward_ds(&hm, wave, offs, 3, ws, 3072, nullptr, nullptr, &ds, ws, sizeof(ws), nullptr));       // factor < 1
+    ds.factor = 4; ds.proj_in = hm.hidden;
+    EXPECT_ARG_ERROR(sl_hubert_forward_ds(&hm, wave, offs, 3, ws, 3072, nullptr, nullptr, &ds, ws, sizeof(ws), nullptr));       // width != f H
+    ds.method = SL_DS_CTC_POOL;
+    EXPECT_ARG_ERROR(sl_hubert_forward_ds(&hm, wave, offs, 3, ws, 3072, nullptr, nullptr, &ds, ws, sizeof(ws), nullptr));       // null tables
+    ds.range_counts_host = cnt3; ds.ranges_dev = (const int64_t*)ws; ds.n_ranges = 5;
+    EXPECT_ARG_ERROR(sl_hubert_forward_ds(&hm, wave, offs, 3, ws, 3072, nullptr, nullptr, &ds, ws, sizeof(ws), nullptr));       // counts add up to 6
+    ds.n_ranges = 6;
+    EXPECT(sl_hubert_workspace_bytes_ds(&hm, offs, 3, &ds) > 0, "ctc_pool workspace");
+    EXPECT_ARG_ERROR(sl_hubert_forward_ds(&hm, wave, offs, 3, ws, 3072, nullptr, nullptr, &ds, ws, sizeof(ws), nullptr));       // workspace too small
+    ds.method = SL_DS_POOL;
+    EXPECT_ARG_ERROR(sl_hubert_forward_ds(&hm, wave, offs, 3, ws, 3072, nullptr, nullptr, &ds, ws, sizeof(ws), nullptr));       // pool has its own entry
+    const int64_t rel[12] = {0, 4, 4, 9, -3, 100, 2, 3, 0, 1, 6, 8};
+    const int64_t frames[3] = {5, 49, 8};
+    int64_t packed[12];
+    EXPECT(sl_segment_ranges_host(rel, cnt3, frames, 3, packed) == 0, "ranges pack");
+    EXPECT(packed[2] == 4 && packed[3] == 5 && packed[4] == 5 + 46 && packed[5] == 5 + 49 && packed[10] == 54 + 6 && packed[11] == 54 + 8, "clamped and offset");
+    const int64_t rel_bad[12] = {0, 4, 5, 9, 0, 1, 2, 3, 0, 1, 6, 8};        // (5, 9) of a 5-frame utterance: empty after clamping
+    EXPECT_ARG_ERROR(sl_segment_ranges_host(rel_bad, cnt3, frames, 3, packed));
+    EXPECT(strstr(sl_last_error(), "utterance 0") && strstr(sl_last_error(), "range 1"), "the message names utterance and range");
+    int64_t row_ptr[63];
+    int32_t cols[64];
+    EXPECT(sl_segment_ranges_host(rel, cnt3, frames, 3, packed) == 0 && sl_segment_csr_host(packed, 6, 62, row_ptr, nullptr, 0) == 0, "csr count");
+    EXPECT(row_ptr[62] == 4 + 1 + 3 + 1 + 1 + 2, "csr size");
+    EXPECT_ARG_ERROR(sl_segment_csr_host(packed, 6, 62, row_ptr, cols, 3));            // cols too small
+    EXPECT(sl_segment_csr_host(packed, 6, 62, row_ptr, cols, 64) == 0 && cols[row_ptr[4]] == 0 + 1 && row_ptr[5] - row_ptr[4] == 1, "csr fill");
+    EXPECT_ARG_ERROR(sl_segment_csr_host(packed, 6, 61, row_ptr, nullptr, 0));          // a range past the rows
+    EXPECT_ARG_ERROR(sl_segment_mean_batch(ws, ws, (const int64_t*)ws, 4, 100, 130, SL_BF16, nullptr));                            // H not a multiple of 8
+    EXPECT_ARG_ERROR(sl_segment_mean_bwd_batch(ws, ws, (const int64_t*)ws, nullptr, nullptr, 4, 100, 128, SL_BF16, nullptr));     // no index
+    EXPECT_ARG_ERROR(sl_stack_rows_batch(ws, ws, (const int64_t*)ws, 2, 10, 128, 0, SL_BF16, nullptr));                           // factor < 1
+    EXPECT_ARG_ERROR(sl_stack_rows_bwd_batch(ws, ws, (const int64_t*)ws, 2, 10, 130, 4, SL_F16, nullptr));                        // H not a multiple of 8
+  }
+
   // ---- Llama runtime
   sl_llama_layer ll[28];
   memset(ll, 0, sizeof(ll));

@@ -6,6 +6,9 @@
 //     one contiguous, fully coalesced row write (1 KiB for C=512 bf16).
 //   * posconv_stage: regroup (T,H) -> (groups, T+k, H/groups) with zero halo.
 //   * avgpool_rows: AvgPool1d over time / ctc range mean.
+//   * segment_mean / stack_rows: the ctc_pool and stack downsamples of a whole ragged batch, and ctc_pool's host-side tables.
+#include <vector>
+
 #include "common.h"
 
 template <typename T, int CPL, int K, int STRIDE>
@@ -313,5 +316,138 @@ extern "C" int sl_avgpool_rows(const void* x, void* y, int64_t T_, int32_t H, in
                        ranges, P);
   });
   SL_CHECK_LAUNCH("avgpool_rows");
+  return 0;
+}
+
+// ----------------------------------------------------------------------------------------------
+// ctc_pool / stack downsampling of a packed ragged batch (ref:model/audio_encoder.py:65-85).
+//   * segment_mean: y[r] = mean(x[first_r : end_r]) over packed rows.  One block per (range, tile of 32 16-byte chunks);
+//     its 256 threads are 32 chunk lanes x 8 row slices: slice s walks rows first + s, first + s + 8, ... (a 1 500-frame
+//     silence gap is 188 loads per thread, not 1 500), the eight partial sums meet in LDS and are added in slice order,
+//     so the result does not depend on scheduling.
+//   * stack_rows: utterance u keeps P_u = T_u / f rows of f frames side by side; the f frames of a row are contiguous in
+//     the packed input, so this is a ragged copy (the inference runtime skips it: the projection reads x with lda = f H).
+// ----------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void segment_mean_kernel(const T* __restrict__ x, T* __restrict__ y, const int64_t* __restrict__ ranges, int64_t NT,
+                                                           int H) {
+  constexpr int VEC = Vec16<T>::VEC;
+  __shared__ float part[8][32][VEC];
+  const int64_t r = blockIdx.x;
+  const int cx = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  const int cpr = H / VEC;
+  const int ch = (int)blockIdx.y * 32 + cx;
+  int64_t s = ranges[2 * r], e = ranges[2 * r + 1];
+  if (s < 0) s = 0;          // the host hands over clamped, non-empty ranges; a bad table must still stay inside x
+  if (e > NT) e = NT;
+  float acc[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
+  if (ch < cpr) {
+    for (int64_t t = s + sl; t < e; t += 8) {
+      float f[VEC];
+      Vec16<T>::unpack(*(const uint4*)(x + t * H + ch * VEC), f);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) acc[j] += f[j];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) part[sl][cx][j] = acc[j];
+  __syncthreads();
+  if (sl != 0 || ch >= cpr) return;
+  const float n = (float)(e - s);
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    float a = acc[j];
+#pragma unroll
+    for (int q = 1; q < 8; ++q) a += part[q][cx][j];
+    acc[j] = e > s ? a / n : 0.f;
+  }
+  *(uint4*)(y + r * H + ch * VEC) = Vec16<T>::pack(acc);
+}
+
+extern "C" int sl_segment_mean_batch(const void* x, void* y, const int64_t* ranges_dev, int64_t n_ranges, int64_t n_rows, int32_t H, int32_t dtype,
+                                     sl_stream stream) {
+  const int vec = dtype == SL_F32 ? 4 : 8;
+  SL_CHECK_ARG(x && y && ranges_dev && n_ranges >= 0 && n_ranges <= 0x7fffffffLL && n_rows > 0 && H > 0, "sl_segment_mean_batch: bad arguments");
+  SL_CHECK_ARG(H % vec == 0, "sl_segment_mean_batch: H=%d must be a multiple of %d", H, vec);
+  if (n_ranges == 0) return 0;
+  const dim3 grid((unsigned)n_ranges, (unsigned)ceil_div64(H / vec, 32));
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
+    hipLaunchKernelGGL((segment_mean_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, ranges_dev, n_rows, H);
+  });
+  SL_CHECK_LAUNCH("segment_mean_batch");
+  return 0;
+}
+
+// desc[u] = {P_u, first frame row of the utterance in x, first stacked row in y, -} (int64); utterance = blockIdx.y
+template <typename T>
+__global__ __launch_bounds__(256) void stack_rows_batch_kernel(const T* __restrict__ x, T* __restrict__ y, const int64_t* __restrict__ desc, int H, int f) {
+  constexpr int VEC = Vec16<T>::VEC;
+  const int64_t* d = desc + 4 * (int64_t)blockIdx.y;
+  const int64_t total = d[0] * f * (H / VEC);          // 16-byte chunks of the utterance's P_u f frames
+  const uint4* src = (const uint4*)(x + d[1] * H);
+  uint4* dst = (uint4*)(y + d[2] * (int64_t)f * H);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) dst[i] = src[i];
+}
+
+extern "C" int sl_stack_rows_batch(const void* x, void* y, const int64_t* desc_dev, int32_t n_utt, int64_t max_P, int32_t H, int32_t factor, int32_t dtype,
+                                   sl_stream stream) {
+  const int vec = dtype == SL_F32 ? 4 : 8;
+  SL_CHECK_ARG(x && y && desc_dev && n_utt > 0 && max_P >= 0 && H > 0, "sl_stack_rows_batch: bad arguments");
+  SL_CHECK_ARG(factor >= 1, "sl_stack_rows_batch: factor=%d must be at least 1", factor);
+  SL_CHECK_ARG(H % vec == 0, "sl_stack_rows_batch: H=%d must be a multiple of %d", H, vec);
+  if (max_P == 0) return 0;      // every utterance shorter than one stacked row
+  const int64_t total = max_P * factor * (H / vec);
+  const unsigned gx = (unsigned)(ceil_div64(total, 256) < 1024 ? ceil_div64(total, 256) : 1024);
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
+    hipLaunchKernelGGL((stack_rows_batch_kernel<T>), dim3(gx, (unsigned)n_utt), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, desc_dev, H, factor);
+  });
+  SL_CHECK_LAUNCH("stack_rows_batch");
+  return 0;
+}
+
+// ---- host side of ctc_pool: no device, no stream -------------------------------------------------
+// Utterance-relative (start, end) pairs, as the dataset stores them, -> packed-row {first, end} records.  Each pair is clamped to the
+// utterance's frames the way a tensor slice clamps it (negative positions count from the end); a pair that is empty afterwards is an error.
+extern "C" int sl_segment_ranges_host(const int64_t* ranges_rel, const int32_t* counts, const int64_t* frames, int32_t n_utt, int64_t* packed_out) {
+  SL_CHECK_ARG(counts && frames && packed_out && n_utt > 0, "sl_segment_ranges_host: bad arguments");
+  int64_t r = 0, row0 = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    const int64_t T_ = frames[u];
+    SL_CHECK_ARG(counts[u] >= 0 && T_ >= 0, "sl_segment_ranges_host: utterance %d: %d ranges, %lld frames", u, counts[u], (long long)T_);
+    SL_CHECK_ARG(counts[u] == 0 || ranges_rel, "sl_segment_ranges_host: null range table");
+    for (int i = 0; i < counts[u]; ++i, ++r) {
+      const int64_t s0 = ranges_rel[2 * r], e0 = ranges_rel[2 * r + 1];
+      int64_t s = s0 < 0 ? s0 + T_ : s0, e = e0 < 0 ? e0 + T_ : e0;
+      s = s < 0 ? 0 : (s > T_ ? T_ : s);
+      e = e < 0 ? 0 : (e > T_ ? T_ : e);
+      SL_CHECK_ARG(e > s, "ctc_pool: utterance %d, range %d (%lld, %lld) is empty after clamping to its %lld frames", u, i, (long long)s0, (long long)e0,
+                   (long long)T_);
+      packed_out[2 * r] = row0 + s;
+      packed_out[2 * r + 1] = row0 + e;
+    }
+    row0 += T_;
+  }
+  return 0;
+}
+
+// Inverse index of a packed range table, frame -> the ranges that cover it, in CSR form: row_ptr (n_rows + 1) always, cols (the range numbers of
+// frame t at row_ptr[t] .. row_ptr[t + 1], in TABLE order) when cols != NULL and cols_cap holds them all (row_ptr[n_rows] = sum of the lengths).
+extern "C" int sl_segment_csr_host(const int64_t* ranges, int64_t n_ranges, int64_t n_rows, int64_t* row_ptr, int32_t* cols, int64_t cols_cap) {
+  SL_CHECK_ARG(row_ptr && n_ranges >= 0 && n_ranges <= 0x7fffffffLL && n_rows >= 0 && (ranges || n_ranges == 0), "sl_segment_csr_host: bad arguments");
+  for (int64_t t = 0; t <= n_rows; ++t) row_ptr[t] = 0;
+  for (int64_t r = 0; r < n_ranges; ++r) {
+    const int64_t s = ranges[2 * r], e = ranges[2 * r + 1];
+    SL_CHECK_ARG(s >= 0 && e > s && e <= n_rows, "sl_segment_csr_host: range %lld (%lld, %lld) is empty or outside the %lld packed rows", (long long)r,
+                 (long long)s, (long long)e, (long long)n_rows);
+    for (int64_t t = s; t < e; ++t) ++row_ptr[t + 1];
+  }
+  for (int64_t t = 0; t < n_rows; ++t) row_ptr[t + 1] += row_ptr[t];
+  if (!cols) return 0;
+  SL_CHECK_ARG(cols_cap >= row_ptr[n_rows], "sl_segment_csr_host: cols holds %lld entries, the index has %lld", (long long)cols_cap, (long long)row_ptr[n_rows]);
+  std::vector<int64_t> cur(row_ptr, row_ptr + n_rows);
+  for (int64_t r = 0; r < n_ranges; ++r)
+    for (int64_t t = ranges[2 * r]; t < ranges[2 * r + 1]; ++t) cols[cur[t]++] = (int32_t)r;
   return 0;
 }

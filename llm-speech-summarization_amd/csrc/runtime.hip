@@ -111,7 +111,8 @@ struct HubertWs {
   float* ln_mr;     //                 [frames][2] {mean, rstd}
 };
 
-static size_t hubert_carve(const sl_hubert_model* m, const HubertPlan& pl, int n_utt, void* base, size_t cap, HubertWs& w) {
+// pooled_rows: rows of the downsampled frames ahead of the projection (default: the AvgPool's; ctc_pool: one per range)
+static size_t hubert_carve(const sl_hubert_model* m, const HubertPlan& pl, int n_utt, void* base, size_t cap, HubertWs& w, int64_t pooled_rows = -1) {
   const size_t sz = sl_dtype_size(m->dtype);
   const int H = m->hidden;
   Carver c(base, cap);
@@ -125,7 +126,7 @@ static size_t hubert_carve(const sl_hubert_model* m, const HubertPlan& pl, int n
   w.mid = c.take(pl.total_T * (int64_t)m->ffn * sz);
   w.xg = c.take((pl.total_T + (int64_t)n_utt * m->pos_k) * H * sz);
   w.desc = (int64_t*)c.take((size_t)((m->n_conv - 1) * n_utt + n_utt * m->pos_groups) * 4 * sizeof(int64_t));
-  w.pooled = c.take(pl.total_P * H * sz);
+  w.pooled = c.take((pooled_rows < 0 ? pl.total_P : pooled_rows) * H * sz);
   w.pdesc = (int64_t*)c.take((size_t)n_utt * 4 * sizeof(int64_t));
   w.c0desc = (int64_t*)c.take((size_t)(n_utt + 1) * 2 * sizeof(int64_t));
   w.cu = (int32_t*)c.take((n_utt + 1) * sizeof(int32_t));
@@ -149,11 +150,38 @@ static void proj_records(const sl_hubert_model* m, const HubertPlan& pl, int n_u
   }
 }
 
-// transformer layers on the packed frames of the batch (varlen attention), final LayerNorm, AvgPool + projection.
+// rows each utterance gives the projection under a stack / ctc_pool descriptor
+static int64_t ds_rows(const sl_downsample_desc* ds, const HubertPlan& pl, int u) {
+  return ds->method == SL_DS_STACK ? pl.T[u] / ds->factor : ds->range_counts_host[u];
+}
+
+// stack / ctc_pool records of the grouped projector GEMM, one per utterance that has rows (a group without rows is left out):
+// {rows, element offset of its first A row, element offset into `out`, 0}.  stack: A is the final LayerNorm's output read with lda = f H
+// (row p = frames f p .. f p + f - 1, contiguous), ctc_pool: the range means.  Returns the number of records.
+static int ds_records(const sl_hubert_model* m, const sl_downsample_desc* ds, const HubertPlan& pl, int n_utt, int64_t out_ld,
+                      const int64_t* out_row_offsets_host, std::vector<int64_t>& rec, int64_t* max_rows) {
+  rec.clear();
+  int64_t prow = 0, mx = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    const int64_t P = ds_rows(ds, pl, u);
+    if (P > 0) {
+      rec.push_back(P);
+      rec.push_back((ds->method == SL_DS_STACK ? pl.tok0[u] : prow) * m->hidden);
+      rec.push_back((out_row_offsets_host ? out_row_offsets_host[u] : prow) * out_ld);
+      rec.push_back(0);
+      if (P > mx) mx = P;
+    }
+    prow += P;
+  }
+  if (max_rows) *max_rows = mx;
+  return (int)(rec.size() / 4);
+}
+
+// transformer layers on the packed frames of the batch (varlen attention), final LayerNorm, downsample (AvgPool, or the descriptor's stack / ctc_pool) + projection.
 // Shared by the HuBERT and Whisper front ends (both are 16x64 pre-LN encoders: hf:...hubert.py:504-547,
 // hf:models/whisper/modeling_whisper.py:360-414).
 static int encoder_tail(const sl_hubert_model* m, HubertWs& w, const HubertPlan& pl, int n_utt, void* out, int64_t out_ld,
-                        const int64_t* out_row_offsets_host, void* last_hidden, hipStream_t st) {
+                        const int64_t* out_row_offsets_host, void* last_hidden, hipStream_t st, const sl_downsample_desc* ds = nullptr) {
   sl_stream stream = (sl_stream)st;
   const int dt = m->dtype, H = m->hidden, NT = (int)pl.total_T;
   const size_t sz = sl_dtype_size(dt);
@@ -214,8 +242,29 @@ static int encoder_tail(const sl_hubert_model* m, HubertWs& w, const HubertPlan&
   }
   void* lh = last_hidden ? last_hidden : w.ln;
   SL_TRY(sl_layernorm(w.x, lh, m->final_ln_g, m->final_ln_b, NT, H, m->ln_eps, 0, dt, stream));
+  if (ds) {
+    // ---- stack / ctc_pool + projection into the caller's (prompt) buffer: at most one downsample launch (stack needs none) and one grouped GEMM
+    std::vector<int64_t> rec;
+    int64_t max_rows = 0;
+    const int n_grp = ds_records(m, ds, pl, n_utt, out_ld, out_row_offsets_host, rec, &max_rows);     // the same records the caller uploaded to w.pdesc
+    if (n_grp == 0) return 0;
+    const bool stack = ds->method == SL_DS_STACK;
+    if (!stack) SL_TRY(sl_segment_mean_batch(lh, w.pooled, ds->ranges_dev, ds->n_ranges, NT, H, dt, stream));
+    const int Kp = stack ? ds->factor * H : H;
+    sl_gemm_args a;
+    memset(&a, 0, sizeof(a));
+    a.A = stack ? lh : w.pooled; a.lda = Kp;
+    a.W = ds->proj_w; a.ldw = Kp;
+    a.C = out; a.ldc = out_ld;
+    a.bias = ds->proj_b;
+    a.M = (int)max_rows; a.N = m->llm_dim; a.K = Kp; a.batch = n_grp; a.dtype = dt; a.act = SL_ACT_NONE;
+    sl_gemm_ex_args ex;
+    memset(&ex, 0, sizeof(ex));
+    ex.groups = w.pdesc; ex.w_mod = 1;
+    return sl_gemm_impl(&a, nullptr, &ex, st);
+  }
   // ---- AvgPool over time + projection into the caller's (prompt) buffer
-  if (!m->proj_w) return 0;  // stack / ctc_pool: the host finishes from last_hidden
+  if (!m->proj_w) return 0;  // stack / ctc_pool through sl_hubert_forward: the host finishes from last_hidden
   // one AvgPool launch and one grouped projector GEMM for the whole ragged batch (records uploaded by the caller: w.pdesc)
   int64_t max_P = 0;
   for (int u = 0; u < n_utt; ++u) max_P = pl.P[u] > max_P ? pl.P[u] : max_P;
@@ -241,11 +290,12 @@ extern "C" size_t sl_hubert_workspace_bytes(const sl_hubert_model* m, const int6
   return hubert_carve(m, pl, n_utt, nullptr, 0, w);
 }
 
-extern "C" int sl_hubert_forward(const sl_hubert_model* m, const float* waves, const int64_t* sample_offsets_host, int32_t n_utt,
-                                 void* out, int64_t out_ld, const int64_t* out_row_offsets_host, void* last_hidden, void* workspace,
-                                 size_t workspace_bytes, sl_stream stream) {
+// ds == nullptr: sl_hubert_forward (pool, or last_hidden only); otherwise a checked stack / ctc_pool descriptor (sl_hubert_forward_ds)
+static int hubert_forward_impl(const sl_hubert_model* m, const float* waves, const int64_t* sample_offsets_host, int32_t n_utt, void* out, int64_t out_ld,
+                               const int64_t* out_row_offsets_host, void* last_hidden, void* workspace, size_t workspace_bytes, sl_stream stream,
+                               const sl_downsample_desc* ds) {
   SL_CHECK_ARG(m && waves && sample_offsets_host && workspace && n_utt > 0, "sl_hubert_forward: bad arguments");
-  SL_CHECK_ARG((m->proj_w && out) || (!m->proj_w && last_hidden), "sl_hubert_forward: need `out` (pool) or `last_hidden` (host-side downsample)");
+  SL_CHECK_ARG(ds || (m->proj_w && out) || (!m->proj_w && last_hidden), "sl_hubert_forward: need `out` (pool) or `last_hidden` (host-side downsample)");
   SL_CHECK_ARG(m->n_conv >= 2 && m->n_conv <= 8 && m->hidden % m->n_heads == 0 && m->hidden / m->n_heads == 64,
                "sl_hubert_forward: need 2..8 conv layers and head_dim 64 (hidden=%d heads=%d)", m->hidden, m->n_heads);
   hipStream_t st = (hipStream_t)stream;
@@ -254,7 +304,7 @@ extern "C" int sl_hubert_forward(const sl_hubert_model* m, const float* waves, c
   HubertPlan pl;
   SL_TRY(hubert_plan(m, sample_offsets_host, n_utt, pl));
   HubertWs w;
-  const size_t need = hubert_carve(m, pl, n_utt, workspace, workspace_bytes, w);
+  const size_t need = hubert_carve(m, pl, n_utt, workspace, workspace_bytes, w, ds && ds->method == SL_DS_CTC_POOL ? ds->n_ranges : -1);
   SL_CHECK_ARG(need <= workspace_bytes, "sl_hubert_forward: workspace %zu B < required %zu B", workspace_bytes, need);
   const int Cl = m->conv_dim[m->n_conv - 1];
 
@@ -293,8 +343,9 @@ extern "C" int sl_hubert_forward(const sl_hubert_model* m, const float* waves, c
     SL_HIP(hipMemcpyAsync(w.klen, kl.data(), n_utt * sizeof(int32_t), hipMemcpyHostToDevice, st));
     SL_HIP(hipMemcpyAsync(w.desc, desc.data(), desc.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     std::vector<int64_t> prec;
-    proj_records(m, pl, n_utt, out_ld, out_row_offsets_host, prec);
-    SL_HIP(hipMemcpyAsync(w.pdesc, prec.data(), prec.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if (ds) ds_records(m, ds, pl, n_utt, out_ld, out_row_offsets_host, prec, nullptr);
+    else proj_records(m, pl, n_utt, out_ld, out_row_offsets_host, prec);
+    if (!prec.empty()) SL_HIP(hipMemcpyAsync(w.pdesc, prec.data(), prec.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     std::vector<int64_t> c0(2 * (size_t)(n_utt + 1));
     for (int u = 0; u <= n_utt; ++u) { c0[u] = sample_offsets_host[u] - sample_offsets_host[0]; c0[n_utt + 1 + u] = row0[0][u]; }
     SL_HIP(hipMemcpyAsync(w.c0desc, c0.data(), c0.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
@@ -346,7 +397,56 @@ extern "C" int sl_hubert_forward(const sl_hubert_model* m, const float* waves, c
     SL_TRY(sl_gemm_impl(&a, nullptr, &ex, st));
     void* t = w.x; w.x = w.ln; w.ln = t;
   }
-  return encoder_tail(m, w, pl, n_utt, out, out_ld, out_row_offsets_host, last_hidden, st);
+  return encoder_tail(m, w, pl, n_utt, out, out_ld, out_row_offsets_host, last_hidden, st, ds);
+}
+
+extern "C" int sl_hubert_forward(const sl_hubert_model* m, const float* waves, const int64_t* sample_offsets_host, int32_t n_utt,
+                                 void* out, int64_t out_ld, const int64_t* out_row_offsets_host, void* last_hidden, void* workspace,
+                                 size_t workspace_bytes, sl_stream stream) {
+  return hubert_forward_impl(m, waves, sample_offsets_host, n_utt, out, out_ld, out_row_offsets_host, last_hidden, workspace, workspace_bytes, stream, nullptr);
+}
+
+// every check of a stack / ctc_pool descriptor that needs no device; `who` names the entry point in the message
+static int ds_check(const char* who, const sl_hubert_model* m, const sl_downsample_desc* ds, int32_t n_utt) {
+  SL_CHECK_ARG(m && ds && n_utt > 0, "%s: null model / descriptor or no utterances", who);
+  SL_CHECK_ARG(ds->method == SL_DS_STACK || ds->method == SL_DS_CTC_POOL, "%s: method %d: 1 (stack) or 2 (ctc_pool); `pool` goes through sl_hubert_forward", who,
+               ds->method);
+  SL_CHECK_ARG(ds->factor >= 1, "%s: downsample factor %d must be at least 1", who, ds->factor);
+  SL_CHECK_ARG(ds->proj_w && ds->proj_b, "%s: null projection", who);
+  if (ds->method == SL_DS_STACK) {
+    SL_CHECK_ARG(ds->proj_in == ds->factor * m->hidden, "%s: stack: the projection reads %d features, factor x hidden = %d x %d", who, ds->proj_in, ds->factor,
+                 m->hidden);
+    return 0;
+  }
+  SL_CHECK_ARG(ds->proj_in == m->hidden, "%s: ctc_pool: the projection reads %d features, hidden = %d", who, ds->proj_in, m->hidden);
+  SL_CHECK_ARG(ds->range_counts_host && (ds->ranges_dev || ds->n_ranges == 0) && ds->n_ranges >= 0, "%s: ctc_pool: null range table / counts", who);
+  int64_t total = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    SL_CHECK_ARG(ds->range_counts_host[u] >= 0, "%s: ctc_pool: utterance %d has %d ranges", who, u, ds->range_counts_host[u]);
+    total += ds->range_counts_host[u];
+  }
+  SL_CHECK_ARG(total == ds->n_ranges, "%s: ctc_pool: the utterances' range counts add up to %lld, the table holds %lld", who, (long long)total,
+               (long long)ds->n_ranges);
+  return 0;
+}
+
+extern "C" size_t sl_hubert_workspace_bytes_ds(const sl_hubert_model* m, const int64_t* sample_offsets_host, int32_t n_utt, const sl_downsample_desc* ds) {
+  if (!sample_offsets_host || ds_check("sl_hubert_workspace_bytes_ds", m, ds, n_utt) != 0) {
+    if (!sample_offsets_host) sl_set_error("sl_hubert_workspace_bytes_ds: null sample offsets");
+    return 0;
+  }
+  HubertPlan pl;
+  if (hubert_plan(m, sample_offsets_host, n_utt, pl) != 0) return 0;
+  HubertWs w;
+  return hubert_carve(m, pl, n_utt, nullptr, 0, w, ds->method == SL_DS_CTC_POOL ? ds->n_ranges : -1);
+}
+
+extern "C" int sl_hubert_forward_ds(const sl_hubert_model* m, const float* waves, const int64_t* sample_offsets_host, int32_t n_utt, void* out, int64_t out_ld,
+                                    const int64_t* out_row_offsets_host, void* last_hidden, const sl_downsample_desc* ds, void* workspace,
+                                    size_t workspace_bytes, sl_stream stream) {
+  SL_TRY(ds_check("sl_hubert_forward_ds", m, ds, n_utt));
+  SL_CHECK_ARG(out && out_ld >= m->llm_dim, "sl_hubert_forward_ds: need `out` with rows of at least llm_dim = %d elements", m->llm_dim);
+  return hubert_forward_impl(m, waves, sample_offsets_host, n_utt, out, out_ld, out_row_offsets_host, last_hidden, workspace, workspace_bytes, stream, ds);
 }
 
 // ================================================================================================

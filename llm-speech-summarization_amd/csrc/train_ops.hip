@@ -1655,6 +1655,77 @@ extern "C" int sl_avgpool_bwd_batch(const void* dy, void* dx, const int64_t* des
   return 0;
 }
 
+// ctc_pool backward as a gather: dx[t] = sum over the ranges r that cover frame t of dy[r] / len_r.  The host's CSR index (sl_segment_csr_host) lists
+// them in table order; one thread owns one (frame, 16-byte chunk), adds its terms in that order and stores once — no atomics, every row written
+// (zeros where nothing covers it), so the result depends on the table alone.
+template <typename T>
+__global__ __launch_bounds__(256) void segment_mean_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx, const int64_t* __restrict__ ranges,
+                                                               const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ cols, int64_t NT, int64_t R,
+                                                               int H) {
+  constexpr int VEC = Vec16<T>::VEC;
+  const int cpr = H / VEC;
+  const int64_t total = NT * cpr;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int ch = (int)(i % cpr);
+    const int64_t t = i / cpr;
+    float acc[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) acc[e] = 0.f;
+    const int64_t q1 = row_ptr[t + 1];
+    for (int64_t q = row_ptr[t]; q < q1; ++q) {
+      const int64_t r = cols[q];
+      if (r < 0 || r >= R) continue;      // (a foreign index must not reach outside dy)
+      const float n = (float)(ranges[2 * r + 1] - ranges[2 * r]);
+      float f[VEC];
+      Vec16<T>::unpack(*(const uint4*)(dy + r * H + ch * VEC), f);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) acc[e] += f[e] / n;
+    }
+    *(uint4*)(dx + t * H + ch * VEC) = Vec16<T>::pack(acc);
+  }
+}
+
+extern "C" int sl_segment_mean_bwd_batch(const void* dy, void* dx, const int64_t* ranges_dev, const int64_t* row_ptr_dev, const int32_t* cols_dev,
+                                         int64_t n_ranges, int64_t n_rows, int32_t H, int32_t dtype, sl_stream stream) {
+  SL_CHECK_ARG(dy && dx && ranges_dev && row_ptr_dev && cols_dev && n_ranges > 0 && n_rows > 0 && H > 0, "sl_segment_mean_bwd_batch: bad arguments");
+  const int vec = dtype == SL_F32 ? 4 : 8;
+  SL_CHECK_ARG(H % vec == 0, "sl_segment_mean_bwd_batch: H must be a multiple of %d", vec);
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
+    hipLaunchKernelGGL((segment_mean_bwd_kernel<T>), dim3(grid_for(n_rows * (H / vec))), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (T*)dx, ranges_dev,
+                       row_ptr_dev, cols_dev, n_rows, n_ranges, H);
+  });
+  SL_CHECK_LAUNCH("segment_mean_bwd_batch");
+  return 0;
+}
+
+// stack backward: desc[u] = {P_u, T_u, first stacked row of the utterance in dy, first frame row in dx} (int64); the first P_u f frames take their
+// stacked row's slice back, the T_u % f cropped ones get zeros.  Utterance = blockIdx.y.
+template <typename T>
+__global__ __launch_bounds__(256) void stack_rows_bwd_batch_kernel(const T* __restrict__ dy, T* __restrict__ dx, const int64_t* __restrict__ desc, int H, int f) {
+  constexpr int VEC = Vec16<T>::VEC;
+  const int64_t* d = desc + 4 * (int64_t)blockIdx.y;
+  const int64_t cpr = H / VEC;
+  const int64_t kept = d[0] * f * cpr, total = d[1] * cpr;
+  const uint4* src = (const uint4*)(dy + d[2] * (int64_t)f * H);
+  uint4* dst = (uint4*)(dx + d[3] * H);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) dst[i] = i < kept ? src[i] : make_uint4(0, 0, 0, 0);
+}
+
+extern "C" int sl_stack_rows_bwd_batch(const void* dy, void* dx, const int64_t* desc_dev, int32_t n_utt, int64_t max_T, int32_t H, int32_t factor,
+                                       int32_t dtype, sl_stream stream) {
+  SL_CHECK_ARG(dy && dx && desc_dev && n_utt > 0 && max_T > 0 && H > 0, "sl_stack_rows_bwd_batch: bad arguments");
+  SL_CHECK_ARG(factor >= 1, "sl_stack_rows_bwd_batch: factor=%d must be at least 1", factor);
+  const int vec = dtype == SL_F32 ? 4 : 8;
+  SL_CHECK_ARG(H % vec == 0, "sl_stack_rows_bwd_batch: H must be a multiple of %d", vec);
+  const unsigned gx = grid_for(max_T * (H / vec), 1024);
+  SL_DISPATCH_DTYPE_INF(dtype, T, {
+    hipLaunchKernelGGL((stack_rows_bwd_batch_kernel<T>), dim3(gx, (unsigned)n_utt), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (T*)dx, desc_dev, H,
+                       factor);
+  });
+  SL_CHECK_LAUNCH("stack_rows_bwd_batch");
+  return 0;
+}
+
 extern "C" int sl_col2im(const void* dcol, void* dx, int64_t Lin, int64_t Lout, int32_t Cc, int32_t k, int32_t s, int32_t dtype, sl_stream stream) {
   SL_CHECK_ARG(dcol && dx && Lin > 0 && Lout > 0 && Cc > 0 && k > 0 && s > 0, "sl_col2im: bad arguments");
   const int vec = dtype == SL_F32 ? 4 : 8;

@@ -125,17 +125,18 @@ class LLMSpeechTextInference():
         return self.generate_llm_response(inputs_embeds=prompt_embeds, max_new_tokens=max_new_tokens)[0]
 
     def generate_audio_response(self, audio, additional_text_prompt="", max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None,
-                                min_new_tokens=None, return_scores=False, num_return_sequences=None):
+                                min_new_tokens=None, return_scores=False, num_return_sequences=None, ctc_pool_ranges=None):
         """num_return_sequences=R > 1 (None: runtime.num_return_sequences): the list of R sampled answers (and, with return_scores, the
-        list of their scores) instead of one answer."""
+        list of their scores) instead of one answer.  ctc_pool_ranges (an extension; the `ctc_pool` downsample only): this utterance's list of
+        (start, end) frame ranges, as the dataset's `pool_ranges_4` holds them; without it `ctc_pool` fails as the reference does (Q2)."""
         audio_tensor = torch.as_tensor(audio, dtype=torch.float32).unsqueeze(0).to(self.device)
-        if self.audio_encoder.downsample_method == "ctc_pool":
+        if self.audio_encoder.downsample_method == "ctc_pool" and ctc_pool_ranges is None:
             # the reference calls an undefined self.get_ctc_pool_ranges here (SURVEY.md §9 Q2)
             raise AttributeError("'LLMSpeechTextInference' object has no attribute 'get_ctc_pool_ranges'")
         if self.audio_encoder.encoder_base == "whisper":
             audio_embeds = self._whisper_audio_embeds(audio)
         else:
-            audio_embeds = self.audio_encoder(audio_tensor, ctc_pool_ranges=None)
+            audio_embeds = self.audio_encoder(audio_tensor, ctc_pool_ranges=None if ctc_pool_ranges is None else [ctc_pool_ranges])
 
         if len(additional_text_prompt) > 0:  # text prompt goes before the audio, BOS dropped (ref:inference.py:113-122)
             additional_text_input_ids = self.llm_tokenizer(additional_text_prompt, return_tensors='pt').input_ids[:, 1:].to(self.device)
@@ -168,8 +169,10 @@ class LLMSpeechTextInference():
         return padded[:, :keep]
 
     def generate_audio_responses(self, audios, additional_text_prompts=None, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None,
-                                 min_new_tokens=None, return_scores=False, num_return_sequences=None):
+                                 min_new_tokens=None, return_scores=False, num_return_sequences=None, ctc_pool_ranges=None):
         """return_scores=True: (texts, scores), one mean token log-probability per answer; chunks are concatenated in order.
+        ctc_pool_ranges (the `ctc_pool` downsample only): one list of (start, end) frame ranges per utterance; without it `ctc_pool` raises the
+        reference's AttributeError (Q2).  All three downsample methods take the batched path below.
         num_return_sequences=R > 1 (None: runtime.num_return_sequences): R sampled answers per utterance from one prefill of each
         (generate_packed num_return), returned prompt-major: answer j of utterance i is entry i * R + j.
         Batched form of generate_audio_response (an extension: the reference answers one utterance per call).
@@ -186,12 +189,11 @@ class LLMSpeechTextInference():
         R = self._num_return(num_return_sequences)
         if R > 1 and self.beams:
             raise L.SpeechLLMError("num_return_sequences > 1 with beam search (beam sampling) is not built")
-        if self.audio_encoder.downsample_method != "pool":       # stack / ctc_pool: the one-utterance path (ctc_pool raises as the reference does)
-            res = [self.generate_audio_response(a, texts[i], max_new_tokens, repetition_penalty, no_repeat_ngram_size, min_new_tokens, return_scores, R)
-                   for i, a in enumerate(audios)]
-            if R > 1:      # each entry is a list of R answers (or a pair of lists): flattened prompt-major
-                return ([t for r in res for t in r[0]], [v for r in res for v in r[1]]) if return_scores else [t for r in res for t in r]
-            return ([r[0] for r in res], [r[1] for r in res]) if return_scores else res
+        ctc = self.audio_encoder.downsample_method == "ctc_pool"
+        if ctc and ctc_pool_ranges is None:                      # the reference calls an undefined self.get_ctc_pool_ranges
+            raise AttributeError("'LLMSpeechTextInference' object has no attribute 'get_ctc_pool_ranges'")
+        if ctc and len(ctc_pool_ranges) != n:
+            raise ValueError(f"{len(ctc_pool_ranges)} lists of ctc_pool ranges for {n} utterances")
         out: List[str] = []
         ids_all = []
         scores_all: List[float] = []
@@ -200,7 +202,8 @@ class LLMSpeechTextInference():
             raise L.SpeechLLMError(f"num_return_sequences={R} exceeds the {L.MAX_DECODE_BATCH} decode rows of one generate call")
         for lo_ in range(0, n, chunk):
             ids = self._generate_chunk(audios[lo_:lo_ + chunk], texts[lo_:lo_ + chunk], max_new_tokens,
-                                       self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens), return_scores, R)
+                                       self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens), return_scores, R,
+                                       ranges=list(ctc_pool_ranges[lo_:lo_ + chunk]) if ctc else None)
             if return_scores:
                 ids, lps = ids
                 scores_all += self._mean_logprobs(ids, lps)
@@ -215,7 +218,7 @@ class LLMSpeechTextInference():
         self.last_generate_ids = torch.cat([torch.nn.functional.pad(i, (0, width - int(i.shape[1])), value=int(pad)) for i in ids_all]) if ids_all else None
         return (out, scores_all) if return_scores else out
 
-    def _generate_chunk(self, audios, texts, max_new_tokens, logits=None, scores=False, num_return=1):
+    def _generate_chunk(self, audios, texts, max_new_tokens, logits=None, scores=False, num_return=1, ranges=None):
         """One generate call's worth of utterances -> LongTensor (n, n_cols) of new tokens (scores: and their (n, n_cols) log-probabilities).
         num_return = R > 1: (n * R, n_cols), R answers per utterance sampled with the llm's generation_config warpers."""
         from .utils import compute_num_audio_embeds, prompt_template
@@ -233,8 +236,12 @@ class LLMSpeechTextInference():
             feats = enc.feature_extractor(waves, return_tensors="pt", sampling_rate=sr).input_features
             padded = enc(feats)                                                  # (n, P_window, llm_dim): every 30 s window in one pass
             Ps = [max(0, min(int(padded.shape[1]), compute_num_audio_embeds(int(w.numel()), sr=sr))) for w in waves]
-        else:
+        elif enc.downsample_method == "pool":
             Ps = [(enc.arch.num_frames(int(w.numel())) - enc.pool_kernel) // enc.pool_stride + 1 for w in waves]
+        elif enc.downsample_method == "stack":
+            Ps = [enc.arch.num_frames(int(w.numel())) // enc.downsample_factor for w in waves]
+        else:                                                                    # ctc_pool: one embedding per range
+            Ps = [len(r) for r in ranges]
         lens, heads = [], []
         for i in range(n):
             n_head = pre_e.shape[0] + (txt_e[i].shape[0] if txt_e[i] is not None else 0)
@@ -253,7 +260,7 @@ class LLMSpeechTextInference():
                 x[o + heads[i]:o + heads[i] + Ps[i]] = padded[i, :Ps[i]]
             x[o + heads[i] + Ps[i]:starts[i + 1]] = suf_e
         if not whisper:
-            enc.encode_packed(waves, out=x, out_row_offsets=[starts[i] + heads[i] for i in range(n)])
+            enc.encode_packed(waves, out=x, out_row_offsets=[starts[i] + heads[i] for i in range(n)], ctc_pool_ranges=ranges)
         # every prompt opens with the same template rows (and the same instruction text when the caller gave one text for all):
         # the batched decode attention reads those cache positions once for the batch (sl_kv_cache.shared_prefix)
         shared = int(pre_e.shape[0])

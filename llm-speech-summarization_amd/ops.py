@@ -849,3 +849,90 @@ def sample_select_sc(logits, temperature, top_k, top_p, seed, eos_ids, pad_id, u
     L.check(L.lib().sl_sample_select_sc(L.ptr(logits), B, V, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, eos, len(eos_ids),
                                         pad_id, int(use_eos), L.ptr(unfinished), L.ptr(ctx_len), L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids),
                                         L.ptr(out_ids), out_ids.shape[1], L.ptr(choice), L.ptr(logprobs), L.stream_ptr()), "sl_sample_select_sc")
+
+
+# -- stack / ctc_pool downsampling of a packed ragged batch (ref:model/audio_encoder.py:65-85) -----------------------------------
+def segment_ranges_pack(ranges_per_utt, frames: Sequence[int]):
+    """ctc_pool ranges as the dataset stores them (one list of (start, end) per utterance, utterance-relative) -> (packed int64 CPU tensor
+    (R, 2) of {first row, end row} in packed-frame coordinates, per-utterance counts).  Pure host routine (sl_segment_ranges_host): each pair is
+    clamped to its utterance's frames like a tensor slice; a pair that is empty afterwards raises SpeechLLMError naming the utterance and the range."""
+    if ranges_per_utt is None or len(ranges_per_utt) != len(frames):
+        raise L.SpeechLLMError(f"ctc_pool needs one list of (start, end) ranges per utterance: got {0 if ranges_per_utt is None else len(ranges_per_utt)} "
+                               f"for {len(frames)} utterances")
+    per = [torch.as_tensor(r, dtype=torch.int64).reshape(-1, 2) for r in ranges_per_utt]
+    counts = [int(p_.shape[0]) for p_ in per]
+    rel = torch.cat(per).contiguous() if per else torch.zeros((0, 2), dtype=torch.int64)
+    packed = torch.empty_like(rel)
+    cnt = (C.c_int32 * len(frames))(*counts)
+    frm = (C.c_int64 * len(frames))(*[int(t) for t in frames])
+    L.check(L.lib().sl_segment_ranges_host(rel.data_ptr(), C.cast(cnt, C.c_void_p), C.cast(frm, C.c_void_p), len(frames), packed.data_ptr()),
+            "sl_segment_ranges_host")
+    return packed, counts
+
+
+def segment_csr(packed_ranges: torch.Tensor, n_rows: int):
+    """Inverse index of a packed range table (sl_segment_csr_host, a pure host routine): (row_ptr int64 (n_rows + 1), cols int32) CPU tensors;
+    frame t is covered by ranges cols[row_ptr[t]:row_ptr[t + 1]], in table order."""
+    r = torch.as_tensor(packed_ranges, dtype=torch.int64).reshape(-1, 2).contiguous()
+    row_ptr = torch.empty(n_rows + 1, dtype=torch.int64)
+    lib = L.lib()
+    L.check(lib.sl_segment_csr_host(r.data_ptr(), r.shape[0], n_rows, row_ptr.data_ptr(), None, 0), "sl_segment_csr_host")
+    cols = torch.empty(int(row_ptr[n_rows]), dtype=torch.int32)
+    L.check(lib.sl_segment_csr_host(r.data_ptr(), r.shape[0], n_rows, row_ptr.data_ptr(), cols.data_ptr(), cols.numel()), "sl_segment_csr_host")
+    return row_ptr, cols
+
+
+def segment_mean_batch(x: torch.Tensor, ranges_dev: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[r] = mean(x[first_r:end_r]) for the int64 (R, 2) device table of packed-row ranges, one launch (sl_segment_mean_batch)."""
+    L.require_gpu(x, "x"); L.require_gpu(ranges_dev, "ranges")
+    R, H = int(ranges_dev.shape[0]), x.shape[1]
+    y = torch.empty((R, H), device=x.device, dtype=x.dtype) if out is None else out
+    L.check(L.lib().sl_segment_mean_batch(L.ptr(x), L.ptr(y), L.ptr(ranges_dev), R, x.shape[0], H, L.dtype_code(x.dtype), L.stream_ptr()),
+            "sl_segment_mean_batch")
+    return y
+
+
+def segment_mean_bwd_batch(dy: torch.Tensor, ranges_dev: torch.Tensor, row_ptr_dev: torch.Tensor, cols_dev: torch.Tensor, n_rows: int,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx[t] = sum of dy[r] / len_r over the ranges covering frame t (sl_segment_mean_bwd_batch); every one of the n_rows rows is written."""
+    L.require_gpu(dy, "dy")
+    H = dy.shape[1]
+    dx = torch.empty((n_rows, H), device=dy.device, dtype=dy.dtype) if out is None else out
+    L.check(L.lib().sl_segment_mean_bwd_batch(L.ptr(dy), L.ptr(dx), L.ptr(ranges_dev), L.ptr(row_ptr_dev), L.ptr(cols_dev), int(ranges_dev.shape[0]), n_rows, H,
+                                              L.dtype_code(dy.dtype), L.stream_ptr()), "sl_segment_mean_bwd_batch")
+    return dx
+
+
+def stack_rows_batch(x: torch.Tensor, seqlens: Sequence[int], factor: int, out: Optional[torch.Tensor] = None):
+    """`stack` downsample of every utterance of a packed batch in one launch -> (dense (sum P_u, factor * H) rows, P list), P_u = T_u // factor."""
+    L.require_gpu(x, "x")
+    H = x.shape[1]
+    P = [int(t) // factor for t in seqlens]
+    desc, row, tok = [], 0, 0
+    for p_, t in zip(P, seqlens):
+        desc.append([p_, tok, row, 0])
+        row += p_
+        tok += int(t)
+    y = torch.empty((row, factor * H), device=x.device, dtype=x.dtype) if out is None else out
+    if row > 0:
+        desc_t = L.h2d(desc, torch.int64, x.device)
+        L.check(L.lib().sl_stack_rows_batch(L.ptr(x), L.ptr(y), desc_t.data_ptr(), len(P), max(P), H, factor, L.dtype_code(x.dtype), L.stream_ptr()),
+                "sl_stack_rows_batch")
+    return y, P
+
+
+def stack_rows_bwd_batch(dy: torch.Tensor, seqlens: Sequence[int], factor: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Backward of stack_rows_batch: (sum P_u, factor * H) -> (sum T_u, H), zeros in the T_u % factor cropped frames (one launch, every row written)."""
+    H = dy.shape[1] // factor
+    P = [int(t) // factor for t in seqlens]
+    desc, row, tok = [], 0, 0
+    for p_, t in zip(P, seqlens):
+        desc.append([p_, int(t), row, tok])
+        row += p_
+        tok += int(t)
+    dx = torch.empty((tok, H), device=dy.device, dtype=dy.dtype) if out is None else out
+    src = dy if dy.numel() else torch.empty((1, factor * H), device=dy.device, dtype=dy.dtype)      # no stacked rows at all: nothing is read
+    desc_t = L.h2d(desc, torch.int64, dy.device)
+    L.check(L.lib().sl_stack_rows_bwd_batch(L.ptr(src), L.ptr(dx), desc_t.data_ptr(), len(P), max(int(t) for t in seqlens), H, factor,
+                                            L.dtype_code(dy.dtype), L.stream_ptr()), "sl_stack_rows_bwd_batch")
+    return dx

@@ -226,10 +226,12 @@ class Trainer():
                 if mine:
                     batch = [self.train_dataset[i] for i in mine]
                     if self.encoder_base == "whisper":      # ref:trainer.py:168-199: the tape computes the log-mel itself from the raw audio
-                        raw, _, _, _, text_ids, resp_ids, _ = self.collate_audio_batch_whisper(batch)
+                        raw, _, _, _, text_ids, resp_ids, ranges = self.collate_audio_batch_whisper(batch)
                     else:
-                        raw, _, _, _, text_ids, resp_ids, _ = self.collate_audio_batch_hubert(batch)
-                    losses = self.kd.micro_batch(raw, text_ids, resp_ids, close_window=True if tail else None)
+                        raw, _, _, _, text_ids, resp_ids, ranges = self.collate_audio_batch_hubert(batch)
+                    # ref:trainer.py:143,278: the sample's pool_ranges_4 feed the ctc_pool downsample (the other methods never read them)
+                    ranges = ranges if self.audio_encoder.downsample_method == "ctc_pool" else None
+                    losses = self.kd.micro_batch(raw, text_ids, resp_ids, close_window=True if tail else None, pool_ranges=ranges)
                 else:
                     self.kd.close_window()                   # tail window with fewer samples than ranks: join the exchange
                 prev, self.step = self.step, self.step + len(window)              # global micro-steps, like the reference's counter
@@ -257,8 +259,9 @@ class Trainer():
             _, feats, _, texts, text_ids, resp_ids, _ = self.collate_audio_batch_whisper([self.val_dataset[sample_idx]])
             audio_embeds = self.audio_encoder(feats.to(self.device))
         else:
-            raw, _, _, texts, text_ids, resp_ids, _ = self.collate_audio_batch_hubert([self.val_dataset[sample_idx]])
-            audio_embeds = self.audio_encoder(raw[0][None].to(self.device))
+            raw, _, _, texts, text_ids, resp_ids, ranges = self.collate_audio_batch_hubert([self.val_dataset[sample_idx]])
+            ranges = ranges if self.audio_encoder.downsample_method == "ctc_pool" else None          # ref:trainer.py:418
+            audio_embeds = self.audio_encoder(raw[0][None].to(self.device), ctc_pool_ranges=ranges)
         return audio_embeds, text_ids[0].to(self.device), resp_ids[0].to(self.device), texts[0]
 
     @torch.no_grad()

@@ -283,14 +283,14 @@ class LlamaTape:
 # audio encoder: forward with a tape, full backward (data + parameter gradients) — ragged batch of utterances
 # ------------------------------------------------------------------------------------------------
 class EncoderTape:
-    """HuBERT + pool + projection for a batch of utterances of arbitrary lengths, composed op by op from the same
-    kernels the fused C runtime (sl_hubert_forward) launches, keeping what the backward needs.  Token-wise work
+    """HuBERT + downsample (pool / stack / ctc_pool) + projection for a batch of utterances of arbitrary lengths, composed op by
+    op from the same kernels the fused C runtime (sl_hubert_forward) launches, keeping what the backward needs.  Token-wise work
     (norms, linear layers) runs on the packed frames of the whole batch; convolutions and attention respect
     utterance boundaries (grouped GEMMs / varlen attention), so results equal per-utterance runs."""
 
     def __init__(self, enc: AudioEncoder):
-        if enc.downsample_method != "pool":
-            raise L.SpeechLLMError("the KD step is built for the `pool` downsample (all shipped configs use it)")
+        if enc.downsample_method not in ("pool", "stack", "ctc_pool"):
+            raise L.SpeechLLMError(f"unknown downsample method {enc.downsample_method!r}")
         self.enc = enc
 
     @property
@@ -338,9 +338,12 @@ class EncoderTape:
         return self.arena.views
 
     def forward(self, waves: Sequence[torch.Tensor], reg: Optional[TrainRegularizers] = None, step: int = 0,
-                masked_spec_embed: Optional[torch.Tensor] = None):
-        """`reg` switches the training-mode regularisers on; `step` (micro-batch counter) salts their seeds."""
+                masked_spec_embed: Optional[torch.Tensor] = None, pool_ranges=None):
+        """`reg` switches the training-mode regularisers on; `step` (micro-batch counter) salts their seeds; `pool_ranges` (ctc_pool only):
+        one list of utterance-relative (start, end) frame ranges per utterance."""
         W, a, enc = self.W, self.enc.arch, self.enc
+        if enc.downsample_method == "ctc_pool" and pool_ranges is None:        # before any launch
+            raise L.SpeechLLMError("the ctc_pool downsample needs pool_ranges: one list of (start, end) frame ranges per utterance")
         t, dt, dev = W.t, enc.dtype, enc.device
         B = len(waves)
         waves = [wv.reshape(-1).to(device=dev, dtype=torch.float32).contiguous() for wv in waves]
@@ -402,7 +405,7 @@ class EncoderTape:
             ops.dropout(x1, reg.hidden_dropout, _site_seed(base, "pos"), out=x1)
         tape.update(fp_ln=fp_ln, xg=xg, xg_off=xg_off, pre_pos=pre_pos, T=T, toff=toff, reg=reg, base=base, spec_rows=spec_rows)
         x, layers = self._stack_forward(x1, T, reg, base)
-        out, head = self._head_forward(x, T, toff)
+        out, head = self._head_forward(x, T, toff, pool_ranges)
         tape.update(layers=layers, x_last=x, **head)
         return out, tape
 
@@ -459,12 +462,22 @@ class EncoderTape:
             out = x
         return out, dict(cfg=cfg, saved=saved, keep=(skip, seeds, cu, klen, bufs, lses, x), skip=[bool(v) for v in skip])
 
-    # -- final LayerNorm, AvgPool1d over time, projection (ref:model/audio_encoder.py:56-63,87)
-    def _head_forward(self, x: torch.Tensor, T: Sequence[int], toff: Sequence[int]):
+    # -- final LayerNorm, downsample over time (AvgPool1d / stack / ctc range means), projection (ref:model/audio_encoder.py:56-87)
+    def _head_forward(self, x: torch.Tensor, T: Sequence[int], toff: Sequence[int], pool_ranges=None):
         W, enc = self.W, self.enc
         t, dt, dev = W.t, enc.dtype, enc.device
         B, H = len(T), self.hidden
         lnf = ops.layernorm(x, t["final_ln_g"], t["final_ln_b"], self.ln_eps)
+        method = enc.downsample_method
+        if method == "stack":          # P_u = T_u // f rows of f frames side by side (f H wide, the projection's K); the T_u % f last frames are cropped
+            pooled, P = ops.stack_rows_batch(lnf, T, int(enc.downsample_factor))
+            return ops.gemm(pooled, t["proj_w"], bias=t["proj_b"]), dict(pooled=pooled, P=P, poff=_offsets(P))
+        if method == "ctc_pool":       # one row per range: the mean of its frames; the backward gathers through the inverse index built here on the host
+            packed, P = ops.segment_ranges_pack(pool_ranges, T)
+            row_ptr, cols = ops.segment_csr(packed, toff[B])
+            seg = (L.h2d(packed, torch.int64, dev), L.h2d(row_ptr, torch.int64, dev), L.h2d(cols, torch.int32, dev))
+            pooled = ops.segment_mean_batch(lnf, seg[0])
+            return ops.gemm(pooled, t["proj_w"], bias=t["proj_b"]), dict(pooled=pooled, P=P, poff=_offsets(P), seg=seg)
         pooled, P = ops.avgpool_batch(lnf, T, enc.pool_kernel, enc.pool_stride)      # one launch for the ragged batch
         poff = _offsets(P)
         out = ops.gemm(pooled, t["proj_w"], bias=t["proj_b"])
@@ -558,8 +571,14 @@ class EncoderTape:
         ops.wgrad_acc(d_out, tape["pooled"], g["proj_w"], db=g["proj_b"])
         d_pooled = ops.dgrad(d_out, t["proj_w"])
         d_lnf = torch.empty((NT, H), device=d_out.device, dtype=dt)
-        ops.avgpool_bwd_batch(d_pooled, d_lnf, [poff[u + 1] - poff[u] for u in range(B)], T, [poff[u] for u in range(B)], [toff[u] for u in range(B)],
-                              enc.pool_kernel, enc.pool_stride)
+        method = getattr(enc, "downsample_method", "pool")
+        if method == "stack":
+            ops.stack_rows_bwd_batch(d_pooled, T, int(enc.downsample_factor), out=d_lnf)
+        elif method == "ctc_pool":
+            ops.segment_mean_bwd_batch(d_pooled, *tape["seg"], NT, out=d_lnf)
+        else:
+            ops.avgpool_bwd_batch(d_pooled, d_lnf, [poff[u + 1] - poff[u] for u in range(B)], T, [poff[u] for u in range(B)], [toff[u] for u in range(B)],
+                                  enc.pool_kernel, enc.pool_stride)
         dx = ops.layernorm_bwd(tape["x_last"], t["final_ln_g"], t["final_ln_b"], d_lnf, self.ln_eps, g["final_ln_g"], g["final_ln_b"])
         done(["proj_w", "proj_b", "final_ln_g", "final_ln_b"])
         return dx
@@ -1082,13 +1101,20 @@ class KDTrainer:
         return self.micro_batch([wave], [text_ids], [response_ids])[0]
 
     def micro_batch(self, waves: Sequence[torch.Tensor], text_ids: Sequence[torch.Tensor], response_ids: Sequence[torch.Tensor],
-                    close_window: Optional[bool] = None) -> List[Dict[str, float]]:
+                    close_window: Optional[bool] = None, pool_ranges=None) -> List[Dict[str, float]]:
         """len(waves) micro-steps of ONE accumulation window processed together as a packed, ragged batch.  The encoder
         weights do not change inside a window, so this is the same arithmetic as the reference's sequential batch-size-1
         micro-steps (each loss still divided by grad_accum_interval, gradients summed) — but every GEMM sees all the
         window's tokens at once instead of ~200 rows.  ids are 1-D with the BOS already stripped (ref:trainer.py:155-156).
-        Returns per-utterance losses (ref:trainer.py:325-370)."""
+        pool_ranges: the samples' `pool_ranges_4` (one list of (start, end) frame ranges per utterance, ref:trainer.py:278) — required by the
+        `ctc_pool` downsample, refused otherwise.  Returns per-utterance losses (ref:trainer.py:325-370)."""
         enc, llm = self.enc, self.llm
+        if enc.downsample_method == "ctc_pool":
+            if pool_ranges is None or len(pool_ranges) != len(waves) or any(r is None for r in pool_ranges):
+                raise L.SpeechLLMError("downsample_method ctc_pool: micro_batch needs pool_ranges, one list of (start, end) frame ranges per utterance "
+                                       "(the dataset's pool_ranges_4)")
+        elif pool_ranges is not None:
+            raise L.SpeechLLMError(f"pool_ranges are read by the ctc_pool downsample only; this encoder downsamples with `{enc.downsample_method}`")
         dev, dt = enc.device, enc.dtype
         emb = llm.model.embed_tokens
         B = len(waves)
@@ -1102,8 +1128,9 @@ class KDTrainer:
         response_ids = [r if r.is_cuda else L.h2d(r, r.dtype, dev) for r in response_ids]      # (asynchronous uploads: nothing in a window may stall the stream)
         text_ids = [t_ if t_.is_cuda else L.h2d(t_, t_.dtype, dev) for t_ in text_ids]
         ns = [int(r.shape[0]) for r in response_ids]
+        ds_kw = {} if pool_ranges is None else dict(pool_ranges=pool_ranges)
         audio, etape = self.enc_tape.forward(waves, self.reg, step=self.micro_batches,
-                                             masked_spec_embed=self.master.get("encoder.masked_spec_embed"))   # (sum P, H) packed
+                                             masked_spec_embed=self.master.get("encoder.masked_spec_embed"), **ds_kw)   # (sum P, H) packed
         self.micro_batches += 1
         poff = etape["poff"]
         pre, suf = emb(self.prefix_ids)[0], emb(self.suffix_ids)[0, 1:]
