@@ -50,6 +50,7 @@ enum sl_status {
 enum sl_act { SL_ACT_NONE = 0, SL_ACT_GELU = 1, SL_ACT_SILU_MUL = 2, SL_ACT_ROPE_KV = 3 };
 enum sl_w_layout { SL_W_ROWMAJOR = 0, SL_W_PACKED = 1 };
 #define SL_W_PACKED_E4M3 2                       /* sl_gemm_args.w_layout: an e4m3 weight image (sl_pack_weight_e4m3) */
+#define SL_W_PACKED_MXFP4 4                      /* sl_gemm_args.w_layout: an MXFP4 weight image (sl_pack_weight_mxfp4); 3 is not a layout */
 
 const char* sl_last_error(void);       /* thread-local, never NULL */
 #define SL_ABI_VERSION 7
@@ -113,6 +114,32 @@ size_t sl_w8_image_bytes(int32_t N, int32_t K);
 int sl_pack_weight_e4m3(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype, sl_stream stream);
 int sl_pack_weight_e4m3_host(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype);
 int32_t sl_w8_max_rows(void);
+
+/* Weight-only 4-bit for the decode step of small batches: the "MXFP4 weight image" of a bf16 / fp16 weight W (N, K), K % 128 == 0,
+ * Np = ceil(N/16)*16.  The OCP MX format: e2m1 elements in blocks of 32 consecutive k of one row, one e8m0 scale byte per block.
+ *   Block scale: amax = max |w| of the block (NaN elements skipped); e = the smallest integer with amax <= 6 * 2^e, clamped to
+ *   [-13, 13]; an all-zero block and every padding row take e = 0; the byte is e + 127.  With the clamp every dequantised value
+ *   (0.5 * 2^-13 .. 6 * 2^13) is a normal number in fp16 as well as in bf16: one image serves both model dtypes.
+ *   Elements: float(w) / 2^e rounded to the e2m1 grid {0, .5, 1, 1.5, 2, 3, 4, 6}, to nearest with ties to the even code, saturating
+ *   at +-6 (inf included; a NaN element becomes code 0); the sign is bit 3; a value that rounds to zero is code 0x0 (no negative zero).
+ *   Layout: fragment-major over QUADS of 32-wide MFMA k-steps, img[f][j][lane][16 B], f < Np/16, j < K/128, 64 lanes.  Dword d (0..3)
+ *   of a lane's 16 bytes holds the 8 elements k = 128 j + 32 d + 8 (lane >> 4) + i of row 16 f + (lane & 15); element 2b is the low
+ *   nibble of byte b, element 2b+1 the high nibble.  A lane load is 16 bytes, a wave load 1 KiB contiguous, and one dword is the A
+ *   fragment of one 16x16x32 MFMA after four v_cvt_scalef32_pk_{bf16,f16}_fp4 (byte select 0..3).
+ *   Scales: behind the elements, at byte offset Np*K/2, as sc[f][j][r][d]: one byte for row 16 f + r, block 4 j + d, so a lane reads
+ *   its four scales as one dword at ((f * K/128 + j) * 16 + (lane & 15)) * 4.  One pointer names a whole weight.
+ *   sl_w4_image_bytes        Np*K/2 + Np*K/32; 0 on a bad argument (N <= 0, K <= 0, K % 128 != 0)
+ *   sl_pack_weight_mxfp4     src (N, K) row stride ld_src on the device -> dst (16-byte aligned, sl_w4_image_bytes) on the device
+ *   sl_pack_weight_mxfp4_host the same routines on host memory (no GPU needed): the same bits
+ *   sl_w4_max_rows           largest row count the MXFP4 skinny kernels take: sl_w8_max_rows()
+ * SL_F32 is SL_ERR_UNSUPPORTED, K % 128 != 0 is SL_ERR_ARG.  sl_gemm / sl_gemm_fused_decode take the image with
+ * w_layout = SL_W_PACKED_MXFP4 for up to sl_w4_max_rows() rows (more: SL_ERR_UNSUPPORTED, nothing is launched).  The MFMA operands are
+ * exactly the dequantised values e2m1 * 2^e (the scale is applied by the conversion), so the product is the 16-bit kernel's on
+ * dq(W): no scale multiply follows the reduction.  fuse_rms may take rstd_in.  GELU, batches, transposes and groups are not built. */
+size_t sl_w4_image_bytes(int32_t N, int32_t K);
+int sl_pack_weight_mxfp4(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype, sl_stream stream);
+int sl_pack_weight_mxfp4_host(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype);
+int32_t sl_w4_max_rows(void);
 
 /* Decode-only fusions on top of sl_gemm (packed weights; M <= 16 rows run the skinny kernel, more rows the
  * LDS-staged streaming kernel of gemm_stream.hip):
@@ -726,11 +753,14 @@ typedef struct {
    * SL_WDEC_E4M3: they are e4m3 weight images (sl_pack_weight_e4m3) of the same rows, in the same order and with the same gain fold,
    * as the 16-bit decode copies; dec_fused_norm must be 1.  The decode step then runs the skinny structure on
    * w_layout = SL_W_PACKED_E4M3 with the unfused lm_head + sl_greedy_select, for up to sl_w8_max_rows() rows: more rows, SL_F32 or a
-   * reduction length that is no multiple of 64 are SL_ERR_UNSUPPORTED before any launch.  Prefill ignores the field. */
+   * reduction length that is no multiple of 64 are SL_ERR_UNSUPPORTED before any launch.  Prefill ignores the field.
+   * SL_WDEC_MXFP4: the same with MXFP4 weight images (sl_pack_weight_mxfp4), w_layout = SL_W_PACKED_MXFP4, sl_w4_max_rows() and
+   * reduction lengths that are multiples of 128.  2 and 3 are not formats. */
   int32_t dec_fused_norm, reserved;
 } sl_llama_model;
 #define SL_WDEC_MODEL_DTYPE 0
 #define SL_WDEC_E4M3        1
+#define SL_WDEC_MXFP4       4
 
 typedef struct {
   void* k_cache; void* v_cache;  /* (n_layers, slots, n_kv, max_ctx, D) each: elements of the model dtype, or bytes (reserved = SL_KV_FP8_E4M3) */

@@ -44,7 +44,7 @@ if __name__ == '__main__':
     config = importlib.import_module("llm-speech-summarization_amd.config").load_config(args.config)
     dtype = importlib.import_module("llm-speech-summarization_amd.config").runtime_dtype(config)
     kv_dtype = importlib.import_module("llm-speech-summarization_amd.config").runtime_kv_dtype(config)     # runtime.kv_dtype: fp8 | model
-    w_dtype = importlib.import_module("llm-speech-summarization_amd.config").runtime_weight_dtype(config)  # runtime.weight_dtype: fp8 | model
+    w_dtype = importlib.import_module("llm-speech-summarization_amd.config").runtime_weight_dtype(config)  # runtime.weight_dtype: fp8 | mxfp4 | model
     llm_inferencer = LLMSpeechTextInference(config=config, audio_encoder_checkpoint=args.audio_encoder_checkpoint,
                                             device=torch.device(f"cuda:{args.gpu_idx}"), dtype=dtype, kv_cache_dtype=kv_dtype, weight_dtype=w_dtype)
     audio, sr = load_audio_16k(args.audio_file)

@@ -21,7 +21,9 @@ KV_MODEL_DTYPE, KV_FP8_E4M3 = 0, 1      # speechllm.h SL_KV_*: the K/V cache for
 ACT_NONE, ACT_GELU, ACT_SILU_MUL, ACT_ROPE_KV = 0, 1, 2, 3
 POST_NONE, POST_DROPOUT, POST_GELU_BWD, POST_SILU_MUL_BWD = 0, 1, 2, 3      # sl_gemm_ex_args.post_op
 W_ROWMAJOR, W_PACKED, W_PACKED_E4M3 = 0, 1, 2     # W_PACKED_E4M3: an e4m3 weight image (sl_pack_weight_e4m3)
+W_PACKED_MXFP4 = 4                          # an MXFP4 weight image (sl_pack_weight_mxfp4); 3 is not a layout
 WDEC_MODEL_DTYPE, WDEC_E4M3 = 0, 1          # speechllm.h SL_WDEC_*: the format of a model's decode weights (sl_llama_model.reserved)
+WDEC_MXFP4 = 4                              # MXFP4 weight images; 2 and 3 are not formats
 COMM_ID_BYTES = 128          # SL_COMM_ID_BYTES = sizeof(ncclUniqueId)
 MAX_DECODE_BATCH = 2048      # SL_MAX_DECODE_BATCH: sequences per generate call / rows per decode step
 
@@ -230,6 +232,10 @@ _PROTOS = {
     "sl_pack_weight_e4m3": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "sl_pack_weight_e4m3_host": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32]),
     "sl_w8_max_rows": (c_i32, []),
+    "sl_w4_image_bytes": (c_sz, [c_i32, c_i32]),
+    "sl_pack_weight_mxfp4": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "sl_pack_weight_mxfp4_host": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32]),
+    "sl_w4_max_rows": (c_i32, []),
     "sl_gemm_fused_decode": (c_i32, [C.POINTER(GemmArgs), C.POINTER(GemmFused), c_vp]),
     "sl_gemm_split_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "sl_gemm_split_count": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
@@ -417,15 +423,18 @@ def kv_format_code(kv_cache_dtype) -> int:
 
 def weight_format_code(weight_dtype) -> int:
     """`weight_dtype` of the Python surface -> SL_WDEC_*: None (decode weights in the model dtype), "fp8" or torch.float8_e4m3fn (e4m3
-    weight images with one fp32 scale per output row, for decode steps of up to sl_w8_max_rows() rows)."""
+    weight images with one fp32 scale per output row, for decode steps of up to sl_w8_max_rows() rows), "mxfp4" or its alias "fp4" (MXFP4
+    weight images: e2m1 elements with one e8m0 scale per 32, for decode steps of up to sl_w4_max_rows() rows)."""
     if weight_dtype is None:
         return WDEC_MODEL_DTYPE
     if isinstance(weight_dtype, str):
         if weight_dtype == "fp8":
             return WDEC_E4M3
+        if weight_dtype in ("mxfp4", "fp4"):
+            return WDEC_MXFP4
     elif weight_dtype == torch.float8_e4m3fn:
         return WDEC_E4M3
-    raise SpeechLLMError(f"unsupported weight_dtype {weight_dtype!r}: None (the model dtype), 'fp8' or torch.float8_e4m3fn")
+    raise SpeechLLMError(f"unsupported weight_dtype {weight_dtype!r}: None (the model dtype), 'fp8' or torch.float8_e4m3fn, 'mxfp4' (alias 'fp4')")
 
 
 def is16(dt: torch.dtype) -> bool:

@@ -70,6 +70,8 @@ class AudioLlamaForCausalLM:
         # weight_dtype: None = decode weights in the model dtype; "fp8" / torch.float8_e4m3fn = decode steps of up to sl_w8_max_rows() rows read e4m3
         # weight images (one byte per element, one fp32 scale per output row: half the bytes a small batch streams per token); larger batches
         # and prefill keep the 16-bit weights.  16-bit models only; results differ from the 16-bit weights' (e4m3_dequantised_state_dict).
+        # "mxfp4" (alias "fp4") = the same with MXFP4 weight images (e2m1 elements, one e8m0 scale per 32: a quarter of the bytes), up to
+        # sl_w4_max_rows() rows; a different model again (mxfp4_dequantised_state_dict).
         self.weight_format = L.WDEC_MODEL_DTYPE
         self.set_weight_dtype(weight_dtype)
         self.config = SimpleNamespace(vocab_size=arch.vocab_size, hidden_size=arch.hidden_size,
@@ -146,6 +148,8 @@ class AudioLlamaForCausalLM:
                 self._w.build_decode_weights()
             if self.weight_format == L.WDEC_E4M3:
                 self._w.build_decode_weights_e4m3()
+            if self.weight_format == L.WDEC_MXFP4:
+                self._w.build_decode_weights_mxfp4()
             self._sd = None  # device copy is the only copy from here on (6.4 GB bf16 for Llama-3.2-3B)
         return self
 
@@ -159,26 +163,29 @@ class AudioLlamaForCausalLM:
             self.kv_format = fmt
 
     def set_weight_dtype(self, weight_dtype) -> None:
-        """Switch the decode-weight format (None / "fp8" / torch.float8_e4m3fn).  The e4m3 images are built on first use and kept; which
-        struct a call runs is decided per call (_struct_for), and a decode graph captured for one struct is never replayed for the other."""
+        """Switch the decode-weight format (None / "fp8" / torch.float8_e4m3fn / "mxfp4").  The images are built on first use and kept; which
+        struct a call runs is decided per call (_struct_for), and a decode graph captured for one struct is never replayed for another."""
         fmt = L.weight_format_code(weight_dtype)
-        if fmt == L.WDEC_E4M3:
+        if fmt != L.WDEC_MODEL_DTYPE:
+            opt, name, kmul = ("mxfp4", "MXFP4", 128) if fmt == L.WDEC_MXFP4 else ("fp8", "e4m3", 64)
             if not L.is16(self.dtype):
-                raise L.SpeechLLMError("weight_dtype='fp8' needs a bfloat16 or float16 model: float32 is the parity mode and keeps its weights in float32")
+                raise L.SpeechLLMError(f"weight_dtype='{opt}' needs a bfloat16 or float16 model: float32 is the parity mode and keeps its weights in float32")
             if not self.pack_decode:
-                raise L.SpeechLLMError("weight_dtype='fp8' needs pack_decode=True: the e4m3 weights are decode copies beside the packed 16-bit ones")
+                raise L.SpeechLLMError(f"weight_dtype='{opt}' needs pack_decode=True: the {name} weights are decode copies beside the packed 16-bit ones")
             a = self.arch
             ks = dict(hidden_size=a.hidden_size, attention_width=a.num_attention_heads * a.head_dim, intermediate_size=a.intermediate_size)
-            bad = {n: k for n, k in ks.items() if k % 64}
+            bad = {n: k for n, k in ks.items() if k % kmul}
             if bad:
-                raise L.SpeechLLMError(f"weight_dtype='fp8' needs every reduction length to be a multiple of 64, not {bad}")
+                raise L.SpeechLLMError(f"weight_dtype='{opt}' needs every reduction length to be a multiple of {kmul}, not {bad}")
             if getattr(self, "_w", None) is not None:
-                self._w.build_decode_weights_e4m3()
+                self._w.build_decode_weights_mxfp4() if fmt == L.WDEC_MXFP4 else self._w.build_decode_weights_e4m3()
         self.weight_format = fmt
 
     def _struct_for(self, B: int):
-        """(model struct, its name) for a call of B sequences: the e4m3 struct when the option is on and the batch is within its range"""
+        """(model struct, its name) for a call of B sequences: the e4m3 / MXFP4 struct when the option is on and the batch is within its range"""
         w = self._dev()
+        if self.weight_format == L.WDEC_MXFP4 and B <= L.lib().sl_w4_max_rows():
+            return w.struct_mxfp4, "mxfp4"
         if self.weight_format == L.WDEC_E4M3 and B <= L.lib().sl_w8_max_rows():
             return w.struct_e4m3, "e4m3"
         return w.struct, "16-bit" if L.is16(self.dtype) else "float32"

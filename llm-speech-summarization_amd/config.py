@@ -58,12 +58,14 @@ def runtime_kv_dtype(config):
 
 def runtime_weight_dtype(config):
     """The decode-weight format a config's `runtime.weight_dtype` names: `model` (default: the model dtype) -> None, `fp8` -> "fp8"
-    (e4m3 weight images for decode steps of small batches, 16-bit models only) — the value the `weight_dtype` keyword of the model
-    classes takes."""
+    (e4m3 weight images for decode steps of small batches, 16-bit models only), `mxfp4` / `fp4` -> "mxfp4" (MXFP4 weight images, the
+    same range) — the value the `weight_dtype` keyword of the model classes takes."""
     rt = config.get("runtime", {}) if hasattr(config, "get") else {}
     name = str((rt or {}).get("weight_dtype", "model"))
-    if name not in ("model", "fp8"):
-        raise ValueError(f"runtime.weight_dtype: {name!r} is not one of ['fp8', 'model']")
+    if name not in ("model", "fp8", "mxfp4", "fp4"):
+        raise ValueError(f"runtime.weight_dtype: {name!r} is not one of ['fp4', 'fp8', 'model', 'mxfp4']")
+    if name in ("mxfp4", "fp4"):      # MXFP4 weight images (e2m1 elements, one e8m0 scale per 32); `fp4` is an alias
+        return "mxfp4"
     return "fp8" if name == "fp8" else None
 
 

@@ -157,6 +157,44 @@ int main() {
     EXPECT_ARG_ERROR(sl_gemm(&wa, nullptr));
     free(src); free(img);
   }
+  {   // MXFP4 weight images: the host packer under the sanitizers on a (40, 384) bf16 weight read with a row stride of 392 out of an
+      // exactly-sized allocation into an exactly-sized image, and the refusals
+    const int N = 40, K = 384, ld = 392;
+    const size_t bytes = sl_w4_image_bytes(N, K);
+    EXPECT(bytes == (size_t)48 * 192 + 48 * 12, "MXFP4 image bytes");
+    EXPECT(sl_w4_image_bytes(N, 192) == 0 && sl_w4_image_bytes(0, 128) == 0, "MXFP4 image bytes of a bad shape");
+    uint16_t* src = (uint16_t*)malloc(((size_t)(N - 1) * ld + K) * sizeof(uint16_t));
+    unsigned char* img = (unsigned char*)aligned_alloc(16, bytes);
+    for (int n = 0; n < N; ++n)
+      for (int k = 0; k < K; ++k) src[(size_t)n * ld + k] = n == 7 ? 0 : (uint16_t)(0x3C00 + ((n * 131 + k * 17) & 0x3FF) + ((k & 1) << 15));   // bf16 bits, row 7 all zero
+    src[(size_t)3 * ld + 5] = 0x7F80; src[(size_t)3 * ld + 40] = 0x7FC0; src[(size_t)4 * ld + 9] = 0x0001;      // +inf, a NaN, the smallest subnormal
+    EXPECT(sl_pack_weight_mxfp4_host(src, ld, img, N, K, SL_BF16) == 0, "host packer runs");
+    const unsigned char* sc = img + (size_t)48 * K / 2;
+    bool range = true, pad = true, neg_zero = false;
+    for (size_t i = 0; i < (size_t)48 * K / 32; ++i) range = range && sc[i] >= 127 - 13 && sc[i] <= 127 + 13;
+    for (int j = 0; j < K / 128; ++j) {
+      for (int d = 0; d < 4; ++d) pad = pad && sc[(((size_t)0 * (K / 128) + j) * 16 + 7) * 4 + d] == 127;      // the all-zero row 7: e = 0
+      for (int r = 8; r < 16; ++r)
+        for (int d = 0; d < 4; ++d) pad = pad && sc[(((size_t)2 * (K / 128) + j) * 16 + r) * 4 + d] == 127;    // fragment 2: rows 40..47
+      for (int lane = 0; lane < 64; ++lane)
+        if ((lane & 15) >= 8)
+          for (int e = 0; e < 16; ++e) pad = pad && img[(((size_t)2 * (K / 128) + j) * 64 + lane) * 16 + e] == 0;
+    }
+    for (size_t i = 0; i < (size_t)48 * K / 2; ++i) neg_zero = neg_zero || (img[i] & 0x0F) == 0x08 || (img[i] & 0xF0) == 0x80;
+    EXPECT(range && pad && !neg_zero, "scale bytes within the clamp; zero and padding rows: e = 0, zero codes; no negative zero");
+    EXPECT(sl_pack_weight_mxfp4_host(src, ld, img, N, K, SL_F32) == SL_ERR_UNSUPPORTED, "MXFP4 image of a float32 weight");
+    EXPECT_ARG_ERROR(sl_pack_weight_mxfp4_host(src, ld, img, N, 192, SL_BF16));
+    EXPECT_ARG_ERROR(sl_pack_weight_mxfp4_host(src, K - 1, img, N, K, SL_BF16));
+    EXPECT_ARG_ERROR(sl_pack_weight_mxfp4(src, ld, img, N, 192, SL_F16, nullptr));
+    EXPECT(sl_w4_max_rows() == 26, "the MXFP4 skinny range");
+    sl_gemm_args wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.A = img; wa.W = img; wa.C = img; wa.lda = wa.ldw = 256; wa.ldc = 256; wa.M = 27; wa.N = 256; wa.K = 256; wa.batch = 1; wa.dtype = SL_BF16; wa.w_layout = SL_W_PACKED_MXFP4;
+    EXPECT(sl_gemm(&wa, nullptr) == SL_ERR_UNSUPPORTED, "MXFP4 layout above sl_w4_max_rows()");
+    wa.M = 4; wa.K = 192; wa.lda = wa.ldw = 192;
+    EXPECT_ARG_ERROR(sl_gemm(&wa, nullptr));
+    free(src); free(img);
+  }
 
   // ---- norms / element-wise / losses
   EXPECT_ARG_ERROR(sl_layernorm(nullptr, nullptr, nullptr, nullptr, 4, 1024, 1e-5f, 0, SL_BF16, nullptr));

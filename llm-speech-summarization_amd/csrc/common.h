@@ -234,6 +234,56 @@ __host__ __device__ inline void sl_w8_chunk(const uint16_t* src, int64_t ld, con
 }
 
 // ----------------------------------------------------------------------------------------------
+// MXFP4 weight images (speechllm.h sl_pack_weight_mxfp4): the routines the device packer and the host entry both run.  Integer
+// arithmetic on the fp32 bits, one exact multiplication by a power of two and comparisons against exact thresholds: the same bits on
+// the host and on the device.  No hardware f32 -> fp4 conversion and no log2f.
+// ----------------------------------------------------------------------------------------------
+// the block exponent: the smallest e with amax <= 6 * 2^e = 1.5 * 2^(e+2), clamped to [-13, 13]; 0 for an all-zero block.  With
+// amax = m * 2^E, 1 <= m < 2 (the fp32 exponent field): e = E - 2 where m <= 1.5, E - 1 above.  inf clamps to 13, fp32 subnormals to -13.
+__host__ __device__ inline int sl_w4_exp(float amax) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, amax) & 0x7fffffffu;
+  if (u == 0u) return 0;
+  const int e = (int)(u >> 23) - 127 - 2 + ((u & 0x7fffffu) > 0x400000u ? 1 : 0);
+  return e < -13 ? -13 : (e > 13 ? 13 : e);
+}
+// fp32 -> e2m1 code of x * 2^-e: round to nearest, ties to the even code (.25 -> 0, .75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4,
+// 5 -> 4), saturating at 6 (inf included); NaN fails every comparison and becomes 0; the sign is bit 3 and never set on code 0.
+__host__ __device__ inline uint32_t sl_q4_e2m1(float x, int e) {
+  const float v = x * __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);      // exact (or a flush far below .25, or inf)
+  const float a = __builtin_fabsf(v);
+  const uint32_t c = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) + (uint32_t)(a > 2.5f) +
+                     (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
+  return (c != 0u && (__builtin_bit_cast(uint32_t, v) >> 31)) ? (c | 8u) : c;
+}
+// the scale byte (e + 127) of row `row`, 32-wide block `blk` (NaN elements are skipped by the comparison, as in sl_w8_absmax)
+__host__ __device__ inline uint32_t sl_w4_scale_byte(const uint16_t* src, int64_t ld, int N, int dtype, int64_t row, int blk) {
+  if (row >= N) return 127u;
+  return (uint32_t)(sl_w4_exp(sl_w8_absmax(src + row * ld + (int64_t)blk * 32, 32, dtype, 0, 1)) + 127);
+}
+// the 16-byte chunk (fragment f, quad step j, lane) of the image; sc4 = the lane's four scale bytes, sc[f][j][lane & 15][0..3], as one dword
+__host__ __device__ inline void sl_w4_chunk(const uint16_t* src, int64_t ld, uint32_t sc4, int N, int dtype, int64_t f, int j, int lane, uint32_t out[4]) {
+  const int64_t row = f * 16 + (lane & 15);
+  out[0] = out[1] = out[2] = out[3] = 0u;
+  if (row >= N) return;
+  const uint16_t* p = src + row * ld + (int64_t)j * 128 + 8 * (lane >> 4);
+  for (int d = 0; d < 4; ++d) {
+    const int e = (int)((sc4 >> (8 * d)) & 0xffu) - 127;
+    for (int i = 0; i < 8; ++i) out[d] |= sl_q4_e2m1(sl_w8_elem_f32(p[32 * d + i], dtype), e) << (4 * i);
+  }
+}
+// 8 e2m1 nibbles (one dword of the image) -> 8 elements of T, each times the block scale: four v_cvt_scalef32_pk_*_fp4, byte select
+// 0..3, every result exact (e2m1 * 2^e is a normal number of both 16-bit types for e in [-13, 13])
+template <typename T> __device__ __forceinline__ u32x4_t sl_dq4x8(uint32_t w, float s);
+template <> __device__ __forceinline__ u32x4_t sl_dq4x8<bf16_t>(uint32_t w, float s) {
+  return u32x4_t{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 0)), __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 1)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 2)), __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, s, 3))};
+}
+template <> __device__ __forceinline__ u32x4_t sl_dq4x8<f16_t>(uint32_t w, float s) {
+  return u32x4_t{__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 0)), __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 1)),
+                 __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 2)), __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, s, 3))};
+}
+
+// ----------------------------------------------------------------------------------------------
 // MFMA 16x16 tile step, dtype-generic.  One "k-step" consumes 64 bytes of K per operand row:
 //   bf16: 32 k  -> one v_mfma_f32_16x16x32_bf16
 //   fp16: 32 k  -> one v_mfma_f32_16x16x32_f16 (same operand / accumulator layout, same cycles)

@@ -366,11 +366,25 @@ __global__ __launch_bounds__(256, 2) void gemm_tiled_glds_kernel(GemmP p) {
 //   v_cvt_scalef32_pk_*: taken as a plain to transcendental VALU slot, 4-8 cycles, that is 50-80 cycles per KiB per wave against the
 //   ~320 cycles per SIMD one KiB of HBM traffic is worth at 8 TB/s over 256 CUs): the loop stays load-bound, so the loads-in-flight
 //   structure (U steps, all loads issued before the first conversion) is carried over from the 16-bit kernel as it is.
+//   W4 (PACKED, 16-bit T, MT 1 / 2): W is an MXFP4 weight image (speechllm.h sl_pack_weight_mxfp4).  The unit is a QUAD of k-steps: one 16-byte
+//   non-temporal load per lane and fragment carries the e2m1 nibbles of four consecutive 32-wide k-steps (one dword each), one dword load carries
+//   the lane's four e8m0 block scales, 16 v_cvt_scalef32_pk_*_fp4 (sl_dq4x8 per dword, the scale operand bit_cast<float>(byte << 23)) make the
+//   four A fragments, four MFMAs take them against the four x fragments of the 256-byte x step.  The MFMA operands are exactly e2m1 * 2^e, so
+//   the accumulation is the 16-bit kernel's on dq(W) and nothing multiplies the sum afterwards (wsc is not used).  All weight and scale loads of
+//   the U steps in flight are issued before the first conversion (U * RF KiB of weights in flight per wave, as in the other forms).
+//   x: a quad step needs 4 * MT 16-byte x fragments where the 16-bit form needs MT; held for U steps that is 16 * MT * U registers, which the
+//   1 024-thread structures (128 registers) cannot give beside fw and acc.  So x is loaded PER STEP, just before that step's conversions and
+//   MFMAs: 16 * MT registers whatever U is.  x is small and re-read by every block (at M = 1 all 16 rows clamp to one row), so these loads are
+//   L1 / L2 hits; but the vector-memory counter retires in order, so waiting for the first x fragment also waits for the weight loads issued
+//   before it — the overlap within a wave is lost after the first step and comes from the other waves of the SIMD.  Staging x through LDS
+//   was not taken: the block's k range is all of K (waves interleave steps), M * K * 2 bytes do not fit for M = 26, K = 8 192, and a chunked
+//   stage needs a barrier per chunk in a loop that has none.  A smaller U alone would cut the bytes in flight instead.  Unmeasured either way.
 // ----------------------------------------------------------------------------------------------
 
-template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false, bool W8 = false>
+template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false, bool W8 = false, bool W4 = false>
 __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX sx) {
   static_assert(!W8 || (PACKED && !KCONT && sizeof(T) == 2 && MT <= 2), "e4m3 weight images: packed layout, bf16 / fp16, up to 32 rows");
+  static_assert(!W4 || (PACKED && !KCONT && !W8 && sizeof(T) == 2 && MT <= 2), "MXFP4 weight images: packed layout, bf16 / fp16, up to 32 rows");
   constexpr int VEC = Vec16<T>::VEC;
   constexpr int KSTEP = MMA<T>::KSTEP;
   constexpr int RB = 16 * RF;
@@ -384,7 +398,8 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
   const int r = lane & 15, q = lane >> 4;
   const int z = blockIdx.y;
   const int n0 = blockIdx.x * RB;
-  const int nks_full = W8 ? p.K / (2 * KSTEP) : p.K / KSTEP;  // full 64-byte steps of W (W8: 64 bytes = a pair of k-steps, 128 bytes of x)
+  // full 64-byte steps of W (W8: 64 bytes = a pair of k-steps, 128 bytes of x; W4: a quad of k-steps, 256 bytes of x)
+  const int nks_full = W4 ? p.K / (4 * KSTEP) : W8 ? p.K / (2 * KSTEP) : p.K / KSTEP;
 
   const T* A = (const T*)p.A + (int64_t)z * p.sA;
   const T* W = (const T*)p.W + (int64_t)z * p.sW;
@@ -430,6 +445,17 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
     if (tid < RB) wsc[tid] = scales[n0 + tid < np ? n0 + tid : np - 16 + (tid & 15)];
   }
 
+  [[maybe_unused]] const uint32_t* scp[W4 ? RF : 1];      // W4: the lane's scale dword of fragment f, quad step 0 (16 dwords per step)
+  if constexpr (W4) {
+    const int nfrag = (p.N + 15) >> 4;
+    const uint32_t* sc = (const uint32_t*)((const unsigned char*)p.W + (int64_t)nfrag * 8 * p.K);      // behind the elements: Np * K / 2 bytes
+#pragma unroll
+    for (int f = 0; f < RF; ++f) {
+      int fi = (n0 >> 4) + f; fi = fi < nfrag ? fi : nfrag - 1;
+      scp[f] = sc + (int64_t)fi * nks_full * 16 + r;
+    }
+  }
+
   auto sumsq = [&](const uint4& u, float& s) {
     float e[VEC];
     Vec16<T>::unpack(u, e);
@@ -448,7 +474,52 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
     ks = wave;
     kend = nks_full;
   }
-  if constexpr (W8) {
+  if constexpr (W4) {
+    constexpr int XSTEP = 4 * KSTEP;      // x elements per quad step
+    auto quad = [&](const uint4& w4, uint32_t sc4, const uint4 (&x)[4][MT], int f) {
+      const uint32_t wd[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const uint4 a = as_uint4(sl_dq4x8<T>(wd[d], __builtin_bit_cast(float, ((sc4 >> (8 * d)) & 0xffu) << 23)));
+#pragma unroll
+        for (int t = 0; t < MT; ++t) MMA<T>::step(acc[f][t], a, x[d][t]);
+      }
+    };
+    auto step = [&](const uint4 (&w4)[RF], const uint32_t (&sc4)[RF], int64_t kk) {
+      uint4 fx[4][MT];      // the step's x, loaded here: see the kernel's header
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+#pragma unroll
+        for (int t = 0; t < MT; ++t) fx[d][t] = *(const uint4*)(xp[t] + kk * XSTEP + d * KSTEP);
+#pragma unroll
+      for (int f = 0; f < RF; ++f) quad(w4[f], sc4[f], fx, f);
+      if (fuse) {
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+          for (int t = 0; t < MT; ++t) sumsq(fx[d][t], ss[t]);
+      }
+    };
+    for (; ks + (U - 1) * KSTR < kend; ks += U * KSTR) {
+      uint4 fw[U][RF];
+      uint32_t fs[U][RF];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t kk = ks + u * KSTR;
+#pragma unroll
+        for (int f = 0; f < RF; ++f) { fw[u][f] = ld_nt16(wp[f] + kk * wstep); fs[u][f] = scp[f][kk * 16]; }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) step(fw[u], fs[u], ks + u * KSTR);
+    }
+    for (; ks < kend; ks += KSTR) {
+      uint4 fw[RF];
+      uint32_t fs[RF];
+#pragma unroll
+      for (int f = 0; f < RF; ++f) { fw[f] = ld_nt16(wp[f] + (int64_t)ks * wstep); fs[f] = scp[f][(int64_t)ks * 16]; }
+      step(fw, fs, ks);
+    }
+  } else if constexpr (W8) {
     constexpr int XSTEP = 2 * KSTEP;      // x elements per pair step
     auto pair = [&](const uint4& w8, const uint4 (&x0)[MT], const uint4 (&x1)[MT], int f) {
       const uint4 a0 = as_uint4(sl_dq8x8<T>(u32x2_t{w8.x, w8.y})), a1 = as_uint4(sl_dq8x8<T>(u32x2_t{w8.z, w8.w}));
@@ -572,7 +643,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
   const void* Rb = p.res ? (const void*)((const T*)p.res + (int64_t)z * p.sR) : nullptr;
   auto row_scale = [&](int m) -> float {
     if (!fuse) return 1.0f;
-    if constexpr (W8) {
+    if constexpr (W8 || W4) {
       if (sx.rstd_in) return sx.rstd_in[m];
     }
     float s = 0.f;
@@ -1020,10 +1091,10 @@ static int run_tiled(const GemmP& p0, const TiledPlan& pl, void* sk_ws, const Sl
   return 0;
 }
 
-template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false, bool W8 = false>
+template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false, bool W8 = false, bool W4 = false>
 static int launch_skinny_cfg(GemmP& p, const SkinnyX& sx, int batch, hipStream_t st) {
   dim3 grid((p.N + 16 * RF - 1) / (16 * RF), batch);
-  hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, ACT, RF, NW, U, PACKED, KCONT, W8>), grid, dim3(NW * 64), 0, st, p, sx);
+  hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, ACT, RF, NW, U, PACKED, KCONT, W8, W4>), grid, dim3(NW * 64), 0, st, p, sx);
   SL_CHECK_LAUNCH("gemm_skinny");
   return 0;
 }
@@ -1104,6 +1175,42 @@ static int launch_skinny_w8(GemmP& p, const SkinnyX& sx, int act, hipStream_t st
   }
 }
 
+// MXFP4 weight images (W4): the (fragments, waves) structures of the e4m3 table above, with QUAD steps as the unit — a load is still 16 bytes per
+// lane, K / 128 of them cover a row, so every trip count halves again (K = 3 072: 24 quad steps; 8 192: 64).
+//   * fragments x waves are CARRIED OVER UNMEASURED, for the reason given there.
+//   * the unroll U follows the same rule on the quad steps of a wave, pw = K / 128 / NW: UA (4; 2 for the 1 024-thread structure with two
+//     fragments and two x tiles) where pw % UA == 0, else 3 where pw % 3 == 0, else UA with the remainder in the tail loop.
+//     K = 3 072: gate/up, lm_head 4 x 4 waves, pw 6 -> U 3; qkv 2 x 8, pw 3 -> U 3; o 1 x 16, 24 steps under 16 waves, pw 1 -> the tail loop alone,
+//     one or two single steps per wave; down (8 192) 1 x 16, pw 4 -> U 4.
+//   Nothing here was tuned: structures and unrolls were written down unmeasured, by carrying the rule over, and tools/bench_w4.py then timed them
+//   as they stand (profiles/w4_vs_16bit.txt).  No alternative structure has been measured against them.
+// Any (NW, U) is correct for any K / 128 >= 1, as above: with fewer quad steps than waves the tail loop gives the first K / 128 waves one step
+// each (tests/test_w4_gpu.py runs K = 128, 384, 2 176, 3 072, 8 192, 8 960).
+template <typename T, int MT, int ACT, int RF, int NW, int UA = 4>
+static int launch_skinny_w4_u(GemmP& p, const SkinnyX& sx, hipStream_t st) {
+  const int pw = p.K / 128 / NW;
+  if (pw % UA != 0 && pw % 3 == 0) return launch_skinny_cfg<T, MT, ACT, RF, NW, 3, true, false, false, true>(p, sx, 1, st);
+  return launch_skinny_cfg<T, MT, ACT, RF, NW, UA, true, false, false, true>(p, sx, 1, st);
+}
+template <typename T, int MT, int ACT>
+static int launch_skinny_w4_mt(GemmP& p, const SkinnyX& sx, hipStream_t st) {
+  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || ACT == SL_ACT_ROPE_KV);
+  const int nfrag = (p.N + 15) / 16;
+  if (nfrag >= 1024) return launch_skinny_w4_u<T, MT, ACT, MT == 1 ? 4 : 2, MT == 1 ? 4 : 8>(p, sx, st);
+  if (nfrag >= 256 || PAIRS) return launch_skinny_w4_u<T, MT, ACT, 2, MT == 1 ? 8 : 16, MT == 1 ? 4 : 2>(p, sx, st);
+  if constexpr (!PAIRS) return launch_skinny_w4_u<T, MT, ACT, 1, 16>(p, sx, st);
+  return 0;
+}
+template <typename T>
+static int launch_skinny_w4(GemmP& p, const SkinnyX& sx, int act, hipStream_t st) {
+  const bool mt1 = sl_family_rows(p.M) <= 16;
+  switch (act) {
+    case SL_ACT_NONE: return mt1 ? launch_skinny_w4_mt<T, 1, SL_ACT_NONE>(p, sx, st) : launch_skinny_w4_mt<T, 2, SL_ACT_NONE>(p, sx, st);
+    case SL_ACT_SILU_MUL: return mt1 ? launch_skinny_w4_mt<T, 1, SL_ACT_SILU_MUL>(p, sx, st) : launch_skinny_w4_mt<T, 2, SL_ACT_SILU_MUL>(p, sx, st);
+    default: return mt1 ? launch_skinny_w4_mt<T, 1, SL_ACT_ROPE_KV>(p, sx, st) : launch_skinny_w4_mt<T, 2, SL_ACT_ROPE_KV>(p, sx, st);
+  }
+}
+
 template <typename T, int ACT>
 static int launch_skinny(GemmP& p, const SkinnyX& sx, int batch, bool packed, const SlEnv& e, hipStream_t st) {
   if (packed) {
@@ -1165,7 +1272,7 @@ static int gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_ge
   SL_CHECK_ARG(both_t || a->K % vec == 0, "sl_gemm: K=%d must be a multiple of %d", a->K, vec);
   SL_CHECK_ARG(a->lda % vec == 0 && a->strideA % vec == 0, "sl_gemm: lda/strideA must keep rows 16-byte aligned");
   SL_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->W & 15) == 0, "sl_gemm: A and W must be 16-byte aligned");
-  const bool w8 = a->w_layout == SL_W_PACKED_E4M3;
+  const bool w8 = a->w_layout == SL_W_PACKED_E4M3, w4 = a->w_layout == SL_W_PACKED_MXFP4;
   if (w8) {
     // an e4m3 weight image: the skinny kernels' W8 form only — refused before any device work where that form is not built
     if (a->dtype == SL_F32) {
@@ -1176,6 +1283,18 @@ static int gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_ge
     SL_CHECK_ARG(a->batch == 1 && !ex && a->act != SL_ACT_GELU, "sl_gemm: e4m3 weight images take one plain product (batch 1, no sl_gemm_ex features, no GELU)");
     if (sl_family_rows(a->M) > sl_w8_max_rows()) {
       sl_set_error("sl_gemm: e4m3 weight images are built for the skinny kernels, up to sl_w8_max_rows() = %d rows (M=%d)", sl_w8_max_rows(), sl_family_rows(a->M));
+      return SL_ERR_UNSUPPORTED;
+    }
+  } else if (w4) {
+    // an MXFP4 weight image: the skinny kernels' W4 form only — refused before any device work where that form is not built
+    if (a->dtype == SL_F32) {
+      sl_set_error("sl_gemm: MXFP4 weight images (w_layout %d) are built for bf16 / fp16, not float32 (the parity mode)", a->w_layout);
+      return SL_ERR_UNSUPPORTED;
+    }
+    SL_CHECK_ARG(a->K % 128 == 0, "sl_gemm: MXFP4 weight images need K %% 128 == 0 (K=%d)", a->K);
+    SL_CHECK_ARG(a->batch == 1 && !ex && a->act != SL_ACT_GELU, "sl_gemm: MXFP4 weight images take one plain product (batch 1, no sl_gemm_ex features, no GELU)");
+    if (sl_family_rows(a->M) > sl_w4_max_rows()) {
+      sl_set_error("sl_gemm: MXFP4 weight images are built for the skinny kernels, up to sl_w4_max_rows() = %d rows (M=%d)", sl_w4_max_rows(), sl_family_rows(a->M));
       return SL_ERR_UNSUPPORTED;
     }
   } else if (a->w_layout == SL_W_PACKED) {
@@ -1283,6 +1402,12 @@ static int gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_ge
     SL_CHECK_ARG(!sx.rstd_out && !sx.norm_out && (!sx.rstd_in || sx.fuse_rms), "sl_gemm: e4m3 weight images take rstd_in (with fuse_rms) but not rstd_out / norm_out");
     if (e.gemm_log == 2) return 0;
     return a->dtype == SL_F16 ? launch_skinny_w8<f16_t>(p, sx, a->act, st) : launch_skinny_w8<bf16_t>(p, sx, a->act, st);
+  }
+  if (w4) {
+    SL_CHECK_ARG(a->act >= SL_ACT_NONE && a->act <= SL_ACT_ROPE_KV, "sl_gemm: unknown act %d", a->act);
+    SL_CHECK_ARG(!sx.rstd_out && !sx.norm_out && (!sx.rstd_in || sx.fuse_rms), "sl_gemm: MXFP4 weight images take rstd_in (with fuse_rms) but not rstd_out / norm_out");
+    if (e.gemm_log == 2) return 0;
+    return a->dtype == SL_F16 ? launch_skinny_w4<f16_t>(p, sx, a->act, st) : launch_skinny_w4<bf16_t>(p, sx, a->act, st);
   }
   SL_CHECK_ARG(!sx.rstd_in && !sx.rstd_out && !sx.norm_out, "sl_gemm: rstd_in / rstd_out / norm_out are features of the streaming path (M > %d rows, packed weights)", e.stream_min_m);
   void* sk_ws = ex ? ex->sk_ws : nullptr;

@@ -779,6 +779,88 @@ extern "C" int sl_pack_weight_e4m3(const void* src, int64_t ld_src, void* dst, i
 }
 
 // ----------------------------------------------------------------------------------------------
+// MXFP4 weight images (speechllm.h sl_pack_weight_mxfp4): the scale bytes first (one thread per 32-element block, in the order the
+// bytes are stored in), then one thread per 16-byte chunk, which reads its four scale bytes as the dword the GEMM reads.  Both kernels
+// and the host entry run the routines of common.h.
+// ----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void w4_scales_kernel(const uint16_t* __restrict__ src, int64_t ld, uint8_t* __restrict__ sc, int N, int Np, int K, int dtype) {
+  const int nkq = K / 128;
+  const int64_t total = (int64_t)Np * (K / 32);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t fj = i >> 6;      // sc[f][j][r][d]
+    sc[i] = (uint8_t)sl_w4_scale_byte(src, ld, N, dtype, (fj / nkq) * 16 + ((i >> 2) & 15), (int)(fj % nkq) * 4 + (int)(i & 3));
+  }
+}
+__global__ __launch_bounds__(256) void w4_pack_kernel(const uint16_t* __restrict__ src, int64_t ld, const uint32_t* __restrict__ sc, uint4* __restrict__ dst, int N, int Np,
+                                                      int K, int dtype) {
+  const int nkq = K / 128;
+  const int64_t total = (int64_t)(Np / 16) * nkq * 64;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t fj = i >> 6;
+    uint32_t o[4];
+    sl_w4_chunk(src, ld, sc[fj * 16 + (i & 15)], N, dtype, fj / nkq, (int)(fj % nkq), (int)(i & 63), o);
+    dst[i] = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+static int w4_pack_check(const char* who, const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype) {
+  SL_CHECK_ARG(src && dst && N > 0 && K > 0, "%s: bad arguments", who);
+  if (dtype == SL_F32) {
+    sl_set_error("%s: MXFP4 weight images are built for bf16 / fp16 weights, not float32 (the parity mode)", who);
+    return SL_ERR_UNSUPPORTED;
+  }
+  SL_CHECK_ARG(sl_is16(dtype), "%s: unknown dtype %d", who, dtype);
+  SL_CHECK_ARG(K % 128 == 0, "%s: K=%d must be a multiple of 128 (quads of 32-wide k-steps)", who, K);
+  SL_CHECK_ARG(ld_src >= K, "%s: ld_src=%lld < K=%d", who, (long long)ld_src, K);
+  SL_CHECK_ARG(((uintptr_t)dst & 15) == 0 && ((uintptr_t)src & 1) == 0, "%s: dst must be 16-byte aligned", who);
+  return 0;
+}
+
+extern "C" size_t sl_w4_image_bytes(int32_t N, int32_t K) {
+  if (N <= 0 || K <= 0 || K % 128 != 0) { sl_set_error("sl_w4_image_bytes: N=%d K=%d (K must be a positive multiple of 128)", N, K); return 0; }
+  const size_t Np = ((size_t)N + 15) / 16 * 16;
+  return Np * (size_t)K / 2 + Np * (size_t)K / 32;
+}
+
+extern "C" int32_t sl_w4_max_rows(void) { return sl_w8_max_rows(); }      // the same skinny structures (MT 1 and 2)
+
+extern "C" int sl_pack_weight_mxfp4_host(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype) {
+  SL_TRY(w4_pack_check("sl_pack_weight_mxfp4_host", src, ld_src, dst, N, K, dtype));
+  const int64_t Np = ((int64_t)N + 15) / 16 * 16;
+  const int nkq = K / 128;
+  const uint16_t* s = (const uint16_t*)src;
+  uint8_t* sc = (uint8_t*)dst + Np * K / 2;      // a multiple of 16 bytes behind dst: the dword reads below are aligned
+  for (int64_t f = 0; f < Np / 16; ++f)
+    for (int j = 0; j < nkq; ++j)
+      for (int r = 0; r < 16; ++r)
+        for (int d = 0; d < 4; ++d) sc[((f * nkq + j) * 16 + r) * 4 + d] = (uint8_t)sl_w4_scale_byte(s, ld_src, N, dtype, f * 16 + r, 4 * j + d);
+  uint32_t* out = (uint32_t*)dst;
+  for (int64_t f = 0; f < Np / 16; ++f)
+    for (int j = 0; j < nkq; ++j)
+      for (int lane = 0; lane < 64; ++lane) {
+        const uint8_t* b = sc + ((f * nkq + j) * 16 + (lane & 15)) * 4;
+        const uint32_t sc4 = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+        sl_w4_chunk(s, ld_src, sc4, N, dtype, f, j, lane, out + ((f * nkq + j) * 64 + lane) * 4);
+      }
+  return 0;
+}
+
+extern "C" int sl_pack_weight_mxfp4(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype, sl_stream stream) {
+  SL_TRY(w4_pack_check("sl_pack_weight_mxfp4", src, ld_src, dst, N, K, dtype));
+  const int Np = (N + 15) / 16 * 16;
+  uint8_t* sc = (uint8_t*)dst + (int64_t)Np * K / 2;
+  const int64_t nsc = (int64_t)Np * (K / 32);
+  const unsigned grid_s = (unsigned)(ceil_div64(nsc, 256) < 16384 ? ceil_div64(nsc, 256) : 16384);
+  hipLaunchKernelGGL(w4_scales_kernel, dim3(grid_s), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src, ld_src, sc, N, Np, K, dtype);
+  SL_CHECK_LAUNCH("w4_scales");
+  const int64_t total = (int64_t)(Np / 16) * (K / 128) * 64;
+  const unsigned grid = (unsigned)(ceil_div64(total, 256) < 16384 ? ceil_div64(total, 256) : 16384);
+  hipLaunchKernelGGL(w4_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)src, ld_src, (const uint32_t*)sc, (uint4*)dst, N, Np, K, dtype);
+  SL_CHECK_LAUNCH("w4_pack");
+  return 0;
+}
+
+// ----------------------------------------------------------------------------------------------
 // Flash-decoding: one-token attention split over the context so that small batches still fill the chip.
 //   grid (kv head, sequence, split); each block owns 64 keys: scores -> local softmax -> partial P.V,
 //   and leaves (O[REP][128], m[REP], l[REP]) in fp32; a second tiny kernel merges the splits.

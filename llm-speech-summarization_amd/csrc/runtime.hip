@@ -585,27 +585,33 @@ static int llama_check(const sl_llama_model* m, const sl_kv_cache* kv) {
 }
 
 // sl_llama_model.reserved, the format of the decode weights (speechllm.h SL_WDEC_*), against what a decode step of `rows` rows can run: checked by
-// every entry that decodes, before any launch.  An e4m3 model decodes on the skinny kernels' W8 form only.
+// every entry that decodes, before any launch.  An e4m3 model decodes on the skinny kernels' W8 form only, an MXFP4 model on their W4 form only.
 static int llama_wdec_check(const char* who, const sl_llama_model* m, int rows) {
   if (m->reserved == SL_WDEC_MODEL_DTYPE) return 0;
-  SL_CHECK_ARG(m->reserved == SL_WDEC_E4M3, "%s: unknown decode-weight format %d (sl_llama_model.reserved: 0 = model dtype, 1 = e4m3 weight images)", who, m->reserved);
+  SL_CHECK_ARG(m->reserved == SL_WDEC_E4M3 || m->reserved == SL_WDEC_MXFP4,
+               "%s: unknown decode-weight format %d (sl_llama_model.reserved: 0 = model dtype, 1 = e4m3 weight images, 4 = MXFP4 weight images)", who, m->reserved);
+  const bool w4 = m->reserved == SL_WDEC_MXFP4;
+  const char* name = w4 ? "MXFP4" : "e4m3";
   if (m->dtype == SL_F32) {
-    sl_set_error("%s: e4m3 decode weights are built for bf16 / fp16 models, not float32 (the parity mode)", who);
+    sl_set_error("%s: %s decode weights are built for bf16 / fp16 models, not float32 (the parity mode)", who, name);
     return SL_ERR_UNSUPPORTED;
   }
-  SL_CHECK_ARG(m->dec_fused_norm == 1 && m->lm_head_dec, "%s: e4m3 decode weights need dec_fused_norm = 1 and lm_head_dec", who);
+  SL_CHECK_ARG(m->dec_fused_norm == 1 && m->lm_head_dec, "%s: %s decode weights need dec_fused_norm = 1 and lm_head_dec", who, name);
   for (int l = 0; l < m->n_layers; ++l) {
     const sl_llama_layer& L = m->layers[l];
-    SL_CHECK_ARG(L.wqkv_dec && L.wo_dec && L.wgu_dec && L.wdown_dec, "%s: e4m3 decode weights: layer %d has a null *_dec image", who, l);
+    SL_CHECK_ARG(L.wqkv_dec && L.wo_dec && L.wgu_dec && L.wdown_dec, "%s: %s decode weights: layer %d has a null *_dec image", who, name, l);
   }
   const int ks[3] = {m->hidden, m->n_heads * m->head_dim, m->ffn};
+  const int kmul = w4 ? 128 : 64;
   for (int k : ks)
-    if (k % 64 != 0) {
-      sl_set_error("%s: e4m3 decode weights need every reduction length to be a multiple of 64 (hidden=%d, n_heads*head_dim=%d, ffn=%d)", who, ks[0], ks[1], ks[2]);
+    if (k % kmul != 0) {
+      sl_set_error("%s: %s decode weights need every reduction length to be a multiple of %d (hidden=%d, n_heads*head_dim=%d, ffn=%d)", who, name, kmul, ks[0], ks[1], ks[2]);
       return SL_ERR_UNSUPPORTED;
     }
-  if (sl_family_rows(rows) > sl_w8_max_rows()) {
-    sl_set_error("%s: e4m3 decode weights run up to sl_w8_max_rows() = %d rows per decode step, not %d (use the 16-bit decode copies)", who, sl_w8_max_rows(), sl_family_rows(rows));
+  const int max_rows = w4 ? sl_w4_max_rows() : sl_w8_max_rows();
+  if (sl_family_rows(rows) > max_rows) {
+    sl_set_error("%s: %s decode weights run up to %s() = %d rows per decode step, not %d (use the 16-bit decode copies)", who, name, w4 ? "sl_w4_max_rows" : "sl_w8_max_rows",
+                 max_rows, sl_family_rows(rows));
     return SL_ERR_UNSUPPORTED;
   }
   return 0;
@@ -729,7 +735,7 @@ static int dec_gemm(const sl_llama_model* m, const LlamaWs& w, const void* A, in
   memset(&a, 0, sizeof(a));
   a.A = A; a.lda = lda; a.W = Wp; a.ldw = K; a.C = C; a.ldc = ldc; a.residual = res; a.ldr = ldc;
   a.M = M; a.N = N; a.K = K; a.batch = 1; a.dtype = m->dtype; a.act = act; a.out_f32 = out_f32;
-  a.w_layout = m->reserved == SL_WDEC_E4M3 ? SL_W_PACKED_E4M3 : SL_W_PACKED;      // sl_llama_model.reserved: the format of the *_dec weights
+  a.w_layout = m->reserved == SL_WDEC_E4M3 ? SL_W_PACKED_E4M3 : m->reserved == SL_WDEC_MXFP4 ? SL_W_PACKED_MXFP4 : SL_W_PACKED;      // sl_llama_model.reserved: the format of the *_dec weights
   return sl_gemm_impl(&a, fx, nullptr, st);
 }
 
@@ -774,9 +780,11 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     // small-batch graphs: the prefetch branch runs two matrices ahead of the chain (DecodePrefetch): released where a consumer is launched
     DecodePrefetch* pf = g_prefetch;
     const size_t esz = sl_dtype_size(dt);
-    const bool w8 = m->reserved == SL_WDEC_E4M3;      // e4m3 weight images: bytes + scales
-    const size_t b_qkv = w8 ? sl_w8_image_bytes(qkv_w, H) : (size_t)qkv_w * H * esz, b_o = w8 ? sl_w8_image_bytes(H, nh * D) : (size_t)H * nh * D * esz,
-                 b_gu = w8 ? sl_w8_image_bytes(2 * m->ffn, H) : (size_t)2 * m->ffn * H * esz, b_down = w8 ? sl_w8_image_bytes(H, m->ffn) : (size_t)H * m->ffn * esz;
+    // e4m3 / MXFP4 weight images: elements + scales
+    auto wbytes = [&](int N, int K) -> size_t {
+      return m->reserved == SL_WDEC_E4M3 ? sl_w8_image_bytes(N, K) : m->reserved == SL_WDEC_MXFP4 ? sl_w4_image_bytes(N, K) : (size_t)N * K * esz;
+    };
+    const size_t b_qkv = wbytes(qkv_w, H), b_o = wbytes(H, nh * D), b_gu = wbytes(2 * m->ffn, H), b_down = wbytes(H, m->ffn);
     const sl_llama_layer* Ln = (l + 1 < m->n_layers) ? &m->layers[l + 1] : nullptr;
     if (pf && l == 0) { SL_TRY(pf->ahead(L.wqkv_dec, b_qkv)); SL_TRY(pf->ahead(L.wo_dec, b_o)); }
     if (pf) SL_TRY(pf->ahead(L.wgu_dec, b_gu));                       // ... while qkv, attention and o run
@@ -1256,7 +1264,7 @@ static int decode_graph_key(const GraphCtx& g, int B, DecodeGraphKey& key) {
   key.slots = kv->slots; key.shared_prefix = kv->shared_prefix; key.dtype = m->dtype; key.n_layers = m->n_layers; key.vocab = m->vocab;
   // + the switches that shape the captured launches
   key.fused = m->dec_fused_norm | (sl_env().decode_tiled << 8) | ((sl_env().attn_decode_ks & 127) << 9) | ((g.pin_rows ? 1 : 0) << 16) |
-              ((sl_env().decode_prefetch ? 1 : 0) << 17) | ((kv->reserved & 3) << 18) | ((m->reserved & 3) << 20);
+              ((sl_env().decode_prefetch ? 1 : 0) << 17) | ((kv->reserved & 3) << 18) | ((m->reserved & 7) << 20);
   key.limits = g.limits;
   key.content = model_content_hash(m);
   SL_HIP(hipGetDevice(&key.device));

@@ -342,6 +342,49 @@ def w8_image_parts(img: torch.Tensor, N: int, K: int):
     return b, s
 
 
+def w4_image_bytes(N: int, K: int) -> int:
+    n = int(L.lib().sl_w4_image_bytes(N, K))
+    if n == 0:
+        L.check(-1, "sl_w4_image_bytes")
+    return n
+
+
+def pack_weight_mxfp4(W: torch.Tensor) -> torch.Tensor:
+    """(N, K) bf16 / fp16 weight (row stride W.stride(0)) -> its MXFP4 weight image (sl_pack_weight_mxfp4): a uint8 buffer of
+    sl_w4_image_bytes(N, K) holding the fragment-major e2m1 nibbles and, behind them, one e8m0 scale byte per row and 32 columns.
+    On the GPU through the device packer, on the CPU through the host entry: the same routines, the same bytes."""
+    n, k = W.shape
+    if W.stride(1) != 1:
+        raise L.SpeechLLMError("pack_weight_mxfp4: rows must be contiguous")
+    out = torch.empty(w4_image_bytes(n, k), device=W.device, dtype=torch.uint8)
+    if W.is_cuda:
+        L.check(L.lib().sl_pack_weight_mxfp4(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype), L.stream_ptr()), "sl_pack_weight_mxfp4")
+    else:
+        L.check(L.lib().sl_pack_weight_mxfp4_host(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype)), "sl_pack_weight_mxfp4_host")
+    return out
+
+
+def w4_image_parts(img: torch.Tensor, N: int, K: int):
+    """An MXFP4 weight image -> (e2m1 codes (Np, K) uint8 in natural row / column order, scale bytes (Np, K/32) uint8); Np = ceil(N/16)*16."""
+    Np = (N + 15) // 16 * 16
+    b = img[:Np * K // 2].view(Np // 16, K // 128, 4, 16, 4, 4)          # [f][j][lane >> 4][lane & 15][dword][byte]
+    c = torch.stack([b & 15, b >> 4], dim=-1)                           # element 2b in the low nibble, 2b + 1 in the high one
+    c = c.permute(0, 3, 1, 4, 2, 5, 6).reshape(Np, K)                   # row 16 f + (lane & 15), column 128 j + 32 dword + 8 (lane >> 4) + 2 byte + half
+    s = img[Np * K // 2:Np * K // 2 + Np * K // 32].view(Np // 16, K // 128, 16, 4)      # [f][j][r][d]
+    return c, s.permute(0, 2, 1, 3).reshape(Np, K // 32)
+
+
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def w4_dequantise(img: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """An MXFP4 weight image -> the (N, K) fp64 matrix the kernels multiply by: e2m1 * 2^(scale byte - 127), every value exact."""
+    c, s = w4_image_parts(img.cpu(), N, K)
+    grid = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float64)
+    v = grid[c.long()].view(c.shape[0], K // 32, 32) * torch.exp2(s.double() - 127)[:, :, None]
+    return v.view(c.shape[0], K)[:N]
+
+
 def gemm_decode(A: torch.Tensor, Wp: torch.Tensor, N: int, *, residual=None, act: int = L.ACT_NONE, out_f32: bool = False,
                 fuse_rms: bool = False, eps: float = 1e-5, rope=None, out: Optional[torch.Tensor] = None,
                 split_k: bool = True, rstd_in: Optional[torch.Tensor] = None, rstd_out: Optional[torch.Tensor] = None,
@@ -349,7 +392,8 @@ def gemm_decode(A: torch.Tensor, Wp: torch.Tensor, N: int, *, residual=None, act
                 w_layout: int = L.W_PACKED) -> torch.Tensor:
     """Decode GEMM on packed weights.  rope = dict(cos, sin, pos, seq, k_cache, v_cache, n_heads, n_kv, max_ctx) for ACT_ROPE_KV.
     split_k: hand the kernel a scratch buffer so that row counts > 64 may split K over blocks (gemm_stream.hip).
-    w_layout = W_PACKED_E4M3: Wp is an e4m3 weight image (pack_weight_e4m3), for up to sl_w8_max_rows() rows."""
+    w_layout = W_PACKED_E4M3: Wp is an e4m3 weight image (pack_weight_e4m3), for up to sl_w8_max_rows() rows.
+    w_layout = W_PACKED_MXFP4: Wp is an MXFP4 weight image (pack_weight_mxfp4), for up to sl_w4_max_rows() rows."""
     M, K = A.shape
     if act == L.ACT_SILU_MUL:
         n_out = N // 2

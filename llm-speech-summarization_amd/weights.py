@@ -603,60 +603,43 @@ class LlamaDeviceWeights:
             return f"fp8 decode weights need every reduction length to be a multiple of 64, not {bad}"
         return None
 
-    def build_decode_weights_e4m3(self) -> None:
-        """Third copy of the decode matrices: e4m3 weight images (sl_pack_weight_e4m3: one byte per element, one fp32 scale per output row)
-        of the same folded, permuted, interleaved tensors build_decode_weights packs, and a second sl_llama_model struct
-        (`struct_e4m3`) that differs from `struct` in the five *_dec pointers and `reserved` = SL_WDEC_E4M3 only.  The 16-bit decode
-        copies stay for batches above sl_w8_max_rows(); the images cost about half a copy of the weights more."""
-        if getattr(self, "struct_e4m3", None) is not None:
-            return
-        why = self.e4m3_supported()
-        if why:
-            raise L.SpeechLLMError(why)
+    def _build_decode_images(self, what: str, pack, reserved: int):
+        """The decode matrices in another format: pack() of the same folded, permuted, interleaved tensors build_decode_weights packs
+        (`_decode_sources`), and an sl_llama_model struct that differs from `struct` in the five *_dec pointers and `reserved` only.
+        -> (struct, its layer array, per-layer images, the lm_head image)"""
         self.build_decode_weights()
         if not self.decode_packed or not self.struct.dec_fused_norm:
-            raise L.SpeechLLMError("fp8 decode weights need the packed, gain-folded decode copies (build_decode_weights with fuse_norm)")
-        from . import ops
+            raise L.SpeechLLMError(f"{what} decode weights need the packed, gain-folded decode copies (build_decode_weights with fuse_norm)")
         a = self.arch
         m = L.LlamaModel()
         C.memmove(C.byref(m), C.byref(self.struct), C.sizeof(L.LlamaModel))
         layers = (L.LlamaLayer * a.num_hidden_layers)()
         C.memmove(layers, self._layers, C.sizeof(layers))
-        self.w8_images: List[Dict[str, torch.Tensor]] = []
+        images: List[Dict[str, torch.Tensor]] = []
         for li in range(a.num_hidden_layers):
-            imgs = {n: ops.pack_weight_e4m3(t.contiguous()) for n, t in zip(("qkv", "o", "gu", "down"), self._decode_sources(li, True))}
-            self.w8_images.append(imgs)
+            imgs = {n: pack(t.contiguous()) for n, t in zip(("qkv", "o", "gu", "down"), self._decode_sources(li, True))}
+            images.append(imgs)
             lay = layers[li]
             lay.wqkv_dec, lay.wo_dec, lay.wgu_dec, lay.wdown_dec = (imgs[n].data_ptr() for n in ("qkv", "o", "gu", "down"))
-        self.w8_lm_head = ops.pack_weight_e4m3(self._decode_sources(-1, True).contiguous())
-        m.lm_head_dec = self.w8_lm_head.data_ptr()
+        lm_head = pack(self._decode_sources(-1, True).contiguous())
+        m.lm_head_dec = lm_head.data_ptr()
         m.layers = C.cast(layers, C.POINTER(L.LlamaLayer))
-        m.reserved = L.WDEC_E4M3
+        m.reserved = reserved
         torch.cuda.synchronize(self.device)
-        self._layers_e4m3 = layers
-        self.struct_e4m3 = m
+        return m, layers, images, lm_head
 
-    def e4m3_dequantised_state_dict(self) -> Dict[str, torch.Tensor]:
-        """HF-keyed fp32 CPU state dict of the model the e4m3 decode step computes: the seven projections of every layer and
-        lm_head.weight are the dequantised images (byte value x s[n], formed in fp64, stored as fp32) in natural row order (q / k rows
-        un-permuted, gate / up de-interleaved); the norm gains folded into them are 1.  For tests and for scoring the quantised model
-        offline."""
-        if getattr(self, "struct_e4m3", None) is None:
-            raise L.SpeechLLMError("e4m3_dequantised_state_dict: call build_decode_weights_e4m3 first")
-        from . import ops
+    def _dequantised_state_dict(self, images, lm_head, dq_image) -> Dict[str, torch.Tensor]:
+        """HF-keyed fp32 CPU state dict of the model a quantised decode step computes: the seven projections of every layer and
+        lm_head.weight are dq_image(image, N, K) in natural row order (q / k rows un-permuted, gate / up de-interleaved); the norm gains
+        folded into them are 1."""
         a = self.arch
         H, D, nh, nkv, F_ = a.hidden_size, a.head_dim, a.num_attention_heads, a.num_key_value_heads, a.intermediate_size
         shapes = self.w8_shapes()
-
-        def dq(img: torch.Tensor, name: str) -> torch.Tensor:
-            n, k = shapes[name]
-            b, s = ops.w8_image_parts(img.cpu(), n, k)
-            return (b.contiguous().view(torch.float8_e4m3fn).double() * s.double()[:, None])[:n].float()
-
+        dq = lambda img, name: dq_image(img, *shapes[name])
         perm = self._rope_perm().cpu()
         ones = torch.ones(H, dtype=torch.float32)
-        sd = {"model.embed_tokens.weight": self.embed.float().cpu(), "model.norm.weight": ones.clone(), "lm_head.weight": dq(self.w8_lm_head, "lm_head")}
-        for li, imgs in enumerate(self.w8_images):
+        sd = {"model.embed_tokens.weight": self.embed.float().cpu(), "model.norm.weight": ones.clone(), "lm_head.weight": dq(lm_head, "lm_head")}
+        for li, imgs in enumerate(images):
             p = f"model.layers.{li}."
             qkv = torch.empty(shapes["qkv"], dtype=torch.float32)
             qkv[perm] = dq(imgs["qkv"], "qkv")
@@ -669,16 +652,79 @@ class LlamaDeviceWeights:
             sd[p + "input_layernorm.weight"], sd[p + "post_attention_layernorm.weight"] = ones.clone(), ones.clone()
         return sd
 
+    def build_decode_weights_e4m3(self) -> None:
+        """Third copy of the decode matrices: e4m3 weight images (sl_pack_weight_e4m3: one byte per element, one fp32 scale per output row)
+        of the same folded, permuted, interleaved tensors build_decode_weights packs, and a second sl_llama_model struct
+        (`struct_e4m3`) that differs from `struct` in the five *_dec pointers and `reserved` = SL_WDEC_E4M3 only.  The 16-bit decode
+        copies stay for batches above sl_w8_max_rows(); the images cost about half a copy of the weights more."""
+        if getattr(self, "struct_e4m3", None) is not None:
+            return
+        why = self.e4m3_supported()
+        if why:
+            raise L.SpeechLLMError(why)
+        from . import ops
+        self.struct_e4m3, self._layers_e4m3, self.w8_images, self.w8_lm_head = self._build_decode_images("fp8", ops.pack_weight_e4m3, L.WDEC_E4M3)
+
+    def e4m3_dequantised_state_dict(self) -> Dict[str, torch.Tensor]:
+        """HF-keyed fp32 CPU state dict of the model the e4m3 decode step computes: the seven projections of every layer and
+        lm_head.weight are the dequantised images (byte value x s[n], formed in fp64, stored as fp32) in natural row order (q / k rows
+        un-permuted, gate / up de-interleaved); the norm gains folded into them are 1.  For tests and for scoring the quantised model
+        offline."""
+        if getattr(self, "struct_e4m3", None) is None:
+            raise L.SpeechLLMError("e4m3_dequantised_state_dict: call build_decode_weights_e4m3 first")
+        from . import ops
+
+        def dq(img: torch.Tensor, n: int, k: int) -> torch.Tensor:
+            b, s = ops.w8_image_parts(img.cpu(), n, k)
+            return (b.contiguous().view(torch.float8_e4m3fn).double() * s.double()[:, None])[:n].float()
+
+        return self._dequantised_state_dict(self.w8_images, self.w8_lm_head, dq)
+
+    # -- opt-in MXFP4 decode weights (include/speechllm.h: MXFP4 weight images, SL_WDEC_MXFP4) -------------------------------------
+    def mxfp4_supported(self) -> Optional[str]:
+        """None, or why this model cannot take MXFP4 decode weights"""
+        if not L.is16(self.dtype):
+            return "mxfp4 decode weights need a bfloat16 or float16 model: float32 is the parity mode"
+        bad = {n: k for n, (_, k) in self.w8_shapes().items() if k % 128}
+        if bad:
+            return f"mxfp4 decode weights need every reduction length to be a multiple of 128, not {bad}"
+        return None
+
+    def build_decode_weights_mxfp4(self) -> None:
+        """A further copy of the decode matrices: MXFP4 weight images (sl_pack_weight_mxfp4: one e2m1 nibble per element, one e8m0 scale
+        byte per row and 32 columns), and the struct `struct_mxfp4` with `reserved` = SL_WDEC_MXFP4.  The 16-bit decode copies stay for
+        batches above sl_w4_max_rows(); the images cost about a quarter copy of the weights more."""
+        if getattr(self, "struct_mxfp4", None) is not None:
+            return
+        why = self.mxfp4_supported()
+        if why:
+            raise L.SpeechLLMError(why)
+        from . import ops
+        self.struct_mxfp4, self._layers_mxfp4, self.w4_images, self.w4_lm_head = self._build_decode_images("mxfp4", ops.pack_weight_mxfp4, L.WDEC_MXFP4)
+
+    def mxfp4_dequantised_state_dict(self) -> Dict[str, torch.Tensor]:
+        """_dequantised_state_dict of the model the MXFP4 decode step computes (every value e2m1 x 2^e, exact in fp32).  For tests and for
+        scoring the quantised model offline: 4-bit weights are a different model."""
+        if getattr(self, "struct_mxfp4", None) is None:
+            raise L.SpeechLLMError("mxfp4_dequantised_state_dict: call build_decode_weights_mxfp4 first")
+        from . import ops
+        return self._dequantised_state_dict(self.w4_images, self.w4_lm_head, lambda img, n, k: ops.w4_dequantise(img, n, k).float())
+
     def n_params(self) -> int:
         return sum(t.numel() for t in self._keep if t.dtype == self.dtype)
 
     def weight_bytes_per_token(self, fmt=None) -> int:
         """Bytes of weights one decode step streams: every layer matrix + final norm + lm_head.  fmt = "fp8" / torch.float8_e4m3fn: the
-        e4m3 weight images instead (bytes and scales; the norm gains are folded in and not read)."""
+        e4m3 weight images instead (bytes and scales; the norm gains are folded in and not read); fmt = "mxfp4": the MXFP4 weight images
+        (4 bits per element + one scale byte per 32: 4.25 bits per weight)."""
         a = self.arch
         if L.weight_format_code(fmt) == L.WDEC_E4M3:
             sh = self.w8_shapes()
             img = lambda n: ((sh[n][0] + 15) // 16 * 16) * (sh[n][1] + 4)
+            return a.num_hidden_layers * sum(img(n) for n in ("qkv", "o", "gu", "down")) + img("lm_head")
+        if L.weight_format_code(fmt) == L.WDEC_MXFP4:
+            sh = self.w8_shapes()
+            img = lambda n: ((sh[n][0] + 15) // 16 * 16) * (sh[n][1] // 2 + sh[n][1] // 32)
             return a.num_hidden_layers * sum(img(n) for n in ("qkv", "o", "gu", "down")) + img("lm_head")
         per_layer = (a.num_attention_heads + 2 * a.num_key_value_heads) * a.head_dim * a.hidden_size \
             + a.num_attention_heads * a.head_dim * a.hidden_size + 3 * a.intermediate_size * a.hidden_size + 2 * a.hidden_size
