@@ -716,6 +716,37 @@ int sl_hubert_forward_ds(const sl_hubert_model* m, const float* waves, const int
                          const int64_t* out_row_offsets_host, void* last_hidden, const sl_downsample_desc* ds, void* workspace,
                          size_t workspace_bytes, sl_stream stream);
 
+/* CTC word segmentation on the device: what lies between a CTC model's last hidden state and a table of ctc_pool ranges that sl_segment_mean_batch /
+ * sl_hubert_forward_ds accept (ref:preprocess_data/utils.py:127-188 does this per utterance on the host).  Additive to ABI 7.
+ *   sl_ctc_greedy_batch: ids[m] = the lowest column v that attains max_v (x[m] . w[v] + bias[v]); x (n_rows, H) packed frames, w (V, H), bias (V) or
+ *     NULL, all in `dtype` (fp32 / bf16 / fp16); fp32 accumulation in a fixed order per row, the logits are never written, and ids[m] depends on row m
+ *     alone.  1 <= V <= 64 and H a positive multiple of 8, otherwise SL_ERR_ARG before any launch.  n_rows = 0 does nothing.
+ *   sl_ctc_pool_ranges_batch: ids (n_rows) packed, row_offsets_dev (n_utt + 1) int64 on the device, utterance u holding rows row_offsets[u] ..
+ *     row_offsets[u + 1].  Words (HF's Wav2Vec2CTCTokenizer word offsets, group_tokens = True, skip_special_tokens = False): inside every maximal stretch
+ *     of frames without delim_id, [first frame whose id is not blank_id, last such frame + 1); a stretch without such a frame has no word; every id other
+ *     than blank_id / delim_id counts as a letter.  Ranges (ref:preprocess_data/utils.py:155-188), for the words (s_i, e_i) in order: (0, s_0); for
+ *     every word the chunks (s_i + k pr, s_i + k pr + pr) while s_i + k pr < e_i, pr = pool_range; (e_i, s_i+1) between words; (e_last, e_last + 2 pr).
+ *     SL_CTC_RANGES_RAW: exactly that list, utterance-relative, unclamped, empty pairs kept (what the reference stores).
+ *     SL_CTC_RANGES_PACKED: each pair clamped to [0, T_u), pairs that are empty afterwards dropped, row_offsets[u] added: {first row, end row} records
+ *       in packed frame rows, none of which leaves its utterance.
+ *     An utterance without a word gives the one range (0, T_u) in both modes (the reference raises IndexError); with T_u = 0 packed mode gives none.
+ *     ranges_out: int64 (ranges_cap, 2), the utterances' records contiguous and in utterance order; counts_out: n_utt int32 on the device.
+ *     words_out / word_counts_out: both NULL, or the int64 (words_cap, 2) utterance-relative word table (same order) and its n_utt int32 counts.
+ *     CAPACITY: an utterance of T frames gives at most T + 2 ranges and (T + 1) / 2 words, so ranges_cap >= sl_ctc_pool_ranges_capacity(n_rows, n_utt) =
+ *     n_rows + 2 n_utt and words_cap >= sl_ctc_words_capacity(n_rows, n_utt) = (n_rows + n_utt) / 2 are required (less: SL_ERR_ARG) and never exceeded.
+ *     Two launches (count, emit), integer arithmetic only, nothing crosses to the host.
+ *   SL_ERR_ARG before any launch: NULL ids / offsets / range table / counts, a word table without word counts or the reverse, n_utt < 1,
+ *   blank_id == delim_id, pool_range < 1, an unknown mode, a capacity below the bound. */
+#define SL_CTC_RANGES_PACKED 0
+#define SL_CTC_RANGES_RAW 1
+int sl_ctc_greedy_batch(const void* x, const void* w, const void* bias, int32_t* ids, int64_t n_rows, int32_t H, int32_t V, int32_t dtype,
+                        sl_stream stream);
+size_t sl_ctc_pool_ranges_capacity(int64_t n_rows, int32_t n_utt);
+size_t sl_ctc_words_capacity(int64_t n_rows, int32_t n_utt);
+int sl_ctc_pool_ranges_batch(const int32_t* ids, const int64_t* row_offsets_dev, int32_t n_utt, int64_t n_rows, int32_t blank_id, int32_t delim_id,
+                             int32_t pool_range, int32_t mode, int64_t* ranges_out, int64_t ranges_cap, int32_t* counts_out, int64_t* words_out,
+                             int64_t words_cap, int32_t* word_counts_out, sl_stream stream);
+
 /* Whisper path (BASELINE configs[3]; ref:model/audio_encoder.py:10-13, ref:trainer.py:168-199, 280-291).
  * sl_whisper_logmel: WhisperFeatureExtractor's torch path (hf:models/whisper/feature_extraction_whisper.py:135-168)
  *   for one utterance: zero-pad/trim to n_frames*hop samples, reflect pad, Hann STFT as an fp32 GEMM against

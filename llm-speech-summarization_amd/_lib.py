@@ -117,6 +117,7 @@ class DownsampleDesc(C.Structure):
 
 
 DS_POOL, DS_STACK, DS_CTC_POOL = 0, 1, 2      # speechllm.h SL_DS_*
+CTC_RANGES_PACKED, CTC_RANGES_RAW = 0, 1      # speechllm.h SL_CTC_RANGES_*: the mode of sl_ctc_pool_ranges_batch
 
 
 class LlamaLayer(C.Structure):
@@ -367,6 +368,11 @@ _PROTOS = {
     "sl_hubert_workspace_bytes_ds": (c_sz, [C.POINTER(HubertModel), C.POINTER(c_i64), c_i32, C.POINTER(DownsampleDesc)]),
     "sl_hubert_forward_ds": (c_i32, [C.POINTER(HubertModel), c_vp, C.POINTER(c_i64), c_i32, c_vp, c_i64, C.POINTER(c_i64), c_vp, C.POINTER(DownsampleDesc),
                                      c_vp, c_sz, c_vp]),
+    # CTC word segmentation on the device (additive to ABI 7)
+    "sl_ctc_greedy_batch": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp]),
+    "sl_ctc_pool_ranges_capacity": (c_sz, [c_i64, c_i32]),
+    "sl_ctc_words_capacity": (c_sz, [c_i64, c_i32]),
+    "sl_ctc_pool_ranges_batch": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "sl_greedy_generate": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, c_i32,
                                    C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32),
                                    C.POINTER(c_f32), c_vp, c_sz, c_vp]),

@@ -190,14 +190,16 @@ class AudioEncoder:
 
     def encode_packed(self, waves: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None,
                       out_row_offsets: Optional[Sequence[int]] = None, want_last_hidden: bool = False, ctc_pool_ranges=None,
-                      _frames_only: bool = False):
+                      _frames_only: bool = False, ctc_pool_ranges_dev=None):
         """Encode utterances of arbitrary lengths.  Returns (out, P_list, last_hidden|None, T_list).
 
         `out` (rows, llm_dim) + `out_row_offsets` let the encoder write each utterance's embeddings
         directly at its place inside a prompt buffer (ref:utils.py:66-72 concatenation becomes a no-op).
         All three downsample methods take ragged batches: `pool` through sl_hubert_forward, `stack` (P_u = T_u // factor) and `ctc_pool`
         (P_u = the utterance's number of ranges; `ctc_pool_ranges`: one list of utterance-relative (start, end) per utterance, as the
-        dataset's `pool_ranges_4` holds them) through sl_hubert_forward_ds.  `_frames_only` (forward()'s one-utterance stack / ctc_pool
+        dataset's `pool_ranges_4` holds them) through sl_hubert_forward_ds.  `ctc_pool_ranges_dev` = (int64 device table (R, 2) of {first row, end
+        row} in packed frame rows, counts per utterance), as CTCSegmenter.ranges_packed derives it on the device for these utterances in this
+        order: taken as it is, no trip through Python lists (lists given with `ctc_pool_ranges` win).  `_frames_only` (forward()'s one-utterance stack / ctc_pool
         path, which composes the head on the host): stop at last_hidden.
         """
         if self.weights is None:
@@ -224,10 +226,18 @@ class AudioEncoder:
         elif self.downsample_method == "stack":
             P = [t // self.downsample_factor for t in T]
         else:
-            if ctc_pool_ranges is None:
+            if ctc_pool_ranges is None and ctc_pool_ranges_dev is not None:
+                ranges_dev, counts = ctc_pool_ranges_dev
+                counts = [int(c) for c in counts]
+                L.require_gpu(ranges_dev, "ctc_pool_ranges_dev table")
+                if ranges_dev.dtype != torch.int64 or ranges_dev.dim() != 2 or ranges_dev.shape[1] != 2 or len(counts) != n_utt or \
+                        sum(counts) != ranges_dev.shape[0] or min(counts) < 0:
+                    raise L.SpeechLLMError(f"ctc_pool_ranges_dev: need an int64 (R, 2) device table and {n_utt} counts adding up to R")
+            elif ctc_pool_ranges is None:
                 raise L.SpeechLLMError("the ctc_pool downsample needs ctc_pool_ranges: one list of (start, end) frame ranges per utterance")
-            packed, counts = ops.segment_ranges_pack(ctc_pool_ranges, T)      # clamped, offset to packed rows; refuses an empty range
-            ranges_dev = L.h2d(packed, torch.int64, self.device)
+            else:
+                packed, counts = ops.segment_ranges_pack(ctc_pool_ranges, T)      # clamped, offset to packed rows; refuses an empty range
+                ranges_dev = L.h2d(packed, torch.int64, self.device)
             P = list(counts)
         last_hidden = None
         if want_last_hidden or not head:

@@ -269,6 +269,21 @@ int main() {
     EXPECT_ARG_ERROR(sl_segment_mean_bwd_batch(ws, ws, (const int64_t*)ws, nullptr, nullptr, 4, 100, 128, SL_BF16, nullptr));     // no index
     EXPECT_ARG_ERROR(sl_stack_rows_batch(ws, ws, (const int64_t*)ws, 2, 10, 128, 0, SL_BF16, nullptr));                           // factor < 1
     EXPECT_ARG_ERROR(sl_stack_rows_bwd_batch(ws, ws, (const int64_t*)ws, 2, 10, 130, 4, SL_F16, nullptr));                        // H not a multiple of 8
+    // CTC segmentation: the head and the ids -> ranges entry, every refusal before any launch
+    int32_t* idp = (int32_t*)ws;
+    EXPECT_ARG_ERROR(sl_ctc_greedy_batch(ws, ws, nullptr, nullptr, 100, 1024, 32, SL_BF16, nullptr));                              // null ids
+    EXPECT_ARG_ERROR(sl_ctc_greedy_batch(ws, ws, nullptr, idp, 100, 1024, 65, SL_BF16, nullptr));                                  // V > 64
+    EXPECT_ARG_ERROR(sl_ctc_greedy_batch(ws, ws, nullptr, idp, 100, 1028, 32, SL_F32, nullptr));                                   // H not a multiple of 8
+    EXPECT(sl_ctc_greedy_batch(ws, ws, nullptr, idp, 0, 1024, 32, SL_F16, nullptr) == 0, "no rows: nothing to do");
+    EXPECT(sl_ctc_pool_ranges_capacity(100, 3) == 106 && sl_ctc_words_capacity(100, 3) == 51, "capacity bounds");
+    const int64_t* ro = (const int64_t*)ws;
+    int64_t* tab = (int64_t*)ws;
+    EXPECT_ARG_ERROR(sl_ctc_pool_ranges_batch(idp, ro, 3, 100, 0, 4, 4, SL_CTC_RANGES_PACKED, nullptr, 106, idp, nullptr, 0, nullptr, nullptr));   // null table
+    EXPECT_ARG_ERROR(sl_ctc_pool_ranges_batch(idp, ro, 3, 100, 4, 4, 4, SL_CTC_RANGES_PACKED, tab, 106, idp, nullptr, 0, nullptr, nullptr));       // blank == delimiter
+    EXPECT_ARG_ERROR(sl_ctc_pool_ranges_batch(idp, ro, 3, 100, 0, 4, 0, SL_CTC_RANGES_RAW, tab, 106, idp, nullptr, 0, nullptr, nullptr));          // pool_range < 1
+    EXPECT_ARG_ERROR(sl_ctc_pool_ranges_batch(idp, ro, 3, 100, 0, 4, 4, SL_CTC_RANGES_PACKED, tab, 105, idp, nullptr, 0, nullptr, nullptr));       // capacity below the bound
+    EXPECT_ARG_ERROR(sl_ctc_pool_ranges_batch(idp, ro, 3, 100, 0, 4, 4, SL_CTC_RANGES_PACKED, tab, 106, idp, tab, 50, idp, nullptr));             // word capacity below the bound
+    EXPECT_ARG_ERROR(sl_ctc_pool_ranges_batch(idp, ro, 3, 100, 0, 4, 4, 2, tab, 106, idp, nullptr, 0, nullptr, nullptr));                          // unknown mode
   }
 
   // ---- Llama runtime

@@ -24,7 +24,8 @@ from .utils import (LLAMA_PROMPT_PREFIX, LLAMA_PROMPT_SUFFIX, MINICHAT_PROMPT_PR
 
 class LLMSpeechTextInference():
     def __init__(self, config, audio_encoder_checkpoint, device, *, tokenizer=None, llm: Optional[AudioLlamaForCausalLM] = None,
-                 audio_encoder: Optional[AudioEncoder] = None, dtype: torch.dtype = torch.bfloat16, kv_cache_dtype=None, weight_dtype=None):
+                 audio_encoder: Optional[AudioEncoder] = None, dtype: torch.dtype = torch.bfloat16, kv_cache_dtype=None, weight_dtype=None,
+                 ctc_segmenter=None):
         self.config = config
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -41,6 +42,17 @@ class LLMSpeechTextInference():
             audio_encoder = AudioEncoder(self.config, self.device, dtype=dtype, load_pretrained=False)
             audio_encoder.load_state_dict(checkpoint)
         self.audio_encoder = audio_encoder.eval().to(self.device)
+
+        # Optional CTC segmenter (an extension): a CTCSegmenter, or a HubertForCTC directory named by the keyword or by the yaml key
+        # model.audio_encoder.ctc_segmenter.  With one, `ctc_pool` inference works from a waveform alone (get_ctc_pool_ranges exists, the
+        # name ref:inference.py:100-105 calls); with none, nothing changes and `ctc_pool` without ranges raises the reference's AttributeError.
+        if ctc_segmenter is None:
+            ae_cfg = self.config.model.audio_encoder
+            ctc_segmenter = ae_cfg.get("ctc_segmenter") if hasattr(ae_cfg, "get") else None
+        if isinstance(ctc_segmenter, str):
+            from .ctc_segmenter import CTCSegmenter
+            ctc_segmenter = CTCSegmenter(ctc_segmenter, self.device, dtype=dtype)
+        self.ctc_segmenter = ctc_segmenter
 
         # Tokenizer (ref:inference.py:31-37).
         self.llm_type = self.config.model.llm_type
@@ -74,6 +86,18 @@ class LLMSpeechTextInference():
             raise ValueError("runtime.num_return_sequences > 1 with runtime.num_beams > 1 (beam sampling) is not built")
         # runtime.repetition_penalty / no_repeat_ngram_size / min_new_tokens (absent in the shipped yamls: off) -> HF's logits processors
         self.logits = runtime_logits(self.config)
+
+    def __getattr__(self, name):
+        # get_ctc_pool_ranges exists only with a segmenter: without one the class has no such attribute, as in the reference
+        if name == "get_ctc_pool_ranges" and self.__dict__.get("ctc_segmenter") is not None:
+            return self._ctc_pool_ranges_of
+        raise AttributeError(f"'{type(self).__name__}' object has no attribute '{name}'")
+
+    def _ctc_pool_ranges_of(self, audio_tensor, pool_range: int = 4):
+        """get_ctc_pool_ranges(audio_tensor): one utterance ((N,) or (1, N) waveform) -> its list of utterance-relative (start, end) frame
+        ranges, clamped to the utterance and without empty pairs: what the encoder's `ctc_pool_ranges=[...]` takes for it."""
+        wave = torch.as_tensor(audio_tensor, dtype=torch.float32).reshape(-1)
+        return self.ctc_segmenter.pool_ranges([wave], pool_range=pool_range)[0]
 
     def _logits_for(self, repetition_penalty, no_repeat_ngram_size, min_new_tokens):
         """the config's logits processors, each overridden by a keyword that is not None -> the keywords of llm.generate"""
@@ -128,11 +152,12 @@ class LLMSpeechTextInference():
                                 min_new_tokens=None, return_scores=False, num_return_sequences=None, ctc_pool_ranges=None):
         """num_return_sequences=R > 1 (None: runtime.num_return_sequences): the list of R sampled answers (and, with return_scores, the
         list of their scores) instead of one answer.  ctc_pool_ranges (an extension; the `ctc_pool` downsample only): this utterance's list of
-        (start, end) frame ranges, as the dataset's `pool_ranges_4` holds them; without it `ctc_pool` fails as the reference does (Q2)."""
+        (start, end) frame ranges, as the dataset's `pool_ranges_4` holds them; without it `ctc_pool` fails as the reference does (Q2) unless a
+        ctc_segmenter is set, which then derives them (get_ctc_pool_ranges)."""
         audio_tensor = torch.as_tensor(audio, dtype=torch.float32).unsqueeze(0).to(self.device)
         if self.audio_encoder.downsample_method == "ctc_pool" and ctc_pool_ranges is None:
-            # the reference calls an undefined self.get_ctc_pool_ranges here (SURVEY.md §9 Q2)
-            raise AttributeError("'LLMSpeechTextInference' object has no attribute 'get_ctc_pool_ranges'")
+            # the reference calls self.get_ctc_pool_ranges here, which it never defines (SURVEY.md §9 Q2): it exists with a ctc_segmenter only
+            ctc_pool_ranges = self.get_ctc_pool_ranges(audio_tensor)
         if self.audio_encoder.encoder_base == "whisper":
             audio_embeds = self._whisper_audio_embeds(audio)
         else:
@@ -172,7 +197,7 @@ class LLMSpeechTextInference():
                                  min_new_tokens=None, return_scores=False, num_return_sequences=None, ctc_pool_ranges=None):
         """return_scores=True: (texts, scores), one mean token log-probability per answer; chunks are concatenated in order.
         ctc_pool_ranges (the `ctc_pool` downsample only): one list of (start, end) frame ranges per utterance; without it `ctc_pool` raises the
-        reference's AttributeError (Q2).  All three downsample methods take the batched path below.
+        reference's AttributeError (Q2) unless a ctc_segmenter is set, which then derives every chunk's ranges on the device.  All three downsample methods take the batched path below.
         num_return_sequences=R > 1 (None: runtime.num_return_sequences): R sampled answers per utterance from one prefill of each
         (generate_packed num_return), returned prompt-major: answer j of utterance i is entry i * R + j.
         Batched form of generate_audio_response (an extension: the reference answers one utterance per call).
@@ -190,9 +215,9 @@ class LLMSpeechTextInference():
         if R > 1 and self.beams:
             raise L.SpeechLLMError("num_return_sequences > 1 with beam search (beam sampling) is not built")
         ctc = self.audio_encoder.downsample_method == "ctc_pool"
-        if ctc and ctc_pool_ranges is None:                      # the reference calls an undefined self.get_ctc_pool_ranges
-            raise AttributeError("'LLMSpeechTextInference' object has no attribute 'get_ctc_pool_ranges'")
-        if ctc and len(ctc_pool_ranges) != n:
+        if ctc and ctc_pool_ranges is None and getattr(self, "ctc_segmenter", None) is None:      # the reference calls an undefined self.get_ctc_pool_ranges
+            raise AttributeError("'LLMSpeechTextInference' object has no attribute 'get_ctc_pool_ranges'")      # (with a segmenter every chunk derives its ranges on the device)
+        if ctc and ctc_pool_ranges is not None and len(ctc_pool_ranges) != n:
             raise ValueError(f"{len(ctc_pool_ranges)} lists of ctc_pool ranges for {n} utterances")
         out: List[str] = []
         ids_all = []
@@ -203,7 +228,7 @@ class LLMSpeechTextInference():
         for lo_ in range(0, n, chunk):
             ids = self._generate_chunk(audios[lo_:lo_ + chunk], texts[lo_:lo_ + chunk], max_new_tokens,
                                        self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens), return_scores, R,
-                                       ranges=list(ctc_pool_ranges[lo_:lo_ + chunk]) if ctc else None)
+                                       ranges=list(ctc_pool_ranges[lo_:lo_ + chunk]) if ctc and ctc_pool_ranges is not None else None)
             if return_scores:
                 ids, lps = ids
                 scores_all += self._mean_logprobs(ids, lps)
@@ -231,6 +256,7 @@ class LLMSpeechTextInference():
         waves = [torch.as_tensor(a, dtype=torch.float32).reshape(-1) for a in audios]
         enc = self.audio_encoder
         whisper = enc.encoder_base == "whisper"
+        ranges_dev = None
         if whisper:
             sr = int(getattr(getattr(self.config, "audio", None), "sampling_rate", 16000) or 16000)
             feats = enc.feature_extractor(waves, return_tensors="pt", sampling_rate=sr).input_features
@@ -240,8 +266,11 @@ class LLMSpeechTextInference():
             Ps = [(enc.arch.num_frames(int(w.numel())) - enc.pool_kernel) // enc.pool_stride + 1 for w in waves]
         elif enc.downsample_method == "stack":
             Ps = [enc.arch.num_frames(int(w.numel())) // enc.downsample_factor for w in waves]
-        else:                                                                    # ctc_pool: one embedding per range
+        elif ranges is not None:                                                 # ctc_pool: one embedding per range
             Ps = [len(r) for r in ranges]
+        else:                                                                    # ctc_pool from the waveforms alone: the chunk's table on the device
+            ranges_dev = self.ctc_segmenter.ranges_packed(waves)
+            Ps = list(ranges_dev[1])
         lens, heads = [], []
         for i in range(n):
             n_head = pre_e.shape[0] + (txt_e[i].shape[0] if txt_e[i] is not None else 0)
@@ -260,7 +289,7 @@ class LLMSpeechTextInference():
                 x[o + heads[i]:o + heads[i] + Ps[i]] = padded[i, :Ps[i]]
             x[o + heads[i] + Ps[i]:starts[i + 1]] = suf_e
         if not whisper:
-            enc.encode_packed(waves, out=x, out_row_offsets=[starts[i] + heads[i] for i in range(n)], ctc_pool_ranges=ranges)
+            enc.encode_packed(waves, out=x, out_row_offsets=[starts[i] + heads[i] for i in range(n)], ctc_pool_ranges=ranges, ctc_pool_ranges_dev=ranges_dev)
         # every prompt opens with the same template rows (and the same instruction text when the caller gave one text for all):
         # the batched decode attention reads those cache positions once for the batch (sl_kv_cache.shared_prefix)
         shared = int(pre_e.shape[0])

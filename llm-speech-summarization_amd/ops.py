@@ -980,3 +980,46 @@ def stack_rows_bwd_batch(dy: torch.Tensor, seqlens: Sequence[int], factor: int, 
     L.check(L.lib().sl_stack_rows_bwd_batch(L.ptr(src), L.ptr(dx), desc_t.data_ptr(), len(P), max(int(t) for t in seqlens), H, factor,
                                             L.dtype_code(dy.dtype), L.stream_ptr()), "sl_stack_rows_bwd_batch")
     return dx
+
+
+# -- CTC word segmentation of a packed ragged batch (ref:preprocess_data/utils.py:127-188 on the device) ---------------------------
+def ctc_greedy(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ids[m] = the lowest column attaining max_v (x[m] . w[v] + bias[v]): the CTC head with its argmax fused (sl_ctc_greedy_batch, one launch,
+    the logits are never written).  x (n_rows, H), w (V <= 64, H), bias (V) or None, one dtype; int32 ids."""
+    L.require_gpu(x, "x"); L.require_gpu(w, "w")
+    if bias is not None:
+        L.require_gpu(bias, "bias")
+    if w.dtype != x.dtype or (bias is not None and bias.dtype != x.dtype):
+        raise L.SpeechLLMError("ctc_greedy: x, w and bias must share one dtype")
+    if x.dim() != 2 or w.dim() != 2 or w.shape[1] != x.shape[1] or (bias is not None and bias.numel() != w.shape[0]):
+        raise L.SpeechLLMError(f"ctc_greedy: x {tuple(x.shape)} against w {tuple(w.shape)}")
+    ids = torch.empty(x.shape[0], dtype=torch.int32, device=x.device) if out is None else out
+    L.check(L.lib().sl_ctc_greedy_batch(L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(ids), x.shape[0], x.shape[1], w.shape[0], L.dtype_code(x.dtype),
+                                        L.stream_ptr()), "sl_ctc_greedy_batch")
+    return ids
+
+
+def ctc_pool_ranges(ids: torch.Tensor, row_offsets_dev: torch.Tensor, blank_id: int = 0, delim_id: int = 4, pool_range: int = 4, raw: bool = False,
+                    want_words: bool = False):
+    """Greedy ids of a packed batch -> (ranges int64 (capacity, 2), counts int32 (n_utt)[, words int64 (capacity, 2), word counts int32]), all on
+    the device (sl_ctc_pool_ranges_batch).  The utterances' records are contiguous and in utterance order: the first sum(counts) rows of `ranges`
+    are the table; packed mode (raw=False) gives {first row, end row} records in packed frame rows that sl_segment_mean_batch / sl_hubert_forward_ds
+    take as they are, raw mode the reference's utterance-relative list.  Nothing is copied to the host here."""
+    L.require_gpu(ids, "ids"); L.require_gpu(row_offsets_dev, "row_offsets")
+    if ids.dtype != torch.int32 or row_offsets_dev.dtype != torch.int64:
+        raise L.SpeechLLMError("ctc_pool_ranges: ids must be int32 and row_offsets int64")
+    lib = L.lib()
+    n_utt, n_rows = int(row_offsets_dev.numel()) - 1, int(ids.numel())
+    cap = int(lib.sl_ctc_pool_ranges_capacity(n_rows, n_utt))
+    ranges = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=ids.device)
+    counts = torch.empty(max(n_utt, 1), dtype=torch.int32, device=ids.device)
+    words = wcounts = None
+    wcap = 0
+    if want_words:
+        wcap = int(lib.sl_ctc_words_capacity(n_rows, n_utt))
+        words = torch.empty((max(wcap, 1), 2), dtype=torch.int64, device=ids.device)
+        wcounts = torch.empty(max(n_utt, 1), dtype=torch.int32, device=ids.device)
+    L.check(lib.sl_ctc_pool_ranges_batch(L.ptr(ids), L.ptr(row_offsets_dev), n_utt, n_rows, int(blank_id), int(delim_id), int(pool_range),
+                                         L.CTC_RANGES_RAW if raw else L.CTC_RANGES_PACKED, L.ptr(ranges), cap, L.ptr(counts), L.ptr(words), wcap,
+                                         L.ptr(wcounts), L.stream_ptr()), "sl_ctc_pool_ranges_batch")
+    return (ranges, counts[:n_utt], words, wcounts[:n_utt]) if want_words else (ranges, counts[:n_utt])

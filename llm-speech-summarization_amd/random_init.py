@@ -78,6 +78,18 @@ def hubert_encoder_state_dict(cfg, llm_dim: int, seed: int = 0, downsample: str 
     return sd
 
 
+def hubert_ctc_state_dict(cfg, vocab_size: int = 32, seed: int = 0, head_std: float = 0.5) -> Dict[str, torch.Tensor]:
+    """A `HubertForCTC`-shaped state dict (what facebook/hubert-large-ls960-ft holds): `hubert.*` = the HubertModel keys of
+    hubert_encoder_state_dict, plus `lm_head.weight` (vocab_size, H) and `lm_head.bias`.  The head is drawn wide (head_std) so that the
+    greedy ids of random frames spread over the vocabulary, blank and delimiter included."""
+    enc = hubert_encoder_state_dict(cfg, 8, seed=seed)
+    sd = {"hubert." + k[len("encoder."):]: v for k, v in enc.items() if k.startswith("encoder.")}
+    g = _g(seed + 7919)
+    sd["lm_head.weight"] = _randn(g, vocab_size, cfg.hidden_size, std=head_std)
+    sd["lm_head.bias"] = _randn(g, vocab_size, std=head_std)
+    return sd
+
+
 def llama_state_dict(cfg, seed: int = 0, std: float = 0.02, dtype=torch.float32) -> Dict[str, torch.Tensor]:
     """cfg: any object with the LlamaCfg fields.  Generated layer by layer in `dtype` to bound memory."""
     g = _g(seed)
