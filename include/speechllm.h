@@ -378,6 +378,19 @@ typedef struct {
   float* lse;
 } sl_attn_args;
 int sl_attn_fwd(const sl_attn_args* a, sl_stream stream);
+/* Causal head_dim 128 prefill attention of CONTINUED sequences (bf16 / fp16): the keys of sequence s come in two segments.
+ *   keys [0, past_s)                 rows of its K/V cache slot: k_past / v_past are ONE layer's cache, (slots, n_kv, max_ctx, D), elements of
+ *                                    a->dtype (kv_format = SL_KV_MODEL_DTYPE) or e4m3 bytes (SL_KV_FP8_E4M3), which are widened on the way
+ *                                    into the LDS tiles by the exact conversion the decode kernels use; past_row0_dev[s] is the first cache
+ *                                    row of the sequence's slot, slot * n_kv * max_ctx (the kv head adds head * max_ctx rows), and
+ *                                    past_len_dev[s] = past_s in [0, max_ctx], not a multiple of anything.
+ *   keys [past_s, past_s + klen_s)   a->k / a->v rows cu_k[s] + t, unquantised; a->klen holds the NEW key counts.
+ * Causal shift as in sl_attn_fwd with klen = past_s + klen_s: key j visible to query i iff j <= i + past_s + klen_s - qlen_s.
+ * Tiles, products and softmax are sl_attn_fwd's 16-bit kernel: with kv_format = SL_KV_MODEL_DTYPE the output is bit for bit what
+ * sl_attn_fwd gives over a cache the new rows were appended to.  SL_F32, head_dim != 128, non-causal, dropout and lse are
+ * SL_ERR_UNSUPPORTED; a format code other than 0 / 1 is SL_ERR_ARG; nothing is launched on either. */
+int sl_attn_fwd_past(const sl_attn_args* a, const void* k_past, const void* v_past, const int32_t* past_len_dev, const int32_t* past_row0_dev,
+                     int32_t max_ctx, int32_t kv_format, sl_stream stream);
 
 /* Flash-style attention BACKWARD for the same packed layouts (the KD step's data gradients through the frozen Llama,
  * data + parameter gradients through the HuBERT / Whisper encoder; autograd of hf:...hubert.py:234-259 /
@@ -1077,6 +1090,39 @@ int sl_generate_n(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const
                   const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
                   sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host, int32_t num_return_sequences);
 int32_t sl_generate_last_attn_path(void);
+
+/* Multi-turn sessions: generation that CONTINUES on a K/V cache the caller keeps between calls.
+ *
+ * sl_llama_prefill_cont: sl_llama_prefill for sequences that already hold a past.  Sequence s lives in cache slot slot_host[s]
+ * (slot_host NULL: slot s); positions [0, past_len_host[s]) of that slot hold its K/V.  The new rows are rotated at positions
+ * past_s + t and appended there, attend [0, past_s + len_s), the last row's logits are written and ctx_len[s] = past_s + len_s.
+ * Checked before any launch: past_s >= 0, past_s + len_s <= max_ctx (<= rope_len), slots distinct and < kv->slots, and, when any
+ * past is > 0, kv->shared_prefix <= every past: the new rows are never deduplicated, the promise then only says that cache
+ * positions [0, shared_prefix) of every slot are equal, which the first call made true.  past_len_host NULL or all zero with
+ * slot_host NULL IS sl_llama_prefill, bit for bit and launch for launch.  hidden_taps are not offered.
+ * 16-bit / fp32 cache: the rows are appended first and sl_attn_fwd attends the cache (klen = past + len).  e4m3 cache: the past
+ * keys exist only as bytes, so sl_attn_fwd_past attends the dequantised past and the unquantised new rows — a continued e4m3
+ * prefill is therefore NOT bit-equal to a one-shot prefill of the same text, which attends every key unquantised.
+ *
+ * sl_generate_cont / sl_generate_workspace_bytes_cont: sl_generate_sc (greedy / sampling, row_limits, logits processors,
+ * optional log-probabilities) + past_len_host + slot_host; the decode loop is sl_generate_sc's.  past + prompt + max_new_tokens
+ * <= max_ctx per sequence.  The logits processors' history starts EMPTY at this call's first generated token (as HF's would over
+ * input_ids of the new tokens only): tokens of earlier turns are neither penalised nor counted into n-grams or min_new_tokens.
+ * opts->compact must be 0 when past_len_host is non-NULL (SL_ERR_ARG): compaction moves live rows into the slots of finished rows
+ * and destroys the K/V the caller wants to keep.  The decode loop keeps row b in slot b, so slot_host must be NULL or the identity
+ * (SL_ERR_UNSUPPORTED otherwise).  NULL / all-zero pasts and NULL slots give exactly sl_generate_sc.
+ * What is valid afterwards is the caller's bookkeeping: finished rows of the uncompacted batch go on appending pad tokens, so
+ * after a call in which sequence s generated g_s tokens (its last one counted) its valid length is past_s + len_s + g_s - 1;
+ * everything above is overwritten by the next call.  The last generated token was never fed back: the next call's rows begin
+ * with its embedding. */
+int sl_llama_prefill_cont(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, const int32_t* past_len_host,
+                          const int32_t* slot_host, int32_t nseq, float* logits, int32_t* ctx_len_dev, void* workspace, size_t workspace_bytes,
+                          sl_stream stream);
+size_t sl_generate_workspace_bytes_cont(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int32_t max_new_tokens, const sl_logits_opts* lp,
+                                        int32_t scores);
+int sl_generate_cont(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                     const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
+                     sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host, const int32_t* past_len_host, const int32_t* slot_host);
 
 /* ---------------------------------------------------------------------------------------------
  * KD step, layer stacks (C++ host runtime of the training tape: one call issues the launches of a whole stack of layers

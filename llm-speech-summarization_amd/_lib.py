@@ -373,6 +373,13 @@ _PROTOS = {
     "sl_ctc_pool_ranges_capacity": (c_sz, [c_i64, c_i32]),
     "sl_ctc_words_capacity": (c_sz, [c_i64, c_i32]),
     "sl_ctc_pool_ranges_batch": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    # multi-turn sessions: generation continued on a kept K/V cache (additive to ABI 7)
+    "sl_attn_fwd_past": (c_i32, [C.POINTER(AttnArgs), c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp]),
+    "sl_llama_prefill_cont": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i32), c_i32, c_vp, c_vp,
+                                      c_vp, c_sz, c_vp]),
+    "sl_generate_workspace_bytes_cont": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, c_i32, C.POINTER(LogitsOpts), c_i32]),
+    "sl_generate_cont": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(GenerateOpts), C.POINTER(c_i32),
+                                 C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts), C.POINTER(c_f32), C.POINTER(c_i32), C.POINTER(c_i32)]),
     "sl_greedy_generate": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, c_i32,
                                    C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32),
                                    C.POINTER(c_f32), c_vp, c_sz, c_vp]),

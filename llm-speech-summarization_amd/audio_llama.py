@@ -36,6 +36,74 @@ class GenerateOutput:
         self.sequences, self.token_logprobs, self.sequences_scores = sequences, token_logprobs, sequences_scores
 
 
+class KVSession:
+    """A K/V cache that outlives a generate call: what `llm.new_session(n_seq)` returns and generate(past_key_values=) /
+    generate_packed(session=) / forward(use_cache=True, past_key_values=) continue on.  It owns its K and V tensors — n_seq slots at
+    the model's max_ctx in the model's kv_format, never the model's shared buffer, so calls without a session leave it alone — and
+    the host bookkeeping the library leaves to its caller:
+      valid_len[s]   cache positions [0, valid_len[s]) of slot s hold the sequence's K/V; everything above is overwritten next call
+      pending_id[s]  the last generated token (EOS, or the last one under the budget): it was selected but never fed back, so the
+                     next call's rows begin with its embedding; None before the first call and after a forward()
+      shared_prefix  the promise of the FIRST call (positions [0, P) of every slot are equal), which later calls keep reading
+    All n_seq sequences take part in every call, in slot order."""
+
+    def __init__(self, n_seq: int, max_ctx: int, kv_format: int = L.KV_MODEL_DTYPE, k: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None):
+        if int(n_seq) < 1:
+            raise L.SpeechLLMError(f"a session needs at least one sequence, not {n_seq}")
+        self.n_seq, self.max_ctx, self.kv_format = int(n_seq), int(max_ctx), int(kv_format)
+        self.k, self.v = k, v
+        self.valid_len: List[int] = [0] * self.n_seq
+        self.pending_id: List[Optional[int]] = [None] * self.n_seq
+        self.shared_prefix = 0
+        self.turns = 0
+
+    @property
+    def fresh(self) -> bool:
+        return not any(self.valid_len)
+
+    def get_seq_length(self, s: int = 0) -> int:
+        return self.valid_len[s]
+
+    def kv_struct(self) -> "L.KVCache":
+        kv = L.KVCache()
+        kv.k_cache, kv.v_cache, kv.slots, kv.max_ctx = self.k.data_ptr(), self.v.data_ptr(), self.n_seq, self.max_ctx
+        kv.shared_prefix, kv.reserved = int(self.shared_prefix), self.kv_format
+        return kv
+
+    def check_room(self, lens: Sequence[int], max_new_tokens: int = 0) -> None:
+        """raises, before anything is launched, when a sequence's past + new rows + budget leave the cache"""
+        if len(lens) != self.n_seq:
+            raise L.SpeechLLMError(f"{len(lens)} sequences for a session of {self.n_seq}: every sequence takes part in every call, in slot order")
+        for s, n in enumerate(lens):
+            if self.valid_len[s] + int(n) + int(max_new_tokens) > self.max_ctx:
+                raise L.SpeechLLMError(f"sequence {s}: past ({self.valid_len[s]}) + prompt ({int(n)}) + max_new_tokens ({int(max_new_tokens)}) exceeds max_ctx={self.max_ctx}")
+
+    def advance(self, lens: Sequence[int], ids=None, eos_ids: Sequence[int] = (), budgets: Optional[Sequence[int]] = None) -> None:
+        """Bookkeeping after a call that fed `lens[s]` rows (a prepended pending token counted) and returned the id matrix `ids` (n_seq, cols):
+        sequence s generated g_s tokens — up to and including its first EOS, else its budget (budgets[s], or every column); pads are not counted —
+        so valid_len = past + len + g - 1 (the last token was selected, not fed) and pending_id = that token.  ids None (a forward()): the rows
+        alone, no pending token."""
+        if len(lens) != self.n_seq:
+            raise L.SpeechLLMError(f"{len(lens)} sequences for a session of {self.n_seq}")
+        rows = None if ids is None else (ids.tolist() if hasattr(ids, "tolist") else [list(r) for r in ids])
+        if rows is not None and len(rows) != self.n_seq:
+            raise L.SpeechLLMError(f"{len(rows)} id rows for a session of {self.n_seq}")
+        eos = set(int(e) for e in eos_ids)
+        for s in range(self.n_seq):
+            if rows is None:
+                self.valid_len[s] += int(lens[s])
+                self.pending_id[s] = None
+                continue
+            row = rows[s]
+            cap = min(len(row), int(budgets[s])) if budgets is not None else len(row)
+            if cap < 1:
+                raise L.SpeechLLMError(f"sequence {s}: no generated token to account for")
+            g = next((i + 1 for i in range(cap) if int(row[i]) in eos), cap)
+            self.valid_len[s] += int(lens[s]) + g - 1
+            self.pending_id[s] = int(row[g - 1])
+        self.turns += 1
+
+
 class _EmbedTokens:
     """`llm.model.embed_tokens(ids)` (ref:utils.py:63-64, ref:inference.py:85,121) as a HIP row gather."""
 
@@ -216,6 +284,40 @@ class AudioLlamaForCausalLM:
         kv.reserved = self.kv_format                 # sl_kv_cache.reserved: the K/V format
         return kv
 
+    # -- multi-turn sessions -----------------------------------------------------------------------
+    def new_session(self, n_seq: int) -> KVSession:
+        """A KVSession of n_seq sequences: its own K / V tensors (n_layers, n_seq, n_kv, max_ctx, D) in this model's kv_format."""
+        a = self.arch
+        w = self._dev()
+        shape = (a.num_hidden_layers, int(n_seq), a.num_key_value_heads, self.max_ctx, a.head_dim)
+        kv_dtype = self.dtype
+        if self.kv_format == L.KV_FP8_E4M3:
+            kv_dtype = torch.uint8
+            assert ops.kv_cache_bytes(w.struct, int(n_seq), self.max_ctx, self.kv_format) == shape[0] * shape[1] * shape[2] * shape[3] * shape[4]
+        return KVSession(n_seq, self.max_ctx, self.kv_format, torch.zeros(shape, device=self.device, dtype=kv_dtype),
+                         torch.zeros(shape, device=self.device, dtype=kv_dtype))
+
+    def _check_session(self, session: KVSession) -> None:
+        if not isinstance(session, KVSession):
+            raise L.SpeechLLMError(f"past_key_values / session must be a KVSession (llm.new_session(n_seq)), not {type(session).__name__}")
+        if session.k is None or session.v is None:
+            raise L.SpeechLLMError("the session owns no cache: create it with llm.new_session(n_seq)")
+        if session.kv_format != self.kv_format or session.max_ctx != self.max_ctx or session.k.dtype != (torch.uint8 if self.kv_format == L.KV_FP8_E4M3 else self.dtype):
+            raise L.SpeechLLMError("the session was created for another kv_cache_dtype, dtype or max_ctx than this model has now")
+
+    def _session_rows(self, session: KVSession, x: torch.Tensor, lens: Sequence[int]):
+        """The rows a continued call feeds: each sequence's pending token (selected by the last call, never fed back) in front of its new rows."""
+        if session.fresh or all(p is None for p in session.pending_id):
+            return x, [int(n) for n in lens]
+        if any(p is None for p in session.pending_id):
+            raise L.SpeechLLMError("some sequences of the session have a pending token and some have none: they take their turns together")
+        pend = self.model.embed_tokens(L.h2d(session.pending_id, torch.int32, self.device)).to(x.dtype)
+        parts, o = [], 0
+        for s, n in enumerate(lens):
+            parts += [pend[s:s + 1], x[o:o + int(n)]]
+            o += int(n)
+        return torch.cat(parts, 0).contiguous(), [int(n) + 1 for n in lens]
+
     def _workspace(self, nbytes: int) -> torch.Tensor:
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
@@ -235,11 +337,16 @@ class AudioLlamaForCausalLM:
 
     # -- forward (prefill with all-position logits; training / validation callers) ----------------
     def forward(self, input_ids=None, attention_mask=None, inputs_embeds=None, labels=None, output_hidden_states=False,
-                **unused):
+                use_cache=None, past_key_values=None, **unused):
+        """use_cache=True with past_key_values=<KVSession> (and neither labels nor output_hidden_states): the rows continue the session's
+        sequences (sl_llama_prefill_cont) — a pending token of an earlier generate is fed first — and the result carries the LAST position's
+        logits only, (B, 1, vocab), with the session in past_key_values.  Otherwise as ever: all-position logits, past_key_values None."""
         w = self._dev()
         a = self.arch
         if inputs_embeds is None:
             inputs_embeds = self.model.embed_tokens(input_ids)
+        if use_cache and past_key_values is not None and labels is None and not output_hidden_states:
+            return self._forward_session(past_key_values, inputs_embeds, attention_mask)
         B, S = inputs_embeds.shape[0], inputs_embeds.shape[1]
         x, lens = self._pack(inputs_embeds.to(self.dtype), attention_mask)
         n_tok = x.shape[0]
@@ -281,6 +388,29 @@ class AudioLlamaForCausalLM:
             loss = acc[0]
         return SimpleNamespace(loss=loss, logits=logits, hidden_states=hidden_states, past_key_values=None, attentions=None)
 
+    def _forward_session(self, session: KVSession, inputs_embeds, attention_mask=None):
+        self._check_session(session)
+        a = self.arch
+        x, lens = self._pack(inputs_embeds.to(self.dtype) if torch.is_tensor(inputs_embeds) else [e.to(self.dtype) for e in inputs_embeds], attention_mask)
+        x, lens = self._session_rows(session, x, lens)
+        session.check_room(lens)
+        B = session.n_seq
+        lib = L.lib()
+        cu = [0]
+        for n in lens:
+            cu.append(cu[-1] + n)
+        cu_c = (C.c_int32 * (B + 1))(*cu)
+        past_c = (C.c_int32 * B)(*session.valid_len)
+        kv = session.kv_struct()
+        struct, _ = self._struct_for(B)
+        ws = self._workspace(lib.sl_llama_workspace_bytes(C.byref(struct), x.shape[0], B))
+        logits = torch.empty((B, a.vocab_size), device=self.device, dtype=torch.float32)
+        ctx = torch.empty(B, device=self.device, dtype=torch.int32)
+        L.check(lib.sl_llama_prefill_cont(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, past_c, None, B, logits.data_ptr(), ctx.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), L.stream_ptr()), "sl_llama_prefill_cont")
+        session.advance(lens)
+        return SimpleNamespace(loss=None, logits=logits.view(B, 1, a.vocab_size), hidden_states=None, past_key_values=session, attentions=None)
+
     __call__ = forward
 
     # -- generation -----------------------------------------------------------------------------
@@ -289,8 +419,11 @@ class AudioLlamaForCausalLM:
                  top_p: Optional[float] = None, seed: Optional[int] = None, num_beams: Optional[int] = None,
                  length_penalty: Optional[float] = None, early_stopping=None, num_return_sequences: Optional[int] = None,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
-                 return_dict_in_generate: Optional[bool] = None, output_scores: Optional[bool] = None, **unused):
-        """do_sample=True with num_return_sequences=R > 1: R sampled answers per prompt -> (B * R, n_cols), prompt-major as HF returns them
+                 return_dict_in_generate: Optional[bool] = None, output_scores: Optional[bool] = None, past_key_values: Optional[KVSession] = None, **unused):
+        """past_key_values=<KVSession> (llm.new_session(B)): the call runs in the session's cache and CONTINUES it — the prompt rows are the
+        new rows only (the follow-up question), the earlier turns are the cache; see generate_packed(session=).  Not with num_beams > 1 or
+        num_return_sequences > 1.
+        do_sample=True with num_return_sequences=R > 1: R sampled answers per prompt -> (B * R, n_cols), prompt-major as HF returns them
         (sl_generate_n: each prompt is prefilled once); greedy search with R > 1 raises, as in HF.
         num_beams > 1: beam search (hf:generation/utils.py _beam_search, sl_beam_generate) -> (B * num_return_sequences, n_cols),
         n_cols the longest returned hypothesis; `last_beam_scores` / `last_beam_lengths` hold HF's sequences_scores and the lengths.
@@ -317,6 +450,10 @@ class AudioLlamaForCausalLM:
             raise L.SpeechLLMError("num_beams > 1 with do_sample=True (beam sampling) is not built: use beam search or sampling")
         if R < 1 or (R > K and not (K == 1 and sampling)):
             raise L.SpeechLLMError(f"num_return_sequences={R} outside [1, num_beams={K}]" + (" (greedy search returns one sequence per prompt: several need do_sample=True)" if K == 1 else ""))
+        session = past_key_values
+        if session is not None and (K > 1 or R > 1):
+            raise L.SpeechLLMError("a session continues one answer per sequence: num_beams > 1 and num_return_sequences > 1 are not built with past_key_values")
+        skw = {} if session is None else dict(session=session)
         w = self._dev()
         a = self.arch
         if inputs_embeds is None:
@@ -342,10 +479,10 @@ class AudioLlamaForCausalLM:
             sample = dict(temperature=float(g.temperature if temperature is None else temperature), top_k=int(g.top_k if top_k is None else top_k),
                           top_p=float(g.top_p if top_p is None else top_p), seed=int(seed))
         if not want_scores:
-            ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits, num_return=R)
+            ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits, num_return=R, **skw)
             seqs = ids[:, :n_cols].to(torch.int64)
             return GenerateOutput(seqs, None, None) if ret_dict else seqs
-        ids, n_cols, lps = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits, scores=True, num_return=R)
+        ids, n_cols, lps = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits, scores=True, num_return=R, **skw)
         seqs, lps = ids[:, :n_cols].to(torch.int64), lps[:, :n_cols].clone()
         self.last_token_logprobs = lps
         return GenerateOutput(seqs, lps, lps.sum(dim=1)) if ret_dict else seqs      # pads hold 0.0: the sum runs over the row's generated length
@@ -404,8 +541,9 @@ class AudioLlamaForCausalLM:
                                     "final_rows": int(st.final_rows), "row_steps": int(st.row_steps), "weight_format": fmt_name, **extra}
 
     def generate_packed(self, x: torch.Tensor, lens: Sequence[int], max_new_tokens: int, use_eos: bool = True, sample: Optional[dict] = None,
-                        shared_prefix: int = 0, row_limits: Optional[Sequence[int]] = None, compact: bool = True, check_every: int = 4,
-                        beams: Optional[dict] = None, logits: Optional[dict] = None, scores: bool = False, num_return: int = 1):
+                        shared_prefix: int = 0, row_limits: Optional[Sequence[int]] = None, compact: Optional[bool] = None, check_every: int = 4,
+                        beams: Optional[dict] = None, logits: Optional[dict] = None, scores: bool = False, num_return: int = 1,
+                        session: Optional[KVSession] = None):
         """x: packed prompt embeddings (sum S_i, h) on the GPU (overwritten).  Returns (int32 (B, max_new) host tensor, n_cols).
         shared_prefix = P: the caller's promise that the first P rows of every sequence are the same rows (one prompt template in
         front of the audio, ref:inference.py:95-113) — the batched decode attention then reads those P cache positions from slot 0
@@ -424,8 +562,27 @@ class AudioLlamaForCausalLM:
         partial.  Not with beams.  False: exactly the call without them.
         num_return = R > 1 (sampling only): R answers per prompt from ONE prefill (sl_generate_n) -> (B * R, max_new) ids / logprobs,
         prompt-major; row_limits then has B * R entries; the cache holds B prompt slots + B * R row slots.  The draws are those of a call
-        on every prompt repeated R times.  `last_generate_stats` has prefill_seqs and attn_path ("copy" / "grouped")."""
+        on every prompt repeated R times.  `last_generate_stats` has prefill_seqs and attn_path ("copy" / "grouped").
+        compact None: True, and False with a session.
+        session: a KVSession of len(lens) sequences (sl_generate_cont).  Its first call is this call run uncompacted into the session's cache;
+        a later call feeds, per sequence, the embedding of the pending token (the last one generated, never fed back) and then the rows of
+        `x`, on top of the valid_len positions the cache holds; valid_len / pending_id are then advanced from the returned ids (up to the
+        first EOS or the row's budget, pads not counted).  shared_prefix is the FIRST call's promise and is kept; later calls pass none.
+        The logits processors see this call's generated tokens only.  Not with beams or num_return > 1; compact=True raises (compaction
+        moves rows into the slots of finished ones and would destroy the K/V the session keeps); a prompt that leaves max_ctx raises
+        before anything is launched."""
         R = int(num_return)
+        if session is not None:
+            self._check_session(session)
+            if beams is not None or R > 1:
+                raise L.SpeechLLMError("a session continues one answer per sequence: beams and num_return > 1 are not built with it")
+            if compact:
+                raise L.SpeechLLMError("compact=True with a session: compaction moves live rows into the slots of finished rows and destroys the K/V the session keeps")
+            if not session.fresh and shared_prefix:
+                raise L.SpeechLLMError("shared_prefix belongs to a session's first call (its promise is kept: session.shared_prefix)")
+            x, lens = self._session_rows(session, x, lens)
+            session.check_room(lens, max_new_tokens)
+        compact = (session is None) if compact is None else bool(compact)
         if R < 1:
             raise L.SpeechLLMError(f"num_return_sequences={R}: must be >= 1")
         if R > 1 and sample is None and beams is None:
@@ -445,7 +602,12 @@ class AudioLlamaForCausalLM:
         if B * R > L.MAX_DECODE_BATCH:
             raise L.SpeechLLMError(f"{B * R} sequences in one generate call; the library takes {L.MAX_DECODE_BATCH} (split the batch: sequences are independent)")
         cu_c, eos_c, n_eos, use_eos, pad = self._generate_preamble(lens, max_new_tokens, use_eos, shared_prefix)
-        kv = self._kv_cache(B * (R + 1) if R > 1 else B, shared_prefix)
+        if session is not None:
+            if session.fresh:
+                session.shared_prefix = int(shared_prefix)
+            kv = session.kv_struct()
+        else:
+            kv = self._kv_cache(B * (R + 1) if R > 1 else B, shared_prefix)
         n_prompts, B = B, B * R      # B: decode rows = rows of every returned array
         out = (C.c_int32 * (B * max_new_tokens))()
         o = L.GenerateOpts()
@@ -478,6 +640,20 @@ class AudioLlamaForCausalLM:
             self._record_generate_stats(st, B, fmt_name, prefill_seqs=n_prompts, num_return_sequences=R,
                                         attn_path={1: "copy", 2: "grouped"}[int(lib.sl_generate_last_attn_path())])
             ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B, max_new_tokens)
+            if scores:
+                return ids, int(st.n_steps), torch.frombuffer(lps, dtype=torch.float32).clone().view(B, max_new_tokens)
+            return ids, int(st.n_steps)
+        if session is not None:
+            lps = (C.c_float * (B * max_new_tokens))() if scores else None
+            past_c = (C.c_int32 * B)(*session.valid_len)
+            ws = self._workspace(lib.sl_generate_workspace_bytes_cont(C.byref(struct), x.shape[0], B, max_new_tokens, lp_ref, int(bool(scores))))
+            L.check(lib.sl_generate_cont(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+                                         L.stream_ptr(), lp_ref, lps, past_c, None), "sl_generate_cont")
+            ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B, max_new_tokens)
+            gen = self.generation_config
+            eos = (list(gen.eos_token_id) if isinstance(gen.eos_token_id, (list, tuple)) else ([] if gen.eos_token_id is None else [gen.eos_token_id])) if use_eos else []
+            session.advance(lens, ids, eos, row_limits)
+            self._record_generate_stats(st, B, fmt_name, session_turn=session.turns)
             if scores:
                 return ids, int(st.n_steps), torch.frombuffer(lps, dtype=torch.float32).clone().view(B, max_new_tokens)
             return ids, int(st.n_steps)

@@ -349,6 +349,56 @@ int main() {
     int32_t lim[1] = {0};
     go.row_limits_host = lim;
     EXPECT_ARG_ERROR_SAYS(sl_generate_sc(&lm, &kv, ws, cu, 1, &go, out_ids, &gs, ws, need, nullptr, nullptr, lps), "row limit");           // row limit 0
+    go.row_limits_host = nullptr;
+    {   // multi-turn sessions: sl_llama_prefill_cont / sl_generate_cont refuse before any device call
+      sl_kv_cache kvs = kv;
+      kvs.slots = 3;
+      const size_t pneed = sl_llama_workspace_bytes(&lm, 137, 1);
+      const size_t pneed2 = sl_llama_workspace_bytes(&lm, 20, 2);
+      int32_t cu2[3] = {0, 10, 20};
+      int32_t past[2] = {-1, 0}, slot[2] = {0, 1};
+      EXPECT_ARG_ERROR_SAYS(sl_llama_prefill_cont(&lm, &kvs, ws, cu2, past, nullptr, 2, logits, ctx, ws, pneed2, nullptr), "negative");
+      past[0] = 120;
+      EXPECT_ARG_ERROR_SAYS(sl_llama_prefill_cont(&lm, &kvs, ws, cu, past, nullptr, 1, logits, ctx, ws, pneed, nullptr), "exceed max_ctx");      // 120 + 137 > 256
+      past[0] = 100; past[1] = 30;
+      kvs.shared_prefix = 31;
+      EXPECT_ARG_ERROR_SAYS(sl_llama_prefill_cont(&lm, &kvs, ws, cu2, past, nullptr, 2, logits, ctx, ws, pneed2, nullptr), "shared_prefix");    // above the shortest past
+      kvs.shared_prefix = 0;
+      slot[0] = 1;
+      EXPECT_ARG_ERROR_SAYS(sl_llama_prefill_cont(&lm, &kvs, ws, cu2, past, slot, 2, logits, ctx, ws, pneed2, nullptr), "two sequences");       // slot 1 twice
+      slot[0] = 3;
+      EXPECT_ARG_ERROR_SAYS(sl_llama_prefill_cont(&lm, &kvs, ws, cu2, nullptr, slot, 2, logits, ctx, ws, pneed2, nullptr), "outside");          // slot 3 of 3
+      slot[0] = 0;
+      EXPECT(sl_generate_workspace_bytes_cont(&lm, 137, 1, 8, nullptr, 1) == need, "cont workspace = sc workspace");
+      past[0] = 50;
+      EXPECT_ARG_ERROR_SAYS(sl_generate_cont(&lm, &kvs, ws, cu, 1, &go, out_ids, &gs, ws, need, nullptr, nullptr, lps, past, nullptr), "compact");   // compact = 1 on a kept cache
+      go.compact = 0;
+      past[0] = 112;
+      EXPECT_ARG_ERROR_SAYS(sl_generate_cont(&lm, &kvs, ws, cu, 1, &go, out_ids, &gs, ws, need, nullptr, nullptr, lps, past, nullptr), "max_ctx");   // 112 + 137 + 8 > 256
+      past[0] = -2;
+      EXPECT_ARG_ERROR_SAYS(sl_generate_cont(&lm, &kvs, ws, cu, 1, &go, out_ids, &gs, ws, need, nullptr, nullptr, lps, past, nullptr), "negative");
+      past[0] = 50; slot[0] = 2;
+      EXPECT_ARG_ERROR_SAYS(sl_generate_cont(&lm, &kvs, ws, cu, 1, &go, out_ids, &gs, ws, need, nullptr, nullptr, lps, past, slot), "slot order");   // a row's slot is its index
+      go.compact = 1;
+      // sl_attn_fwd_past: the forms that are not built, and a format code that is none
+      sl_attn_args pa;
+      memset(&pa, 0, sizeof(pa));
+      void* fk = (void*)(uintptr_t)(1 << 20);
+      const int32_t* fi = (const int32_t*)fk;
+      pa.q = pa.k = pa.v = fk; pa.out = fk; pa.cu_q = pa.cu_k = pa.klen = fi;
+      pa.nseq = 1; pa.max_qlen = 4; pa.n_heads = 4; pa.n_kv_heads = 2; pa.head_dim = 128; pa.causal = 1; pa.dtype = SL_BF16;
+      pa.q_row_stride = pa.k_row_stride = pa.v_row_stride = pa.o_row_stride = 1024; pa.q_head_stride = pa.k_head_stride = pa.v_head_stride = pa.o_head_stride = 128;
+      EXPECT(sl_attn_fwd_past(&pa, fk, fk, fi, fi, 64, 2, nullptr) == SL_ERR_ARG, "format code 2 is SL_ERR_ARG");
+      EXPECT(sl_attn_fwd_past(&pa, fk, fk, fi, fi, 64, -1, nullptr) == SL_ERR_ARG, "format code -1 is SL_ERR_ARG");
+      EXPECT(sl_attn_fwd_past(&pa, nullptr, fk, fi, fi, 64, 1, nullptr) == SL_ERR_ARG, "null cache");
+      pa.dtype = SL_F32;
+      EXPECT(sl_attn_fwd_past(&pa, fk, fk, fi, fi, 64, 1, nullptr) == SL_ERR_UNSUPPORTED, "fp32 is SL_ERR_UNSUPPORTED");
+      pa.dtype = SL_F16; pa.head_dim = 64;
+      EXPECT(sl_attn_fwd_past(&pa, fk, fk, fi, fi, 64, 0, nullptr) == SL_ERR_UNSUPPORTED, "head_dim 64 is SL_ERR_UNSUPPORTED");
+      pa.head_dim = 128; pa.causal = 0;
+      EXPECT(sl_attn_fwd_past(&pa, fk, fk, fi, fi, 64, 0, nullptr) == SL_ERR_UNSUPPORTED, "non-causal is SL_ERR_UNSUPPORTED");
+    }
+    go.row_limits_host = lim;
     sl_kv_cache kv4 = kv;
     kv4.slots = 4;
     sl_beam_opts bo;

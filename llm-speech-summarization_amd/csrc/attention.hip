@@ -5,6 +5,7 @@
 // both run on the dtype-generic 16x16 MFMA step (bf16: 16x16x32, fp32: exact 16x16x4), softmax state
 // (running max / sum) in fp32 registers, scores never leave the CU.
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
 
 struct AttnP {
@@ -19,6 +20,13 @@ struct AttnP {
   float drop_scale;
   uint64_t drop_seed;
   float* lse;            // training mode: log-sum-exp per (query row, head), natural log (NULL = not wanted)
+};
+// sl_attn_fwd_past: keys [0, past) of a sequence are rows of its K/V cache slot, keys [past, past + klen) the rows of AttnP.k / .v
+struct AttnPastP : AttnP {
+  const void* k_past; const void* v_past;   // one layer's cache, (slots, n_kv, max_ctx, D): T elements or e4m3 bytes
+  const int32_t* past_len;                  // per sequence
+  const int32_t* past_row0;                 // per sequence: first cache row of its slot (slot * n_kv * max_ctx)
+  int max_ctx;
 };
 
 // swizzled byte offset of 16-byte chunk `ch` of row `row`; rows hold `cpr` chunks (8, 16 or 32)
@@ -234,8 +242,11 @@ __device__ __forceinline__ int v_img_off(int row, int ch) {
 // per 64: the knock-outs of profiles/r06_i_attn_fwd_knockouts.txt put staging + barriers at 22 % of the kernel) and measured it EQUAL to ST = 1
 // (1 132-1 154 against 1 133-1 146 us at 512 x 499, encoder pass 107.9 against 107.8 ms, profiles/r06_l_attn_fwd_st_ab.txt): the barrier count is not what
 // the staging costs.  Default ST = 1; SL_ATTN_FWD_ST=2 selects the other form.
-template <typename T, int D, bool CAUSAL, int QT, bool DROP = false, int ST = 1>
-__global__ __launch_bounds__(256, 2) void attn_fwd_tr_kernel(AttnP p) {
+// PAST (sl_attn_fwd_past): 0 = every key from p.k / p.v; 1 / 2 = keys below the sequence's past length from its cache slot, in T (1) or as e4m3
+// bytes (2) widened by sl_dq8x8 between the prefetch registers and the LDS tile.  Only the staging differs: tiles, products and softmax are
+// the same code on the same key order, so PAST = 1 gives the bits of PAST = 0 over a cache the new rows were appended to.
+template <typename T, int D, bool CAUSAL, int QT, bool DROP = false, int ST = 1, int PAST = 0>
+__global__ __launch_bounds__(256, 2) void attn_fwd_tr_kernel(typename std::conditional<PAST != 0, AttnPastP, AttnP>::type p) {
   static_assert(sizeof(T) == 2, "the transposed-score kernel is built for the 16-bit types (bf16 / fp16)");
   constexpr int KS_D = D / 32;             // 32-wide steps across the head dim (S^T)
   constexpr int NF_O = D / 16;             // 16-wide output fragments
@@ -250,7 +261,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_tr_kernel(AttnP p) {
   const int seq = blockIdx.z, head = blockIdx.y;
   const int kvh = head / (p.n_heads / p.n_kv);
   const int q0 = p.cu_q[seq], qlen = p.cu_q[seq + 1] - q0;
-  const int klen = p.klen[seq];
+  int past = 0;
+  int64_t prow0 = 0;      // first cache row of this sequence's slot and kv head
+  if constexpr (PAST != 0) {
+    past = p.past_len[seq];
+    past = past < 0 ? 0 : (past > p.max_ctx ? p.max_ctx : past);      // never a cache row outside the slot
+    prow0 = (int64_t)p.past_row0[seq] + (int64_t)kvh * p.max_ctx;
+  }
+  const int klen = past + p.klen[seq];
   const int qt0 = blockIdx.x * QB;
   if (qt0 >= qlen) return;
   const int shift = klen - qlen;           // causal: key j visible to query i iff j <= i + shift
@@ -307,19 +325,43 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_tr_kernel(AttnP p) {
     for (int i = 0; i < NLD; ++i) {
       const int cidx = tid + 256 * i, row = cidx / CPR, ch = cidx % CPR;
       int kr = sb * (64 * ST) + row; kr = kr < klen ? kr : klen - 1;
+      if constexpr (PAST != 0) {
+        if (kr < past) {      // a cache row: the tile that straddles `past` takes rows from both sources
+          const int64_t e = (prow0 + kr) * D + ch * 8;
+          if constexpr (PAST == 2) {      // 8 e4m3 bytes, widened in sstore (the load stays in flight behind the products)
+            const u32x2_t kb8 = *(const u32x2_t*)((const unsigned char*)p.k_past + e), vb8 = *(const u32x2_t*)((const unsigned char*)p.v_past + e);
+            kreg[i] = u32x4_t{kb8.x, kb8.y, 0u, 0u};
+            vreg[i] = u32x4_t{vb8.x, vb8.y, 0u, 0u};
+          } else {
+            kreg[i] = *(const u32x4_t*)((const T*)p.k_past + e);
+            vreg[i] = *(const u32x4_t*)((const T*)p.v_past + e);
+          }
+        } else {
+          kreg[i] = *(const u32x4_t*)(kb + (int64_t)(kr - past) * p.k_rs + ch * 8);
+          vreg[i] = *(const u32x4_t*)(vb + (int64_t)(kr - past) * p.v_rs + ch * 8);
+        }
+        continue;
+      }
       kreg[i] = *(const u32x4_t*)(kb + (int64_t)kr * p.k_rs + ch * 8);
       vreg[i] = *(const u32x4_t*)(vb + (int64_t)kr * p.v_rs + ch * 8);
     }
   };
-  auto sstore = [&](int buf) {
+  auto sstore = [&](int buf, int sb) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int cidx = tid + 256 * i, row = cidx / CPR, ch = cidx % CPR;
+      if constexpr (PAST == 2) {
+        int kr = sb * (64 * ST) + row; kr = kr < klen ? kr : klen - 1;
+        if (kr < past) {
+          kreg[i] = sl_dq8x8<T>(u32x2_t{kreg[i].x, kreg[i].y});
+          vreg[i] = sl_dq8x8<T>(u32x2_t{vreg[i].x, vreg[i].y});
+        }
+      }
       *(u32x4_t*)(&smem[buf][0][0] + (row >> 6) * TILE_B + swz_off<CPR>(row & 63, ch)) = kreg[i];
       *(u32x4_t*)(&smem[buf][1][0] + (row >> 6) * TILE_B + v_img_off<D>(row & 63, ch)) = vreg[i];
     }
   };
-  if (nkt > 0) { gload(0); sstore(0); }
+  if (nkt > 0) { gload(0); sstore(0, 0); }
   __syncthreads();
 
   const int qq = r >> 2, pp = r & 3;   // transposed read: lane 4 qq + pp of a 16-lane group addresses row qq, 8-byte piece pp
@@ -450,7 +492,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_tr_kernel(AttnP p) {
     }
    }
 #if !defined(SL_ATTN_KO) || SL_ATTN_KO != 4
-    if (sb + 1 < nsb) sstore(buf ^ 1);
+    if (sb + 1 < nsb) sstore(buf ^ 1, sb + 1);
     __syncthreads();
 #endif
   }
@@ -544,4 +586,50 @@ extern "C" int sl_attn_fwd(const sl_attn_args* a, sl_stream stream) {
     sl_set_error("sl_attn_fwd: head_dim %d not built (64, 128)", a->head_dim);
     return SL_ERR_UNSUPPORTED;
   });
+}
+
+// Causal head_dim 128 prefill attention of a continued sequence: keys [0, past_s) from the cache slot, keys [past_s, past_s + klen_s) from a->k / a->v
+template <typename T>
+static int launch_attn_past(const sl_attn_args* a, const void* k_past, const void* v_past, const int32_t* past_len, const int32_t* past_row0, int max_ctx,
+                            int kv_format, hipStream_t st) {
+  AttnPastP p;
+  p.q = a->q; p.q_rs = a->q_row_stride; p.q_hs = a->q_head_stride;
+  p.k = a->k; p.k_rs = a->k_row_stride; p.k_hs = a->k_head_stride;
+  p.v = a->v; p.v_rs = a->v_row_stride; p.v_hs = a->v_head_stride;
+  p.o = a->out; p.o_rs = a->o_row_stride; p.o_hs = a->o_head_stride;
+  p.cu_q = a->cu_q; p.cu_k = a->cu_k; p.klen = a->klen;
+  p.n_heads = a->n_heads; p.n_kv = a->n_kv_heads; p.scale = a->scale;
+  p.drop_thr = 0; p.drop_scale = 1.f; p.drop_seed = 0; p.lse = nullptr;
+  p.k_past = k_past; p.v_past = v_past; p.past_len = past_len; p.past_row0 = past_row0; p.max_ctx = max_ctx;
+  constexpr int QT = 2;      // the head_dim 128 form sl_attn_fwd launches
+  dim3 grid((a->max_qlen + QT * 64 - 1) / (QT * 64), a->n_heads, a->nseq);
+  if (kv_format == SL_KV_FP8_E4M3) hipLaunchKernelGGL((attn_fwd_tr_kernel<T, 128, true, QT, false, 1, 2>), grid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((attn_fwd_tr_kernel<T, 128, true, QT, false, 1, 1>), grid, dim3(256), 0, st, p);
+  SL_CHECK_LAUNCH("attn_fwd_past");
+  return 0;
+}
+
+extern "C" int sl_attn_fwd_past(const sl_attn_args* a, const void* k_past, const void* v_past, const int32_t* past_len_dev, const int32_t* past_row0_dev,
+                                int32_t max_ctx, int32_t kv_format, sl_stream stream) {
+  SL_CHECK_ARG(a && a->q && a->k && a->v && a->out && a->cu_q && a->cu_k && a->klen && k_past && v_past && past_len_dev && past_row0_dev,
+               "sl_attn_fwd_past: null pointer");
+  SL_CHECK_ARG(a->nseq > 0 && a->max_qlen > 0 && a->n_heads > 0 && a->n_kv_heads > 0 && a->n_heads % a->n_kv_heads == 0 && max_ctx > 0,
+               "sl_attn_fwd_past: bad shape");
+  SL_CHECK_ARG(kv_format == SL_KV_MODEL_DTYPE || kv_format == SL_KV_FP8_E4M3, "sl_attn_fwd_past: unknown K/V cache format %d (0 = model dtype, 1 = fp8 e4m3)",
+               kv_format);
+  SL_CHECK_ARG(a->dtype == SL_F32 || a->dtype == SL_BF16 || a->dtype == SL_F16, "sl_attn_fwd_past: unknown dtype %d", a->dtype);
+  if (a->dtype == SL_F32 || a->head_dim != 128 || !a->causal || a->dropout_p != 0.f || a->lse) {
+    sl_set_error("sl_attn_fwd_past: built for causal bf16 / fp16 inference at head_dim 128 (dtype %d, head_dim %d, causal %d, dropout_p %f, lse %s)", a->dtype,
+                 a->head_dim, a->causal, (double)a->dropout_p, a->lse ? "set" : "NULL");
+    return SL_ERR_UNSUPPORTED;
+  }
+  SL_CHECK_ARG(a->q_row_stride % 8 == 0 && a->k_row_stride % 8 == 0 && a->v_row_stride % 8 == 0 && a->q_head_stride % 8 == 0 && a->k_head_stride % 8 == 0 &&
+                   a->v_head_stride % 8 == 0,
+               "sl_attn_fwd_past: strides must keep 16-byte alignment");
+  SL_CHECK_ARG(a->o_row_stride % 4 == 0 && a->o_head_stride % 4 == 0 && ((uintptr_t)a->out & 7) == 0, "sl_attn_fwd_past: the output needs 8-byte aligned rows");
+  SL_CHECK_ARG((((uintptr_t)k_past | (uintptr_t)v_past) & (kv_format == SL_KV_FP8_E4M3 ? 7 : 15)) == 0, "sl_attn_fwd_past: the cache needs %d-byte alignment",
+               kv_format == SL_KV_FP8_E4M3 ? 8 : 16);
+  hipStream_t st = (hipStream_t)stream;
+  if (a->dtype == SL_BF16) return launch_attn_past<bf16_t>(a, k_past, v_past, past_len_dev, past_row0_dev, max_ctx, kv_format, st);
+  return launch_attn_past<f16_t>(a, k_past, v_past, past_len_dev, past_row0_dev, max_ctx, kv_format, st);
 }

@@ -752,7 +752,7 @@ static int dec_gemm(const sl_llama_model* m, const LlamaWs& w, const void* A, in
 static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, void* x, int64_t n, LlamaWs& w, bool decode, int nseq,
                        int max_qlen, const int32_t* ctx_len_dev, hipStream_t st, bool rstd_chain = false, const float* rstd_qkv = nullptr,
                        int prefix_bcast = 0, int bcast_slots = 0, bool rstd_pass = false, const int32_t* tail_rows = nullptr, int n_tail = 0,
-                       const DecodeAttn* da = nullptr) {
+                       const DecodeAttn* da = nullptr, const int32_t* past_len_dev = nullptr) {
   const sl_llama_layer& L = m->layers[l];
   const int dt = m->dtype, H = m->hidden, D = m->head_dim, nh = m->n_heads, nkv = m->n_kv_heads;
   const int qkv_w = (nh + 2 * nkv) * D;
@@ -862,7 +862,10 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
       a.cu_k = w.cu;
     }
     a.nseq = nseq; a.max_qlen = max_qlen; a.n_heads = nh; a.n_kv_heads = nkv; a.head_dim = D; a.causal = 1; a.dtype = dt; a.scale = scale;
-    SL_TRY(sl_attn_fwd(&a, (sl_stream)st));
+    // continued prefill on an e4m3 cache (past_len_dev set, w.klen = the NEW key counts, w.cuk = each slot's first cache row): the past keys exist
+    // only as the cache's bytes — the values decode reads — and the new ones are attended unquantised out of qkv, as above
+    if (kv->reserved == SL_KV_FP8_E4M3 && past_len_dev) SL_TRY(sl_attn_fwd_past(&a, kc, vc, past_len_dev, w.cuk, kv->max_ctx, kv->reserved, (sl_stream)st));
+    else SL_TRY(sl_attn_fwd(&a, (sl_stream)st));
   }
   if (tail_rows && !decode) {
     const size_t esz = sl_dtype_size(dt);
@@ -887,8 +890,20 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
 // into the slot of its first beam — without the shared-prefix dedupe, whose broadcast assumes consecutive slots)
 static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
                               float* logits, int32_t* ctx_len_dev, void* hidden_taps, void* workspace, size_t workspace_bytes,
-                              sl_stream stream, int slot_stride) {
+                              sl_stream stream, int slot_stride, const int32_t* past_host = nullptr, const int32_t* slot_host = nullptr) {
   SL_TRY(llama_check(m, kv));
+  // continued prefill (sl_llama_prefill_cont): sequence s already holds positions [0, past_host[s]) of cache slot slot_host[s].  All-zero pasts on
+  // the identity slots ARE the plain call: every line below then runs as it did
+  if (past_host && nseq > 0) {
+    bool any = false;
+    for (int s = 0; s < nseq; ++s) {
+      SL_CHECK_ARG(past_host[s] >= 0, "sl_llama_prefill_cont: past length %d of sequence %d is negative", past_host[s], s);
+      any = any || past_host[s] > 0;
+    }
+    if (!any) past_host = nullptr;
+  }
+  const bool cont = past_host || slot_host;
+  if (cont) SL_CHECK_ARG(!hidden_taps && slot_stride == 1, "sl_llama_prefill_cont: hidden_taps are not offered");
   SL_CHECK_ARG(x && cu_seqlens_host && logits && ctx_len_dev && workspace && nseq > 0 && slot_stride >= 1 && (int64_t)nseq * slot_stride <= kv->slots,
                "sl_llama_prefill: bad arguments");
   hipStream_t st = (hipStream_t)stream;
@@ -910,12 +925,28 @@ static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, vo
   // Not with e4m3 rows either: that prefill reads K / V from its own qkv rows, not from the cache, so there is nothing to broadcast
   // (decode still reads the positions below shared_prefix from slot 0).
   int P = (kv->shared_prefix > 0 && nseq > 1 && !hidden_taps && sl_env().prefill_share_prefix && kv->reserved != SL_KV_FP8_E4M3 && slot_stride == 1) ? kv->shared_prefix : 0;
+  if (cont) P = 0;      // the new rows are never deduplicated: the promise then only says that cache positions [0, shared_prefix) are equal, which the first call made true
   for (int s = 0; s < nseq; ++s) {
     const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
     SL_CHECK_ARG(len > 0 && len <= kv->max_ctx, "sl_llama_prefill: sequence %d length %d outside (0, max_ctx=%d]", s, len, kv->max_ctx);
-    SL_CHECK_ARG(kv->shared_prefix <= len, "sl_llama_prefill: kv cache shared_prefix %d exceeds sequence %d (%d tokens)", kv->shared_prefix, s, len);
+    if (past_host) {      // (max_ctx <= rope_len: llama_check)
+      SL_CHECK_ARG((int64_t)past_host[s] + len <= kv->max_ctx, "sl_llama_prefill_cont: sequence %d: past %d + %d new rows exceed max_ctx %d", s, past_host[s], len, kv->max_ctx);
+      SL_CHECK_ARG(kv->shared_prefix <= past_host[s], "sl_llama_prefill_cont: kv cache shared_prefix %d exceeds the past length %d of sequence %d", kv->shared_prefix,
+                   past_host[s], s);
+    } else {
+      SL_CHECK_ARG(kv->shared_prefix <= len, "sl_llama_prefill: kv cache shared_prefix %d exceeds sequence %d (%d tokens)", kv->shared_prefix, s, len);
+    }
     if (len <= P) P = 0;
   }
+  if (slot_host) {
+    std::vector<char> used(kv->slots, 0);
+    for (int s = 0; s < nseq; ++s) {
+      SL_CHECK_ARG(slot_host[s] >= 0 && slot_host[s] < kv->slots, "sl_llama_prefill_cont: slot %d of sequence %d outside [0, %d)", slot_host[s], s, kv->slots);
+      SL_CHECK_ARG(!used[slot_host[s]], "sl_llama_prefill_cont: slot %d is given to two sequences", slot_host[s]);
+      used[slot_host[s]] = 1;
+    }
+  }
+  std::vector<int32_t> pastv;      // cont: per sequence, for the e4m3 attention
   int64_t n_run = n_tok;       // rows the layers run over
   int nseq_attn = nseq;
   if (P > 0) {
@@ -942,6 +973,21 @@ static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, vo
     SL_TRY(gather_rows(x, w.mid, w.tok_pos, n_run, (size_t)H * sz, st));
     SL_HIP(hipMemcpyAsync(x, w.mid, (size_t)n_run * H * sz, hipMemcpyDeviceToDevice, st));
     SL_HIP(hipStreamSynchronize(st));      // `map` leaves scope / tok_pos is rewritten below
+  } else if (cont) {
+    // rows rotated at and appended to positions past + t of their slot.  16-bit / fp32 cache: attention over the cache, klen = past + len > qlen,
+    // as the shared-prefix tails above.  e4m3: sl_attn_fwd_past takes the new key counts and the pasts apart (llama_layer)
+    const bool kv8 = kv->reserved == SL_KV_FP8_E4M3;
+    pastv.resize(nseq);
+    for (int s = 0; s < nseq; ++s) {
+      const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s], past = past_host ? past_host[s] : 0, slot = slot_host ? slot_host[s] : s;
+      for (int t = 0; t < len; ++t) { tseq[cu_seqlens_host[s] + t] = slot; tpos[cu_seqlens_host[s] + t] = past + t; }
+      cuk[s] = slot * m->n_kv_heads * kv->max_ctx;
+      kl[s] = kv8 ? len : past + len; ctx[s] = past + len; pastv[s] = past;
+      cuq[s] = cu_seqlens_host[s];
+      last_row[s] = cu_seqlens_host[s + 1] - 1;
+      if (len > max_q) max_q = len;
+    }
+    cuq[nseq] = cu_seqlens_host[nseq];
   } else {
     for (int s = 0; s < nseq; ++s) {
       const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
@@ -961,6 +1007,9 @@ static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, vo
   SL_HIP(hipMemcpyAsync(w.klen, kl.data(), nseq_attn * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipMemcpyAsync(ctx_len_dev, ctx.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipMemcpyAsync(w.last_row, last_row.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  // the pasts ride in the decode chain's RMSNorm-scale array, nseq 4-byte entries no prefill touches
+  int32_t* past_dev = (cont && kv->reserved == SL_KV_FP8_E4M3) ? (int32_t*)w.rstd_a : nullptr;
+  if (past_dev) SL_HIP(hipMemcpyAsync(past_dev, pastv.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipStreamSynchronize(st));
   // Only each sequence's last row is read after the final layer (lm_head below): without hidden_taps that layer runs everything behind
   // attention on those nseq rows alone (llama_layer tail_rows) — at 137-row prompts, 136 of 137 rows of o / gate/up / down of one layer
@@ -969,7 +1018,7 @@ static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, vo
   for (int l = 0; l < m->n_layers; ++l) {
     if (hidden_taps) SL_HIP(hipMemcpyAsync(bptr(hidden_taps) + (size_t)l * n_tok * H * sz, x, n_tok * H * sz, hipMemcpyDeviceToDevice, st));
     const bool tail = prune && l == m->n_layers - 1;
-    SL_TRY(llama_layer(m, kv, l, x, n_run, w, false, nseq_attn, max_q, nullptr, st, false, nullptr, P, nseq, false, tail ? w.last_row : nullptr, nseq));
+    SL_TRY(llama_layer(m, kv, l, x, n_run, w, false, nseq_attn, max_q, nullptr, st, false, nullptr, P, nseq, false, tail ? w.last_row : nullptr, nseq, nullptr, past_dev));
   }
   if (hidden_taps) {
     SL_TRY(sl_rmsnorm(x, bptr(hidden_taps) + (size_t)m->n_layers * n_tok * H * sz, m->final_norm, n_tok, H, m->rms_eps, dt, stream));
@@ -985,6 +1034,12 @@ extern "C" int sl_llama_prefill(const sl_llama_model* m, const sl_kv_cache* kv, 
                                 float* logits, int32_t* ctx_len_dev, void* hidden_taps, void* workspace, size_t workspace_bytes,
                                 sl_stream stream) {
   return llama_prefill_impl(m, kv, x, cu_seqlens_host, nseq, logits, ctx_len_dev, hidden_taps, workspace, workspace_bytes, stream, 1);
+}
+
+extern "C" int sl_llama_prefill_cont(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, const int32_t* past_len_host,
+                                     const int32_t* slot_host, int32_t nseq, float* logits, int32_t* ctx_len_dev, void* workspace, size_t workspace_bytes,
+                                     sl_stream stream) {
+  return llama_prefill_impl(m, kv, x, cu_seqlens_host, nseq, logits, ctx_len_dev, nullptr, workspace, workspace_bytes, stream, 1, past_len_host, slot_host);
 }
 
 // decode-step state carved from the tail of the workspace by sl_greedy_generate, or supplied by the caller
@@ -1443,8 +1498,25 @@ extern "C" size_t sl_generate_workspace_bytes_n(const sl_llama_model* m, int64_t
 
 static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
                          const sl_generate_opts* o, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
-                         sl_stream stream, const sl_logits_opts* lp_opts = nullptr, float* out_lp_host = nullptr, int N = 1) {
+                         sl_stream stream, const sl_logits_opts* lp_opts = nullptr, float* out_lp_host = nullptr, int N = 1, const int32_t* past_host = nullptr,
+                         const int32_t* slot_host = nullptr) {
   SL_CHECK_ARG(o != nullptr, "sl_generate: null options");
+  // sl_generate_cont: the caller keeps the cache.  Refused before anything is launched: compaction (it moves live rows into the slots of finished
+  // ones and destroys their K / V), several answers per prompt, and slots other than the identity (a decode row's slot is its row index)
+  bool past_any = false;      // some sequence continues: the shared-prefix promise is then about the cache ([0, P) below every past)
+  if (past_host)
+    for (int s = 0; s < nseq; ++s) past_any = past_any || past_host[s] > 0;
+  if (past_host) {
+    SL_CHECK_ARG(o->compact == 0,"sl_generate_cont: compact must be 0 when the caller keeps the cache (past_len_host is set)");
+    SL_CHECK_ARG(N == 1, "sl_generate_cont: one answer per sequence");
+    for (int s = 0; s < nseq; ++s) SL_CHECK_ARG(past_host[s] >= 0, "sl_generate_cont: past length %d of sequence %d is negative", past_host[s], s);
+  }
+  if (slot_host)
+    for (int s = 0; s < nseq; ++s)
+      if (slot_host[s] != s) {
+        sl_set_error("sl_generate_cont: sequence %d in slot %d: the decode loop keeps row b in slot b, pass the sequences in slot order (or NULL)", s, slot_host[s]);
+        return SL_ERR_UNSUPPORTED;
+      }
   SL_TRY(sl_logits_opts_check("sl_generate", lp_opts, o->max_new_tokens));
   SL_TRY(llama_check(m, kv));
   // several answers per prompt: refused before anything is launched
@@ -1471,12 +1543,13 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   hipStream_t st = (hipStream_t)stream;
   const int64_t n_tok = cu_seqlens_host[nseq];
   for (int s = 0; s < nseq; ++s)
-    SL_CHECK_ARG(cu_seqlens_host[s + 1] - cu_seqlens_host[s] + max_new_tokens <= kv->max_ctx,
+    SL_CHECK_ARG((int64_t)(past_host ? past_host[s] : 0) + cu_seqlens_host[s + 1] - cu_seqlens_host[s] + max_new_tokens <= kv->max_ctx,
                  "sl_generate: prompt %d (%d tokens) + %d new tokens exceeds max_ctx %d", s,
-                 cu_seqlens_host[s + 1] - cu_seqlens_host[s], max_new_tokens, kv->max_ctx);
+                 (past_host ? past_host[s] : 0) + cu_seqlens_host[s + 1] - cu_seqlens_host[s], max_new_tokens, kv->max_ctx);
   for (int s = 0; s < nseq; ++s)
-    SL_CHECK_ARG(kv->shared_prefix <= cu_seqlens_host[s + 1] - cu_seqlens_host[s], "sl_generate: kv cache shared_prefix %d exceeds prompt %d (%d tokens)",
-                 kv->shared_prefix, s, cu_seqlens_host[s + 1] - cu_seqlens_host[s]);
+    SL_CHECK_ARG(kv->shared_prefix <= (past_any ? past_host[s] : cu_seqlens_host[s + 1] - cu_seqlens_host[s]),
+                 "sl_generate: kv cache shared_prefix %d exceeds prompt %d (%d tokens)", kv->shared_prefix, s,
+                 past_any ? past_host[s] : cu_seqlens_host[s + 1] - cu_seqlens_host[s]);
   if (o->row_limits_host)
     for (int s = 0; s < B0; ++s)
       SL_CHECK_ARG(o->row_limits_host[s] >= 1 && o->row_limits_host[s] <= max_new_tokens, "sl_generate: row limit %d of sequence %d outside [1, max_new_tokens=%d]",
@@ -1527,7 +1600,8 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   Events3 ev;
   SL_TRY(ev.create());
   SL_HIP(hipEventRecord(ev.e[0], st));
-  SL_TRY(sl_llama_prefill(m, kv, x, cu_seqlens_host, nseq, N > 1 ? sn.logits_stage : logits, rs.ctx_len, nullptr, scratch, scratch_bytes, stream));
+  SL_TRY(llama_prefill_impl(m, kv, x, cu_seqlens_host, nseq, N > 1 ? sn.logits_stage : logits, rs.ctx_len, nullptr, scratch, scratch_bytes, stream, 1, past_host,
+                            slot_host));
   const int kv_row_vec = (int)(m->head_dim * kv_elem_bytes(m, kv) / 16);
   if (N > 1) {
     // each prompt was prefilled once: its logits row and its length go to its N rows; then either the group records (grouped) or a
@@ -1692,6 +1766,18 @@ extern "C" int sl_generate_sc(const sl_llama_model* m, const sl_kv_cache* kv, vo
                               const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
                               sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host) {
   return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream, lp, out_logprobs_host);
+}
+
+/* sl_generate_cont: sl_generate_sc on a cache the caller keeps (speechllm.h) */
+extern "C" size_t sl_generate_workspace_bytes_cont(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int32_t max_new_tokens, const sl_logits_opts* lp,
+                                                   int32_t scores) {
+  return sl_generate_workspace_bytes_sc(m, n_tok, nseq, max_new_tokens, lp, scores);
+}
+extern "C" int sl_generate_cont(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                                const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
+                                sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host, const int32_t* past_len_host, const int32_t* slot_host) {
+  return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream, lp, out_logprobs_host, 1, past_len_host,
+                       slot_host);
 }
 
 extern "C" int sl_generate_n(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,

@@ -243,7 +243,7 @@ class LLMSpeechTextInference():
         self.last_generate_ids = torch.cat([torch.nn.functional.pad(i, (0, width - int(i.shape[1])), value=int(pad)) for i in ids_all]) if ids_all else None
         return (out, scores_all) if return_scores else out
 
-    def _generate_chunk(self, audios, texts, max_new_tokens, logits=None, scores=False, num_return=1, ranges=None):
+    def _generate_chunk(self, audios, texts, max_new_tokens, logits=None, scores=False, num_return=1, ranges=None, session=None, sample=None):
         """One generate call's worth of utterances -> LongTensor (n, n_cols) of new tokens (scores: and their (n, n_cols) log-probabilities).
         num_return = R > 1: (n * R, n_cols), R answers per utterance sampled with the llm's generation_config warpers."""
         from .utils import compute_num_audio_embeds, prompt_template
@@ -295,15 +295,89 @@ class LLMSpeechTextInference():
         shared = int(pre_e.shape[0])
         if txt_e[0] is not None and all(t_ == texts[0] for t_ in texts):
             shared += int(txt_e[0].shape[0])
-        sample = None
+        skw = {} if session is None else dict(session=session)      # a conversation: the call runs in (and leaves its K/V in) the session's cache
         if num_return > 1:      # several answers are sampled ones: HF's warpers as llm.generate builds them
             g = self.llm.generation_config
             seed, self.llm.sample_seed = self.llm.sample_seed, self.llm.sample_seed + 1
             sample = dict(temperature=float(g.temperature), top_k=int(g.top_k), top_p=float(g.top_p), seed=int(seed))
         if scores:
             ids, n_cols, lps = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None,
-                                                        scores=True, sample=sample, num_return=num_return)
+                                                        scores=True, sample=sample, num_return=num_return, **skw)
             return ids[:, :n_cols].to(torch.int64), lps[:, :n_cols]
         ids, n_cols = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None,
-                                               sample=sample, num_return=num_return)
+                                               sample=sample, num_return=num_return, **skw)
         return ids[:, :n_cols].to(torch.int64)
+
+    # -- conversations: follow-up questions about the same recordings (an extension) -------------------------------------------------
+    def _sample_for(self, do_sample=None, temperature=None, top_k=None, top_p=None, seed=None):
+        """HF's sampling keywords -> the `sample` dict of generate_packed (None: greedy), as llm.generate builds it"""
+        g = self.llm.generation_config
+        if not bool(g.do_sample if do_sample is None else do_sample):
+            return None
+        if seed is None:
+            seed, self.llm.sample_seed = self.llm.sample_seed, self.llm.sample_seed + 1
+        return dict(temperature=float(g.temperature if temperature is None else temperature), top_k=int(g.top_k if top_k is None else top_k),
+                    top_p=float(g.top_p if top_p is None else top_p), seed=int(seed))
+
+    def start_conversation(self, audios, additional_text_prompts=None, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None,
+                           min_new_tokens=None, return_scores=False, ctc_pool_ranges=None, **sampling):
+        """generate_audio_responses that KEEPS what it computed: -> (texts, conversation).  The utterances are answered in one batch whose K/V
+        stays in a session of the llm (llm.new_session), and conversation.ask(texts) then answers a follow-up question per utterance for the
+        cost of the new rows alone — no second pass over the audio prompt or the first answer.  One generate call's worth of utterances
+        (SL_MAX_DECODE_BATCH); greedy or sampled (do_sample / temperature / top_k / top_p / seed), never beams or several answers.
+        return_scores: ((texts, scores), conversation)."""
+        n = len(audios)
+        texts = list(additional_text_prompts) if additional_text_prompts is not None else [""] * n
+        if len(texts) != n:
+            raise ValueError(f"{len(texts)} text prompts for {n} utterances")
+        if self.beams or self._num_return(None) > 1:
+            raise L.SpeechLLMError("a conversation continues one greedy or sampled answer per utterance: beam search and num_return_sequences > 1 are not built with it")
+        if n > L.MAX_DECODE_BATCH:
+            raise L.SpeechLLMError(f"{n} utterances in one conversation; a generate call takes {L.MAX_DECODE_BATCH}")
+        ctc = self.audio_encoder.downsample_method == "ctc_pool"
+        if ctc and ctc_pool_ranges is None and getattr(self, "ctc_segmenter", None) is None:
+            raise AttributeError("'LLMSpeechTextInference' object has no attribute 'get_ctc_pool_ranges'")
+        conv = Conversation(self, self.llm.new_session(n))
+        res = self._generate_chunk(audios, texts, max_new_tokens, self._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens), return_scores, 1,
+                                   ranges=list(ctc_pool_ranges) if ctc and ctc_pool_ranges is not None else None, session=conv.session,
+                                   sample=self._sample_for(**sampling))
+        return conv._decode(res, return_scores), conv
+
+
+class Conversation:
+    """What LLMSpeechTextInference.start_conversation returns beside the first answers: the llm's KVSession of the batch and `ask`."""
+
+    def __init__(self, owner: LLMSpeechTextInference, session):
+        self.owner, self.session = owner, session
+        self.last_generate_ids = None
+
+    def _decode(self, res, return_scores):
+        o = self.owner
+        ids, lps = res if return_scores else (res, None)
+        self.last_generate_ids = o.last_generate_ids = ids
+        texts = o.llm_tokenizer.batch_decode(ids, skip_special_tokens=True, clean_up_tokenization_spaces=True)
+        return (texts, o._mean_logprobs(ids, lps)) if return_scores else texts
+
+    def follow_up_ids(self, texts) -> List[torch.Tensor]:
+        """One id row per utterance: utils.follow_up_prompt tokenised without BOS; where the pending token already is an EOS / eot id the
+        template's leading eot is dropped, so that it is not fed twice."""
+        from .utils import follow_up_ids
+        o = self.owner
+        e = o.llm.generation_config.eos_token_id
+        eos = set(e if isinstance(e, (list, tuple)) else ([] if e is None else [e]))
+        return [follow_up_ids(o.llm_tokenizer, o.llm_type, t_, drop_eot=p in eos) for t_, p in zip(texts, self.session.pending_id)]
+
+    def ask(self, texts, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None, min_new_tokens=None, return_scores=False, **sampling):
+        """One follow-up question per utterance (a string for all, or a list) -> the answers (return_scores: (texts, scores))."""
+        o, n = self.owner, self.session.n_seq
+        texts = [texts] * n if isinstance(texts, str) else list(texts)
+        if len(texts) != n:
+            raise ValueError(f"{len(texts)} questions for a conversation of {n} utterances")
+        rows = [o.llm.model.embed_tokens(i.to(o.device)) for i in self.follow_up_ids(texts)]
+        x = torch.cat(rows, 0).to(o.llm.dtype).contiguous()
+        logits = o._logits_for(repetition_penalty, no_repeat_ngram_size, min_new_tokens) or None
+        out = o.llm.generate_packed(x, [int(r.shape[0]) for r in rows], max_new_tokens, use_eos=True, logits=logits, scores=bool(return_scores),
+                                    sample=o._sample_for(**sampling), session=self.session)
+        n_cols = out[1]
+        ids = out[0][:, :n_cols].to(torch.int64)
+        return self._decode((ids, out[2][:, :n_cols]) if return_scores else ids, return_scores)

@@ -153,6 +153,23 @@ def attn_fwd(q, k, v, out, cu_q, cu_k, klen, *, q_strides, k_strides, v_strides,
     return out
 
 
+def attn_fwd_past(q, k, v, out, cu_q, cu_k, klen, k_past, v_past, past_len, past_row0, *, q_strides, k_strides, v_strides, o_strides, nseq, max_qlen,
+                  n_heads, n_kv_heads, head_dim, max_ctx, kv_format, scale, causal=True, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """sl_attn_fwd_past: causal prefill attention of continued sequences — keys [0, past_len[s]) from one layer's cache (k_past / v_past
+    (slots, n_kv, max_ctx, D), elements of the dtype or e4m3 bytes; past_row0[s] = slot * n_kv * max_ctx), then the klen[s] new rows of k / v."""
+    a = L.AttnArgs()
+    a.q, a.q_row_stride, a.q_head_stride = L.ptr(q), q_strides[0], q_strides[1]
+    a.k, a.k_row_stride, a.k_head_stride = L.ptr(k), k_strides[0], k_strides[1]
+    a.v, a.v_row_stride, a.v_head_stride = L.ptr(v), v_strides[0], v_strides[1]
+    a.out, a.o_row_stride, a.o_head_stride = L.ptr(out), o_strides[0], o_strides[1]
+    a.cu_q, a.cu_k, a.klen = L.ptr(cu_q), L.ptr(cu_k), L.ptr(klen)
+    a.nseq, a.max_qlen, a.n_heads, a.n_kv_heads = nseq, max_qlen, n_heads, n_kv_heads
+    a.head_dim, a.causal, a.dtype, a.scale = head_dim, int(causal), L.dtype_code(out.dtype if dtype is None else dtype), scale
+    L.check(L.lib().sl_attn_fwd_past(C.byref(a), L.ptr(k_past), L.ptr(v_past), L.ptr(past_len), L.ptr(past_row0), int(max_ctx), int(kv_format),
+                                     L.stream_ptr()), "sl_attn_fwd_past")
+    return out
+
+
 def attn_bwd(q, k, v, out, d_out, lse, dq, dk, dv, cu_q, cu_k, klen, *, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides,
              dk_strides, dv_strides, nseq, max_qlen, max_klen, n_tok_q, n_heads, n_kv_heads, head_dim, causal, scale, dropout_p: float = 0.0,
              dropout_seed: int = 0, delta: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -31,6 +31,28 @@ def prompt_template(llm_type: str):
     raise Exception("Unknown LLM type.")
 
 
+LLAMA_EOT, LLAMA_USER_HEADER = "<|eot_id|>", "<|start_header_id|>user<|end_header_id|>\n\n"
+MINICHAT_EOT, MINICHAT_USER_HEADER = "</s>", "[|User|]"
+
+
+def follow_up_prompt(llm_type: str, text: str, drop_eot: bool = False) -> str:
+    """A follow-up turn of a conversation (an extension: the reference answers one question per recording), built from the constants
+    above: "{eot}{user header}{text}{PROMPT_SUFFIX}" — the eot closes the assistant's answer, the suffix opens the next one.  drop_eot:
+    the answer already ended with the eot token and that token is fed first (KVSession.pending_id), so the template's own is left out."""
+    _, suffix = prompt_template(llm_type)
+    eot, header = (MINICHAT_EOT, MINICHAT_USER_HEADER) if suffix == MINICHAT_PROMPT_SUFFIX else (LLAMA_EOT, LLAMA_USER_HEADER)
+    return f"{'' if drop_eot else eot}{header}{text}{suffix}"
+
+
+def follow_up_ids(tokenizer, llm_type: str, text: str, drop_eot: bool = False) -> torch.Tensor:
+    """follow_up_prompt tokenised -> (n,) ids without a BOS (a turn in the middle of a sequence carries none)"""
+    ids = tokenizer(follow_up_prompt(llm_type, text, drop_eot), return_tensors="pt").input_ids[0]
+    bos = getattr(tokenizer, "bos_token_id", None)
+    if bos is not None and ids.numel() > 0 and int(ids[0]) == int(bos):
+        ids = ids[1:]
+    return ids
+
+
 def compute_num_audio_embeds(audio_samples, sr=16000):
     """ref:utils.py:13-24, reproduced bit for bit (it defines the crop; may be one short)."""
     num_embeds = (audio_samples - (sr * 0.01)) // (sr * 0.02)
