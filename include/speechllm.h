@@ -1125,6 +1125,58 @@ int sl_generate_cont(const sl_llama_model* m, const sl_kv_cache* kv, void* x, co
                      sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host, const int32_t* past_len_host, const int32_t* slot_host);
 
 /* ---------------------------------------------------------------------------------------------
+ * Teacher-forced scoring: the log-probability of GIVEN tokens, batched; additive to ABI 7.
+ * For a scored row with hidden state h and label y:  logprob = log_softmax(lm_head(final_norm(h)))[y] in fp32, NaN counted as -inf, one
+ * fixed order of additions (no float atomics).  A label outside [0, vocab) (HF's -100) marks an IGNORED position: its logprob is 0.0f, it
+ * is counted in no sum, and nothing is read at its place.  top1 = the row's first maximum (sl_greedy_select's rule: the larger value, then
+ * the lower column; NaN never wins).  A row without a finite maximum yields a non-finite logprob.
+ *
+ * sl_gemm_top1_lse_tgt: sl_gemm_top1_lse (same checks, same three planes bit for bit) plus tgt_val[m] = the value at (m, tgt_col[m]) — the
+ * acc + bias value the top-1 compared, stored by the one lane that holds that element.  A row whose tgt_col lies outside [0, N) is written
+ * by nobody: tgt_val[m] keeps what it held.  tgt_col (M int32) and tgt_val (M floats) are device pointers and come both or neither
+ * (neither: this IS sl_gemm_top1_lse).
+ *
+ * sl_score_finalize: the three planes ([g][rows], n_groups = ceil(vocab / 64)) and tgt_val -> logprob_out[r] = (tgt_val[r] - m) -
+ * logf(sum_g amax_sum[g] * expf(amax_val[g] - m)), m the row maximum, and top1_out[r] (may be NULL).  tgt_val[r] is not read for an
+ * ignored label.  Groups are added in index order within each of 32 stripes (g mod 32), the stripes in order.
+ * sl_score_rows: the same two outputs from fp32 logits (rows, vocab) of pitch ld, one block per row through the row reduce of
+ * sl_greedy_select_sc / sl_logits_process; logits[r][label] is not read for an ignored label.
+ * sl_score_segment_sums: per sequence s over rows [row_offsets[s], row_offsets[s + 1]) (device, nseq + 1 entries): sum_logprob[s], n_counted[s]
+ * (rows that are not ignored) and n_top1[s] (counted rows whose top1 equals the label; top1 and n_top1 come both or neither).
+ *
+ * sl_llama_score: sl_llama_prefill's layers over the packed sequences of x (modified in place, K/V left in slots [0, nseq) like prefill;
+ * no generation state, captured graph or session is touched), then row score_start_host[s] + j of sequence s is scored against
+ * labels_dev[off_s + j], off_s = sum of n_score_host below s; logprob_dev / top1_dev (may be NULL) have sum n_score entries in that
+ * order; seq_sum_dev / seq_counted_dev / seq_top1_dev (nseq each, all three or none) take sl_score_segment_sums' results.  The final
+ * layer computes nothing behind attention except for the scored rows; the lm_head runs in passes of opts->row_chunk rows (0 = 2 048): a
+ * pass of more than 64 rows through sl_gemm_top1_lse_tgt + sl_score_finalize (no logit is written), a pass of at most 64 rows — a short
+ * remainder included — through fp32 logits + sl_score_rows.  force_path: 0 = that rule, 1 = always fp32 logits + sl_score_rows, 2 = fused
+ * wherever a pass has more than 64 rows.  The shared-prefix prefill is not used (kv->shared_prefix is ignored).  The e4m3 K/V format is
+ * accepted: prefill under it attends the unquantised rows and that path is the one prefill runs.  One host synchronisation, as in prefill.
+ * Checked before any launch: SL_ERR_ARG for null pointers, n_score < 0, start < 0, start + n > length, sum n_score == 0, the per-sequence
+ * outputs given partly, row_chunk < 0, a workspace below sl_llama_score_workspace_bytes (0 on a bad argument); SL_ERR_UNSUPPORTED for a
+ * cache with fewer than nseq slots or a sequence longer than max_ctx.  sl_llama_score_last_paths(): what the calling thread's last
+ * sl_llama_score ran — bit 0 = fp32 logits + sl_score_rows, bit 1 = the fused planes. */
+typedef struct {
+  int32_t row_chunk;   /* lm_head rows per pass; 0 = default */
+  int32_t force_path;  /* 0 = rule above, 1 = always fp32 logits + sl_score_rows, 2 = fused wherever M > 64 */
+  int32_t reserved[6];
+} sl_score_opts;
+int sl_gemm_top1_lse_tgt(const sl_gemm_args* args, const sl_gemm_ex_args* ex, float* amax_sum, const int32_t* tgt_col, float* tgt_val, sl_stream stream);
+int sl_score_finalize(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int32_t n_groups, int32_t vocab, const float* tgt_val,
+                      const int32_t* labels, int32_t rows, float* logprob_out, int32_t* top1_out, sl_stream stream);
+int sl_score_rows(const float* logits, int64_t ld, const int32_t* labels, int32_t rows, int32_t vocab, float* logprob_out, int32_t* top1_out,
+                  sl_stream stream);
+int sl_score_segment_sums(const float* logprob, const int32_t* labels, const int32_t* top1, const int32_t* row_offsets, int32_t nseq, int32_t vocab,
+                          float* sum_logprob, int32_t* n_counted, int32_t* n_top1, sl_stream stream);
+size_t sl_llama_score_workspace_bytes(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int64_t n_rows, const sl_score_opts* opts);
+int sl_llama_score(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                   const int32_t* score_start_host, const int32_t* n_score_host, const int32_t* labels_dev, float* logprob_dev, int32_t* top1_dev,
+                   float* seq_sum_dev, int32_t* seq_counted_dev, int32_t* seq_top1_dev, const sl_score_opts* opts, void* workspace,
+                   size_t workspace_bytes, sl_stream stream);
+int32_t sl_llama_score_last_paths(void);
+
+/* ---------------------------------------------------------------------------------------------
  * KD step, layer stacks (C++ host runtime of the training tape: one call issues the launches of a whole stack of layers
  * over a packed ragged batch; ref:trainer.py:270-384 runs the same arithmetic through autograd, one utterance at a time).
  * Saved activations, hidden states and fp32 gradient accumulators are caller-owned; temporaries come from `workspace`.

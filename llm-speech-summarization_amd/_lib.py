@@ -201,6 +201,14 @@ class LogitsOpts(C.Structure):
     _fields_ = [("repetition_penalty", c_f32), ("no_repeat_ngram_size", c_i32), ("min_new_tokens", c_i32), ("reserved", c_i32)]
 
 
+class ScoreOpts(C.Structure):
+    """sl_score_opts: lm_head rows per pass of sl_llama_score (0 = default) and the path switch (0 = rule, 1 = fp32 logits, 2 = fused)"""
+    _fields_ = [("row_chunk", c_i32), ("force_path", c_i32), ("reserved", c_i32 * 6)]
+
+
+SCORE_PATH_ROWS, SCORE_PATH_FUSED = 1, 2      # bits of sl_llama_score_last_paths()
+
+
 EARLY_STOPPING = {False: 0, True: 1, "never": 2}      # sl_beam_opts.early_stopping
 
 
@@ -380,6 +388,15 @@ _PROTOS = {
     "sl_generate_workspace_bytes_cont": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, c_i32, C.POINTER(LogitsOpts), c_i32]),
     "sl_generate_cont": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(GenerateOpts), C.POINTER(c_i32),
                                  C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts), C.POINTER(c_f32), C.POINTER(c_i32), C.POINTER(c_i32)]),
+    # teacher-forced scoring (additive to ABI 7)
+    "sl_gemm_top1_lse_tgt": (c_i32, [C.POINTER(GemmArgs), C.POINTER(GemmEx), c_vp, c_vp, c_vp, c_vp]),
+    "sl_score_finalize": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "sl_score_rows": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "sl_score_segment_sums": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "sl_llama_score_workspace_bytes": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, c_i64, C.POINTER(ScoreOpts)]),
+    "sl_llama_score": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(c_i32), C.POINTER(c_i32), c_vp, c_vp, c_vp,
+                               c_vp, c_vp, c_vp, C.POINTER(ScoreOpts), c_vp, c_sz, c_vp]),
+    "sl_llama_score_last_paths": (c_i32, []),
     "sl_greedy_generate": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, c_i32,
                                    C.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32, C.POINTER(c_i32), C.POINTER(c_i32),
                                    C.POINTER(c_f32), c_vp, c_sz, c_vp]),

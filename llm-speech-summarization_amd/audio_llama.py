@@ -36,6 +36,62 @@ class GenerateOutput:
         self.sequences, self.token_logprobs, self.sequences_scores = sequences, token_logprobs, sequences_scores
 
 
+class ScoreOutput:
+    """What score() returns: the log-probabilities of GIVEN answers (teacher forcing).
+      token_logprobs      list of float32 (n_b,) tensors: log_softmax(logits)[target] per position, 0.0 at an ignored position (id < 0)
+      sequence_logprobs   (B,) float32: the sum over a sequence's counted positions
+      n_tokens            (B,) int64: counted (not ignored) positions
+      top1_match          list of bool (n_b,) tensors, with return_top1: the target IS the model's first maximum (False at ignored positions)
+      paths               set of the lm_head forms the call ran: "rows" (fp32 logits + sl_score_rows) and / or "fused" (the planes)"""
+    __slots__ = ("token_logprobs", "sequence_logprobs", "n_tokens", "top1_match", "paths")
+
+    def __init__(self, token_logprobs, sequence_logprobs, n_tokens, top1_match=None, paths=()):
+        self.token_logprobs, self.sequence_logprobs, self.n_tokens, self.top1_match, self.paths = token_logprobs, sequence_logprobs, n_tokens, top1_match, set(paths)
+
+    @property
+    def nll(self) -> torch.Tensor:
+        """(B,) per-sequence mean negative log-probability over the counted positions (nan for a sequence that counts none)"""
+        return -self.sequence_logprobs.double() / self.n_tokens.double()
+
+    def perplexity(self) -> float:
+        """exp(mean over sequences of nll): the quantity Trainer.validate logs"""
+        return float(torch.exp(self.nll.mean()))
+
+
+def score_plan(prompt_lens: Sequence[int], targets: Sequence[Sequence[int]], max_ctx: int, max_seqs: int, pad_id: int = 0):
+    """Host bookkeeping of score(), no device work: sequence b is its P_b prompt rows followed by the embeddings of target[:-1], rows
+    [P_b - 1, P_b - 1 + n_b) are scored against target (row P_b - 1 + j predicts target[j]).  Ids < 0 are ignored positions: they stay in the
+    labels as they are and feed the pad row as input.  Returns a list of calls of at most max_seqs sequences, each a dict of
+    seqs (indices), lens, score_start, n_score, labels (packed, sequence-major) and input_ids (the appended rows' ids, packed).
+    Raises SpeechLLMError for an empty target, a prompt of zero rows or a sequence beyond max_ctx."""
+    if len(prompt_lens) != len(targets):
+        raise L.SpeechLLMError(f"{len(prompt_lens)} prompts for {len(targets)} targets")
+    if len(targets) == 0:
+        raise L.SpeechLLMError("score needs at least one sequence")
+    if int(max_seqs) < 1:
+        raise L.SpeechLLMError(f"max_seqs={max_seqs}: a call takes at least one sequence")
+    for b, (P, tg) in enumerate(zip(prompt_lens, targets)):
+        if int(P) < 1:
+            raise L.SpeechLLMError(f"sequence {b}: a prompt of zero rows has no position that predicts the first target token")
+        if len(tg) < 1:
+            raise L.SpeechLLMError(f"sequence {b}: empty target")
+        if int(P) + len(tg) - 1 > int(max_ctx):
+            raise L.SpeechLLMError(f"sequence {b}: prompt ({int(P)}) + target ({len(tg)}) - 1 rows exceed max_ctx={int(max_ctx)}")
+    calls = []
+    for b0 in range(0, len(targets), int(max_seqs)):
+        seqs = list(range(b0, min(b0 + int(max_seqs), len(targets))))
+        call = dict(seqs=seqs, lens=[], score_start=[], n_score=[], labels=[], input_ids=[])
+        for b in seqs:
+            tg = [int(v) for v in targets[b]]
+            call["lens"].append(int(prompt_lens[b]) + len(tg) - 1)
+            call["score_start"].append(int(prompt_lens[b]) - 1)
+            call["n_score"].append(len(tg))
+            call["labels"] += tg
+            call["input_ids"] += [v if v >= 0 else int(pad_id) for v in tg[:-1]]
+        calls.append(call)
+    return calls
+
+
 class KVSession:
     """A K/V cache that outlives a generate call: what `llm.new_session(n_seq)` returns and generate(past_key_values=) /
     generate_packed(session=) / forward(use_cache=True, past_key_values=) continue on.  It owns its K and V tensors — n_seq slots at
@@ -160,7 +216,8 @@ class AudioLlamaForCausalLM:
         self._w: Optional[LlamaDeviceWeights] = None
         self._kv = None
         self._ws: Optional[torch.Tensor] = None
-        self.model = SimpleNamespace(embed_tokens=_EmbedTokens(self))
+        self._score_ws: Optional[torch.Tensor] = None      # score()'s own workspace
+        self.model =SimpleNamespace(embed_tokens=_EmbedTokens(self))
         self.last_timings_ms = None
         self.last_generate_stats = None
         self.last_beam_scores = None       # beam search: (B * num_return_sequences) float32 sequences_scores of the last call
@@ -412,6 +469,94 @@ class AudioLlamaForCausalLM:
         return SimpleNamespace(loss=None, logits=logits.view(B, 1, a.vocab_size), hidden_states=None, past_key_values=session, attentions=None)
 
     __call__ = forward
+
+    # -- teacher-forced scoring -------------------------------------------------------------------
+    def _score_slots(self) -> int:
+        """sequences one sl_llama_score call takes: the slots of the K/V cache the model already holds (score never replaces it, so a
+        generate() after it finds its buffers — and its captured graphs — where they were), max_batch when there is none yet"""
+        if self._kv is not None and self._kv[0].shape[3] == self.max_ctx:
+            return min(int(self._kv[0].shape[1]), L.MAX_DECODE_BATCH)
+        return min(max(1, int(self.max_batch)), L.MAX_DECODE_BATCH)
+
+    def score(self, prompt_embeds, target_ids, *, attention_mask=None, return_top1: bool = False, row_chunk: Optional[int] = None, force_path: int = 0) -> ScoreOutput:
+        """Log-probabilities of given answers under given prompts, batched (sl_llama_score).
+        prompt_embeds: list of (P_b, H) tensors, or a left-padded (B, S, H) tensor with attention_mask.  target_ids: list of 1-D id tensors
+        (or id lists).  Sequence b is its prompt followed by embed_tokens(target[:-1]); rows [P_b - 1, P_b - 1 + n_b) are scored against
+        target_b, so token_logprobs[b][j] = log P(target_b[j] | prompt_b, target_b[:j]).  Ids < 0 (HF's -100) are ignored positions: 0.0,
+        counted nowhere, their input embedding is the pad row.  Batches beyond the K/V cache's slots (or SL_MAX_DECODE_BATCH) are split
+        into consecutive calls.  row_chunk: lm_head rows per pass (None / 0: the library's default); force_path: 0 = the library's rule,
+        1 = fp32 logits everywhere, 2 = the fused planes wherever a pass has more than 64 rows.  An empty target, a prompt of zero rows or
+        a sequence beyond max_ctx raises before any device work.  No generation state, captured graph or session is touched; the
+        model's K/V cache is overwritten in slots [0, B) as by any prefill."""
+        if torch.is_tensor(prompt_embeds):
+            if prompt_embeds.dim() != 3:
+                raise L.SpeechLLMError("prompt_embeds must be a list of (P_b, H) tensors or a (B, S, H) tensor")
+            Bp, S, _ = prompt_embeds.shape
+            if attention_mask is None:
+                prompts = [prompt_embeds[b] for b in range(Bp)]
+            else:
+                plens = attention_mask.sum(dim=1).tolist()
+                prompts = [prompt_embeds[b, S - int(n):] for b, n in enumerate(plens)]      # left padding (ref:utils.py:76-82)
+        else:
+            prompts = list(prompt_embeds)
+        targets = [tg.reshape(-1).tolist() if torch.is_tensor(tg) else [int(v) for v in tg] for tg in target_ids]
+        chunk = 0 if row_chunk is None else int(row_chunk)
+        if chunk < 0:
+            raise L.SpeechLLMError(f"row_chunk={row_chunk}: must be >= 0 (0 / None = the library's default)")
+        if int(force_path) not in (0, 1, 2):
+            raise L.SpeechLLMError(f"force_path={force_path}: 0 (rule), 1 (fp32 logits) or 2 (fused)")
+        pad = self.generation_config.pad_token_id
+        calls = score_plan([int(p.shape[0]) for p in prompts], targets, self.max_ctx, self._score_slots(), 0 if pad is None else int(pad))
+        self._dev()
+        a = self.arch
+        lib = L.lib()
+        opts = L.ScoreOpts()
+        opts.row_chunk, opts.force_path = chunk, int(force_path)
+        token_lps, seq_sums, seq_counts, matches, paths = [], [], [], [], set()
+        for call in calls:
+            nseq, n_rows = len(call["seqs"]), len(call["labels"])
+            emb = self.model.embed_tokens(L.h2d(call["input_ids"], torch.int32, self.device)).to(self.dtype) if call["input_ids"] else None
+            parts, o = [], 0
+            for i, b in enumerate(call["seqs"]):
+                parts.append(prompts[b].to(self.device, self.dtype))
+                k = call["n_score"][i] - 1
+                if k:
+                    parts.append(emb[o:o + k])
+                    o += k
+            x = torch.cat(parts, 0).contiguous() if len(parts) > 1 else parts[0].contiguous().clone()      # the library overwrites x
+            cu = [0]
+            for n in call["lens"]:
+                cu.append(cu[-1] + n)
+            cu_c = (C.c_int32 * (nseq + 1))(*cu)
+            start_c, ns_c = (C.c_int32 * nseq)(*call["score_start"]), (C.c_int32 * nseq)(*call["n_score"])
+            labels = L.h2d(call["labels"], torch.int32, self.device)
+            kv = self._kv_cache(max(nseq, self._score_slots()))
+            struct, _ = self._struct_for(nseq)      # the layers read the row-major set of either struct
+            nbytes = lib.sl_llama_score_workspace_bytes(C.byref(struct), x.shape[0], nseq, n_rows, C.byref(opts))
+            if nbytes == 0:
+                L.check(-1, "sl_llama_score_workspace_bytes")
+            if self._score_ws is None or self._score_ws.numel() < nbytes:      # its own buffer: generate()'s workspace stays where its graphs expect it
+                self._score_ws = None
+                self._score_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+            ws = self._score_ws
+            lp = torch.empty(n_rows, device=self.device, dtype=torch.float32)
+            top1 = torch.empty(n_rows, device=self.device, dtype=torch.int32) if return_top1 else None
+            ssum = torch.empty(nseq, device=self.device, dtype=torch.float32)
+            scnt = torch.empty(nseq, device=self.device, dtype=torch.int32)
+            shit = torch.empty(nseq, device=self.device, dtype=torch.int32)
+            L.check(lib.sl_llama_score(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, nseq, start_c, ns_c, labels.data_ptr(), lp.data_ptr(), L.ptr(top1),
+                                       ssum.data_ptr(), scnt.data_ptr(), shit.data_ptr(), C.byref(opts), ws.data_ptr(), ws.numel(), L.stream_ptr()), "sl_llama_score")
+            bits = int(lib.sl_llama_score_last_paths())
+            paths |= {name for bit, name in ((L.SCORE_PATH_ROWS, "rows"), (L.SCORE_PATH_FUSED, "fused")) if bits & bit}
+            o = 0
+            for n in call["n_score"]:
+                token_lps.append(lp[o:o + n])
+                if return_top1:
+                    matches.append((top1[o:o + n] == labels[o:o + n]) & (labels[o:o + n] >= 0))
+                o += n
+            seq_sums.append(ssum)
+            seq_counts.append(scnt)
+        return ScoreOutput(token_lps, torch.cat(seq_sums), torch.cat(seq_counts).to(torch.int64), matches if return_top1 else None, paths)
 
     # -- generation -----------------------------------------------------------------------------
     def generate(self, input_ids=None, inputs_embeds=None, max_new_tokens: int = 256, attention_mask=None, use_eos: bool = True,

@@ -350,6 +350,25 @@ int main() {
     go.row_limits_host = lim;
     EXPECT_ARG_ERROR_SAYS(sl_generate_sc(&lm, &kv, ws, cu, 1, &go, out_ids, &gs, ws, need, nullptr, nullptr, lps), "row limit");           // row limit 0
     go.row_limits_host = nullptr;
+    {   // teacher-forced scoring: sl_llama_score refuses before any device call; the workspace arithmetic
+      int32_t start[1] = {130}, nsc[1] = {7};
+      const int32_t* lab = (const int32_t*)ws;
+      int32_t* iws = (int32_t*)ws;
+      const size_t sneed = sl_llama_score_workspace_bytes(&lm, 137, 1, 7, nullptr);
+      EXPECT(sneed > sl_llama_workspace_bytes(&lm, 137, 1), "score workspace above the prefill workspace");
+      EXPECT(sl_llama_score_workspace_bytes(&lm, 137, 1, 138, nullptr) == 0, "more scored rows than rows");
+      EXPECT_ARG_ERROR_SAYS(sl_llama_score(&lm, &kv, ws, cu, 1, start, nsc, lab, lps, iws, nullptr, nullptr, nullptr, nullptr, ws, sneed - 1, nullptr), "workspace");
+      nsc[0] = 8;
+      EXPECT_ARG_ERROR_SAYS(sl_llama_score(&lm, &kv, ws, cu, 1, start, nsc, lab, lps, iws, nullptr, nullptr, nullptr, nullptr, ws, sneed, nullptr), "leave its 137 rows");
+      nsc[0] = 0;
+      EXPECT_ARG_ERROR_SAYS(sl_llama_score(&lm, &kv, ws, cu, 1, start, nsc, lab, lps, iws, nullptr, nullptr, nullptr, nullptr, ws, sneed, nullptr), "nothing to score");
+      nsc[0] = 7;
+      EXPECT_ARG_ERROR_SAYS(sl_llama_score(&lm, &kv, ws, cu, 1, start, nsc, lab, lps, iws, lps, nullptr, iws, nullptr, ws, sneed, nullptr), "all three or none");
+      sl_score_opts so;
+      memset(&so, 0, sizeof(so));
+      so.row_chunk = -1;
+      EXPECT_ARG_ERROR_SAYS(sl_llama_score(&lm, &kv, ws, cu, 1, start, nsc, lab, lps, iws, nullptr, nullptr, nullptr, &so, ws, sneed, nullptr), "row_chunk");
+    }
     {   // multi-turn sessions: sl_llama_prefill_cont / sl_generate_cont refuse before any device call
       sl_kv_cache kvs = kv;
       kvs.slots = 3;

@@ -1260,8 +1260,10 @@ static int gemm_typed(const sl_gemm_args* a, GemmP& p, const SkinnyX& sx, hipStr
   }
 }
 
-// amax_sum: the third plane of the fused top-1 (sl_gemm_top1_lse); NULL everywhere else
-static int gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st, float* amax_sum) {
+// amax_sum: the third plane of the fused top-1 (sl_gemm_top1_lse); NULL everywhere else.  tgt_col / tgt_val: the wanted column's value per row
+// beside the planes (sl_gemm_top1_lse_tgt); NULL everywhere else
+static int gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st, float* amax_sum, const int32_t* tgt_col = nullptr,
+                     float* tgt_val = nullptr) {
   SL_CHECK_ARG(a != nullptr, "sl_gemm: null args");
   const SlEnv& e = sl_env();      // ONE snapshot of the tuning table per product: a concurrent sl_tuning_reload() cannot split a plan
   SL_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0 && a->batch > 0, "sl_gemm: bad shape M=%d N=%d K=%d batch=%d", a->M, a->N, a->K, a->batch);
@@ -1372,6 +1374,10 @@ static int gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_ge
   }
   SL_CHECK_ARG(!amax_sum || p.amax_val, "sl_gemm_top1_lse: amax_sum rides on the fused top-1: amax_val and amax_idx must be set");
   p.amax_sum = amax_sum;
+  SL_CHECK_ARG((tgt_col != nullptr) == (tgt_val != nullptr), "sl_gemm_top1_lse_tgt: tgt_col and tgt_val come together (tgt_col %s, tgt_val %s)", tgt_col ? "set" : "NULL",
+               tgt_val ? "set" : "NULL");
+  SL_CHECK_ARG(!tgt_val || p.amax_val, "sl_gemm_top1_lse_tgt: tgt_val rides on the fused top-1: amax_val and amax_idx must be set");
+  p.tgt_col = tgt_col; p.tgt_val = tgt_val;
   SL_CHECK_ARG(p.amax_val || a->C, "sl_gemm: null C");
   if (e.gemm_log)     // SL_GEMM_LOG: one line per product on stderr (tools/kd_gemm_shapes.py turns a KD window's lines into a per-shape table)
     fprintf(stderr, "SLGEMM M=%d N=%d K=%d batch=%d act=%d ta=%d tw=%d res=%d resf32=%d outf32=%d aux=%d grp=%d bias=%d packed=%d dt=%d\n", a->M, a->N, a->K, a->batch, a->act,
@@ -1427,6 +1433,16 @@ int sl_gemm_top1_lse_impl(const sl_gemm_args* a, const sl_gemm_ex_args* ex, floa
 
 extern "C" int sl_gemm_top1_lse(const sl_gemm_args* a, const sl_gemm_ex_args* ex, float* amax_sum, sl_stream stream) {
   return sl_gemm_top1_lse_impl(a, ex, amax_sum, (hipStream_t)stream);
+}
+
+// teacher-forced scoring: the three planes of sl_gemm_top1_lse plus tgt_val[m] = the value at (m, tgt_col[m]); both NULL: sl_gemm_top1_lse
+int sl_gemm_top1_lse_tgt_impl(const sl_gemm_args* a, const sl_gemm_ex_args* ex, float* amax_sum, const int32_t* tgt_col, float* tgt_val, hipStream_t st) {
+  SL_CHECK_ARG(ex != nullptr && amax_sum != nullptr, "sl_gemm_top1_lse_tgt: null ex args or amax_sum");
+  return gemm_impl(a, nullptr, ex, st, amax_sum, tgt_col, tgt_val);
+}
+
+extern "C" int sl_gemm_top1_lse_tgt(const sl_gemm_args* a, const sl_gemm_ex_args* ex, float* amax_sum, const int32_t* tgt_col, float* tgt_val, sl_stream stream) {
+  return sl_gemm_top1_lse_tgt_impl(a, ex, amax_sum, tgt_col, tgt_val, (hipStream_t)stream);
 }
 
 extern "C" int32_t sl_gemm_split_count(int32_t M, int32_t N, int32_t K, int32_t dtype) {

@@ -83,6 +83,27 @@ __device__ __forceinline__ void tile_argmax(const GemmP& p, f32x4 (&acc)[MT][NT]
         }
       }
     }
+    if (p.tgt_val) {
+      // teacher-forced scoring: the wanted column's value beside the planes.  Element (row, col) of the product lives in
+      // exactly one lane of one wave of one block, so the lane whose column IS tgt_col[row] stores and nobody else does: one writer per
+      // row, no atomics, no reduction.  col < N here, so a wanted column outside [0, N) equals no lane's column and the row keeps
+      // whatever tgt_val held.  v is the value the compare and the third plane saw.
+      int tc[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = row_base + m * 16 + 4 * q + i;
+        tc[i] = row < p.M ? p.tgt_col[row] : -1;
+      }
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        const int col = col_base + n * 16 + r;
+        if (col >= p.N) continue;
+        const float b = bias ? to_f32(bias[col]) : 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (tc[i] == col) p.tgt_val[row_base + m * 16 + 4 * q + i] = acc[m][n][i] + b;
+      }
+    }
   }
 }
 

@@ -29,6 +29,9 @@ struct GemmP {
   int* amax_idx;       // columns [64 g, 64 g + 64) at [g][m] and its column index; C is then not written at all
   float* amax_sum;     // optional third plane (sl_gemm_top1_lse): sum over the group's valid columns of exp(v - group max) at [g][m], 0 for a group of
                        // nothing but -inf / NaN; NULL: tile_argmax is the code it was
+  const int* tgt_col;  // teacher-forced scoring (sl_gemm_top1_lse_tgt): per row the one column whose value is wanted beside the planes, and
+  float* tgt_val;      // where it goes: tgt_val[m] = acc + bias at (m, tgt_col[m]), stored by the one lane that holds that element; a row whose
+                       // column lies outside [0, N) is written by nobody.  Both or neither; NULL: tile_argmax is the code it was
   // training-tape epilogue fusions (sl_gemm_ex_args.post_op ...): rows epilogue (generic form) / direct epilogue / split-K reduce pass
   int post;            // SL_POST_*
   uint32_t drop_thr24; // keep iff u24(hash) >= thr (0: no mask)

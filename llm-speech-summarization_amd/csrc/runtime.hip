@@ -31,6 +31,12 @@ bool sl_attn_decode_grouped_built(int n_heads, int n_kv, int D, int dtype, int k
 int sl_rmsnorm_rstd_impl(const void* x, void* y, const void* w, float* rstd_out, int64_t rows, int32_t cols, float eps, int32_t dtype, hipStream_t st);
 int sl_gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_gemm_ex_args* ex, hipStream_t st);
 int sl_gemm_top1_lse_impl(const sl_gemm_args* a, const sl_gemm_ex_args* ex, float* amax_sum, hipStream_t st);
+int sl_gemm_top1_lse_tgt_impl(const sl_gemm_args* a, const sl_gemm_ex_args* ex, float* amax_sum, const int32_t* tgt_col, float* tgt_val, hipStream_t st);
+int sl_score_finalize_impl(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int32_t n_groups, int32_t V, const float* tgt_val,
+                           const int32_t* labels, int32_t rows, float* logprob_out, int32_t* top1_out, hipStream_t st);
+int sl_score_rows_impl(const float* logits, int64_t ld, const int32_t* labels, int32_t rows, int32_t V, float* logprob_out, int32_t* top1_out, hipStream_t st);
+int sl_score_segment_sums_impl(const float* logprob, const int32_t* labels, const int32_t* top1, const int32_t* row_offsets, int32_t nseq, int32_t V,
+                               float* sum_logprob, int32_t* n_counted, int32_t* n_top1, hipStream_t st);
 
 namespace {
 
@@ -1040,6 +1046,166 @@ extern "C" int sl_llama_prefill_cont(const sl_llama_model* m, const sl_kv_cache*
                                      const int32_t* slot_host, int32_t nseq, float* logits, int32_t* ctx_len_dev, void* workspace, size_t workspace_bytes,
                                      sl_stream stream) {
   return llama_prefill_impl(m, kv, x, cu_seqlens_host, nseq, logits, ctx_len_dev, nullptr, workspace, workspace_bytes, stream, 1, past_len_host, slot_host);
+}
+
+// ---- teacher-forced scoring: log_softmax(lm_head(final_norm(h)))[label] for rows [start, start + n) of every sequence ----
+// The prefill body without hidden_taps and without the shared-prefix dedupe (every sequence runs its own rows: a scored batch shares no
+// promised prefix): the final layer runs everything behind attention on the scored rows alone (llama_layer tail_rows = all of them), the
+// final RMSNorm runs over those gathered rows, and the lm_head runs in passes of row_chunk rows.  A pass of more than 64 rows leaves
+// the three planes and the labels' logits (sl_gemm_top1_lse_tgt) and sl_score_finalize turns them into log-probabilities; a pass of at most
+// 64 rows — a short remainder included — writes fp32 logits and sl_score_rows reads them.  The remainder of a chunked call stays pinned
+// to the family of a full pass (SlFamilyPin), so its logits come out of the tiled kernel, and the K order, the full passes went through.
+constexpr int SL_SCORE_ROW_CHUNK = 2048;      // default rows per lm_head pass: planes of 2 048 x 2 004 groups x 12 B = 49.3 MB at vocab 128 256
+constexpr int SL_SCORE_UNFUSED_MAX = 64;      // the fused top-1 lives in the tiled kernels: sl_family_rows(M) > 64 (gemm.hip)
+
+struct ScoreWs {
+  LlamaWs w;
+  void* last;            // (n_rows, H): the scored rows behind the final layer
+  int32_t *rows, *offs;  // scored row of the packed batch per label; first label of each sequence (nseq + 1)
+  int32_t* top1;         // (n_rows) when the caller keeps none
+  float *planes, *tgt;   // [3][n_groups][pass rows] and the labels' logits of one pass
+  float* logits;         // fp32 logits of one unfused pass
+  int chunk, plane_rows, logit_rows;
+};
+
+static thread_local int g_score_paths = 0;      // sl_llama_score_last_paths: 1 = fp32 logits + sl_score_rows ran, 2 = the fused planes ran
+
+static size_t score_carve(const sl_llama_model* m, int64_t n_tok, int nseq, int64_t n_rows, const sl_score_opts* o, void* base, size_t cap, ScoreWs& s) {
+  const size_t sz = sl_dtype_size(m->dtype);
+  const int force = o ? o->force_path : 0;
+  const int64_t chunk = (o && o->row_chunk > 0) ? o->row_chunk : SL_SCORE_ROW_CHUNK;
+  const int64_t pass = chunk < n_rows ? chunk : n_rows;      // the longest pass
+  s.chunk = (int)chunk;
+  s.plane_rows = (force != 1 && pass > SL_SCORE_UNFUSED_MAX) ? (int)pass : 0;
+  s.logit_rows = force == 1 ? (int)pass : (int)(n_rows < SL_SCORE_UNFUSED_MAX ? n_rows : SL_SCORE_UNFUSED_MAX);
+  const size_t head = (llama_carve(m, n_tok, nseq, base, cap, s.w) + 255) & ~(size_t)255;      // the pieces below keep the base's 256-byte alignment
+  Carver c(base ? bptr(base) + head : nullptr, cap > head ? cap - head : 0);
+  const int64_t ng = (m->vocab + 63) / 64;
+  s.last = c.take((size_t)n_rows * m->hidden * sz);
+  s.rows = (int32_t*)c.take((size_t)n_rows * sizeof(int32_t));
+  s.offs = (int32_t*)c.take((size_t)(nseq + 1) * sizeof(int32_t));
+  s.top1 = (int32_t*)c.take((size_t)n_rows * sizeof(int32_t));
+  s.planes = (float*)c.take((size_t)3 * ng * s.plane_rows * sizeof(float));
+  s.tgt = (float*)c.take((size_t)s.plane_rows * sizeof(float));
+  s.logits = (float*)c.take((size_t)s.logit_rows * m->vocab * sizeof(float));
+  return head + c.off + 256;
+}
+
+static bool score_opts_ok(const sl_score_opts* o) { return !o || (o->row_chunk >= 0 && o->force_path >= 0 && o->force_path <= 2); }
+
+extern "C" size_t sl_llama_score_workspace_bytes(const sl_llama_model* m, int64_t n_tok, int32_t nseq, int64_t n_rows, const sl_score_opts* opts) {
+  if (!m || n_tok <= 0 || nseq <= 0 || n_rows <= 0 || n_rows > n_tok || n_tok > 0x7fffffff || !score_opts_ok(opts)) {
+    sl_set_error("sl_llama_score_workspace_bytes: bad arguments (n_tok=%lld nseq=%d n_rows=%lld row_chunk=%d force_path=%d)", (long long)n_tok, nseq, (long long)n_rows,
+                 opts ? opts->row_chunk : 0, opts ? opts->force_path : 0);
+    return 0;
+  }
+  ScoreWs s;
+  return score_carve(m, n_tok, nseq, n_rows, opts, nullptr, 0, s);
+}
+
+extern "C" int32_t sl_llama_score_last_paths(void) { return g_score_paths; }
+
+extern "C" int sl_llama_score(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                              const int32_t* score_start_host, const int32_t* n_score_host, const int32_t* labels_dev, float* logprob_dev, int32_t* top1_dev,
+                              float* seq_sum_dev, int32_t* seq_counted_dev, int32_t* seq_top1_dev, const sl_score_opts* opts, void* workspace,
+                              size_t workspace_bytes, sl_stream stream) {
+  // every check comes before the first launch
+  SL_TRY(llama_check(m, kv));
+  SL_CHECK_ARG(x && cu_seqlens_host && score_start_host && n_score_host && labels_dev && logprob_dev && workspace, "sl_llama_score: null pointer");
+  SL_CHECK_ARG(nseq > 0, "sl_llama_score: nseq=%d", nseq);
+  SL_CHECK_ARG((seq_sum_dev != nullptr) == (seq_counted_dev != nullptr) && (seq_sum_dev != nullptr) == (seq_top1_dev != nullptr),
+               "sl_llama_score: seq_sum_dev, seq_counted_dev and seq_top1_dev come all three or none (%s, %s, %s)", seq_sum_dev ? "set" : "NULL",
+               seq_counted_dev ? "set" : "NULL", seq_top1_dev ? "set" : "NULL");
+  SL_CHECK_ARG(!opts || opts->row_chunk >= 0, "sl_llama_score: row_chunk %d is negative", opts ? opts->row_chunk : 0);
+  SL_CHECK_ARG(!opts || (opts->force_path >= 0 && opts->force_path <= 2), "sl_llama_score: force_path %d outside [0, 2]", opts ? opts->force_path : 0);
+  if (nseq > kv->slots) {
+    sl_set_error("sl_llama_score: %d sequences need %d cache slots, the kv cache has %d", nseq, nseq, kv->slots);
+    return SL_ERR_UNSUPPORTED;
+  }
+  int64_t n_rows = 0;
+  int max_q = 0;
+  for (int s = 0; s < nseq; ++s) {
+    const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
+    SL_CHECK_ARG(len > 0, "sl_llama_score: sequence %d length %d outside (0, max_ctx=%d]", s, len, kv->max_ctx);
+    if (len > kv->max_ctx) {
+      sl_set_error("sl_llama_score: sequence %d length %d outside (0, max_ctx=%d]", s, len, kv->max_ctx);
+      return SL_ERR_UNSUPPORTED;
+    }
+    const int st0 = score_start_host[s], ns = n_score_host[s];
+    SL_CHECK_ARG(ns >= 0, "sl_llama_score: n_score %d of sequence %d is negative", ns, s);
+    SL_CHECK_ARG(st0 >= 0, "sl_llama_score: score_start %d of sequence %d is negative", st0, s);
+    SL_CHECK_ARG((int64_t)st0 + ns <= len, "sl_llama_score: sequence %d: rows [%d, %d + %d) leave its %d rows", s, st0, st0, ns, len);
+    n_rows += ns;
+    if (len > max_q) max_q = len;
+  }
+  SL_CHECK_ARG(n_rows > 0, "sl_llama_score: nothing to score (sum of n_score is 0)");
+  const int64_t n_tok = cu_seqlens_host[nseq];
+  const int dt = m->dtype, H = m->hidden, V = m->vocab;
+  const size_t sz = sl_dtype_size(dt);
+  SL_CHECK_ARG(((size_t)H * sz) % 16 == 0, "sl_llama_score: hidden rows must be a multiple of 16 bytes");
+  ScoreWs sw;
+  const size_t need = score_carve(m, n_tok, nseq, n_rows, opts, workspace, workspace_bytes, sw);
+  SL_CHECK_ARG(need <= workspace_bytes, "sl_llama_score: workspace %zu B < required %zu B", workspace_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  LlamaWs& w = sw.w;
+  g_score_paths = 0;
+  std::vector<int32_t> tseq(n_tok), tpos(n_tok), cuk(nseq), kl(nseq), cuq(nseq + 1), rows(n_rows), offs(nseq + 1);
+  int64_t at = 0;
+  for (int s = 0; s < nseq; ++s) {
+    const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
+    for (int t = 0; t < len; ++t) { tseq[cu_seqlens_host[s] + t] = s; tpos[cu_seqlens_host[s] + t] = t; }
+    cuk[s] = s * m->n_kv_heads * kv->max_ctx;
+    kl[s] = len;
+    cuq[s] = cu_seqlens_host[s];
+    offs[s] = (int32_t)at;
+    for (int j = 0; j < n_score_host[s]; ++j) rows[at++] = cu_seqlens_host[s] + score_start_host[s] + j;
+  }
+  cuq[nseq] = cu_seqlens_host[nseq];
+  offs[nseq] = (int32_t)at;
+  SL_HIP(hipMemcpyAsync(w.tok_seq, tseq.data(), n_tok * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(w.tok_pos, tpos.data(), n_tok * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(w.cu, cuq.data(), (nseq + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(w.cuk, cuk.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(w.klen, kl.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(sw.rows, rows.data(), n_rows * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipMemcpyAsync(sw.offs, offs.data(), (nseq + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  SL_HIP(hipStreamSynchronize(st));      // the one host synchronisation prefill has too: the host vectors leave scope
+  w.last = sw.last;                       // the tail of the final layer holds every scored row, not one per sequence
+  for (int l = 0; l < m->n_layers; ++l) {
+    const bool tail = l == m->n_layers - 1;
+    SL_TRY(llama_layer(m, kv, l, x, n_tok, w, false, nseq, max_q, nullptr, st, false, nullptr, 0, nseq, false, tail ? sw.rows : nullptr, (int)n_rows));
+  }
+  if (m->n_layers == 0) SL_TRY(gather_rows(x, sw.last, sw.rows, n_rows, (size_t)H * sz, st));
+  SL_TRY(sl_rmsnorm(sw.last, sw.last, m->final_norm, n_rows, H, m->rms_eps, dt, stream));
+  int32_t* top1 = top1_dev ? top1_dev : (seq_top1_dev ? sw.top1 : nullptr);
+  const int force = opts ? opts->force_path : 0;
+  const int64_t ng = (V + 63) / 64;
+  for (int64_t r0 = 0; r0 < n_rows; r0 += sw.chunk) {
+    const int M = (int)(n_rows - r0 < sw.chunk ? n_rows - r0 : sw.chunk);
+    const void* A = bptr(sw.last) + (size_t)r0 * H * sz;
+    if (force != 1 && M > SL_SCORE_UNFUSED_MAX) {
+      sl_gemm_args a;
+      memset(&a, 0, sizeof(a));
+      a.A = A; a.lda = H; a.W = m->lm_head; a.ldw = H; a.C = nullptr; a.ldc = V;
+      a.M = M; a.N = V; a.K = H; a.batch = 1; a.dtype = dt; a.act = SL_ACT_NONE; a.out_f32 = 1; a.w_layout = SL_W_ROWMAJOR;
+      sl_gemm_ex_args ex;
+      memset(&ex, 0, sizeof(ex));
+      ex.w_mod = 1;
+      ex.amax_val = sw.planes;
+      ex.amax_idx = (int32_t*)(sw.planes + ng * M);
+      float* psum = sw.planes + 2 * ng * M;
+      SL_TRY(sl_gemm_top1_lse_tgt_impl(&a, &ex, psum, labels_dev + r0, sw.tgt, st));
+      SL_TRY(sl_score_finalize_impl(ex.amax_val, ex.amax_idx, psum, (int)ng, V, sw.tgt, labels_dev + r0, M, logprob_dev + r0, top1 ? top1 + r0 : nullptr, st));
+      g_score_paths |= 2;
+    } else {
+      SlFamilyPin pin(n_rows > sw.chunk ? sw.chunk : sl_family_rows(0));      // (sl_family_rows(0) = the caller's pin: unchanged)
+      SL_TRY(gemm(dt, A, H, m->lm_head, H, sw.logits, V, nullptr, nullptr, 0, M, V, H, SL_ACT_NONE, 1, st));
+      SL_TRY(sl_score_rows_impl(sw.logits, V, labels_dev + r0, M, V, logprob_dev + r0, top1 ? top1 + r0 : nullptr, st));
+      g_score_paths |= 1;
+    }
+  }
+  if (seq_sum_dev) SL_TRY(sl_score_segment_sums_impl(logprob_dev, labels_dev, top1, sw.offs, nseq, V, seq_sum_dev, seq_counted_dev, seq_top1_dev, st));
+  return 0;
 }
 
 // decode-step state carved from the tail of the workspace by sl_greedy_generate, or supplied by the caller

@@ -246,6 +246,24 @@ class LLMSpeechTextInference():
     def _generate_chunk(self, audios, texts, max_new_tokens, logits=None, scores=False, num_return=1, ranges=None, session=None, sample=None):
         """One generate call's worth of utterances -> LongTensor (n, n_cols) of new tokens (scores: and their (n, n_cols) log-probabilities).
         num_return = R > 1: (n * R, n_cols), R answers per utterance sampled with the llm's generation_config warpers."""
+        x, lens, shared = self._prompt_chunk(audios, texts, ranges)
+        skw = {} if session is None else dict(session=session)      # a conversation: the call runs in (and leaves its K/V in) the session's cache
+        if num_return > 1:      # several answers are sampled ones: HF's warpers as llm.generate builds them
+            g = self.llm.generation_config
+            seed, self.llm.sample_seed = self.llm.sample_seed, self.llm.sample_seed + 1
+            sample = dict(temperature=float(g.temperature), top_k=int(g.top_k), top_p=float(g.top_p), seed=int(seed))
+        if scores:
+            ids, n_cols, lps = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None,
+                                                        scores=True, sample=sample, num_return=num_return, **skw)
+            return ids[:, :n_cols].to(torch.int64), lps[:, :n_cols]
+        ids, n_cols = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None,
+                                               sample=sample, num_return=num_return, **skw)
+        return ids[:, :n_cols].to(torch.int64)
+
+    def _prompt_chunk(self, audios, texts, ranges=None):
+        """The packed prompt buffer of a chunk of utterances, `[prefix | text[1:] | audio | suffix[1:]]` per utterance with the encoder's
+        embeddings written in place -> (x (sum lens, H), lens, the rows every prompt shares at its head).  What _generate_chunk generates
+        from and score_audio_responses scores under."""
         from .utils import compute_num_audio_embeds, prompt_template
         n = len(audios)
         emb = self.llm.model.embed_tokens
@@ -295,18 +313,64 @@ class LLMSpeechTextInference():
         shared = int(pre_e.shape[0])
         if txt_e[0] is not None and all(t_ == texts[0] for t_ in texts):
             shared += int(txt_e[0].shape[0])
-        skw = {} if session is None else dict(session=session)      # a conversation: the call runs in (and leaves its K/V in) the session's cache
-        if num_return > 1:      # several answers are sampled ones: HF's warpers as llm.generate builds them
-            g = self.llm.generation_config
-            seed, self.llm.sample_seed = self.llm.sample_seed, self.llm.sample_seed + 1
-            sample = dict(temperature=float(g.temperature), top_k=int(g.top_k), top_p=float(g.top_p), seed=int(seed))
-        if scores:
-            ids, n_cols, lps = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None,
-                                                        scores=True, sample=sample, num_return=num_return, **skw)
-            return ids[:, :n_cols].to(torch.int64), lps[:, :n_cols]
-        ids, n_cols = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None,
-                                               sample=sample, num_return=num_return, **skw)
-        return ids[:, :n_cols].to(torch.int64)
+        return x, lens, shared
+
+    # -- teacher-forced scoring of given answers (an extension) ----------------------------------------------------------------------
+    def _response_ids(self, responses) -> List[List[int]]:
+        """responses as strings -> ids without BOS, the end-of-turn token appended as the model would emit it (its first EOS id); id lists
+        (or id tensors) are taken as they are"""
+        e = self.llm.generation_config.eos_token_id
+        eos = list(e) if isinstance(e, (list, tuple)) else ([] if e is None else [e])
+        out = []
+        for r in responses:
+            if isinstance(r, str):
+                ids = [int(v) for v in self.llm_tokenizer(r, add_special_tokens=False).input_ids]
+                out.append(ids + [int(eos[0])] if eos else ids)
+            else:
+                out.append([int(v) for v in (r.reshape(-1).tolist() if torch.is_tensor(r) else r)])
+        return out
+
+    @staticmethod
+    def _merge_scores(parts):
+        from .audio_llama import ScoreOutput
+        if len(parts) == 1:
+            return parts[0]
+        tm = None if parts[0].top1_match is None else [m for p in parts for m in p.top1_match]
+        return ScoreOutput([t_ for p in parts for t_ in p.token_logprobs], torch.cat([p.sequence_logprobs for p in parts]),
+                           torch.cat([p.n_tokens for p in parts]), tm, set().union(*[p.paths for p in parts]))
+
+    def score_audio_responses(self, audios, responses, additional_text_prompts=None, ctc_pool_ranges=None, return_top1=False):
+        """The log-probabilities of given `responses` (strings or id lists, one per utterance) under the prompts generate_audio_responses
+        builds for `audios`: the same template, the same encoder pass, in chunks -> the llm's ScoreOutput (token_logprobs, sequence_logprobs,
+        n_tokens, .nll, .perplexity()).  Strings are tokenised without BOS and end with the end-of-turn token."""
+        n = len(audios)
+        texts = list(additional_text_prompts) if additional_text_prompts is not None else [""] * n
+        if len(texts) != n or len(responses) != n:
+            raise ValueError(f"{len(texts)} text prompts and {len(responses)} responses for {n} utterances")
+        ctc = self.audio_encoder.downsample_method == "ctc_pool"
+        if ctc and ctc_pool_ranges is None and getattr(self, "ctc_segmenter", None) is None:
+            raise AttributeError("'LLMSpeechTextInference' object has no attribute 'get_ctc_pool_ranges'")
+        if ctc and ctc_pool_ranges is not None and len(ctc_pool_ranges) != n:
+            raise ValueError(f"{len(ctc_pool_ranges)} lists of ctc_pool ranges for {n} utterances")
+        targets = self._response_ids(responses)
+        parts = []
+        for lo_ in range(0, n, L.MAX_DECODE_BATCH):
+            hi_ = min(n, lo_ + L.MAX_DECODE_BATCH)
+            x, lens, _ = self._prompt_chunk(audios[lo_:hi_], texts[lo_:hi_], list(ctc_pool_ranges[lo_:hi_]) if ctc and ctc_pool_ranges is not None else None)
+            prompts, o = [], 0
+            for ln in lens:
+                prompts.append(x[o:o + ln])
+                o += ln
+            parts.append(self.llm.score(prompts, targets[lo_:hi_], return_top1=return_top1))
+        return self._merge_scores(parts)
+
+    def score_text_responses(self, texts, responses, return_top1=False):
+        """score_audio_responses for the text prompt generate_text_response builds: `{prefix} {text}{suffix} ` per input text"""
+        if len(texts) != len(responses):
+            raise ValueError(f"{len(responses)} responses for {len(texts)} texts")
+        emb = self.llm.model.embed_tokens
+        prompts = [emb(self.llm_tokenizer(f"{self.prompt_prefix} {t_}{self.prompt_suffix} ", return_tensors='pt').input_ids.to(self.device))[0] for t_ in texts]
+        return self.llm.score(prompts, self._response_ids(responses), return_top1=return_top1)
 
     # -- conversations: follow-up questions about the same recordings (an extension) -------------------------------------------------
     def _sample_for(self, do_sample=None, temperature=None, top_k=None, top_p=None, seed=None):

@@ -912,6 +912,74 @@ def sample_select_sc(logits, temperature, top_k, top_p, seed, eos_ids, pad_id, u
                                         L.ptr(out_ids), out_ids.shape[1], L.ptr(choice), L.ptr(logprobs), L.stream_ptr()), "sl_sample_select_sc")
 
 
+# ---- teacher-forced scoring (speechllm.h: sl_gemm_top1_lse_tgt, sl_score_*)
+def gemm_top1_lse_tgt(A: torch.Tensor, W: torch.Tensor, tgt_col: torch.Tensor, bias: Optional[torch.Tensor] = None, out=None, tgt_val=None):
+    """gemm_top1_lse plus the wanted column's value per row: returns (val, idx, sum, tgt_val); tgt_val[m] = the logit at (m, tgt_col[m]),
+    untouched where tgt_col[m] lies outside [0, N).  out / tgt_val: optional buffers to write into (tgt_val is NOT initialised here when
+    given: the caller's contents survive in the rows nobody writes)."""
+    L.require_gpu(A, "A"); L.require_gpu(W, "W"); L.require_gpu(tgt_col, "tgt_col")
+    M, K = A.shape
+    N = W.shape[0]
+    ng = (N + 63) // 64
+    if tgt_col.dtype != torch.int32 or tgt_col.numel() != M:
+        raise L.SpeechLLMError(f"tgt_col must hold M={M} int32 columns")
+    if out is None:
+        out = (torch.empty((ng, M), device=A.device, dtype=torch.float32), torch.empty((ng, M), device=A.device, dtype=torch.int32),
+               torch.empty((ng, M), device=A.device, dtype=torch.float32))
+    if tgt_val is None:
+        tgt_val = torch.zeros(M, device=A.device, dtype=torch.float32)
+    val, idx, ssum = out
+    a = L.GemmArgs()
+    a.A, a.lda, a.W, a.ldw, a.C, a.ldc = L.ptr(A), A.stride(0), L.ptr(W), W.stride(0), None, N
+    a.bias = L.ptr(bias)
+    a.M, a.N, a.K, a.batch = M, N, K, 1
+    a.dtype, a.act, a.out_f32 = L.dtype_code(A.dtype), L.ACT_NONE, 1
+    ex = L.GemmEx()
+    ex.w_mod, ex.amax_val, ex.amax_idx = 1, L.ptr(val), L.ptr(idx)
+    L.check(L.lib().sl_gemm_top1_lse_tgt(C.byref(a), C.byref(ex), L.ptr(ssum), L.ptr(tgt_col), L.ptr(tgt_val), L.stream_ptr()), "sl_gemm_top1_lse_tgt")
+    return val, idx, ssum, tgt_val
+
+
+def score_finalize(val, idx, ssum, tgt_val, labels, vocab: int, logprob=None, top1=None):
+    """the three planes (ceil(vocab / 64), rows) + the labels' logits -> (logprob (rows) float32, top1 (rows) int32); labels outside
+    [0, vocab) are ignored: 0.0, tgt_val not read."""
+    ng, rows = val.shape
+    if logprob is None:
+        logprob = torch.empty(rows, device=val.device, dtype=torch.float32)
+    if top1 is None:
+        top1 = torch.empty(rows, device=val.device, dtype=torch.int32)
+    L.check(L.lib().sl_score_finalize(L.ptr(val), L.ptr(idx), L.ptr(ssum), ng, int(vocab), L.ptr(tgt_val), L.ptr(labels), rows, L.ptr(logprob), L.ptr(top1),
+                                      L.stream_ptr()), "sl_score_finalize")
+    return logprob, top1
+
+
+def score_rows(logits: torch.Tensor, labels: torch.Tensor, logprob=None, top1=None):
+    """fp32 logits (rows, V) (rows may be strided) -> (logprob, top1) as score_finalize gives them; logits[r][label] is not read for an ignored label"""
+    L.require_gpu(labels, "labels")
+    if logits.dtype != torch.float32 or logits.stride(1) != 1 or labels.dtype != torch.int32:
+        raise L.SpeechLLMError("score_rows takes float32 logits with contiguous rows and int32 labels")
+    rows, V = logits.shape
+    if logprob is None:
+        logprob = torch.empty(rows, device=logits.device, dtype=torch.float32)
+    if top1 is None:
+        top1 = torch.empty(rows, device=logits.device, dtype=torch.int32)
+    L.check(L.lib().sl_score_rows(L.ptr(logits), logits.stride(0), L.ptr(labels), rows, V, L.ptr(logprob), L.ptr(top1), L.stream_ptr()), "sl_score_rows")
+    return logprob, top1
+
+
+def score_segment_sums(logprob, labels, top1, row_offsets, vocab: int, out=None):
+    """per sequence over rows [row_offsets[s], row_offsets[s + 1]): (sum of logprob float32, counted rows int32, counted rows whose top1 is the
+    label int32); ignored rows count in none"""
+    nseq = row_offsets.numel() - 1
+    if out is None:
+        out = (torch.empty(nseq, device=logprob.device, dtype=torch.float32), torch.empty(nseq, device=logprob.device, dtype=torch.int32),
+               torch.empty(nseq, device=logprob.device, dtype=torch.int32))
+    ssum, cnt, hit = out
+    L.check(L.lib().sl_score_segment_sums(L.ptr(logprob), L.ptr(labels), L.ptr(top1), L.ptr(row_offsets), nseq, int(vocab), L.ptr(ssum), L.ptr(cnt), L.ptr(hit),
+                                          L.stream_ptr()), "sl_score_segment_sums")
+    return ssum, cnt, hit
+
+
 # -- stack / ctc_pool downsampling of a packed ragged batch (ref:model/audio_encoder.py:65-85) -----------------------------------
 def segment_ranges_pack(ranges_per_utt, frames: Sequence[int]):
     """ctc_pool ranges as the dataset stores them (one list of (start, end) per utterance, utterance-relative) -> (packed int64 CPU tensor

@@ -272,7 +272,22 @@ class Trainer():
         emb = self.llm.model.embed_tokens
         pre, suf = emb(self.prefix_ids.to(self.device)), emb(self.suffix_ids.to(self.device))[:, 1:]
         sums = torch.zeros(3, dtype=torch.float64)
-        for sample_idx in range(self.rank, len(self.val_dataset), self.world):
+        # log.validation_batch_size: N (opt-in; absent = the per-sample loop below, as ever): the rank's samples go through llm.score() N at a
+        # time, for the audio and the text prompt.  The reference's labels[1:] convention is kept: the targets are resp[1:], scored from the
+        # prompt's last row on — the rows the loop's forward(labels=) reads — and a sample's nll is their mean, so the sums mean the same.
+        vbs = int(self.config.log.get("validation_batch_size", 0) or 0)
+        mine = list(range(self.rank, len(self.val_dataset), self.world))
+        for i0 in range(0, len(mine) if vbs > 0 else 0, max(vbs, 1)):
+            a_prompts, t_prompts, targets = [], [], []
+            for sample_idx in mine[i0:i0 + vbs]:
+                audio_embeds, text_ids, resp, _ = self._val_sample(sample_idx)
+                a_prompts.append(torch.cat([pre[0], audio_embeds[0], suf[0]], dim=0))
+                t_prompts.append(torch.cat([pre[0], emb(text_ids[None])[0], suf[0]], dim=0))
+                targets.append(resp[1:])
+            sums[0] += float(self.llm.score(a_prompts, targets).nll.sum())
+            sums[1] += float(self.llm.score(t_prompts, targets).nll.sum())
+            sums[2] += len(targets)
+        for sample_idx in ([] if vbs > 0 else mine):
             audio_embeds, text_ids, resp, _ = self._val_sample(sample_idx)
             r = emb(resp[None])[:, 1:]
             a_seq = torch.cat([pre, audio_embeds, suf, r], dim=1)
