@@ -236,6 +236,7 @@ __global__ __launch_bounds__(256) void avgpool_rows_kernel(const T* __restrict__
     const int64_t p = i / cpr;
     int64_t s = ranges ? ranges[2 * p] : p * stride;
     int64_t e = ranges ? ranges[2 * p + 1] : s + kernel;
+    if (s < 0) s = 0;          // segment_mean_kernel's contract: a range is clamped to x's rows, one that is empty afterwards gives zeros
     if (e > T_) e = T_;
     float acc[VEC];
 #pragma unroll
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(256) void avgpool_rows_kernel(const T* __restrict__
 #pragma unroll
       for (int j = 0; j < VEC; ++j) acc[j] += f[j];
     }
-    const float inv = 1.0f / (float)(ranges ? (e - s) : kernel);
+    const float inv = !ranges ? 1.0f / (float)kernel : (e > s ? 1.0f / (float)(e - s) : 0.f);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) acc[j] *= inv;
     *(uint4*)(y + p * H + ch * VEC) = Vec16<T>::pack(acc);

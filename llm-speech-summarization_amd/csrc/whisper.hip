@@ -14,7 +14,8 @@ __global__ __launch_bounds__(256) void whisper_pad_kernel(const float* __restric
     int64_t j = i - pad;
     if (j < 0) j = -j;
     if (j >= n_total) j = 2 * (n_total - 1) - j;
-    out[i] = j < n_samples ? audio[j] : 0.f;
+    // one frame (n_total <= pad) reflects twice behind the samples any frame reads: j < 0 there, which must not index audio
+    out[i] = (j >= 0 && j < n_samples) ? audio[j] : 0.f;
   }
 }
 

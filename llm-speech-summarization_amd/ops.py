@@ -113,6 +113,9 @@ def posconv_stage_batch(x: torch.Tensor, seqlens: Sequence[int], groups: int, k:
 
 def avgpool_batch(x: torch.Tensor, seqlens: Sequence[int], kernel: int, stride: int):
     """AvgPool1d over time of every utterance of a packed batch in one launch -> (packed pooled rows, P list)."""
+    for u, t in enumerate(seqlens):          # as hubert_plan does in C: no zero or negative row count reaches the records
+        if int(t) < kernel:
+            raise L.SpeechLLMError(f"avgpool_batch: utterance {u} gives {int(t)} frames < pool kernel {kernel}")
     cu, klen = seq_descriptors(seqlens, x.device)
     H = x.shape[1]
     P = [(int(t) - kernel) // stride + 1 for t in seqlens]

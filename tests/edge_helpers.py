@@ -1,5 +1,5 @@
 """Helpers shared by the chapters of the edge suite (tests/test_kernel_edges_gpu.py, tests/test_train_edges_gpu.py,
-tests/test_train_gemm_edges_gpu.py): dtypes and their half-ulps, finite poison, the output sentinel, guarded output buffers, poisoned
+tests/test_train_gemm_edges_gpu.py, tests/test_frontend_edges_gpu.py): dtypes and their half-ulps, finite poison, the output sentinel, guarded output buffers, poisoned
 operand views, the per-element comparison and the `tuning` fixture.  A plain module, not a conftest: the test files import what they use."""
 import pytest
 import torch
@@ -63,6 +63,29 @@ def untouched(buf, rows, cols):
     chk = buf.clone()
     chk[1:rows + 1, 8:8 + cols] = FILL
     return bool((chk == FILL).all())
+
+
+def guarded_flat(n, dtype, pad=64):
+    """(buffer, view): n contiguous elements inside a sentinel-filled buffer, `pad` elements (a multiple of 8) in front and behind - for
+    the kernels that write packed rows and take no leading dimension"""
+    buf = torch.full((n + 2 * pad,), FILL, dtype=dtype, device=DEV)
+    return buf, buf[pad:pad + n]
+
+
+def untouched_flat(buf, n, pad=64):
+    return bool((buf[:pad] == FILL).all()) and bool((buf[pad + n:] == FILL).all())
+
+
+def operand_flat(x64, dtype, pad=64, poison=None):
+    """x64 of any shape -> (contiguous device view of that shape, its exact stored value in fp64 on the CPU); `pad` elements of
+    +-poison in front of and behind it inside the same allocation"""
+    big = BIG[dtype] if poison is None else poison
+    buf = torch.full((x64.numel() + 2 * pad,), big, dtype=torch.float64)
+    buf[::2] *= -1.0
+    buf[pad:pad + x64.numel()] = x64.reshape(-1)
+    buf = buf.float().to(dtype).to(DEV)
+    v = buf[pad:pad + x64.numel()].view(x64.shape)
+    return v, v.double().cpu()
 
 
 def operand(x64, dtype, poison=None):
