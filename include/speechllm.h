@@ -141,6 +141,56 @@ int sl_pack_weight_mxfp4(const void* src, int64_t ld_src, void* dst, int32_t N, 
 int sl_pack_weight_mxfp4_host(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype);
 int32_t sl_w4_max_rows(void);
 
+/* Block-scaled ("MX") linears, opt-in (sl_llama_model.reserved = SL_WDEC_MX_LINEAR): MXFP8 activations x MXFP4 weights on
+ * v_mfma_scale_f32_16x16x128_f8f6f4 -> fp32 -> model dtype, at every row count.
+ *
+ * The "MX weight image" of a bf16 / fp16 weight W (N, K), K % 128 == 0, Np = ceil(N/16)*16.  Element codes and scale bytes are
+ * EXACTLY those of the MXFP4 weight image above (block scale rule, clamp of e to [-13, 13], e2m1 rounding, saturation, NaN and
+ * zero handling; padding rows are zero codes with scale byte 127); only the arrangement differs, because the scaled MFMA wants,
+ * per lane, 32 CONSECUTIVE k of one row and ONE scale:
+ *   Elements: img[f][j][lane][16 B], f < Np/16, j < K/128, 64 lanes.  A lane's 16 bytes are one whole 32-element block: byte b
+ *   holds the elements k = 128 j + 32 (lane >> 4) + 2 b (low nibble) and + 2 b + 1 (high nibble) of row 16 f + (lane & 15).
+ *   A lane load is 16 bytes, a wave load 1 KiB contiguous, and the 16 bytes are the low four operand registers of one
+ *   v_mfma_scale_f32_16x16x128_f8f6f4 with the e2m1 operand format.
+ *   Scales: behind the elements, at byte offset Np*K/2, as sc[f][j][lane]: one byte, the scale of that lane's block (row
+ *   16 f + (lane & 15), block 4 j + (lane >> 4)), so a lane reads its own scale with one byte load at (f * K/128 + j) * 64 + lane.
+ *   One pointer names a whole weight.
+ *   sl_mx_weight_image_bytes  Np*K/2 + Np*K/32; 0 on a bad argument (N <= 0, K <= 0, K % 128 != 0)
+ *   sl_pack_weight_mx         src (N, K) row stride ld_src on the device -> dst (16-byte aligned) on the device
+ *   sl_pack_weight_mx_host    the same routines on host memory (no GPU needed): the same bits
+ * SL_F32 is SL_ERR_UNSUPPORTED, K % 128 != 0 is SL_ERR_ARG.
+ *
+ * "MXFP8 activation rows" of x (M, K) bf16 / fp16, row stride ldx, K % 32 == 0: q (M, K) bytes, row-major, OCP e4m3fn, and
+ * scales (M, K/32) e8m0 bytes, row-major, one per 32 consecutive k of one row.
+ *   Block scale: amax = max |x| over the FINITE elements of the block; e = the smallest integer with amax <= 448 * 2^e, clamped
+ *   to [-127, 127]; a block without a nonzero finite element takes e = 0; the byte is e + 127.
+ *   Elements: x / 2^e rounded to e4m3, to nearest with ties to even, subnormals (multiples of 2^-9) included, saturating at
+ *   +-448: with this rule no finite element is ever clipped, +-inf becomes +-448 (0x7E / 0xFE) and NaN becomes 0x7F.  The sign bit
+ *   is the element's own: a negative value that rounds to zero, and -0, are 0x80.
+ *   sl_mxfp8_quantize_rows_host is the definition (host memory, no GPU needed); sl_mxfp8_quantize_rows gives the same bytes
+ *   on the device (q 16-byte aligned).  SL_F32 is SL_ERR_UNSUPPORTED, K % 32 != 0 is SL_ERR_ARG.
+ *
+ * sl_gemm_mx: C = act(dq(Aq) . dq(W)^T) + residual, dq(.) = element * 2^(scale byte - 127), accumulated in fp32.
+ *   Aq (M, K) e4m3 bytes with row stride lda (a multiple of 16, 16-byte aligned), a_scales (M, K/32), W an MX weight image of
+ *   (N, K); any M >= 1, any N >= 1 (the image's padding rows produce columns that are not stored), K % 128 == 0.
+ *   act: SL_ACT_NONE, or SL_ACT_SILU_MUL with sl_gemm's 16 gate / 16 up row interleave (N % 32 == 0, N/2 output columns).
+ *   residual (M, Nout; row stride ldr; may be C itself) is of the output type `dtype` (SL_BF16 / SL_F16); out_f32 != 0 writes
+ *   C as float.  A row's result does not depend on M: no K split, one accumulation chain per output. */
+size_t sl_mx_weight_image_bytes(int32_t N, int32_t K);
+int sl_pack_weight_mx(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype, sl_stream stream);
+int sl_pack_weight_mx_host(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype);
+int sl_mxfp8_quantize_rows(const void* x, int64_t ldx, void* q, void* scales, int64_t M, int32_t K, int32_t dtype, sl_stream stream);
+int sl_mxfp8_quantize_rows_host(const void* x, int64_t ldx, void* q, void* scales, int64_t M, int32_t K, int32_t dtype);
+typedef struct {
+  const void* Aq; int64_t lda; const void* a_scales;
+  const void* W;
+  void* C; int64_t ldc;
+  const void* residual; int64_t ldr;
+  int32_t M, N, K;
+  int32_t dtype, act, out_f32;
+} sl_gemm_mx_args;
+int sl_gemm_mx(const sl_gemm_mx_args* a, sl_stream stream);
+
 /* Decode-only fusions on top of sl_gemm (packed weights; M <= 16 rows run the skinny kernel, more rows the
  * LDS-staged streaming kernel of gemm_stream.hip):
  *   fuse_rms  — the consuming Linear absorbs the preceding LlamaRMSNorm (hf:...llama.py:62-67): the
@@ -799,12 +849,24 @@ typedef struct {
    * w_layout = SL_W_PACKED_E4M3 with the unfused lm_head + sl_greedy_select, for up to sl_w8_max_rows() rows: more rows, SL_F32 or a
    * reduction length that is no multiple of 64 are SL_ERR_UNSUPPORTED before any launch.  Prefill ignores the field.
    * SL_WDEC_MXFP4: the same with MXFP4 weight images (sl_pack_weight_mxfp4), w_layout = SL_W_PACKED_MXFP4, sl_w4_max_rows() and
-   * reduction lengths that are multiples of 128.  2 and 3 are not formats. */
+   * reduction lengths that are multiples of 128.  2 and 3 are not formats.
+   * SL_WDEC_MX_LINEAR (opt-in MX linears): the ROW-MAJOR pointers wqkv / wo / wgu / wdown of every layer are MX weight images
+   * (sl_pack_weight_mx) of the same rows, and the four *_dec pointers of every layer must be NULL.  embed, lm_head, lm_head_dec,
+   * final_norm and the layers' norms are what the 16-bit struct holds, and the lm_head part of every path runs as it does for that
+   * struct.  The four products of every layer (qkv, o, gate/up + SiLU.mul, down) then run as sl_mxfp8_quantize_rows of the input
+   * rows + sl_gemm_mx, at every row count: sl_llama_prefill, sl_llama_prefill_cont, sl_llama_decode_step and the sl_generate family
+   * (sl_generate, _lp, _sc, _cont, sl_greedy_generate, sl_sample_generate).  Embedding, RMSNorm, RoPE, attention, the K/V cache
+   * (both formats), lm_head, sampling, logits processors and scores stay as they are.  sl_llama_workspace_bytes and the
+   * sl_generate_workspace_bytes family grow by the quantised-row buffer, n_tok * Kmax * (1 + 1/32) bytes + alignment,
+   * Kmax = max(hidden, n_heads * head_dim, ffn), for this format only.  SL_F32, a reduction length that is no multiple of 128 and a
+   * non-null *_dec pointer are refused before any launch; sl_beam_generate*, sl_generate_n with several answers and sl_llama_score
+   * return SL_ERR_UNSUPPORTED for this format. */
   int32_t dec_fused_norm, reserved;
 } sl_llama_model;
 #define SL_WDEC_MODEL_DTYPE 0
 #define SL_WDEC_E4M3        1
 #define SL_WDEC_MXFP4       4
+#define SL_WDEC_MX_LINEAR   5
 
 typedef struct {
   void* k_cache; void* v_cache;  /* (n_layers, slots, n_kv, max_ctx, D) each: elements of the model dtype, or bytes (reserved = SL_KV_FP8_E4M3) */

@@ -45,8 +45,10 @@ if __name__ == '__main__':
     dtype = importlib.import_module("llm-speech-summarization_amd.config").runtime_dtype(config)
     kv_dtype = importlib.import_module("llm-speech-summarization_amd.config").runtime_kv_dtype(config)     # runtime.kv_dtype: fp8 | model
     w_dtype = importlib.import_module("llm-speech-summarization_amd.config").runtime_weight_dtype(config)  # runtime.weight_dtype: fp8 | mxfp4 | model
+    l_dtype = importlib.import_module("llm-speech-summarization_amd.config").runtime_linear_dtype(config)  # runtime.linear_dtype: mx | model
     llm_inferencer = LLMSpeechTextInference(config=config, audio_encoder_checkpoint=args.audio_encoder_checkpoint,
-                                            device=torch.device(f"cuda:{args.gpu_idx}"), dtype=dtype, kv_cache_dtype=kv_dtype, weight_dtype=w_dtype)
+                                            device=torch.device(f"cuda:{args.gpu_idx}"), dtype=dtype, kv_cache_dtype=kv_dtype, weight_dtype=w_dtype,
+                                            linear_dtype=l_dtype)
     audio, sr = load_audio_16k(args.audio_file)
     print("LLM Response:\n")
     print(llm_inferencer.generate_audio_response(audio, max_new_tokens=512))

@@ -24,6 +24,7 @@ W_ROWMAJOR, W_PACKED, W_PACKED_E4M3 = 0, 1, 2     # W_PACKED_E4M3: an e4m3 weigh
 W_PACKED_MXFP4 = 4                          # an MXFP4 weight image (sl_pack_weight_mxfp4); 3 is not a layout
 WDEC_MODEL_DTYPE, WDEC_E4M3 = 0, 1          # speechllm.h SL_WDEC_*: the format of a model's decode weights (sl_llama_model.reserved)
 WDEC_MXFP4 = 4                              # MXFP4 weight images; 2 and 3 are not formats
+WDEC_MX_LINEAR = 5                          # SL_WDEC_MX_LINEAR: the layers' row-major pointers are MX weight images (sl_pack_weight_mx), every product MXFP8 x MXFP4
 COMM_ID_BYTES = 128          # SL_COMM_ID_BYTES = sizeof(ncclUniqueId)
 MAX_DECODE_BATCH = 2048      # SL_MAX_DECODE_BATCH: sequences per generate call / rows per decode step
 
@@ -42,6 +43,11 @@ class GemmArgs(C.Structure):
                 ("residual", c_vp), ("ldr", c_i64), ("strideR", c_i64),
                 ("M", c_i32), ("N", c_i32), ("K", c_i32), ("batch", c_i32),
                 ("dtype", c_i32), ("act", c_i32), ("out_f32", c_i32), ("w_layout", c_i32)]
+
+
+class GemmMxArgs(C.Structure):
+    _fields_ = [("Aq", c_vp), ("lda", c_i64), ("a_scales", c_vp), ("W", c_vp), ("C", c_vp), ("ldc", c_i64), ("residual", c_vp), ("ldr", c_i64),
+                ("M", c_i32), ("N", c_i32), ("K", c_i32), ("dtype", c_i32), ("act", c_i32), ("out_f32", c_i32)]
 
 
 class GemmFused(C.Structure):
@@ -245,6 +251,12 @@ _PROTOS = {
     "sl_pack_weight_mxfp4": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "sl_pack_weight_mxfp4_host": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32]),
     "sl_w4_max_rows": (c_i32, []),
+    "sl_mx_weight_image_bytes": (c_sz, [c_i32, c_i32]),
+    "sl_pack_weight_mx": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "sl_pack_weight_mx_host": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32]),
+    "sl_mxfp8_quantize_rows": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
+    "sl_mxfp8_quantize_rows_host": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32]),
+    "sl_gemm_mx": (c_i32, [C.POINTER(GemmMxArgs), c_vp]),
     "sl_gemm_fused_decode": (c_i32, [C.POINTER(GemmArgs), C.POINTER(GemmFused), c_vp]),
     "sl_gemm_split_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "sl_gemm_split_count": (c_i32, [c_i32, c_i32, c_i32, c_i32]),
@@ -465,6 +477,16 @@ def weight_format_code(weight_dtype) -> int:
     elif weight_dtype == torch.float8_e4m3fn:
         return WDEC_E4M3
     raise SpeechLLMError(f"unsupported weight_dtype {weight_dtype!r}: None (the model dtype), 'fp8' or torch.float8_e4m3fn, 'mxfp4' (alias 'fp4')")
+
+
+def linear_format_code(linear_dtype) -> int:
+    """`linear_dtype` of the Python surface -> SL_WDEC_*: None (every product in the model dtype) or "mx" / "mxfp8_mxfp4" (the four
+    products of every decoder layer as MXFP8 activations x MXFP4 weights on the block-scaled MFMA, at every row count)."""
+    if linear_dtype is None:
+        return WDEC_MODEL_DTYPE
+    if isinstance(linear_dtype, str) and linear_dtype in ("mx", "mxfp8_mxfp4"):
+        return WDEC_MX_LINEAR
+    raise SpeechLLMError(f"unsupported linear_dtype {linear_dtype!r}: None (the model dtype) or 'mx' (alias 'mxfp8_mxfp4')")
 
 
 def is16(dt: torch.dtype) -> bool:

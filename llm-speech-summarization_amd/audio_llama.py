@@ -179,7 +179,8 @@ class _EmbedTokens:
 
 class AudioLlamaForCausalLM:
     def __init__(self, arch: LlamaArch, state_dict: Dict[str, torch.Tensor], torch_dtype: torch.dtype = torch.bfloat16,
-                 device=None, max_ctx: int = 2048, max_batch: int = 16, pack_decode: bool = True, kv_cache_dtype=None, weight_dtype=None):
+                 device=None, max_ctx: int = 2048, max_batch: int = 16, pack_decode: bool = True, kv_cache_dtype=None, weight_dtype=None,
+                 linear_dtype=None):
         # float16 computes in fp16 (the reference's torch_dtype=float16, ref:inference.py:47-51); bfloat16 in bf16; float32 is the
         # exact parity mode.  Logits are fp32 in every mode.
         L.dtype_code(torch_dtype)    # raises for anything else
@@ -197,7 +198,12 @@ class AudioLlamaForCausalLM:
         # "mxfp4" (alias "fp4") = the same with MXFP4 weight images (e2m1 elements, one e8m0 scale per 32: a quarter of the bytes), up to
         # sl_w4_max_rows() rows; a different model again (mxfp4_dequantised_state_dict).
         self.weight_format = L.WDEC_MODEL_DTYPE
+        self.linear_format = L.WDEC_MODEL_DTYPE
         self.set_weight_dtype(weight_dtype)
+        # linear_dtype: None = every product in the model dtype; "mx" (alias "mxfp8_mxfp4") = the four products of every decoder layer run as
+        # MXFP8 activations x MXFP4 weights on the block-scaled MFMA, in prefill and at every decode batch.  16-bit models only; a
+        # different model (mx_dequantised_state_dict + MXFP8 activations); independent of kv_cache_dtype, exclusive with weight_dtype.
+        self.set_linear_dtype(linear_dtype)
         self.config = SimpleNamespace(vocab_size=arch.vocab_size, hidden_size=arch.hidden_size,
                                       num_hidden_layers=arch.num_hidden_layers, eos_token_id=list(arch.eos_token_ids),
                                       pad_token_id=arch.pad_token_id, use_return_dict=True)
@@ -216,6 +222,7 @@ class AudioLlamaForCausalLM:
         self._w: Optional[LlamaDeviceWeights] = None
         self._kv = None
         self._ws: Optional[torch.Tensor] = None
+        self._ws_mx: Optional[torch.Tensor] = None         # linear_dtype='mx' calls' workspace
         self._score_ws: Optional[torch.Tensor] = None      # score()'s own workspace
         self.model =SimpleNamespace(embed_tokens=_EmbedTokens(self))
         self.last_timings_ms = None
@@ -275,6 +282,8 @@ class AudioLlamaForCausalLM:
                 self._w.build_decode_weights_e4m3()
             if self.weight_format == L.WDEC_MXFP4:
                 self._w.build_decode_weights_mxfp4()
+            if self.linear_format == L.WDEC_MX_LINEAR:
+                self._w.build_linear_weights_mx()
             self._sd = None  # device copy is the only copy from here on (6.4 GB bf16 for Llama-3.2-3B)
         return self
 
@@ -291,6 +300,8 @@ class AudioLlamaForCausalLM:
         """Switch the decode-weight format (None / "fp8" / torch.float8_e4m3fn / "mxfp4").  The images are built on first use and kept; which
         struct a call runs is decided per call (_struct_for), and a decode graph captured for one struct is never replayed for another."""
         fmt = L.weight_format_code(weight_dtype)
+        if fmt != L.WDEC_MODEL_DTYPE and getattr(self, "linear_format", L.WDEC_MODEL_DTYPE) != L.WDEC_MODEL_DTYPE:
+            raise L.SpeechLLMError("weight_dtype and linear_dtype exclude each other: linear_dtype='mx' already runs every layer product on 4-bit weights")
         if fmt != L.WDEC_MODEL_DTYPE:
             opt, name, kmul = ("mxfp4", "MXFP4", 128) if fmt == L.WDEC_MXFP4 else ("fp8", "e4m3", 64)
             if not L.is16(self.dtype):
@@ -306,9 +317,35 @@ class AudioLlamaForCausalLM:
                 self._w.build_decode_weights_mxfp4() if fmt == L.WDEC_MXFP4 else self._w.build_decode_weights_e4m3()
         self.weight_format = fmt
 
-    def _struct_for(self, B: int):
-        """(model struct, its name) for a call of B sequences: the e4m3 / MXFP4 struct when the option is on and the batch is within its range"""
+    def set_linear_dtype(self, linear_dtype) -> None:
+        """Switch the layer products between the model dtype (None) and MXFP8 x MXFP4 ("mx", alias "mxfp8_mxfp4").  The MX weight images are built
+        on first use and kept; which struct a call runs is decided per call (_struct_for), and a decode graph captured for one struct is never
+        replayed for another."""
+        fmt = L.linear_format_code(linear_dtype)
+        if fmt != L.WDEC_MODEL_DTYPE:
+            if self.weight_format != L.WDEC_MODEL_DTYPE:
+                raise L.SpeechLLMError("linear_dtype and weight_dtype exclude each other: linear_dtype='mx' already runs every layer product on 4-bit weights")
+            if not L.is16(self.dtype):
+                raise L.SpeechLLMError("linear_dtype='mx' needs a bfloat16 or float16 model: float32 is the parity mode and keeps its products in float32")
+            a = self.arch
+            ks = dict(hidden_size=a.hidden_size, attention_width=a.num_attention_heads * a.head_dim, intermediate_size=a.intermediate_size)
+            bad = {n: k for n, k in ks.items() if k % 128}
+            if bad:
+                raise L.SpeechLLMError(f"linear_dtype='mx' needs every reduction length to be a multiple of 128, not {bad}")
+            if getattr(self, "_w", None) is not None:
+                self._w.build_linear_weights_mx()
+        self.linear_format = fmt
+
+    _MX_REFUSED = {"beam": "beam search", "generate_n": "several sampled answers per prompt (num_return_sequences > 1)", "score": "teacher-forced scoring"}
+
+    def _struct_for(self, B: int, entry: Optional[str] = None):
+        """(model struct, its name) for a call of B sequences: the e4m3 / MXFP4 struct when the option is on and the batch is within its range;
+        with linear_dtype='mx' the MX struct at every B — the entries that do not run it (`entry` in _MX_REFUSED) raise, they never fall back"""
         w = self._dev()
+        if self.linear_format == L.WDEC_MX_LINEAR:
+            if entry in self._MX_REFUSED:
+                raise L.SpeechLLMError(f"linear_dtype='mx' does not run {self._MX_REFUSED[entry]}: call set_linear_dtype(None) for it")
+            return w.struct_mx, "mx"
         if self.weight_format == L.WDEC_MXFP4 and B <= L.lib().sl_w4_max_rows():
             return w.struct_mxfp4, "mxfp4"
         if self.weight_format == L.WDEC_E4M3 and B <= L.lib().sl_w8_max_rows():
@@ -376,6 +413,12 @@ class AudioLlamaForCausalLM:
         return torch.cat(parts, 0).contiguous(), [int(n) + 1 for n in lens]
 
     def _workspace(self, nbytes: int) -> torch.Tensor:
+        if self.linear_format == L.WDEC_MX_LINEAR:
+            # linear_dtype='mx' needs more bytes (the quantised rows): its own buffer, so that the other setting's workspace — and the decode
+            # graphs captured on it — are where they were when the option is switched off again
+            if self._ws_mx is None or self._ws_mx.numel() < nbytes:
+                self._ws_mx = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+            return self._ws_mx
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
         return self._ws
@@ -531,7 +574,7 @@ class AudioLlamaForCausalLM:
             start_c, ns_c = (C.c_int32 * nseq)(*call["score_start"]), (C.c_int32 * nseq)(*call["n_score"])
             labels = L.h2d(call["labels"], torch.int32, self.device)
             kv = self._kv_cache(max(nseq, self._score_slots()))
-            struct, _ = self._struct_for(nseq)      # the layers read the row-major set of either struct
+            struct, _ = self._struct_for(nseq, "score")      # the layers read the row-major set of either struct
             nbytes = lib.sl_llama_score_workspace_bytes(C.byref(struct), x.shape[0], nseq, n_rows, C.byref(opts))
             if nbytes == 0:
                 L.check(-1, "sl_llama_score_workspace_bytes")
@@ -771,7 +814,7 @@ class AudioLlamaForCausalLM:
         st = L.GenerateStats()
         lp = self._logits_struct(logits, max_new_tokens)
         lp_ref = C.byref(lp) if lp is not None else None
-        struct, fmt_name = self._struct_for(B)
+        struct, fmt_name = self._struct_for(B, "generate_n" if R > 1 else None)
         lps = None
         if R > 1:
             if scores:
@@ -844,7 +887,7 @@ class AudioLlamaForCausalLM:
         st = L.GenerateStats()
         lp = self._logits_struct(logits, max_new_tokens)
         lp_ref = C.byref(lp) if lp is not None else None
-        struct, fmt_name = self._struct_for(B * K)
+        struct, fmt_name = self._struct_for(B * K, "beam")
         nbytes = lib.sl_beam_generate_workspace_bytes_lp(C.byref(struct), x.shape[0], B, C.byref(kv), C.byref(o), lp_ref)
         if nbytes == 0:
             L.check(-1, "sl_beam_generate_workspace_bytes")

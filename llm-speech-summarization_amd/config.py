@@ -69,6 +69,17 @@ def runtime_weight_dtype(config):
     return "fp8" if name == "fp8" else None
 
 
+def runtime_linear_dtype(config):
+    """The layer-product format a config's `runtime.linear_dtype` names: `model` (default: the model dtype) -> None, `mx` /
+    `mxfp8_mxfp4` -> "mx" (MXFP8 activations x MXFP4 weights in every decoder-layer product, 16-bit models only) — the value the
+    `linear_dtype` keyword of the model classes takes."""
+    rt = config.get("runtime", {}) if hasattr(config, "get") else {}
+    name = str((rt or {}).get("linear_dtype", "model"))
+    if name not in ("model", "mx", "mxfp8_mxfp4"):
+        raise ValueError(f"runtime.linear_dtype: {name!r} is not one of ['model', 'mx', 'mxfp8_mxfp4']")
+    return None if name == "model" else "mx"
+
+
 def runtime_dtype(config) -> "torch.dtype":
     """The compute dtype a config's `runtime.dtype` names (default bf16): fp32 (exact-fp32 parity mode), bf16, or fp16
     (inference only, the reference's torch_dtype=float16 regime; training rejects it)."""

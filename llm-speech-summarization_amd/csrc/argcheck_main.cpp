@@ -195,6 +195,47 @@ int main() {
     EXPECT_ARG_ERROR(sl_gemm(&wa, nullptr));
     free(src); free(img);
   }
+  {   // MX linears: the host packer and the host activation quantiser under the sanitizers, strided sources out of exactly-sized
+      // allocations into exactly-sized outputs; the MX image holds the MXFP4 image's scale bytes, rearranged; and the refusals
+    const int N = 40, K = 384, ld = 392, M = 5;
+    const size_t bytes = sl_mx_weight_image_bytes(N, K);
+    EXPECT(bytes == (size_t)48 * 192 + 48 * 12 && bytes == sl_w4_image_bytes(N, K), "MX image bytes");
+    EXPECT(sl_mx_weight_image_bytes(N, 192) == 0 && sl_mx_weight_image_bytes(0, 128) == 0, "MX image bytes of a bad shape");
+    uint16_t* src = (uint16_t*)malloc(((size_t)(N - 1) * ld + K) * sizeof(uint16_t));
+    unsigned char* img = (unsigned char*)aligned_alloc(16, bytes);
+    unsigned char* img4 = (unsigned char*)aligned_alloc(16, bytes);
+    for (int n = 0; n < N; ++n)
+      for (int k = 0; k < K; ++k) src[(size_t)n * ld + k] = n == 7 ? 0 : (uint16_t)(0x3C00 + ((n * 131 + k * 17) & 0x3FF) + ((k & 1) << 15));
+    src[(size_t)3 * ld + 5] = 0x7F80; src[(size_t)3 * ld + 40] = 0x7FC0; src[(size_t)4 * ld + 9] = 0x0001;      // +inf, a NaN, the smallest subnormal
+    EXPECT(sl_pack_weight_mx_host(src, ld, img, N, K, SL_BF16) == 0 && sl_pack_weight_mxfp4_host(src, ld, img4, N, K, SL_BF16) == 0, "host packers run");
+    bool same = true;
+    const unsigned char *sc = img + (size_t)48 * K / 2, *sc4 = img4 + (size_t)48 * K / 2;
+    for (int f = 0; f < 3; ++f)
+      for (int j = 0; j < K / 128; ++j)
+        for (int lane = 0; lane < 64; ++lane)       // sc[f][j][lane] against the MXFP4 image's sc[f][j][r][d], r = lane & 15, d = lane >> 4
+          same = same && sc[((size_t)f * (K / 128) + j) * 64 + lane] == sc4[(((size_t)f * (K / 128) + j) * 16 + (lane & 15)) * 4 + (lane >> 4)];
+    EXPECT(same, "MX image scale bytes = the MXFP4 image's");
+    EXPECT(sl_pack_weight_mx_host(src, ld, img, N, K, SL_F32) == SL_ERR_UNSUPPORTED, "MX image of a float32 weight");
+    EXPECT_ARG_ERROR(sl_pack_weight_mx_host(src, ld, img, N, 192, SL_BF16));
+    EXPECT_ARG_ERROR(sl_pack_weight_mx_host(src, K - 1, img, N, K, SL_BF16));
+    EXPECT_ARG_ERROR(sl_pack_weight_mx(src, ld, img, N, 192, SL_F16, nullptr));
+    unsigned char* q = (unsigned char*)aligned_alloc(16, (size_t)M * K);
+    unsigned char* qs = (unsigned char*)malloc((size_t)M * (K / 32));
+    EXPECT(sl_mxfp8_quantize_rows_host(src, ld, q, qs, M, K, SL_BF16) == 0, "host quantiser runs");
+    EXPECT(q[(size_t)3 * K + 5] == 0x7E && q[(size_t)3 * K + 40] == 0x7F, "+inf -> 448, NaN -> 0x7F");
+    EXPECT(sl_mxfp8_quantize_rows_host(src, ld, q, qs, M, K, SL_F32) == SL_ERR_UNSUPPORTED, "MXFP8 rows of float32 activations");
+    EXPECT_ARG_ERROR(sl_mxfp8_quantize_rows_host(src, ld, q, qs, M, 48, SL_BF16));
+    EXPECT_ARG_ERROR(sl_mxfp8_quantize_rows(src, K - 1, q, qs, M, K, SL_F16, nullptr));
+    sl_gemm_mx_args ma;
+    memset(&ma, 0, sizeof(ma));
+    ma.Aq = q; ma.lda = K; ma.a_scales = qs; ma.W = img; ma.C = img4; ma.ldc = N; ma.M = M; ma.N = N; ma.K = 192; ma.dtype = SL_BF16;
+    EXPECT_ARG_ERROR(sl_gemm_mx(&ma, nullptr));
+    ma.K = K; ma.dtype = SL_F32;
+    EXPECT(sl_gemm_mx(&ma, nullptr) == SL_ERR_UNSUPPORTED, "MX product in float32");
+    ma.dtype = SL_BF16; ma.act = SL_ACT_GELU;
+    EXPECT_ARG_ERROR(sl_gemm_mx(&ma, nullptr));
+    free(src); free(img); free(img4); free(q); free(qs);
+  }
 
   // ---- norms / element-wise / losses
   EXPECT_ARG_ERROR(sl_layernorm(nullptr, nullptr, nullptr, nullptr, 4, 1024, 1e-5f, 0, SL_BF16, nullptr));

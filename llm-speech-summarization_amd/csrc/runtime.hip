@@ -538,6 +538,7 @@ extern "C" int sl_whisper_forward(const sl_hubert_model* m, const void* mel, int
 
 struct LlamaWs {
   void *h, *qkv, *att, *mid, *last, *part, *split;
+  void *mxq = nullptr, *mxs = nullptr;   // SL_WDEC_MX_LINEAR only: the MXFP8 rows (bytes, scales) of the product being fed
   size_t split_bytes;
   float *rstd_a, *rstd_b;   // RMSNorm scales handed from the o / down projection's reduce pass to the next fused GEMM
   int32_t *tok_seq, *tok_pos, *cu, *cuk, *klen;
@@ -572,6 +573,13 @@ static size_t llama_carve(const sl_llama_model* m, int64_t n_tok, int nseq, void
   w.cuk = (int32_t*)c.take((nseq + 1) * sizeof(int32_t));
   w.klen = (int32_t*)c.take((nseq + 1) * sizeof(int32_t));
   w.last_row = (int32_t*)c.take((size_t)nseq * sizeof(int32_t));
+  if (m->reserved == SL_WDEC_MX_LINEAR) {      // behind everything else: the other formats keep their layout and their byte count
+    int kmax = m->hidden;
+    if (m->n_heads * m->head_dim > kmax) kmax = m->n_heads * m->head_dim;
+    if (m->ffn > kmax) kmax = m->ffn;
+    w.mxq = c.take((size_t)n_tok * kmax);
+    w.mxs = c.take((size_t)n_tok * (kmax / 32));
+  }
   return c.off + 256;
 }
 
@@ -590,12 +598,59 @@ static int llama_check(const sl_llama_model* m, const sl_kv_cache* kv) {
   return 0;
 }
 
+// MX linears (gemm_mx.hip)
+int sl_gemm_mx_impl(const sl_gemm_mx_args* a, hipStream_t st);
+int sl_mxfp8_quantize_rows_impl(const void* x, int64_t ldx, void* q, void* scales, int64_t M, int32_t K, int32_t dtype, hipStream_t st);
+
+// sl_llama_model.reserved = SL_WDEC_MX_LINEAR (format 5): the layers' row-major pointers are MX weight images and every layer product runs MXFP8 x MXFP4, at
+// every row count.  Checked by every entry that runs such a model, before any launch.
+static int llama_mx_check(const char* who, const sl_llama_model* m) {
+  if (m->dtype == SL_F32) {
+    sl_set_error("%s: MX linears (format 5) are built for bf16 / fp16 models, not float32 (the parity mode)", who);
+    return SL_ERR_UNSUPPORTED;
+  }
+  SL_CHECK_ARG(sl_is16(m->dtype), "%s: unknown dtype %d", who, m->dtype);
+  for (int l = 0; l < m->n_layers; ++l) {
+    const sl_llama_layer& L = m->layers[l];
+    SL_CHECK_ARG(L.wqkv && L.wo && L.wgu && L.wdown, "%s: MX linears (format 5): layer %d has a null weight image", who, l);
+    SL_CHECK_ARG(!L.wqkv_dec && !L.wo_dec && !L.wgu_dec && !L.wdown_dec, "%s: MX linears (format 5): layer %d has a non-null *_dec pointer (the four must be NULL)", who, l);
+  }
+  const int ks[3] = {m->hidden, m->n_heads * m->head_dim, m->ffn};
+  for (int k : ks)
+    if (k % 128 != 0) {
+      sl_set_error("%s: MX linears (format 5) need every reduction length to be a multiple of 128 (hidden=%d, n_heads*head_dim=%d, ffn=%d)", who, ks[0], ks[1], ks[2]);
+      return SL_ERR_UNSUPPORTED;
+    }
+  return 0;
+}
+// entries that do not run MX linears refuse the format before any launch
+static int llama_mx_refuse(const char* who, const sl_llama_model* m) {
+  if (m && m->reserved == SL_WDEC_MX_LINEAR) {
+    sl_set_error("%s: MX linears (sl_llama_model.reserved = 5, format 5) are not built for this entry: prefill, decode step and sl_generate* run them", who);
+    return SL_ERR_UNSUPPORTED;
+  }
+  return 0;
+}
+// one product of a decoder layer on the row-major weight set: C = act(A . W^T) + res.  Format 5: quantise the M input rows (one launch), then the MX product
+// on the weight image; every other format: the call it always was, launch for launch.
+static int layer_gemm(const sl_llama_model* m, const LlamaWs& w, const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* res,
+                      int64_t ldr, int M, int N, int K, int act, hipStream_t st) {
+  if (m->reserved != SL_WDEC_MX_LINEAR) return gemm(m->dtype, A, lda, W, ldw, C, ldc, nullptr, res, ldr, M, N, K, act, 0, st);
+  SL_TRY(sl_mxfp8_quantize_rows_impl(A, lda, w.mxq, w.mxs, M, K, m->dtype, st));
+  sl_gemm_mx_args a;
+  memset(&a, 0, sizeof(a));
+  a.Aq = w.mxq; a.lda = K; a.a_scales = w.mxs; a.W = W; a.C = C; a.ldc = ldc; a.residual = res; a.ldr = ldr;
+  a.M = M; a.N = N; a.K = K; a.dtype = m->dtype; a.act = act; a.out_f32 = 0;
+  return sl_gemm_mx_impl(&a, st);
+}
+
 // sl_llama_model.reserved, the format of the decode weights (speechllm.h SL_WDEC_*), against what a decode step of `rows` rows can run: checked by
 // every entry that decodes, before any launch.  An e4m3 model decodes on the skinny kernels' W8 form only, an MXFP4 model on their W4 form only.
 static int llama_wdec_check(const char* who, const sl_llama_model* m, int rows) {
   if (m->reserved == SL_WDEC_MODEL_DTYPE) return 0;
+  if (m->reserved == SL_WDEC_MX_LINEAR) return llama_mx_check(who, m);
   SL_CHECK_ARG(m->reserved == SL_WDEC_E4M3 || m->reserved == SL_WDEC_MXFP4,
-               "%s: unknown decode-weight format %d (sl_llama_model.reserved: 0 = model dtype, 1 = e4m3 weight images, 4 = MXFP4 weight images)", who, m->reserved);
+               "%s: unknown decode-weight format %d (sl_llama_model.reserved: 0 = model dtype, 1 = e4m3 weight images, 4 = MXFP4 weight images, 5 = MX linears)", who, m->reserved);
   const bool w4 = m->reserved == SL_WDEC_MXFP4;
   const char* name = w4 ? "MXFP4" : "e4m3";
   if (m->dtype == SL_F32) {
@@ -840,7 +895,7 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     return 0;
   }
   SL_TRY(sl_rmsnorm(x, w.h, L.norm1, n, H, m->rms_eps, dt, (sl_stream)st));
-  SL_TRY(gemm(dt, w.h, H, L.wqkv, H, w.qkv, qkv_w, nullptr, nullptr, 0, (int)n, qkv_w, H, SL_ACT_NONE, 0, st));
+  SL_TRY(layer_gemm(m, w, w.h, H, L.wqkv, H, w.qkv, qkv_w, nullptr, 0, (int)n, qkv_w, H, SL_ACT_NONE, st));
   SL_TRY(sl_rope_kv_append_ex(w.qkv, kc, vc, w.tok_seq, decode ? ctx_len_dev : w.tok_pos, m->rope_cos, m->rope_sin, n, nh, nkv, D, kv->max_ctx,
                               dt, kv->reserved, (sl_stream)st));
   if (decode) {
@@ -879,25 +934,27 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     SL_TRY(gather_rows(w.att, att_t, tail_rows, n_tail, (size_t)nh * D * esz, st));
     SL_TRY(gather_rows(x, w.last, tail_rows, n_tail, (size_t)H * esz, st));
     SlFamilyPin pin((int)n);
-    SL_TRY(gemm(dt, att_t, (int64_t)nh * D, L.wo, (int64_t)nh * D, w.last, H, nullptr, w.last, H, n_tail, H, nh * D, SL_ACT_NONE, 0, st));
+    SL_TRY(layer_gemm(m, w, att_t, (int64_t)nh * D, L.wo, (int64_t)nh * D, w.last, H, w.last, H, n_tail, H, nh * D, SL_ACT_NONE, st));
     SL_TRY(sl_rmsnorm(w.last, w.h, L.norm2, n_tail, H, m->rms_eps, dt, (sl_stream)st));
-    SL_TRY(gemm(dt, w.h, H, L.wgu, H, w.mid, m->ffn, nullptr, nullptr, 0, n_tail, 2 * m->ffn, H, SL_ACT_SILU_MUL, 0, st));
-    SL_TRY(gemm(dt, w.mid, m->ffn, L.wdown, m->ffn, w.last, H, nullptr, w.last, H, n_tail, H, m->ffn, SL_ACT_NONE, 0, st));
+    SL_TRY(layer_gemm(m, w, w.h, H, L.wgu, H, w.mid, m->ffn, nullptr, 0, n_tail, 2 * m->ffn, H, SL_ACT_SILU_MUL, st));
+    SL_TRY(layer_gemm(m, w, w.mid, m->ffn, L.wdown, m->ffn, w.last, H, w.last, H, n_tail, H, m->ffn, SL_ACT_NONE, st));
     return 0;
   }
-  SL_TRY(gemm(dt, w.att, (int64_t)nh * D, L.wo, (int64_t)nh * D, x, H, nullptr, x, H, (int)n, H, nh * D, SL_ACT_NONE, 0, st));
+  SL_TRY(layer_gemm(m, w, w.att, (int64_t)nh * D, L.wo, (int64_t)nh * D, x, H, x, H, (int)n, H, nh * D, SL_ACT_NONE, st));
   SL_TRY(sl_rmsnorm(x, w.h, L.norm2, n, H, m->rms_eps, dt, (sl_stream)st));
-  SL_TRY(gemm(dt, w.h, H, L.wgu, H, w.mid, m->ffn, nullptr, nullptr, 0, (int)n, 2 * m->ffn, H, SL_ACT_SILU_MUL, 0, st));
-  SL_TRY(gemm(dt, w.mid, m->ffn, L.wdown, m->ffn, x, H, nullptr, x, H, (int)n, H, m->ffn, SL_ACT_NONE, 0, st));
+  SL_TRY(layer_gemm(m, w, w.h, H, L.wgu, H, w.mid, m->ffn, nullptr, 0, (int)n, 2 * m->ffn, H, SL_ACT_SILU_MUL, st));
+  SL_TRY(layer_gemm(m, w, w.mid, m->ffn, L.wdown, m->ffn, x, H, x, H, (int)n, H, m->ffn, SL_ACT_NONE, st));
   return 0;
 }
 
+static inline const char* cont_name(const int32_t* past_host, const int32_t* slot_host) { return (past_host || slot_host) ? "sl_llama_prefill_cont" : "sl_llama_prefill"; }
 // slot_stride: sequence s is written to cache slot s * slot_stride (1 for every public caller; the beam search prefills each prompt once,
 // into the slot of its first beam — without the shared-prefix dedupe, whose broadcast assumes consecutive slots)
 static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
                               float* logits, int32_t* ctx_len_dev, void* hidden_taps, void* workspace, size_t workspace_bytes,
                               sl_stream stream, int slot_stride, const int32_t* past_host = nullptr, const int32_t* slot_host = nullptr) {
   SL_TRY(llama_check(m, kv));
+  if (m->reserved == SL_WDEC_MX_LINEAR) SL_TRY(llama_mx_check(cont_name(past_host, slot_host), m));
   // continued prefill (sl_llama_prefill_cont): sequence s already holds positions [0, past_host[s]) of cache slot slot_host[s].  All-zero pasts on
   // the identity slots ARE the plain call: every line below then runs as it did
   if (past_host && nseq > 0) {
@@ -1111,6 +1168,7 @@ extern "C" int sl_llama_score(const sl_llama_model* m, const sl_kv_cache* kv, vo
                               size_t workspace_bytes, sl_stream stream) {
   // every check comes before the first launch
   SL_TRY(llama_check(m, kv));
+  SL_TRY(llama_mx_refuse("sl_llama_score", m));
   SL_CHECK_ARG(x && cu_seqlens_host && score_start_host && n_score_host && labels_dev && logprob_dev && workspace, "sl_llama_score: null pointer");
   SL_CHECK_ARG(nseq > 0, "sl_llama_score: nseq=%d", nseq);
   SL_CHECK_ARG((seq_sum_dev != nullptr) == (seq_counted_dev != nullptr) && (seq_sum_dev != nullptr) == (seq_top1_dev != nullptr),
@@ -1688,6 +1746,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   // several answers per prompt: refused before anything is launched
   SL_CHECK_ARG(N >= 1, "sl_generate_n: num_return_sequences %d < 1", N);
   if (N > 1) {
+    SL_TRY(llama_mx_refuse("sl_generate_n", m));
     SL_CHECK_ARG(o->sample != 0, "sl_generate_n: num_return_sequences %d > 1 needs sample = 1 (greedy answers of one prompt are all the same)", N);
     SL_CHECK_ARG(nseq > 0 && (int64_t)nseq * N <= SL_MAX_DECODE_BATCH, "sl_generate_n: nseq %d x num_return_sequences %d decode rows outside (0, %d]", nseq, N,
                  SL_MAX_DECODE_BATCH);
@@ -2103,6 +2162,7 @@ extern "C" int sl_beam_generate_lp(const sl_llama_model* m, const sl_kv_cache* k
   SL_CHECK_ARG(x && cu_seqlens_host && out_ids_host && out_scores_host && out_lens_host && workspace, "sl_beam_generate: null buffer");
   const int K = o->num_beams, R = nseq * K, Rn = o->num_return_sequences, max_new = o->max_new_tokens;
   const int n_eos = o->use_eos ? o->n_eos : 0;
+  SL_TRY(llama_mx_refuse("sl_beam_generate", m));
   SL_TRY(llama_wdec_check("sl_beam_generate", m, R));
   for (int s = 0; s < nseq; ++s) {
     const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];

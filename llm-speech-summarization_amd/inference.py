@@ -25,7 +25,7 @@ from .utils import (LLAMA_PROMPT_PREFIX, LLAMA_PROMPT_SUFFIX, MINICHAT_PROMPT_PR
 class LLMSpeechTextInference():
     def __init__(self, config, audio_encoder_checkpoint, device, *, tokenizer=None, llm: Optional[AudioLlamaForCausalLM] = None,
                  audio_encoder: Optional[AudioEncoder] = None, dtype: torch.dtype = torch.bfloat16, kv_cache_dtype=None, weight_dtype=None,
-                 ctc_segmenter=None):
+                 ctc_segmenter=None, linear_dtype=None):
         self.config = config
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -71,11 +71,14 @@ class LLMSpeechTextInference():
 
         # Frozen LLM (ref:inference.py:46-52).
         if llm is None:
-            llm = AudioLlamaForCausalLM.from_pretrained(self.llm_type, use_cache=True, torch_dtype=dtype, kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype)
+            llm = AudioLlamaForCausalLM.from_pretrained(self.llm_type, use_cache=True, torch_dtype=dtype, kv_cache_dtype=kv_cache_dtype, weight_dtype=weight_dtype,
+                                                        linear_dtype=linear_dtype)
         elif L.kv_format_code(kv_cache_dtype) != llm.kv_format and kv_cache_dtype is not None:
             raise L.SpeechLLMError("kv_cache_dtype differs from the K/V cache format of the llm that was passed in: construct that llm with the same kv_cache_dtype")
         if llm.weight_format != L.weight_format_code(weight_dtype) and weight_dtype is not None:
             raise L.SpeechLLMError("weight_dtype differs from the decode-weight format of the llm that was passed in: construct that llm with the same weight_dtype")
+        if llm.linear_format != L.linear_format_code(linear_dtype) and linear_dtype is not None:
+            raise L.SpeechLLMError("linear_dtype differs from the layer-product format of the llm that was passed in: construct that llm with the same linear_dtype")
         self.llm = llm.eval().to(self.device)
         # runtime.num_beams / length_penalty / early_stopping of the config (absent in the shipped yamls: greedy) -> beam search
         from .config import runtime_beams, runtime_logits, runtime_num_return

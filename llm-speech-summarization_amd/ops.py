@@ -405,6 +405,97 @@ def w4_dequantise(img: torch.Tensor, N: int, K: int) -> torch.Tensor:
     return v.view(c.shape[0], K)[:N]
 
 
+# ---- MX linears (speechllm.h "MX weight image", "MXFP8 activation rows", sl_gemm_mx) ---------------------------------------------
+def mx_weight_image_bytes(N: int, K: int) -> int:
+    n = int(L.lib().sl_mx_weight_image_bytes(N, K))
+    if n == 0:
+        L.check(-1, "sl_mx_weight_image_bytes")
+    return n
+
+
+def pack_weight_mx(W: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(N, K) bf16 / fp16 weight (row stride W.stride(0)) -> its MX weight image (sl_pack_weight_mx): the MXFP4 image's codes and scale
+    bytes, arranged one 32-element block per lane for the block-scaled MFMA.  GPU tensor: the device packer; CPU tensor: the host entry."""
+    n, k = W.shape
+    if W.stride(1) != 1:
+        raise L.SpeechLLMError("pack_weight_mx: rows must be contiguous")
+    if out is None:
+        out = torch.empty(mx_weight_image_bytes(n, k), device=W.device, dtype=torch.uint8)
+    if out.numel() != mx_weight_image_bytes(n, k) or not out.is_contiguous() or out.dtype != torch.uint8:
+        raise L.SpeechLLMError("pack_weight_mx: out must be a contiguous uint8 buffer of mx_weight_image_bytes(N, K)")
+    if W.is_cuda:
+        L.check(L.lib().sl_pack_weight_mx(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype), L.stream_ptr()), "sl_pack_weight_mx")
+    else:
+        L.check(L.lib().sl_pack_weight_mx_host(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype)), "sl_pack_weight_mx_host")
+    return out
+
+
+def mx_image_parts(img: torch.Tensor, N: int, K: int):
+    """An MX weight image -> (e2m1 codes (Np, K) uint8 in natural row / column order, scale bytes (Np, K/32) uint8); Np = ceil(N/16)*16."""
+    Np = (N + 15) // 16 * 16
+    b = img[:Np * K // 2].view(Np // 16, K // 128, 4, 16, 16)           # [f][j][lane >> 4][lane & 15][byte]
+    c = torch.stack([b & 15, b >> 4], dim=-1)                           # element 2b in the low nibble, 2b + 1 in the high one
+    c = c.permute(0, 3, 1, 2, 4, 5).reshape(Np, K)                      # row 16 f + (lane & 15), column 128 j + 32 (lane >> 4) + 2 byte + half
+    s = img[Np * K // 2:Np * K // 2 + Np * K // 32].view(Np // 16, K // 128, 4, 16)      # [f][j][lane >> 4][lane & 15]
+    return c, s.permute(0, 3, 1, 2).reshape(Np, K // 32)
+
+
+def mx_dequantise(img: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """An MX weight image -> the (N, K) fp64 matrix the product multiplies by: e2m1 * 2^(scale byte - 127), every value exact."""
+    c, s = mx_image_parts(img.cpu(), N, K)
+    grid = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float64)
+    v = grid[c.long()].view(c.shape[0], K // 32, 32) * torch.exp2(s.double() - 127)[:, :, None]
+    return v.view(c.shape[0], K)[:N]
+
+
+def mxfp8_quantize_rows(x: torch.Tensor, out=None):
+    """(M, K) bf16 / fp16 rows (row stride x.stride(0)), K % 32 == 0 -> (q (M, K) uint8 e4m3 bytes, scales (M, K/32) uint8 e8m0 bytes).
+    GPU tensor: sl_mxfp8_quantize_rows; CPU tensor: sl_mxfp8_quantize_rows_host, the definition."""
+    m, k = x.shape
+    if x.stride(1) != 1:
+        raise L.SpeechLLMError("mxfp8_quantize_rows: rows must be contiguous")
+    if out is not None:      # (q, scales): contiguous uint8 buffers of M * K and M * K/32 bytes
+        q, s = out
+        if q.numel() != m * k or s.numel() != m * (k // 32) or not q.is_contiguous() or not s.is_contiguous():
+            raise L.SpeechLLMError("mxfp8_quantize_rows: out must be contiguous buffers of M * K and M * K/32 bytes")
+    else:
+        q = torch.empty((m, k), device=x.device, dtype=torch.uint8)
+        s = torch.empty((m, max(k // 32, 0)), device=x.device, dtype=torch.uint8)
+    if x.is_cuda:
+        L.check(L.lib().sl_mxfp8_quantize_rows(L.ptr(x), x.stride(0), L.ptr(q), L.ptr(s), m, k, L.dtype_code(x.dtype), L.stream_ptr()), "sl_mxfp8_quantize_rows")
+    else:
+        L.check(L.lib().sl_mxfp8_quantize_rows_host(L.ptr(x), x.stride(0), L.ptr(q), L.ptr(s), m, k, L.dtype_code(x.dtype)), "sl_mxfp8_quantize_rows_host")
+    return q, s
+
+
+def mxfp8_dequantise(q: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """MXFP8 rows -> the (M, K) fp64 values the product multiplies by: e4m3 * 2^(scale byte - 127); a NaN byte (0x7F / 0xFF) stays NaN."""
+    q, scales = q.cpu(), scales.cpu()
+    v = q.contiguous().view(torch.float8_e4m3fn).double()
+    m, k = q.shape
+    return (v.view(m, k // 32, 32) * torch.exp2(scales.double() - 127)[:, :, None]).view(m, k)
+
+
+def gemm_mx(Aq: torch.Tensor, a_scales: torch.Tensor, Wimg: torch.Tensor, N: int, *, dtype: torch.dtype = torch.bfloat16, act: int = L.ACT_NONE,
+            residual: Optional[torch.Tensor] = None, out_f32: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """act(dq(Aq) . dq(Wimg)^T) + residual (sl_gemm_mx): Aq (M, K) e4m3 bytes (row stride Aq.stride(0)) with a_scales (M, K/32), Wimg the
+    MX weight image of an (N, K) weight.  `dtype` is the output's (and the residual's) 16-bit type; out_f32 writes float."""
+    L.require_gpu(Aq, "Aq")
+    m, k = Aq.shape
+    if Aq.stride(1) != 1 or not a_scales.is_contiguous() or tuple(a_scales.shape) != (m, k // 32):
+        raise L.SpeechLLMError("gemm_mx: Aq rows must be contiguous and a_scales a contiguous (M, K/32) tensor")
+    nout = N // 2 if act == L.ACT_SILU_MUL else N
+    if out is None:
+        out = torch.empty((m, nout), device=Aq.device, dtype=torch.float32 if out_f32 else dtype)
+    a = L.GemmMxArgs()
+    a.Aq, a.lda, a.a_scales, a.W = L.ptr(Aq), Aq.stride(0), L.ptr(a_scales), L.ptr(Wimg)
+    a.C, a.ldc = L.ptr(out), out.stride(0)
+    a.residual, a.ldr = L.ptr(residual), (residual.stride(0) if residual is not None else 0)
+    a.M, a.N, a.K, a.dtype, a.act, a.out_f32 = m, N, k, L.dtype_code(dtype), act, int(bool(out_f32))
+    L.check(L.lib().sl_gemm_mx(C.byref(a), L.stream_ptr()), "sl_gemm_mx")
+    return out
+
+
 def gemm_decode(A: torch.Tensor, Wp: torch.Tensor, N: int, *, residual=None, act: int = L.ACT_NONE, out_f32: bool = False,
                 fuse_rms: bool = False, eps: float = 1e-5, rope=None, out: Optional[torch.Tensor] = None,
                 split_k: bool = True, rstd_in: Optional[torch.Tensor] = None, rstd_out: Optional[torch.Tensor] = None,

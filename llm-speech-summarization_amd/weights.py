@@ -710,6 +710,69 @@ class LlamaDeviceWeights:
         from . import ops
         return self._dequantised_state_dict(self.w4_images, self.w4_lm_head, lambda img, n, k: ops.w4_dequantise(img, n, k).float())
 
+    # -- opt-in MX linears (include/speechllm.h: MX weight images, SL_WDEC_MX_LINEAR) -----------------------------------------------
+    def mx_supported(self) -> Optional[str]:
+        """None, or why this model cannot run its layer products as MXFP8 x MXFP4"""
+        if not L.is16(self.dtype):
+            return "linear_dtype='mx' needs a bfloat16 or float16 model: float32 is the parity mode"
+        bad = {n: k for n, (_, k) in self.w8_shapes().items() if n != "lm_head" and k % 128}
+        if bad:
+            return f"linear_dtype='mx' needs every reduction length to be a multiple of 128, not {bad}"
+        return None
+
+    def build_linear_weights_mx(self) -> None:
+        """MX weight images (ops.pack_weight_mx) of the ROW-MAJOR layer matrices — wqkv, wo, the gate/up interleave, wdown: no gain fold,
+        no q / k permutation — and the struct `struct_mx`: `struct` with those four pointers of every layer replaced by the images, the
+        four *_dec pointers NULL and `reserved` = SL_WDEC_MX_LINEAR.  Embedding, norms and both lm_head pointers are `struct`'s.  The
+        16-bit matrices stay (the option can be switched off again); the images cost about a quarter copy of the layer weights more."""
+        if getattr(self, "struct_mx", None) is not None:
+            return
+        why = self.mx_supported()
+        if why:
+            raise L.SpeechLLMError(why)
+        from . import ops
+        a = self.arch
+        m = L.LlamaModel()
+        C.memmove(C.byref(m), C.byref(self.struct), C.sizeof(L.LlamaModel))
+        layers = (L.LlamaLayer * a.num_hidden_layers)()
+        C.memmove(layers, self._layers, C.sizeof(layers))
+        images: List[Dict[str, torch.Tensor]] = []
+        for li in range(a.num_hidden_layers):
+            t = self.layer_t[li]
+            imgs = {n: ops.pack_weight_mx(t[src]) for n, src in (("qkv", "wqkv"), ("o", "wo"), ("gu", "wgu"), ("down", "wdown"))}
+            images.append(imgs)
+            lay = layers[li]
+            lay.wqkv, lay.wo, lay.wgu, lay.wdown = (imgs[n].data_ptr() for n in ("qkv", "o", "gu", "down"))
+            lay.wqkv_dec = lay.wo_dec = lay.wgu_dec = lay.wdown_dec = None
+        m.layers = C.cast(layers, C.POINTER(L.LlamaLayer))
+        m.reserved = L.WDEC_MX_LINEAR
+        torch.cuda.synchronize(self.device)
+        self.struct_mx, self._layers_mx, self.mx_images = m, layers, images
+
+    def mx_dequantised_state_dict(self) -> Dict[str, torch.Tensor]:
+        """HF-keyed fp32 CPU state dict of the WEIGHTS the MX linears multiply by: the seven projections of every layer are the dequantised
+        MX images (e2m1 x 2^e, exact in fp32) in natural row order (gate / up de-interleaved); norms, embedding and lm_head are the
+        model's own.  The activations' MXFP8 rounding is not part of a state dict: a reference applies it in front of these seven."""
+        if getattr(self, "struct_mx", None) is None:
+            raise L.SpeechLLMError("mx_dequantised_state_dict: call build_linear_weights_mx first")
+        from . import ops
+        a = self.arch
+        H, D, nh, nkv, F_ = a.hidden_size, a.head_dim, a.num_attention_heads, a.num_key_value_heads, a.intermediate_size
+        shapes = self.w8_shapes()
+        dq = lambda img, name: ops.mx_dequantise(img, *shapes[name]).float()
+        sd = {"model.embed_tokens.weight": self.embed.float().cpu(), "model.norm.weight": self.final_norm.float().cpu(), "lm_head.weight": self.lm_head.float().cpu()}
+        for li, imgs in enumerate(self.mx_images):
+            p = f"model.layers.{li}."
+            sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.v_proj.weight"] = \
+                (t.contiguous() for t in dq(imgs["qkv"], "qkv").split([nh * D, nkv * D, nkv * D], 0))
+            sd[p + "self_attn.o_proj.weight"] = dq(imgs["o"], "o")
+            gu = dq(imgs["gu"], "gu").view(F_ // 16, 2, 16, H)
+            sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"] = gu[:, 0].reshape(F_, H).contiguous(), gu[:, 1].reshape(F_, H).contiguous()
+            sd[p + "mlp.down_proj.weight"] = dq(imgs["down"], "down")
+            sd[p + "input_layernorm.weight"] = self.layer_t[li]["norm1"].float().cpu()
+            sd[p + "post_attention_layernorm.weight"] = self.layer_t[li]["norm2"].float().cpu()
+        return sd
+
     def n_params(self) -> int:
         return sum(t.numel() for t in self._keep if t.dtype == self.dtype)
 
