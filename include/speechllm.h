@@ -867,6 +867,11 @@ typedef struct {
 #define SL_WDEC_E4M3        1
 #define SL_WDEC_MXFP4       4
 #define SL_WDEC_MX_LINEAR   5
+/* The rules of weight format `code`, from the library's one table of them: the multiple every reduction length must be (1 for the model
+ * dtype), the most decode rows the format runs (sl_w8_max_rows() / sl_w4_max_rows(); 0 = no limit) and the w_layout its *_dec images are
+ * read with (-1: the format has no *_dec images).  Any out pointer may be NULL.  A code that is no format (2, 3, 6, negatives, ...) is
+ * SL_ERR_ARG and the message lists the four formats. */
+int sl_weight_format_info(int32_t code, int32_t* k_multiple, int32_t* max_rows, int32_t* w_layout);
 
 typedef struct {
   void* k_cache; void* v_cache;  /* (n_layers, slots, n_kv, max_ctx, D) each: elements of the model dtype, or bytes (reserved = SL_KV_FP8_E4M3) */

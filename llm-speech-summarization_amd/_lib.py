@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass, field
 
 import torch
 
@@ -251,6 +252,7 @@ _PROTOS = {
     "sl_pack_weight_mxfp4": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "sl_pack_weight_mxfp4_host": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32]),
     "sl_w4_max_rows": (c_i32, []),
+    "sl_weight_format_info": (c_i32, [c_i32, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i32)]),
     "sl_mx_weight_image_bytes": (c_sz, [c_i32, c_i32]),
     "sl_pack_weight_mx": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "sl_pack_weight_mx_host": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_i32]),
@@ -463,30 +465,65 @@ def kv_format_code(kv_cache_dtype) -> int:
     raise SpeechLLMError(f"unsupported kv_cache_dtype {kv_cache_dtype!r}: None (the model dtype), 'fp8' or torch.float8_e4m3fn")
 
 
+@dataclass(frozen=True)
+class WeightFormat:
+    """One weight format of the Python surface.  What the library knows — the reduction-length multiple, the row limit, the layout — is read
+    from its own table (sl_weight_format_info, csrc/wformat.h), never restated here."""
+    code: int                   # SL_WDEC_*
+    option: str                 # the constructor option / setter that selects it
+    spellings: tuple            # the option's values that select it; the first is the one messages use
+    name: str                   # what _struct_for calls its struct
+    images: str                 # what messages call its weights
+    decode_images: bool         # True: images of the packed, gain-folded decode copies (lm_head included) beside them, so it needs pack_decode;
+                                # False: images of the layers' row-major matrices — lm_head, its K and the norm gains stay the model's own
+    pack: str = ""              # ops functions: weight -> image, image -> the fp64 matrix it stands for, (N, K) -> bytes of an image
+    dequantise: str = ""
+    image_bytes: str = ""
+    refused: dict = field(default_factory=dict)     # _struct_for entries that do not run it -> what to call them in the refusal
+
+    @property
+    def label(self) -> str:
+        return f"{self.option}='{self.spellings[0]}'"
+
+    def _info(self, i: int) -> int:
+        out = (c_i32(), c_i32(), c_i32())
+        check(lib().sl_weight_format_info(self.code, *(C.byref(v) for v in out)), "sl_weight_format_info")
+        return out[i].value
+
+    k_multiple = property(lambda self: self._info(0))       # every reduction length is a multiple of this
+    max_rows = property(lambda self: self._info(1))         # most decode rows it runs; 0: no limit
+    w_layout = property(lambda self: self._info(2))         # gemm_decode's w_layout for its images; -1: none
+
+
+WEIGHT_FORMATS = {f.code: f for f in (
+    WeightFormat(WDEC_MODEL_DTYPE, "weight_dtype", (None,), "16-bit", "16-bit", True),
+    WeightFormat(WDEC_E4M3, "weight_dtype", ("fp8", torch.float8_e4m3fn), "e4m3", "e4m3", True, "pack_weight_e4m3", "w8_dequantise", "w8_image_bytes"),
+    WeightFormat(WDEC_MXFP4, "weight_dtype", ("mxfp4", "fp4"), "mxfp4", "MXFP4", True, "pack_weight_mxfp4", "w4_dequantise", "w4_image_bytes"),
+    WeightFormat(WDEC_MX_LINEAR, "linear_dtype", ("mx", "mxfp8_mxfp4"), "mx", "MX", False, "pack_weight_mx", "mx_dequantise", "mx_weight_image_bytes",
+                 {"beam": "beam search", "generate_n": "several sampled answers per prompt (num_return_sequences > 1)", "score": "teacher-forced scoring"}),
+)}
+
+
+def _format_code(option: str, value, accepted: str) -> int:
+    if value is None:
+        return WDEC_MODEL_DTYPE
+    for f in WEIGHT_FORMATS.values():
+        if f.option == option and value in f.spellings:
+            return f.code
+    raise SpeechLLMError(f"unsupported {option} {value!r}: {accepted}")
+
+
 def weight_format_code(weight_dtype) -> int:
     """`weight_dtype` of the Python surface -> SL_WDEC_*: None (decode weights in the model dtype), "fp8" or torch.float8_e4m3fn (e4m3
     weight images with one fp32 scale per output row, for decode steps of up to sl_w8_max_rows() rows), "mxfp4" or its alias "fp4" (MXFP4
     weight images: e2m1 elements with one e8m0 scale per 32, for decode steps of up to sl_w4_max_rows() rows)."""
-    if weight_dtype is None:
-        return WDEC_MODEL_DTYPE
-    if isinstance(weight_dtype, str):
-        if weight_dtype == "fp8":
-            return WDEC_E4M3
-        if weight_dtype in ("mxfp4", "fp4"):
-            return WDEC_MXFP4
-    elif weight_dtype == torch.float8_e4m3fn:
-        return WDEC_E4M3
-    raise SpeechLLMError(f"unsupported weight_dtype {weight_dtype!r}: None (the model dtype), 'fp8' or torch.float8_e4m3fn, 'mxfp4' (alias 'fp4')")
+    return _format_code("weight_dtype", weight_dtype, "None (the model dtype), 'fp8' or torch.float8_e4m3fn, 'mxfp4' (alias 'fp4')")
 
 
 def linear_format_code(linear_dtype) -> int:
     """`linear_dtype` of the Python surface -> SL_WDEC_*: None (every product in the model dtype) or "mx" / "mxfp8_mxfp4" (the four
     products of every decoder layer as MXFP8 activations x MXFP4 weights on the block-scaled MFMA, at every row count)."""
-    if linear_dtype is None:
-        return WDEC_MODEL_DTYPE
-    if isinstance(linear_dtype, str) and linear_dtype in ("mx", "mxfp8_mxfp4"):
-        return WDEC_MX_LINEAR
-    raise SpeechLLMError(f"unsupported linear_dtype {linear_dtype!r}: None (the model dtype) or 'mx' (alias 'mxfp8_mxfp4')")
+    return _format_code("linear_dtype", linear_dtype, "None (the model dtype) or 'mx' (alias 'mxfp8_mxfp4')")
 
 
 def is16(dt: torch.dtype) -> bool:

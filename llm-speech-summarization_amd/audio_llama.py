@@ -23,7 +23,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .weights import KNOWN_LLAMA, LlamaArch, LlamaDeviceWeights
+from .weights import KNOWN_LLAMA, LlamaArch, LlamaDeviceWeights, format_unsupported
 
 
 class GenerateOutput:
@@ -278,12 +278,9 @@ class AudioLlamaForCausalLM:
             self._w = LlamaDeviceWeights(self.arch, self._sd, self.device, self.dtype, rope_len=max(self.max_ctx, 64))
             if self.pack_decode:
                 self._w.build_decode_weights()
-            if self.weight_format == L.WDEC_E4M3:
-                self._w.build_decode_weights_e4m3()
-            if self.weight_format == L.WDEC_MXFP4:
-                self._w.build_decode_weights_mxfp4()
-            if self.linear_format == L.WDEC_MX_LINEAR:
-                self._w.build_linear_weights_mx()
+            for code in (self.weight_format, self.linear_format):
+                if code != L.WDEC_MODEL_DTYPE:
+                    self._w.build_format(L.WEIGHT_FORMATS[code])
             self._sd = None  # device copy is the only copy from here on (6.4 GB bf16 for Llama-3.2-3B)
         return self
 
@@ -296,25 +293,28 @@ class AudioLlamaForCausalLM:
             self._kv = None
             self.kv_format = fmt
 
+    def _check_format(self, code: int) -> None:
+        """Refuse a weight format this model cannot take, before it is set; build its images where the weights are on the device already.
+        weight_dtype and linear_dtype exclude each other; the format's own rules are weights.format_unsupported's."""
+        if code == L.WDEC_MODEL_DTYPE:
+            return
+        fmt = L.WEIGHT_FORMATS[code]
+        this, other = ("weight", "linear") if fmt.option == "weight_dtype" else ("linear", "weight")
+        if getattr(self, other + "_format", L.WDEC_MODEL_DTYPE) != L.WDEC_MODEL_DTYPE:
+            raise L.SpeechLLMError(f"{this}_dtype and {other}_dtype exclude each other: linear_dtype='mx' already runs every layer product on 4-bit weights")
+        why = format_unsupported(fmt, self.arch, self.dtype)
+        if why:
+            raise L.SpeechLLMError(why)
+        if fmt.decode_images and not self.pack_decode:
+            raise L.SpeechLLMError(f"{fmt.label} needs pack_decode=True: the {fmt.images} weights are decode copies beside the packed 16-bit ones")
+        if getattr(self, "_w", None) is not None:
+            self._w.build_format(fmt)
+
     def set_weight_dtype(self, weight_dtype) -> None:
         """Switch the decode-weight format (None / "fp8" / torch.float8_e4m3fn / "mxfp4").  The images are built on first use and kept; which
         struct a call runs is decided per call (_struct_for), and a decode graph captured for one struct is never replayed for another."""
         fmt = L.weight_format_code(weight_dtype)
-        if fmt != L.WDEC_MODEL_DTYPE and getattr(self, "linear_format", L.WDEC_MODEL_DTYPE) != L.WDEC_MODEL_DTYPE:
-            raise L.SpeechLLMError("weight_dtype and linear_dtype exclude each other: linear_dtype='mx' already runs every layer product on 4-bit weights")
-        if fmt != L.WDEC_MODEL_DTYPE:
-            opt, name, kmul = ("mxfp4", "MXFP4", 128) if fmt == L.WDEC_MXFP4 else ("fp8", "e4m3", 64)
-            if not L.is16(self.dtype):
-                raise L.SpeechLLMError(f"weight_dtype='{opt}' needs a bfloat16 or float16 model: float32 is the parity mode and keeps its weights in float32")
-            if not self.pack_decode:
-                raise L.SpeechLLMError(f"weight_dtype='{opt}' needs pack_decode=True: the {name} weights are decode copies beside the packed 16-bit ones")
-            a = self.arch
-            ks = dict(hidden_size=a.hidden_size, attention_width=a.num_attention_heads * a.head_dim, intermediate_size=a.intermediate_size)
-            bad = {n: k for n, k in ks.items() if k % kmul}
-            if bad:
-                raise L.SpeechLLMError(f"weight_dtype='{opt}' needs every reduction length to be a multiple of {kmul}, not {bad}")
-            if getattr(self, "_w", None) is not None:
-                self._w.build_decode_weights_mxfp4() if fmt == L.WDEC_MXFP4 else self._w.build_decode_weights_e4m3()
+        self._check_format(fmt)
         self.weight_format = fmt
 
     def set_linear_dtype(self, linear_dtype) -> None:
@@ -322,34 +322,22 @@ class AudioLlamaForCausalLM:
         on first use and kept; which struct a call runs is decided per call (_struct_for), and a decode graph captured for one struct is never
         replayed for another."""
         fmt = L.linear_format_code(linear_dtype)
-        if fmt != L.WDEC_MODEL_DTYPE:
-            if self.weight_format != L.WDEC_MODEL_DTYPE:
-                raise L.SpeechLLMError("linear_dtype and weight_dtype exclude each other: linear_dtype='mx' already runs every layer product on 4-bit weights")
-            if not L.is16(self.dtype):
-                raise L.SpeechLLMError("linear_dtype='mx' needs a bfloat16 or float16 model: float32 is the parity mode and keeps its products in float32")
-            a = self.arch
-            ks = dict(hidden_size=a.hidden_size, attention_width=a.num_attention_heads * a.head_dim, intermediate_size=a.intermediate_size)
-            bad = {n: k for n, k in ks.items() if k % 128}
-            if bad:
-                raise L.SpeechLLMError(f"linear_dtype='mx' needs every reduction length to be a multiple of 128, not {bad}")
-            if getattr(self, "_w", None) is not None:
-                self._w.build_linear_weights_mx()
+        self._check_format(fmt)
         self.linear_format = fmt
 
-    _MX_REFUSED = {"beam": "beam search", "generate_n": "several sampled answers per prompt (num_return_sequences > 1)", "score": "teacher-forced scoring"}
-
     def _struct_for(self, B: int, entry: Optional[str] = None):
-        """(model struct, its name) for a call of B sequences: the e4m3 / MXFP4 struct when the option is on and the batch is within its range;
-        with linear_dtype='mx' the MX struct at every B — the entries that do not run it (`entry` in _MX_REFUSED) raise, they never fall back"""
+        """(model struct, its name) for a call of B sequences: the struct of the format that is switched on, where the batch is within the format's
+        row limit (e4m3, MXFP4; MX linears have none) — an entry the format does not run (WeightFormat.refused) raises, it never falls back"""
         w = self._dev()
-        if self.linear_format == L.WDEC_MX_LINEAR:
-            if entry in self._MX_REFUSED:
-                raise L.SpeechLLMError(f"linear_dtype='mx' does not run {self._MX_REFUSED[entry]}: call set_linear_dtype(None) for it")
-            return w.struct_mx, "mx"
-        if self.weight_format == L.WDEC_MXFP4 and B <= L.lib().sl_w4_max_rows():
-            return w.struct_mxfp4, "mxfp4"
-        if self.weight_format == L.WDEC_E4M3 and B <= L.lib().sl_w8_max_rows():
-            return w.struct_e4m3, "e4m3"
+        for code in (self.linear_format, self.weight_format):
+            fmt = L.WEIGHT_FORMATS[code]
+            if code == L.WDEC_MODEL_DTYPE:
+                continue
+            if entry in fmt.refused:
+                raise L.SpeechLLMError(f"{fmt.label} does not run {fmt.refused[entry]}: call set_{fmt.option}(None) for it")
+            max_rows = fmt.max_rows
+            if not max_rows or B <= max_rows:
+                return w.format_built(code)[0], fmt.name
         return w.struct, "16-bit" if L.is16(self.dtype) else "float32"
 
     def _dev(self) -> LlamaDeviceWeights:

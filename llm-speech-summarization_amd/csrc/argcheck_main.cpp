@@ -187,6 +187,12 @@ int main() {
     EXPECT_ARG_ERROR(sl_pack_weight_mxfp4_host(src, K - 1, img, N, K, SL_BF16));
     EXPECT_ARG_ERROR(sl_pack_weight_mxfp4(src, ld, img, N, 192, SL_F16, nullptr));
     EXPECT(sl_w4_max_rows() == 26, "the MXFP4 skinny range");
+    int32_t kmul = 0, rows = -1, layout = 0;
+    EXPECT(sl_weight_format_info(SL_WDEC_MXFP4, &kmul, &rows, &layout) == 0 && kmul == 128 && rows == sl_w4_max_rows() && layout == SL_W_PACKED_MXFP4, "MXFP4 format row");
+    EXPECT(sl_weight_format_info(SL_WDEC_E4M3, &kmul, &rows, &layout) == 0 && kmul == 64 && rows == sl_w8_max_rows() && layout == SL_W_PACKED_E4M3, "e4m3 format row");
+    EXPECT(sl_weight_format_info(SL_WDEC_MX_LINEAR, &kmul, &rows, nullptr) == 0 && kmul == 128 && rows == 0, "MX linears format row");
+    EXPECT(sl_weight_format_info(SL_WDEC_MODEL_DTYPE, &kmul, &rows, &layout) == 0 && kmul == 1 && rows == 0 && layout == SL_W_PACKED, "model dtype format row");
+    EXPECT_ARG_ERROR(sl_weight_format_info(3, &kmul, &rows, &layout));
     sl_gemm_args wa;
     memset(&wa, 0, sizeof(wa));
     wa.A = img; wa.W = img; wa.C = img; wa.lda = wa.ldw = 256; wa.ldc = 256; wa.M = 27; wa.N = 256; wa.K = 256; wa.batch = 1; wa.dtype = SL_BF16; wa.w_layout = SL_W_PACKED_MXFP4;

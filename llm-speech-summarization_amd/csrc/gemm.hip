@@ -11,6 +11,7 @@
 
 #include "common.h"
 #include "gemm_internal.h"
+#include "wformat.h"
 
 #include "gemm_epilogue.h"
 
@@ -355,7 +356,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tiled_glds_kernel(GemmP p) {
 //   pairs = the two rotate_half halves of a head; q is written rotated, k/v go straight into the cache).
 //   fuse_rms: the RMSNorm gain is pre-folded into W and the per-row rsqrt(mean(x^2)+eps) is computed
 //   from the x fragments the block loads anyway, then applied to the accumulators.
-//   W8 (PACKED, 16-bit T, MT 1 / 2): W is an e4m3 weight image (speechllm.h sl_pack_weight_e4m3).  The fragment-major layout is the
+//   W8 = the form WQ == 8 (PACKED, 16-bit T, MT 1 / 2): W is an e4m3 weight image (speechllm.h sl_pack_weight_e4m3).  The fragment-major layout is the
 //   same with PAIRS of k-steps as its unit: one 16-byte non-temporal load per lane and fragment carries the A fragments of two
 //   consecutive 32-wide k-steps (8 bytes each), two exact conversions (sl_dq8x8: 4 v_cvt_scalef32_pk_*_fp8 each) make them 16-bit,
 //   two MFMAs take them against the two x fragments of the 128-byte x step.  The accumulation is therefore the 16-bit kernel's on the
@@ -366,7 +367,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tiled_glds_kernel(GemmP p) {
 //   v_cvt_scalef32_pk_*: taken as a plain to transcendental VALU slot, 4-8 cycles, that is 50-80 cycles per KiB per wave against the
 //   ~320 cycles per SIMD one KiB of HBM traffic is worth at 8 TB/s over 256 CUs): the loop stays load-bound, so the loads-in-flight
 //   structure (U steps, all loads issued before the first conversion) is carried over from the 16-bit kernel as it is.
-//   W4 (PACKED, 16-bit T, MT 1 / 2): W is an MXFP4 weight image (speechllm.h sl_pack_weight_mxfp4).  The unit is a QUAD of k-steps: one 16-byte
+//   W4 = the form WQ == 4 (PACKED, 16-bit T, MT 1 / 2): W is an MXFP4 weight image (speechllm.h sl_pack_weight_mxfp4).  The unit is a QUAD of k-steps: one 16-byte
 //   non-temporal load per lane and fragment carries the e2m1 nibbles of four consecutive 32-wide k-steps (one dword each), one dword load carries
 //   the lane's four e8m0 block scales, 16 v_cvt_scalef32_pk_*_fp4 (sl_dq4x8 per dword, the scale operand bit_cast<float>(byte << 23)) make the
 //   four A fragments, four MFMAs take them against the four x fragments of the 256-byte x step.  The MFMA operands are exactly e2m1 * 2^e, so
@@ -381,10 +382,9 @@ __global__ __launch_bounds__(256, 2) void gemm_tiled_glds_kernel(GemmP p) {
 //   stage needs a barrier per chunk in a loop that has none.  A smaller U alone would cut the bytes in flight instead.  Unmeasured either way.
 // ----------------------------------------------------------------------------------------------
 
-template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false, bool W8 = false, bool W4 = false>
+template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false, int WQ = 0>      // WQ: 0 = W holds T, 8 = an e4m3 weight image, 4 = an MXFP4 weight image
 __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX sx) {
-  static_assert(!W8 || (PACKED && !KCONT && sizeof(T) == 2 && MT <= 2), "e4m3 weight images: packed layout, bf16 / fp16, up to 32 rows");
-  static_assert(!W4 || (PACKED && !KCONT && !W8 && sizeof(T) == 2 && MT <= 2), "MXFP4 weight images: packed layout, bf16 / fp16, up to 32 rows");
+  static_assert(WQ == 0 || ((WQ == 8 || WQ == 4) && PACKED && !KCONT && sizeof(T) == 2 && MT <= 2), "e4m3 / MXFP4 weight images: packed layout, bf16 / fp16, up to 32 rows");
   constexpr int VEC = Vec16<T>::VEC;
   constexpr int KSTEP = MMA<T>::KSTEP;
   constexpr int RB = 16 * RF;
@@ -392,14 +392,14 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
   static_assert(!PAIRS || RF % 2 == 0, "pair epilogues need an even number of fragments");
   __shared__ float red[NW][RB][MT * 16 + 1];
   __shared__ float red_ss[NW][4][MT * 16];
-  __shared__ float wsc[W8 ? RB : 1];   // W8: the scales of the block's weight rows
+  __shared__ float wsc[WQ == 8 ? RB : 1];   // W8: the scales of the block's weight rows
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, q = lane >> 4;
   const int z = blockIdx.y;
   const int n0 = blockIdx.x * RB;
   // full 64-byte steps of W (W8: 64 bytes = a pair of k-steps, 128 bytes of x; W4: a quad of k-steps, 256 bytes of x)
-  const int nks_full = W4 ? p.K / (4 * KSTEP) : W8 ? p.K / (2 * KSTEP) : p.K / KSTEP;
+  const int nks_full = WQ == 4 ? p.K / (4 * KSTEP) : WQ == 8 ? p.K / (2 * KSTEP) : p.K / KSTEP;
 
   const T* A = (const T*)p.A + (int64_t)z * p.sA;
   const T* W = (const T*)p.W + (int64_t)z * p.sW;
@@ -438,15 +438,15 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
     for (int f = 0; f < RF; ++f) acc[f][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const bool fuse = sx.fuse_rms != 0;
-  if constexpr (W8) {
+  if constexpr (WQ == 8) {
     // rows past N inside the last fragment are padding rows of the image (scale 1); fragments past the last one repeat it, as wp does
     const int np = ((p.N + 15) >> 4) << 4;
     const float* scales = (const float*)((const unsigned char*)p.W + (int64_t)np * p.K);
     if (tid < RB) wsc[tid] = scales[n0 + tid < np ? n0 + tid : np - 16 + (tid & 15)];
   }
 
-  [[maybe_unused]] const uint32_t* scp[W4 ? RF : 1];      // W4: the lane's scale dword of fragment f, quad step 0 (16 dwords per step)
-  if constexpr (W4) {
+  [[maybe_unused]] const uint32_t* scp[WQ == 4 ? RF : 1];      // W4: the lane's scale dword of fragment f, quad step 0 (16 dwords per step)
+  if constexpr (WQ == 4) {
     const int nfrag = (p.N + 15) >> 4;
     const uint32_t* sc = (const uint32_t*)((const unsigned char*)p.W + (int64_t)nfrag * 8 * p.K);      // behind the elements: Np * K / 2 bytes
 #pragma unroll
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
     ks = wave;
     kend = nks_full;
   }
-  if constexpr (W4) {
+  if constexpr (WQ == 4) {
     constexpr int XSTEP = 4 * KSTEP;      // x elements per quad step
     auto quad = [&](const uint4& w4, uint32_t sc4, const uint4 (&x)[4][MT], int f) {
       const uint32_t wd[4] = {w4.x, w4.y, w4.z, w4.w};
@@ -519,7 +519,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
       for (int f = 0; f < RF; ++f) { fw[f] = ld_nt16(wp[f] + (int64_t)ks * wstep); fs[f] = scp[f][(int64_t)ks * 16]; }
       step(fw, fs, ks);
     }
-  } else if constexpr (W8) {
+  } else if constexpr (WQ == 8) {
     constexpr int XSTEP = 2 * KSTEP;      // x elements per pair step
     auto pair = [&](const uint4& w8, const uint4 (&x0)[MT], const uint4 (&x1)[MT], int f) {
       const uint4 a0 = as_uint4(sl_dq8x8<T>(u32x2_t{w8.x, w8.y})), a1 = as_uint4(sl_dq8x8<T>(u32x2_t{w8.z, w8.w}));
@@ -643,7 +643,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
   const void* Rb = p.res ? (const void*)((const T*)p.res + (int64_t)z * p.sR) : nullptr;
   auto row_scale = [&](int m) -> float {
     if (!fuse) return 1.0f;
-    if constexpr (W8 || W4) {
+    if constexpr (WQ != 0) {
       if (sx.rstd_in) return sx.rstd_in[m];
     }
     float s = 0.f;
@@ -655,7 +655,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(GemmP p, SkinnyX s
     float v = 0.f;
 #pragma unroll
     for (int w = 0; w < NW; ++w) v += red[w][n][m];
-    if constexpr (W8) v *= wsc[n];      // the weight row's scale: on the reduced fp32 sum, before bias / row factor / pair epilogue
+    if constexpr (WQ == 8) v *= wsc[n];      // the weight row's scale: on the reduced fp32 sum, before bias / row factor / pair epilogue
     return v;
   };
 
@@ -1091,10 +1091,10 @@ static int run_tiled(const GemmP& p0, const TiledPlan& pl, void* sk_ws, const Sl
   return 0;
 }
 
-template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false, bool W8 = false, bool W4 = false>
+template <typename T, int MT, int ACT, int RF, int NW, int U, bool PACKED, bool KCONT = false, int WQ = 0>
 static int launch_skinny_cfg(GemmP& p, const SkinnyX& sx, int batch, hipStream_t st) {
   dim3 grid((p.N + 16 * RF - 1) / (16 * RF), batch);
-  hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, ACT, RF, NW, U, PACKED, KCONT, W8, W4>), grid, dim3(NW * 64), 0, st, p, sx);
+  hipLaunchKernelGGL((gemm_skinny_kernel<T, MT, ACT, RF, NW, U, PACKED, KCONT, WQ>), grid, dim3(NW * 64), 0, st, p, sx);
   SL_CHECK_LAUNCH("gemm_skinny");
   return 0;
 }
@@ -1137,77 +1137,46 @@ static int launch_skinny_mt(GemmP& p, const SkinnyX& sx, int batch, const SlEnv&
   return 0;
 }
 
-// e4m3 weight images (W8): the (fragments, waves) structures of the 16-bit table above, re-derived for PAIR steps — a load is still 16 bytes per
-// lane, but K / 64 of them cover a row where the 16-bit kernel has K / 32, so every trip count halves (K = 3 072: 48 pair steps; 8 192: 128).
+// Quantised weight images (WQ 8: e4m3, WQ 4: MXFP4): the (fragments, waves) structures of the 16-bit table above, re-derived for the image's STEP — a
+// load is still 16 bytes per lane, but it covers a PAIR of k-steps (64 elements) of an e4m3 row and a QUAD (128) of an MXFP4 row, so K / 64 or K / 128
+// of them cover a row where the 16-bit kernel has K / 32: every trip count halves, and halves again (K = 3 072: 48 pair steps, 24 quad steps; 8 192: 128, 64).
 //   * fragments x waves are CARRIED OVER UNMEASURED: they set the block count and the bytes in flight per CU, which do not depend on what a byte
-//     means.  Whether fewer waves would now do (o at M <= 8: 3 pair steps per wave of 16) has not been measured.
-//   * the unroll U is chosen so that a wave's share of the pair steps, pw = K / 64 / NW, splits evenly — the rule the 16-bit o / down structures
-//     follow (gemm.hip above: 6 = 2 x 3, 16 = 4 x 4): 4 where pw % 4 == 0, else 3 where pw % 3 == 0, else 4 with the remainder in the tail loop
-//     (2 in place of 4 for the one structure of 1 024 threads per block that holds two fragments and two x tiles).
-//     K = 3 072: gate/up, lm_head 4 x 4 waves, pw 12 -> U 4; qkv 2 x 8, pw 6 -> U 3; o 1 x 16, pw 3 -> U 3; down (8 192) 1 x 16, pw 8 -> U 4.
-//     Also unmeasured.
-// Any (NW, U) is correct for any K / 64 >= 1: the unrolled loop takes a wave's steps ks, ks + NW, ... only while U of them remain, the tail loop
-// takes the rest one at a time — with fewer pair steps than waves (K = 192 under 16 waves) the unrolled loop runs for no wave and the tail loop
-// gives the first K / 64 waves one step each (tests/test_w8_gpu.py runs K = 64, 192, 1 088, 3 072, 4 480, 8 192).
-template <typename T, int MT, int ACT, int RF, int NW, int UA = 4>
-static int launch_skinny_w8_u(GemmP& p, const SkinnyX& sx, hipStream_t st) {
-  const int pw = p.K / 64 / NW;
-  if (pw % UA != 0 && pw % 3 == 0) return launch_skinny_cfg<T, MT, ACT, RF, NW, 3, true, false, true>(p, sx, 1, st);
-  return launch_skinny_cfg<T, MT, ACT, RF, NW, UA, true, false, true>(p, sx, 1, st);
+//     means.  Whether fewer waves would now do (e4m3 o at M <= 8: 3 pair steps per wave of 16) has not been measured.
+//   * the unroll U is chosen so that a wave's share of the steps, pw = K / step / NW, splits evenly — the rule the 16-bit o / down structures
+//     follow (gemm.hip above: 6 = 2 x 3, 16 = 4 x 4): UA where pw % UA == 0, else 3 where pw % 3 == 0, else UA with the remainder in the tail loop
+//     (UA is 4; 2 for the one structure of 1 024 threads per block that holds two fragments and two x tiles).  Also unmeasured.
+//     e4m3,  K = 3 072: gate/up, lm_head 4 x 4 waves, pw 12 -> U 4; qkv 2 x 8, pw 6 -> U 3; o 1 x 16, pw 3 -> U 3; down (8 192) 1 x 16, pw 8 -> U 4.
+//     MXFP4, K = 3 072: gate/up, lm_head 4 x 4 waves, pw 6 -> U 3; qkv 2 x 8, pw 3 -> U 3; o 1 x 16, 24 steps under 16 waves, pw 1 -> the tail loop
+//     alone, one or two single steps per wave; down (8 192) 1 x 16, pw 4 -> U 4.
+//   Nothing in the MXFP4 column was tuned: structures and unrolls were written down unmeasured, by carrying the rule over, and tools/bench_w4.py then
+//   timed them as they stand (profiles/w4_vs_16bit.txt).  No alternative structure has been measured against them.
+// Any (NW, U) is correct for any K / step >= 1: the unrolled loop takes a wave's steps ks, ks + NW, ... only while U of them remain, the tail loop
+// takes the rest one at a time — with fewer steps than waves (e4m3 K = 192, MXFP4 K = 384 under 16 waves) the unrolled loop runs for no wave and the
+// tail loop gives the first K / step waves one step each (tests/test_w8_gpu.py runs K = 64, 192, 1 088, 3 072, 4 480, 8 192; tests/test_w4_gpu.py
+// K = 128, 384, 2 176, 3 072, 8 192, 8 960).
+template <typename T, int WQ, int MT, int ACT, int RF, int NW, int UA = 4>
+static int launch_skinny_wq_u(GemmP& p, const SkinnyX& sx, hipStream_t st) {
+  const int pw = p.K / (WQ == 8 ? 64 : 128) / NW;
+  if (pw % UA != 0 && pw % 3 == 0) return launch_skinny_cfg<T, MT, ACT, RF, NW, 3, true, false, WQ>(p, sx, 1, st);
+  return launch_skinny_cfg<T, MT, ACT, RF, NW, UA, true, false, WQ>(p, sx, 1, st);
 }
-template <typename T, int MT, int ACT>
-static int launch_skinny_w8_mt(GemmP& p, const SkinnyX& sx, hipStream_t st) {
+template <typename T, int WQ, int MT, int ACT>
+static int launch_skinny_wq_mt(GemmP& p, const SkinnyX& sx, hipStream_t st) {
   constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || ACT == SL_ACT_ROPE_KV);
   const int nfrag = (p.N + 15) / 16;
-  if (nfrag >= 1024) return launch_skinny_w8_u<T, MT, ACT, MT == 1 ? 4 : 2, MT == 1 ? 4 : 8>(p, sx, st);
+  if (nfrag >= 1024) return launch_skinny_wq_u<T, WQ, MT, ACT, MT == 1 ? 4 : 2, MT == 1 ? 4 : 8>(p, sx, st);
   // 17..32 rows, 2 fragments x 16 waves: 1 024 threads leave 128 registers, which 4 steps of loads in flight do not fit (the compiler spills): 2, or 3
-  if (nfrag >= 256 || PAIRS) return launch_skinny_w8_u<T, MT, ACT, 2, MT == 1 ? 8 : 16, MT == 1 ? 4 : 2>(p, sx, st);
-  if constexpr (!PAIRS) return launch_skinny_w8_u<T, MT, ACT, 1, 16>(p, sx, st);
+  if (nfrag >= 256 || PAIRS) return launch_skinny_wq_u<T, WQ, MT, ACT, 2, MT == 1 ? 8 : 16, MT == 1 ? 4 : 2>(p, sx, st);
+  if constexpr (!PAIRS) return launch_skinny_wq_u<T, WQ, MT, ACT, 1, 16>(p, sx, st);
   return 0;
 }
-template <typename T>
-static int launch_skinny_w8(GemmP& p, const SkinnyX& sx, int act, hipStream_t st) {
+template <typename T, int WQ>
+static int launch_skinny_wq(GemmP& p, const SkinnyX& sx, int act, hipStream_t st) {
   const bool mt1 = sl_family_rows(p.M) <= 16;
   switch (act) {
-    case SL_ACT_NONE: return mt1 ? launch_skinny_w8_mt<T, 1, SL_ACT_NONE>(p, sx, st) : launch_skinny_w8_mt<T, 2, SL_ACT_NONE>(p, sx, st);
-    case SL_ACT_SILU_MUL: return mt1 ? launch_skinny_w8_mt<T, 1, SL_ACT_SILU_MUL>(p, sx, st) : launch_skinny_w8_mt<T, 2, SL_ACT_SILU_MUL>(p, sx, st);
-    default: return mt1 ? launch_skinny_w8_mt<T, 1, SL_ACT_ROPE_KV>(p, sx, st) : launch_skinny_w8_mt<T, 2, SL_ACT_ROPE_KV>(p, sx, st);
-  }
-}
-
-// MXFP4 weight images (W4): the (fragments, waves) structures of the e4m3 table above, with QUAD steps as the unit — a load is still 16 bytes per
-// lane, K / 128 of them cover a row, so every trip count halves again (K = 3 072: 24 quad steps; 8 192: 64).
-//   * fragments x waves are CARRIED OVER UNMEASURED, for the reason given there.
-//   * the unroll U follows the same rule on the quad steps of a wave, pw = K / 128 / NW: UA (4; 2 for the 1 024-thread structure with two
-//     fragments and two x tiles) where pw % UA == 0, else 3 where pw % 3 == 0, else UA with the remainder in the tail loop.
-//     K = 3 072: gate/up, lm_head 4 x 4 waves, pw 6 -> U 3; qkv 2 x 8, pw 3 -> U 3; o 1 x 16, 24 steps under 16 waves, pw 1 -> the tail loop alone,
-//     one or two single steps per wave; down (8 192) 1 x 16, pw 4 -> U 4.
-//   Nothing here was tuned: structures and unrolls were written down unmeasured, by carrying the rule over, and tools/bench_w4.py then timed them
-//   as they stand (profiles/w4_vs_16bit.txt).  No alternative structure has been measured against them.
-// Any (NW, U) is correct for any K / 128 >= 1, as above: with fewer quad steps than waves the tail loop gives the first K / 128 waves one step
-// each (tests/test_w4_gpu.py runs K = 128, 384, 2 176, 3 072, 8 192, 8 960).
-template <typename T, int MT, int ACT, int RF, int NW, int UA = 4>
-static int launch_skinny_w4_u(GemmP& p, const SkinnyX& sx, hipStream_t st) {
-  const int pw = p.K / 128 / NW;
-  if (pw % UA != 0 && pw % 3 == 0) return launch_skinny_cfg<T, MT, ACT, RF, NW, 3, true, false, false, true>(p, sx, 1, st);
-  return launch_skinny_cfg<T, MT, ACT, RF, NW, UA, true, false, false, true>(p, sx, 1, st);
-}
-template <typename T, int MT, int ACT>
-static int launch_skinny_w4_mt(GemmP& p, const SkinnyX& sx, hipStream_t st) {
-  constexpr bool PAIRS = (ACT == SL_ACT_SILU_MUL || ACT == SL_ACT_ROPE_KV);
-  const int nfrag = (p.N + 15) / 16;
-  if (nfrag >= 1024) return launch_skinny_w4_u<T, MT, ACT, MT == 1 ? 4 : 2, MT == 1 ? 4 : 8>(p, sx, st);
-  if (nfrag >= 256 || PAIRS) return launch_skinny_w4_u<T, MT, ACT, 2, MT == 1 ? 8 : 16, MT == 1 ? 4 : 2>(p, sx, st);
-  if constexpr (!PAIRS) return launch_skinny_w4_u<T, MT, ACT, 1, 16>(p, sx, st);
-  return 0;
-}
-template <typename T>
-static int launch_skinny_w4(GemmP& p, const SkinnyX& sx, int act, hipStream_t st) {
-  const bool mt1 = sl_family_rows(p.M) <= 16;
-  switch (act) {
-    case SL_ACT_NONE: return mt1 ? launch_skinny_w4_mt<T, 1, SL_ACT_NONE>(p, sx, st) : launch_skinny_w4_mt<T, 2, SL_ACT_NONE>(p, sx, st);
-    case SL_ACT_SILU_MUL: return mt1 ? launch_skinny_w4_mt<T, 1, SL_ACT_SILU_MUL>(p, sx, st) : launch_skinny_w4_mt<T, 2, SL_ACT_SILU_MUL>(p, sx, st);
-    default: return mt1 ? launch_skinny_w4_mt<T, 1, SL_ACT_ROPE_KV>(p, sx, st) : launch_skinny_w4_mt<T, 2, SL_ACT_ROPE_KV>(p, sx, st);
+    case SL_ACT_NONE: return mt1 ? launch_skinny_wq_mt<T, WQ, 1, SL_ACT_NONE>(p, sx, st) : launch_skinny_wq_mt<T, WQ, 2, SL_ACT_NONE>(p, sx, st);
+    case SL_ACT_SILU_MUL: return mt1 ? launch_skinny_wq_mt<T, WQ, 1, SL_ACT_SILU_MUL>(p, sx, st) : launch_skinny_wq_mt<T, WQ, 2, SL_ACT_SILU_MUL>(p, sx, st);
+    default: return mt1 ? launch_skinny_wq_mt<T, WQ, 1, SL_ACT_ROPE_KV>(p, sx, st) : launch_skinny_wq_mt<T, WQ, 2, SL_ACT_ROPE_KV>(p, sx, st);
   }
 }
 
@@ -1274,29 +1243,17 @@ static int gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_ge
   SL_CHECK_ARG(both_t || a->K % vec == 0, "sl_gemm: K=%d must be a multiple of %d", a->K, vec);
   SL_CHECK_ARG(a->lda % vec == 0 && a->strideA % vec == 0, "sl_gemm: lda/strideA must keep rows 16-byte aligned");
   SL_CHECK_ARG(((uintptr_t)a->A & 15) == 0 && ((uintptr_t)a->W & 15) == 0, "sl_gemm: A and W must be 16-byte aligned");
-  const bool w8 = a->w_layout == SL_W_PACKED_E4M3, w4 = a->w_layout == SL_W_PACKED_MXFP4;
-  if (w8) {
-    // an e4m3 weight image: the skinny kernels' W8 form only — refused before any device work where that form is not built
+  const SlWFormat* wq = sl_wformat_of_layout(a->w_layout);
+  if (wq) {
+    // an e4m3 / MXFP4 weight image: the skinny kernels' W8 / W4 form only — refused before any device work where that form is not built
     if (a->dtype == SL_F32) {
-      sl_set_error("sl_gemm: e4m3 weight images (w_layout %d) are built for bf16 / fp16, not float32 (the parity mode)", a->w_layout);
+      sl_set_error("sl_gemm: %s weight images (w_layout %d) are built for bf16 / fp16, not float32 (the parity mode)", wq->name, a->w_layout);
       return SL_ERR_UNSUPPORTED;
     }
-    SL_CHECK_ARG(a->K % 64 == 0, "sl_gemm: e4m3 weight images need K %% 64 == 0 (K=%d)", a->K);
-    SL_CHECK_ARG(a->batch == 1 && !ex && a->act != SL_ACT_GELU, "sl_gemm: e4m3 weight images take one plain product (batch 1, no sl_gemm_ex features, no GELU)");
-    if (sl_family_rows(a->M) > sl_w8_max_rows()) {
-      sl_set_error("sl_gemm: e4m3 weight images are built for the skinny kernels, up to sl_w8_max_rows() = %d rows (M=%d)", sl_w8_max_rows(), sl_family_rows(a->M));
-      return SL_ERR_UNSUPPORTED;
-    }
-  } else if (w4) {
-    // an MXFP4 weight image: the skinny kernels' W4 form only — refused before any device work where that form is not built
-    if (a->dtype == SL_F32) {
-      sl_set_error("sl_gemm: MXFP4 weight images (w_layout %d) are built for bf16 / fp16, not float32 (the parity mode)", a->w_layout);
-      return SL_ERR_UNSUPPORTED;
-    }
-    SL_CHECK_ARG(a->K % 128 == 0, "sl_gemm: MXFP4 weight images need K %% 128 == 0 (K=%d)", a->K);
-    SL_CHECK_ARG(a->batch == 1 && !ex && a->act != SL_ACT_GELU, "sl_gemm: MXFP4 weight images take one plain product (batch 1, no sl_gemm_ex features, no GELU)");
-    if (sl_family_rows(a->M) > sl_w4_max_rows()) {
-      sl_set_error("sl_gemm: MXFP4 weight images are built for the skinny kernels, up to sl_w4_max_rows() = %d rows (M=%d)", sl_w4_max_rows(), sl_family_rows(a->M));
+    SL_CHECK_ARG(a->K % wq->k_multiple == 0, "sl_gemm: %s weight images need K %% %d == 0 (K=%d)", wq->name, wq->k_multiple, a->K);
+    SL_CHECK_ARG(a->batch == 1 && !ex && a->act != SL_ACT_GELU, "sl_gemm: %s weight images take one plain product (batch 1, no sl_gemm_ex features, no GELU)", wq->name);
+    if (sl_family_rows(a->M) > wq->max_rows()) {
+      sl_set_error("sl_gemm: %s weight images are built for the skinny kernels, up to %s() = %d rows (M=%d)", wq->name, wq->max_rows_name, wq->max_rows(), sl_family_rows(a->M));
       return SL_ERR_UNSUPPORTED;
     }
   } else if (a->w_layout == SL_W_PACKED) {
@@ -1395,25 +1352,20 @@ static int gemm_impl(const sl_gemm_args* a, const sl_gemm_fused* fx, const sl_ge
     SL_CHECK_ARG(fx && fx->rope_cos && fx->rope_sin && fx->tok_pos && fx->tok_seq && fx->k_cache && fx->v_cache,
                  "sl_gemm: ROPE_KV epilogue needs the sl_gemm_fused tables");
     SL_CHECK_ARG(a->N == (fx->n_heads + 2 * fx->n_kv_heads) * 128 && a->batch == 1, "sl_gemm: ROPE_KV expects N = (n_heads + 2 n_kv) * 128");
-    SL_TRY(sl_kv_format_check("sl_gemm (ROPE_KV)", fx->reserved, a->dtype, 128));     // sl_gemm_fused.reserved: the caches' K/V format
-    sx.kv8 = fx->reserved == SL_KV_FP8_E4M3;
+    SL_TRY(sl_kv_format_check("sl_gemm (ROPE_KV)", sl_kv_format(fx), a->dtype, 128));
+    sx.kv8 = sl_kv_format(fx) == SL_KV_FP8_E4M3;
   }
   // packed weights with more than SL_STREAM_MIN_M rows: LDS-staged streaming kernel (gemm_stream.hip)
   if (a->w_layout == SL_W_PACKED && sl_family_rows(a->M) > e.stream_min_m && a->batch == 1 && !ex && a->act != SL_ACT_GELU &&
       a->K % slab_elems(a->dtype) == 0)
     return e.gemm_log == 2 ? 0 : sl_gemm_stream_launch(p, sx, a->dtype, a->act, fx ? fx->split_ws : nullptr, fx ? fx->split_ws_bytes : 0, st);
   SL_CHECK_ARG(a->w_layout != SL_W_PACKED || sl_family_rows(a->M) <= 64, "sl_gemm: packed weights with M=%d > 64 need batch 1 and K %% 64 == 0", a->M);
-  if (w8) {
+  if (wq) {
     SL_CHECK_ARG(a->act >= SL_ACT_NONE && a->act <= SL_ACT_ROPE_KV, "sl_gemm: unknown act %d", a->act);
-    SL_CHECK_ARG(!sx.rstd_out && !sx.norm_out && (!sx.rstd_in || sx.fuse_rms), "sl_gemm: e4m3 weight images take rstd_in (with fuse_rms) but not rstd_out / norm_out");
+    SL_CHECK_ARG(!sx.rstd_out && !sx.norm_out && (!sx.rstd_in || sx.fuse_rms), "sl_gemm: %s weight images take rstd_in (with fuse_rms) but not rstd_out / norm_out", wq->name);
     if (e.gemm_log == 2) return 0;
-    return a->dtype == SL_F16 ? launch_skinny_w8<f16_t>(p, sx, a->act, st) : launch_skinny_w8<bf16_t>(p, sx, a->act, st);
-  }
-  if (w4) {
-    SL_CHECK_ARG(a->act >= SL_ACT_NONE && a->act <= SL_ACT_ROPE_KV, "sl_gemm: unknown act %d", a->act);
-    SL_CHECK_ARG(!sx.rstd_out && !sx.norm_out && (!sx.rstd_in || sx.fuse_rms), "sl_gemm: MXFP4 weight images take rstd_in (with fuse_rms) but not rstd_out / norm_out");
-    if (e.gemm_log == 2) return 0;
-    return a->dtype == SL_F16 ? launch_skinny_w4<f16_t>(p, sx, a->act, st) : launch_skinny_w4<bf16_t>(p, sx, a->act, st);
+    if (wq->code == SL_WDEC_E4M3) return a->dtype == SL_F16 ? launch_skinny_wq<f16_t, 8>(p, sx, a->act, st) : launch_skinny_wq<bf16_t, 8>(p, sx, a->act, st);
+    return a->dtype == SL_F16 ? launch_skinny_wq<f16_t, 4>(p, sx, a->act, st) : launch_skinny_wq<bf16_t, 4>(p, sx, a->act, st);
   }
   SL_CHECK_ARG(!sx.rstd_in && !sx.rstd_out && !sx.norm_out, "sl_gemm: rstd_in / rstd_out / norm_out are features of the streaming path (M > %d rows, packed weights)", e.stream_min_m);
   void* sk_ws = ex ? ex->sk_ws : nullptr;

@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "common.h"
+#include "wformat.h"
 
 // ----------------------------------------------------------------------------------------------
 template <typename T>
@@ -823,6 +824,16 @@ extern "C" size_t sl_w4_image_bytes(int32_t N, int32_t K) {
 }
 
 extern "C" int32_t sl_w4_max_rows(void) { return sl_w8_max_rows(); }      // the same skinny structures (MT 1 and 2)
+
+// the rules of a weight format (wformat.h), for callers that would otherwise restate them
+extern "C" int sl_weight_format_info(int32_t code, int32_t* k_multiple, int32_t* max_rows, int32_t* w_layout) {
+  const SlWFormat* f = sl_wformat(code);
+  SL_CHECK_ARG(f, "sl_weight_format_info: unknown weight format %d (" SL_WFORMAT_LIST ")", code);
+  if (k_multiple) *k_multiple = f->k_multiple;
+  if (max_rows) *max_rows = f->max_rows ? f->max_rows() : 0;
+  if (w_layout) *w_layout = f->w_layout;
+  return 0;
+}
 
 extern "C" int sl_pack_weight_mxfp4_host(const void* src, int64_t ld_src, void* dst, int32_t N, int32_t K, int32_t dtype) {
   SL_TRY(w4_pack_check("sl_pack_weight_mxfp4_host", src, ld_src, dst, N, K, dtype));

@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "gemm_internal.h"
+#include "wformat.h"
 
 int sl_attn_decode_impl(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, void* out, const int32_t* ctx_len,
                         int ctx_add, int32_t B, int32_t n_heads, int32_t n_kv, int32_t D, int32_t max_ctx, float scale, int32_t dtype,
@@ -573,7 +574,7 @@ static size_t llama_carve(const sl_llama_model* m, int64_t n_tok, int nseq, void
   w.cuk = (int32_t*)c.take((nseq + 1) * sizeof(int32_t));
   w.klen = (int32_t*)c.take((nseq + 1) * sizeof(int32_t));
   w.last_row = (int32_t*)c.take((size_t)nseq * sizeof(int32_t));
-  if (m->reserved == SL_WDEC_MX_LINEAR) {      // behind everything else: the other formats keep their layout and their byte count
+  if (sl_wformat_code(m) == SL_WDEC_MX_LINEAR) {      // behind everything else: the other formats keep their layout and their byte count
     int kmax = m->hidden;
     if (m->n_heads * m->head_dim > kmax) kmax = m->n_heads * m->head_dim;
     if (m->ffn > kmax) kmax = m->ffn;
@@ -590,7 +591,7 @@ extern "C" size_t sl_llama_workspace_bytes(const sl_llama_model* m, int64_t n_to
 
 static int llama_check(const sl_llama_model* m, const sl_kv_cache* kv) {
   SL_CHECK_ARG(m && kv && m->layers && m->embed && m->lm_head && m->final_norm && m->rope_cos && m->rope_sin, "llama: null model field");
-  if (kv->reserved != SL_KV_MODEL_DTYPE) SL_TRY(sl_kv_format_check("llama (sl_kv_cache.reserved)", kv->reserved, m->dtype, m->head_dim));
+  if (sl_kv_format(kv) != SL_KV_MODEL_DTYPE) SL_TRY(sl_kv_format_check("llama (sl_kv_cache.reserved)", sl_kv_format(kv), m->dtype, m->head_dim));
   SL_CHECK_ARG(m->head_dim == 128, "llama: head_dim %d not built (128)", m->head_dim);
   SL_CHECK_ARG(kv->k_cache && kv->v_cache && kv->slots > 0 && kv->max_ctx > 0, "llama: bad kv cache");
   SL_CHECK_ARG(kv->shared_prefix >= 0 && kv->shared_prefix <= kv->max_ctx, "llama: kv cache shared_prefix %d outside [0, max_ctx=%d]", kv->shared_prefix, kv->max_ctx);
@@ -602,40 +603,11 @@ static int llama_check(const sl_llama_model* m, const sl_kv_cache* kv) {
 int sl_gemm_mx_impl(const sl_gemm_mx_args* a, hipStream_t st);
 int sl_mxfp8_quantize_rows_impl(const void* x, int64_t ldx, void* q, void* scales, int64_t M, int32_t K, int32_t dtype, hipStream_t st);
 
-// sl_llama_model.reserved = SL_WDEC_MX_LINEAR (format 5): the layers' row-major pointers are MX weight images and every layer product runs MXFP8 x MXFP4, at
-// every row count.  Checked by every entry that runs such a model, before any launch.
-static int llama_mx_check(const char* who, const sl_llama_model* m) {
-  if (m->dtype == SL_F32) {
-    sl_set_error("%s: MX linears (format 5) are built for bf16 / fp16 models, not float32 (the parity mode)", who);
-    return SL_ERR_UNSUPPORTED;
-  }
-  SL_CHECK_ARG(sl_is16(m->dtype), "%s: unknown dtype %d", who, m->dtype);
-  for (int l = 0; l < m->n_layers; ++l) {
-    const sl_llama_layer& L = m->layers[l];
-    SL_CHECK_ARG(L.wqkv && L.wo && L.wgu && L.wdown, "%s: MX linears (format 5): layer %d has a null weight image", who, l);
-    SL_CHECK_ARG(!L.wqkv_dec && !L.wo_dec && !L.wgu_dec && !L.wdown_dec, "%s: MX linears (format 5): layer %d has a non-null *_dec pointer (the four must be NULL)", who, l);
-  }
-  const int ks[3] = {m->hidden, m->n_heads * m->head_dim, m->ffn};
-  for (int k : ks)
-    if (k % 128 != 0) {
-      sl_set_error("%s: MX linears (format 5) need every reduction length to be a multiple of 128 (hidden=%d, n_heads*head_dim=%d, ffn=%d)", who, ks[0], ks[1], ks[2]);
-      return SL_ERR_UNSUPPORTED;
-    }
-  return 0;
-}
-// entries that do not run MX linears refuse the format before any launch
-static int llama_mx_refuse(const char* who, const sl_llama_model* m) {
-  if (m && m->reserved == SL_WDEC_MX_LINEAR) {
-    sl_set_error("%s: MX linears (sl_llama_model.reserved = 5, format 5) are not built for this entry: prefill, decode step and sl_generate* run them", who);
-    return SL_ERR_UNSUPPORTED;
-  }
-  return 0;
-}
 // one product of a decoder layer on the row-major weight set: C = act(A . W^T) + res.  Format 5: quantise the M input rows (one launch), then the MX product
 // on the weight image; every other format: the call it always was, launch for launch.
 static int layer_gemm(const sl_llama_model* m, const LlamaWs& w, const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* res,
                       int64_t ldr, int M, int N, int K, int act, hipStream_t st) {
-  if (m->reserved != SL_WDEC_MX_LINEAR) return gemm(m->dtype, A, lda, W, ldw, C, ldc, nullptr, res, ldr, M, N, K, act, 0, st);
+  if (sl_wformat_code(m) != SL_WDEC_MX_LINEAR) return gemm(m->dtype, A, lda, W, ldw, C, ldc, nullptr, res, ldr, M, N, K, act, 0, st);
   SL_TRY(sl_mxfp8_quantize_rows_impl(A, lda, w.mxq, w.mxs, M, K, m->dtype, st));
   sl_gemm_mx_args a;
   memset(&a, 0, sizeof(a));
@@ -644,42 +616,50 @@ static int layer_gemm(const sl_llama_model* m, const LlamaWs& w, const void* A, 
   return sl_gemm_mx_impl(&a, st);
 }
 
-// sl_llama_model.reserved, the format of the decode weights (speechllm.h SL_WDEC_*), against what a decode step of `rows` rows can run: checked by
-// every entry that decodes, before any launch.  An e4m3 model decodes on the skinny kernels' W8 form only, an MXFP4 model on their W4 form only.
-static int llama_wdec_check(const char* who, const sl_llama_model* m, int rows) {
-  if (m->reserved == SL_WDEC_MODEL_DTYPE) return 0;
-  if (m->reserved == SL_WDEC_MX_LINEAR) return llama_mx_check(who, m);
-  SL_CHECK_ARG(m->reserved == SL_WDEC_E4M3 || m->reserved == SL_WDEC_MXFP4,
-               "%s: unknown decode-weight format %d (sl_llama_model.reserved: 0 = model dtype, 1 = e4m3 weight images, 4 = MXFP4 weight images, 5 = MX linears)", who, m->reserved);
-  const bool w4 = m->reserved == SL_WDEC_MXFP4;
-  const char* name = w4 ? "MXFP4" : "e4m3";
-  if (m->dtype == SL_F32) {
-    sl_set_error("%s: %s decode weights are built for bf16 / fp16 models, not float32 (the parity mode)", who, name);
+// The model's weight format against what `entry` (SL_ENTRY_*) runs: checked by every entry of the runtime at the point it always was, before any launch.
+// rows: the rows of the entry's decode steps; 0 where it runs none (prefill, scoring) — those read the row-major weights, so the decode-image
+// formats, and a code that names no format, pass.  MX linears are checked at every row count: their images ARE the row-major weights.
+static int llama_wformat_check(const char* who, const sl_llama_model* m, int rows, unsigned entry) {
+  const SlWFormat* f = sl_wformat(sl_wformat_code(m));
+  if (f && !(f->runs & entry)) {
+    sl_set_error("%s: MX linears (sl_llama_model.reserved = 5, format 5) are not built for this entry: prefill, decode step and sl_generate* run them", who);
     return SL_ERR_UNSUPPORTED;
   }
-  SL_CHECK_ARG(m->dec_fused_norm == 1 && m->lm_head_dec, "%s: %s decode weights need dec_fused_norm = 1 and lm_head_dec", who, name);
+  if (rows <= 0 && (!f || f->dec_images)) return 0;
+  SL_CHECK_ARG(f, "%s: unknown decode-weight format %d (sl_llama_model.reserved: " SL_WFORMAT_LIST ")", who, sl_wformat_code(m));
+  if (f->code == SL_WDEC_MODEL_DTYPE) return 0;
+  const char* kind = f->dec_images ? " decode weights" : "";
+  if (m->dtype == SL_F32) {
+    sl_set_error("%s: %s%s are built for bf16 / fp16 models, not float32 (the parity mode)", who, f->name, kind);
+    return SL_ERR_UNSUPPORTED;
+  }
+  if (f->dec_images) SL_CHECK_ARG(m->dec_fused_norm == 1 && m->lm_head_dec, "%s: %s decode weights need dec_fused_norm = 1 and lm_head_dec", who, f->name);
+  else SL_CHECK_ARG(sl_is16(m->dtype), "%s: unknown dtype %d", who, m->dtype);
   for (int l = 0; l < m->n_layers; ++l) {
     const sl_llama_layer& L = m->layers[l];
-    SL_CHECK_ARG(L.wqkv_dec && L.wo_dec && L.wgu_dec && L.wdown_dec, "%s: %s decode weights: layer %d has a null *_dec image", who, name, l);
+    const bool dec = L.wqkv_dec && L.wo_dec && L.wgu_dec && L.wdown_dec, no_dec = !L.wqkv_dec && !L.wo_dec && !L.wgu_dec && !L.wdown_dec;
+    if (f->dec_images) SL_CHECK_ARG(dec, "%s: %s decode weights: layer %d has a null *_dec image", who, f->name, l);
+    else {
+      SL_CHECK_ARG(L.wqkv && L.wo && L.wgu && L.wdown, "%s: %s: layer %d has a null weight image", who, f->name, l);
+      SL_CHECK_ARG(no_dec, "%s: %s: layer %d has a non-null *_dec pointer (the four must be NULL)", who, f->name, l);
+    }
   }
   const int ks[3] = {m->hidden, m->n_heads * m->head_dim, m->ffn};
-  const int kmul = w4 ? 128 : 64;
   for (int k : ks)
-    if (k % kmul != 0) {
-      sl_set_error("%s: %s decode weights need every reduction length to be a multiple of %d (hidden=%d, n_heads*head_dim=%d, ffn=%d)", who, name, kmul, ks[0], ks[1], ks[2]);
+    if (k % f->k_multiple != 0) {
+      sl_set_error("%s: %s%s need every reduction length to be a multiple of %d (hidden=%d, n_heads*head_dim=%d, ffn=%d)", who, f->name, kind, f->k_multiple, ks[0], ks[1], ks[2]);
       return SL_ERR_UNSUPPORTED;
     }
-  const int max_rows = w4 ? sl_w4_max_rows() : sl_w8_max_rows();
-  if (sl_family_rows(rows) > max_rows) {
-    sl_set_error("%s: %s decode weights run up to %s() = %d rows per decode step, not %d (use the 16-bit decode copies)", who, name, w4 ? "sl_w4_max_rows" : "sl_w8_max_rows",
-                 max_rows, sl_family_rows(rows));
+  if (f->max_rows && sl_family_rows(rows) > f->max_rows()) {
+    sl_set_error("%s: %s decode weights run up to %s() = %d rows per decode step, not %d (use the 16-bit decode copies)", who, f->name, f->max_rows_name, f->max_rows(),
+                 sl_family_rows(rows));
     return SL_ERR_UNSUPPORTED;
   }
   return 0;
 }
 
 // K / V rows are head_dim elements of the cache's own element size: 1 byte in the e4m3 format, the model dtype's otherwise
-static inline size_t kv_elem_bytes(const sl_llama_model* m, const sl_kv_cache* kv) { return sl_kv_elem_size(kv->reserved, m->dtype); }
+static inline size_t kv_elem_bytes(const sl_llama_model* m, const sl_kv_cache* kv) { return sl_kv_elem_size(sl_kv_format(kv), m->dtype); }
 static inline size_t kv_layer_bytes(const sl_llama_model* m, const sl_kv_cache* kv) {
   return (size_t)kv->slots * m->n_kv_heads * kv->max_ctx * m->head_dim * kv_elem_bytes(m, kv);
 }
@@ -796,7 +776,8 @@ static int dec_gemm(const sl_llama_model* m, const LlamaWs& w, const void* A, in
   memset(&a, 0, sizeof(a));
   a.A = A; a.lda = lda; a.W = Wp; a.ldw = K; a.C = C; a.ldc = ldc; a.residual = res; a.ldr = ldc;
   a.M = M; a.N = N; a.K = K; a.batch = 1; a.dtype = m->dtype; a.act = act; a.out_f32 = out_f32;
-  a.w_layout = m->reserved == SL_WDEC_E4M3 ? SL_W_PACKED_E4M3 : m->reserved == SL_WDEC_MXFP4 ? SL_W_PACKED_MXFP4 : SL_W_PACKED;      // sl_llama_model.reserved: the format of the *_dec weights
+  const SlWFormat* f = sl_wformat(sl_wformat_code(m));
+  a.w_layout = f && f->w_layout >= 0 ? f->w_layout : SL_W_PACKED;      // a format without *_dec images of its own decodes lm_head on the 16-bit lm_head_dec
   return sl_gemm_impl(&a, fx, nullptr, st);
 }
 
@@ -828,8 +809,8 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
   auto decode_attn = [&](int64_t q_stride) -> int {
     if (da && da->groups)
       return sl_attn_decode_grouped_impl(w.qkv, q_stride, kc0, vc0, w.att, da->gws, ctx_len_dev, 1, da->prefix_len, da->groups, (int)n, da->row_slot0, nh, nkv,
-                                         D, kv->max_ctx, scale, dt, kv->reserved, st);
-    return sl_attn_decode_split_impl(w.qkv, q_stride, kc, vc, w.att, w.part, ctx_len_dev, 1, (int)n, nh, nkv, D, kv->max_ctx, scale, dt, st, 1, kv->shared_prefix, kv->reserved);
+                                         D, kv->max_ctx, scale, dt, sl_kv_format(kv), st);
+    return sl_attn_decode_split_impl(w.qkv, q_stride, kc, vc, w.att, w.part, ctx_len_dev, 1, (int)n, nh, nkv, D, kv->max_ctx, scale, dt, st, 1, kv->shared_prefix, sl_kv_format(kv));
   };
   if (decode && L.wqkv_dec && L.wo_dec && L.wgu_dec && L.wdown_dec) {
     // 5-6 launches per layer: [norm+]qkv+rope+append | attention (split + merge) | o+res | [norm+]gate/up+silu.mul | down+res
@@ -837,14 +818,12 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     memset(&fx, 0, sizeof(fx));
     fx.fuse_rms = m->dec_fused_norm; fx.rms_eps = m->rms_eps;
     fx.rope_cos = m->rope_cos; fx.rope_sin = m->rope_sin; fx.tok_pos = ctx_len_dev; fx.tok_seq = w.tok_seq;
-    fx.k_cache = kc; fx.v_cache = vc; fx.n_heads = nh; fx.n_kv_heads = nkv; fx.max_ctx = kv->max_ctx; fx.reserved = kv->reserved;
+    fx.k_cache = kc; fx.v_cache = vc; fx.n_heads = nh; fx.n_kv_heads = nkv; fx.max_ctx = kv->max_ctx; fx.reserved = sl_kv_format(kv);
     // small-batch graphs: the prefetch branch runs two matrices ahead of the chain (DecodePrefetch): released where a consumer is launched
     DecodePrefetch* pf = g_prefetch;
     const size_t esz = sl_dtype_size(dt);
-    // e4m3 / MXFP4 weight images: elements + scales
-    auto wbytes = [&](int N, int K) -> size_t {
-      return m->reserved == SL_WDEC_E4M3 ? sl_w8_image_bytes(N, K) : m->reserved == SL_WDEC_MXFP4 ? sl_w4_image_bytes(N, K) : (size_t)N * K * esz;
-    };
+    const SlWFormat* wf = sl_wformat(sl_wformat_code(m));
+    auto wbytes = [&](int N, int K) -> size_t { return sl_wformat_bytes(wf, N, K, esz); };      // weight images: elements + scales
     const size_t b_qkv = wbytes(qkv_w, H), b_o = wbytes(H, nh * D), b_gu = wbytes(2 * m->ffn, H), b_down = wbytes(H, m->ffn);
     const sl_llama_layer* Ln = (l + 1 < m->n_layers) ? &m->layers[l + 1] : nullptr;
     if (pf && l == 0) { SL_TRY(pf->ahead(L.wqkv_dec, b_qkv)); SL_TRY(pf->ahead(L.wo_dec, b_o)); }
@@ -897,7 +876,7 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
   SL_TRY(sl_rmsnorm(x, w.h, L.norm1, n, H, m->rms_eps, dt, (sl_stream)st));
   SL_TRY(layer_gemm(m, w, w.h, H, L.wqkv, H, w.qkv, qkv_w, nullptr, 0, (int)n, qkv_w, H, SL_ACT_NONE, st));
   SL_TRY(sl_rope_kv_append_ex(w.qkv, kc, vc, w.tok_seq, decode ? ctx_len_dev : w.tok_pos, m->rope_cos, m->rope_sin, n, nh, nkv, D, kv->max_ctx,
-                              dt, kv->reserved, (sl_stream)st));
+                              dt, sl_kv_format(kv), (sl_stream)st));
   if (decode) {
     SL_TRY(decode_attn(qkv_w));
   } else {
@@ -914,7 +893,7 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     a.v = vc; a.v_row_stride = D; a.v_head_stride = (int64_t)kv->max_ctx * D;
     a.out = w.att; a.o_row_stride = (int64_t)nh * D; a.o_head_stride = D;
     a.cu_q = w.cu; a.cu_k = w.cuk; a.klen = w.klen;
-    if (kv->reserved == SL_KV_FP8_E4M3) {
+    if (sl_kv_format(kv) == SL_KV_FP8_E4M3) {
       // e4m3 cache: the prompt attends the unquantised keys — the rotated K rows sl_rope_kv_append_ex left in qkv and the V rows beside
       // them (same values, same key order as the 16-bit cache gives: the prefill logits are those of the 16-bit mode, bit for bit)
       const size_t esz = sl_dtype_size(dt);
@@ -925,7 +904,7 @@ static int llama_layer(const sl_llama_model* m, const sl_kv_cache* kv, int l, vo
     a.nseq = nseq; a.max_qlen = max_qlen; a.n_heads = nh; a.n_kv_heads = nkv; a.head_dim = D; a.causal = 1; a.dtype = dt; a.scale = scale;
     // continued prefill on an e4m3 cache (past_len_dev set, w.klen = the NEW key counts, w.cuk = each slot's first cache row): the past keys exist
     // only as the cache's bytes — the values decode reads — and the new ones are attended unquantised out of qkv, as above
-    if (kv->reserved == SL_KV_FP8_E4M3 && past_len_dev) SL_TRY(sl_attn_fwd_past(&a, kc, vc, past_len_dev, w.cuk, kv->max_ctx, kv->reserved, (sl_stream)st));
+    if (sl_kv_format(kv) == SL_KV_FP8_E4M3 && past_len_dev) SL_TRY(sl_attn_fwd_past(&a, kc, vc, past_len_dev, w.cuk, kv->max_ctx, sl_kv_format(kv), (sl_stream)st));
     else SL_TRY(sl_attn_fwd(&a, (sl_stream)st));
   }
   if (tail_rows && !decode) {
@@ -954,7 +933,7 @@ static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, vo
                               float* logits, int32_t* ctx_len_dev, void* hidden_taps, void* workspace, size_t workspace_bytes,
                               sl_stream stream, int slot_stride, const int32_t* past_host = nullptr, const int32_t* slot_host = nullptr) {
   SL_TRY(llama_check(m, kv));
-  if (m->reserved == SL_WDEC_MX_LINEAR) SL_TRY(llama_mx_check(cont_name(past_host, slot_host), m));
+  SL_TRY(llama_wformat_check(cont_name(past_host, slot_host), m, 0, SL_ENTRY_PREFILL));
   // continued prefill (sl_llama_prefill_cont): sequence s already holds positions [0, past_host[s]) of cache slot slot_host[s].  All-zero pasts on
   // the identity slots ARE the plain call: every line below then runs as it did
   if (past_host && nseq > 0) {
@@ -987,7 +966,7 @@ static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, vo
   // logits).  Not with hidden_taps (they are per row of the caller's layout) or when a sequence is nothing but the prefix.
   // Not with e4m3 rows either: that prefill reads K / V from its own qkv rows, not from the cache, so there is nothing to broadcast
   // (decode still reads the positions below shared_prefix from slot 0).
-  int P = (kv->shared_prefix > 0 && nseq > 1 && !hidden_taps && sl_env().prefill_share_prefix && kv->reserved != SL_KV_FP8_E4M3 && slot_stride == 1) ? kv->shared_prefix : 0;
+  int P = (kv->shared_prefix > 0 && nseq > 1 && !hidden_taps && sl_env().prefill_share_prefix && sl_kv_format(kv) != SL_KV_FP8_E4M3 && slot_stride == 1) ? kv->shared_prefix : 0;
   if (cont) P = 0;      // the new rows are never deduplicated: the promise then only says that cache positions [0, shared_prefix) are equal, which the first call made true
   for (int s = 0; s < nseq; ++s) {
     const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
@@ -1039,7 +1018,7 @@ static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, vo
   } else if (cont) {
     // rows rotated at and appended to positions past + t of their slot.  16-bit / fp32 cache: attention over the cache, klen = past + len > qlen,
     // as the shared-prefix tails above.  e4m3: sl_attn_fwd_past takes the new key counts and the pasts apart (llama_layer)
-    const bool kv8 = kv->reserved == SL_KV_FP8_E4M3;
+    const bool kv8 = sl_kv_format(kv) == SL_KV_FP8_E4M3;
     pastv.resize(nseq);
     for (int s = 0; s < nseq; ++s) {
       const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s], past = past_host ? past_host[s] : 0, slot = slot_host ? slot_host[s] : s;
@@ -1071,7 +1050,7 @@ static int llama_prefill_impl(const sl_llama_model* m, const sl_kv_cache* kv, vo
   SL_HIP(hipMemcpyAsync(ctx_len_dev, ctx.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipMemcpyAsync(w.last_row, last_row.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
   // the pasts ride in the decode chain's RMSNorm-scale array, nseq 4-byte entries no prefill touches
-  int32_t* past_dev = (cont && kv->reserved == SL_KV_FP8_E4M3) ? (int32_t*)w.rstd_a : nullptr;
+  int32_t* past_dev = (cont && sl_kv_format(kv) == SL_KV_FP8_E4M3) ? (int32_t*)w.rstd_a : nullptr;
   if (past_dev) SL_HIP(hipMemcpyAsync(past_dev, pastv.data(), nseq * sizeof(int32_t), hipMemcpyHostToDevice, st));
   SL_HIP(hipStreamSynchronize(st));
   // Only each sequence's last row is read after the final layer (lm_head below): without hidden_taps that layer runs everything behind
@@ -1168,7 +1147,7 @@ extern "C" int sl_llama_score(const sl_llama_model* m, const sl_kv_cache* kv, vo
                               size_t workspace_bytes, sl_stream stream) {
   // every check comes before the first launch
   SL_TRY(llama_check(m, kv));
-  SL_TRY(llama_mx_refuse("sl_llama_score", m));
+  SL_TRY(llama_wformat_check("sl_llama_score", m, 0, SL_ENTRY_SCORE));
   SL_CHECK_ARG(x && cu_seqlens_host && score_start_host && n_score_host && labels_dev && logprob_dev && workspace, "sl_llama_score: null pointer");
   SL_CHECK_ARG(nseq > 0, "sl_llama_score: nseq=%d", nseq);
   SL_CHECK_ARG((seq_sum_dev != nullptr) == (seq_counted_dev != nullptr) && (seq_sum_dev != nullptr) == (seq_top1_dev != nullptr),
@@ -1347,7 +1326,7 @@ extern "C" int sl_llama_decode_step(const sl_llama_model* m, const sl_kv_cache* 
                                     int32_t B, float* logits, void* workspace, size_t workspace_bytes, sl_stream stream) {
   SL_TRY(llama_check(m, kv));
   SL_CHECK_ARG(next_ids_dev && ctx_len_dev && logits && workspace && B > 0 && B <= kv->slots && B <= SL_MAX_DECODE_BATCH, "sl_llama_decode_step: bad arguments (B<=%d)", SL_MAX_DECODE_BATCH);
-  SL_TRY(llama_wdec_check("sl_llama_decode_step", m, B));
+  SL_TRY(llama_wformat_check("sl_llama_decode_step", m, B, SL_ENTRY_DECODE));
   hipStream_t st = (hipStream_t)stream;
   LlamaWs w;
   Carver c(workspace, workspace_bytes);
@@ -1543,7 +1522,7 @@ static int decode_graph_key(const GraphCtx& g, int B, DecodeGraphKey& key) {
   key.slots = kv->slots; key.shared_prefix = kv->shared_prefix; key.dtype = m->dtype; key.n_layers = m->n_layers; key.vocab = m->vocab;
   // + the switches that shape the captured launches
   key.fused = m->dec_fused_norm | (sl_env().decode_tiled << 8) | ((sl_env().attn_decode_ks & 127) << 9) | ((g.pin_rows ? 1 : 0) << 16) |
-              ((sl_env().decode_prefetch ? 1 : 0) << 17) | ((kv->reserved & 3) << 18) | ((m->reserved & 7) << 20);
+              ((sl_env().decode_prefetch ? 1 : 0) << 17) | ((sl_kv_format(kv) & 3) << 18) | ((sl_wformat_code(m) & 7) << 20);
   key.limits = g.limits;
   key.content = model_content_hash(m);
   SL_HIP(hipGetDevice(&key.device));
@@ -1746,7 +1725,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   // several answers per prompt: refused before anything is launched
   SL_CHECK_ARG(N >= 1, "sl_generate_n: num_return_sequences %d < 1", N);
   if (N > 1) {
-    SL_TRY(llama_mx_refuse("sl_generate_n", m));
+    SL_TRY(llama_wformat_check("sl_generate_n", m, 0, SL_ENTRY_GENERATE_N));
     SL_CHECK_ARG(o->sample != 0, "sl_generate_n: num_return_sequences %d > 1 needs sample = 1 (greedy answers of one prompt are all the same)", N);
     SL_CHECK_ARG(nseq > 0 && (int64_t)nseq * N <= SL_MAX_DECODE_BATCH, "sl_generate_n: nseq %d x num_return_sequences %d decode rows outside (0, %d]", nseq, N,
                  SL_MAX_DECODE_BATCH);
@@ -1760,7 +1739,7 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   SL_CHECK_ARG(x && cu_seqlens_host && out_ids_host && workspace && nseq > 0 && nseq <= SL_MAX_DECODE_BATCH && max_new_tokens > 0,
                "sl_generate: bad arguments (nseq<=%d)", SL_MAX_DECODE_BATCH);
   const int B0 = nseq * N;         // decode rows: row s * N + j is answer j of prompt s
-  SL_TRY(llama_wdec_check("sl_generate", m, B0));      // compaction only moves down the row ladder: a call that starts within the e4m3 range stays within it
+  SL_TRY(llama_wformat_check("sl_generate", m, B0, SL_ENTRY_DECODE));      // compaction only moves down the row ladder: a call that starts within the e4m3 range stays within it
   SL_CHECK_ARG(n_eos >= 0 && n_eos <= 8 && (n_eos == 0 || eos_ids_host != nullptr), "sl_generate: 0..8 eos ids");
   SampleOpts smp_s{o->temperature, o->top_k, o->top_p, o->seed};
   const SampleOpts* smp = o->sample ? &smp_s : nullptr;
@@ -1788,8 +1767,8 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   DecodeAttn da;
   da.row_slot0 = N > 1 ? nseq : 0;
   const int rep_heads = m->n_kv_heads > 0 ? m->n_heads / m->n_kv_heads : 0;
-  const bool grouped = N > 1 && sl_attn_decode_grouped_built(m->n_heads, m->n_kv_heads, m->head_dim, m->dtype, kv->reserved) &&
-                       (sl_env().gen_group_attn == 1 || (sl_env().gen_group_attn < 0 && gen_group_attn_rule(B0, kv->reserved)));
+  const bool grouped = N > 1 && sl_attn_decode_grouped_built(m->n_heads, m->n_kv_heads, m->head_dim, m->dtype, sl_kv_format(kv)) &&
+                       (sl_env().gen_group_attn == 1 || (sl_env().gen_group_attn < 0 && gen_group_attn_rule(B0, sl_kv_format(kv))));
   g_last_attn_path = N == 1 ? 0 : (grouped ? 2 : 1);
   // carve: generation state first, then the prefill/decode scratch
   Carver c(workspace, workspace_bytes);
@@ -2162,8 +2141,7 @@ extern "C" int sl_beam_generate_lp(const sl_llama_model* m, const sl_kv_cache* k
   SL_CHECK_ARG(x && cu_seqlens_host && out_ids_host && out_scores_host && out_lens_host && workspace, "sl_beam_generate: null buffer");
   const int K = o->num_beams, R = nseq * K, Rn = o->num_return_sequences, max_new = o->max_new_tokens;
   const int n_eos = o->use_eos ? o->n_eos : 0;
-  SL_TRY(llama_mx_refuse("sl_beam_generate", m));
-  SL_TRY(llama_wdec_check("sl_beam_generate", m, R));
+  SL_TRY(llama_wformat_check("sl_beam_generate", m, R, SL_ENTRY_BEAM));
   for (int s = 0; s < nseq; ++s) {
     const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
     SL_CHECK_ARG(len > 0 && len + max_new <= kv->max_ctx, "sl_beam_generate: prompt %d (%d tokens) + %d new tokens exceeds max_ctx %d", s, len, max_new, kv->max_ctx);

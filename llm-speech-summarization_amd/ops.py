@@ -331,26 +331,49 @@ def pack_weight(W: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def w8_image_bytes(N: int, K: int) -> int:
-    n = int(L.lib().sl_w8_image_bytes(N, K))
+# ---- weight images (speechllm.h "e4m3 weight image", "MXFP4 weight image", "MX weight image"): bytes, packer, parts, dequantiser ----
+def _image_bytes(fn_name: str, N: int, K: int) -> int:
+    n = int(getattr(L.lib(), fn_name)(N, K))
     if n == 0:
-        L.check(-1, "sl_w8_image_bytes")
+        L.check(-1, fn_name)
     return n
 
 
-def pack_weight_e4m3(W: torch.Tensor) -> torch.Tensor:
-    """(N, K) bf16 / fp16 weight (row stride W.stride(0)) -> its e4m3 weight image (sl_pack_weight_e4m3): a uint8 buffer of
-    sl_w8_image_bytes(N, K) holding the fragment-major bytes and, behind them, one fp32 scale per (padded) output row.  On the GPU
-    through the device packer, on the CPU through the host entry: the same routine, the same bytes."""
+def _pack_image(name: str, W: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(N, K) bf16 / fp16 weight (row stride W.stride(0)) -> its `name` weight image, a uint8 buffer of the image's bytes.  On the GPU
+    through the device packer sl_pack_weight_<name>, on the CPU through the host entry: the same routines, the same bytes."""
     n, k = W.shape
     if W.stride(1) != 1:
-        raise L.SpeechLLMError("pack_weight_e4m3: rows must be contiguous")
-    out = torch.empty(w8_image_bytes(n, k), device=W.device, dtype=torch.uint8)
+        raise L.SpeechLLMError(f"pack_weight_{name}: rows must be contiguous")
+    bytes_fn = {"e4m3": "sl_w8_image_bytes", "mxfp4": "sl_w4_image_bytes", "mx": "sl_mx_weight_image_bytes"}[name]
+    if out is None:
+        out = torch.empty(_image_bytes(bytes_fn, n, k), device=W.device, dtype=torch.uint8)
+    if out.numel() != _image_bytes(bytes_fn, n, k) or not out.is_contiguous() or out.dtype != torch.uint8:
+        raise L.SpeechLLMError(f"pack_weight_{name}: out must be a contiguous uint8 buffer of {bytes_fn[3:]}(N, K)")
     if W.is_cuda:
-        L.check(L.lib().sl_pack_weight_e4m3(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype), L.stream_ptr()), "sl_pack_weight_e4m3")
+        L.check(getattr(L.lib(), f"sl_pack_weight_{name}")(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype), L.stream_ptr()), f"sl_pack_weight_{name}")
     else:
-        L.check(L.lib().sl_pack_weight_e4m3_host(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype)), "sl_pack_weight_e4m3_host")
+        L.check(getattr(L.lib(), f"sl_pack_weight_{name}_host")(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype)), f"sl_pack_weight_{name}_host")
     return out
+
+
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def _e2m1_block_dequantise(codes: torch.Tensor, scale_bytes: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """e2m1 codes (Np, K) and e8m0 scale bytes (Np, K/32) -> the (N, K) fp64 matrix e2m1 * 2^(scale byte - 127), every value exact."""
+    grid = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float64)
+    v = grid[codes.long()].view(codes.shape[0], K // 32, 32) * torch.exp2(scale_bytes.double() - 127)[:, :, None]
+    return v.view(codes.shape[0], K)[:N]
+
+
+def w8_image_bytes(N: int, K: int) -> int:
+    return _image_bytes("sl_w8_image_bytes", N, K)
+
+
+def pack_weight_e4m3(W: torch.Tensor) -> torch.Tensor:
+    """_pack_image of the e4m3 weight image (sl_pack_weight_e4m3): the fragment-major bytes and, behind them, one fp32 scale per (padded) output row."""
+    return _pack_image("e4m3", W)
 
 
 def w8_image_parts(img: torch.Tensor, N: int, K: int):
@@ -362,26 +385,20 @@ def w8_image_parts(img: torch.Tensor, N: int, K: int):
     return b, s
 
 
+def w8_dequantise(img: torch.Tensor, N: int, K: int) -> torch.Tensor:
+    """An e4m3 weight image -> the (N, K) fp64 matrix the kernels multiply by: byte value x s[n], formed in fp64."""
+    b, s = w8_image_parts(img.cpu(), N, K)
+    return (b.contiguous().view(torch.float8_e4m3fn).double() * s.double()[:, None])[:N]
+
+
 def w4_image_bytes(N: int, K: int) -> int:
-    n = int(L.lib().sl_w4_image_bytes(N, K))
-    if n == 0:
-        L.check(-1, "sl_w4_image_bytes")
-    return n
+    return _image_bytes("sl_w4_image_bytes", N, K)
 
 
 def pack_weight_mxfp4(W: torch.Tensor) -> torch.Tensor:
-    """(N, K) bf16 / fp16 weight (row stride W.stride(0)) -> its MXFP4 weight image (sl_pack_weight_mxfp4): a uint8 buffer of
-    sl_w4_image_bytes(N, K) holding the fragment-major e2m1 nibbles and, behind them, one e8m0 scale byte per row and 32 columns.
-    On the GPU through the device packer, on the CPU through the host entry: the same routines, the same bytes."""
-    n, k = W.shape
-    if W.stride(1) != 1:
-        raise L.SpeechLLMError("pack_weight_mxfp4: rows must be contiguous")
-    out = torch.empty(w4_image_bytes(n, k), device=W.device, dtype=torch.uint8)
-    if W.is_cuda:
-        L.check(L.lib().sl_pack_weight_mxfp4(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype), L.stream_ptr()), "sl_pack_weight_mxfp4")
-    else:
-        L.check(L.lib().sl_pack_weight_mxfp4_host(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype)), "sl_pack_weight_mxfp4_host")
-    return out
+    """_pack_image of the MXFP4 weight image (sl_pack_weight_mxfp4): the fragment-major e2m1 nibbles and, behind them, one e8m0 scale byte per
+    row and 32 columns."""
+    return _pack_image("mxfp4", W)
 
 
 def w4_image_parts(img: torch.Tensor, N: int, K: int):
@@ -394,40 +411,20 @@ def w4_image_parts(img: torch.Tensor, N: int, K: int):
     return c, s.permute(0, 2, 1, 3).reshape(Np, K // 32)
 
 
-_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
-
-
 def w4_dequantise(img: torch.Tensor, N: int, K: int) -> torch.Tensor:
-    """An MXFP4 weight image -> the (N, K) fp64 matrix the kernels multiply by: e2m1 * 2^(scale byte - 127), every value exact."""
-    c, s = w4_image_parts(img.cpu(), N, K)
-    grid = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float64)
-    v = grid[c.long()].view(c.shape[0], K // 32, 32) * torch.exp2(s.double() - 127)[:, :, None]
-    return v.view(c.shape[0], K)[:N]
+    """An MXFP4 weight image -> the (N, K) fp64 matrix the kernels multiply by (_e2m1_block_dequantise)."""
+    return _e2m1_block_dequantise(*w4_image_parts(img.cpu(), N, K), N, K)
 
 
 # ---- MX linears (speechllm.h "MX weight image", "MXFP8 activation rows", sl_gemm_mx) ---------------------------------------------
 def mx_weight_image_bytes(N: int, K: int) -> int:
-    n = int(L.lib().sl_mx_weight_image_bytes(N, K))
-    if n == 0:
-        L.check(-1, "sl_mx_weight_image_bytes")
-    return n
+    return _image_bytes("sl_mx_weight_image_bytes", N, K)
 
 
 def pack_weight_mx(W: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """(N, K) bf16 / fp16 weight (row stride W.stride(0)) -> its MX weight image (sl_pack_weight_mx): the MXFP4 image's codes and scale
-    bytes, arranged one 32-element block per lane for the block-scaled MFMA.  GPU tensor: the device packer; CPU tensor: the host entry."""
-    n, k = W.shape
-    if W.stride(1) != 1:
-        raise L.SpeechLLMError("pack_weight_mx: rows must be contiguous")
-    if out is None:
-        out = torch.empty(mx_weight_image_bytes(n, k), device=W.device, dtype=torch.uint8)
-    if out.numel() != mx_weight_image_bytes(n, k) or not out.is_contiguous() or out.dtype != torch.uint8:
-        raise L.SpeechLLMError("pack_weight_mx: out must be a contiguous uint8 buffer of mx_weight_image_bytes(N, K)")
-    if W.is_cuda:
-        L.check(L.lib().sl_pack_weight_mx(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype), L.stream_ptr()), "sl_pack_weight_mx")
-    else:
-        L.check(L.lib().sl_pack_weight_mx_host(L.ptr(W), W.stride(0), L.ptr(out), n, k, L.dtype_code(W.dtype)), "sl_pack_weight_mx_host")
-    return out
+    """_pack_image of the MX weight image (sl_pack_weight_mx): the MXFP4 image's codes and scale bytes, arranged one 32-element block per
+    lane for the block-scaled MFMA."""
+    return _pack_image("mx", W, out)
 
 
 def mx_image_parts(img: torch.Tensor, N: int, K: int):
@@ -441,11 +438,8 @@ def mx_image_parts(img: torch.Tensor, N: int, K: int):
 
 
 def mx_dequantise(img: torch.Tensor, N: int, K: int) -> torch.Tensor:
-    """An MX weight image -> the (N, K) fp64 matrix the product multiplies by: e2m1 * 2^(scale byte - 127), every value exact."""
-    c, s = mx_image_parts(img.cpu(), N, K)
-    grid = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float64)
-    v = grid[c.long()].view(c.shape[0], K // 32, 32) * torch.exp2(s.double() - 127)[:, :, None]
-    return v.view(c.shape[0], K)[:N]
+    """An MX weight image -> the (N, K) fp64 matrix the product multiplies by (_e2m1_block_dequantise)."""
+    return _e2m1_block_dequantise(*mx_image_parts(img.cpu(), N, K), N, K)
 
 
 def mxfp8_quantize_rows(x: torch.Tensor, out=None):

@@ -587,212 +587,150 @@ class LlamaDeviceWeights:
         wqkv, wo, wgu, wdown = by_ptr[lay.wqkv], by_ptr[lay.wo], by_ptr[lay.wgu], by_ptr[lay.wdown]
         return fold(wqkv, by_ptr[lay.norm1])[self._rope_perm()], wo, fold(wgu, by_ptr[lay.norm2]), wdown
 
-    # -- opt-in fp8 decode weights (include/speechllm.h: e4m3 weight images, SL_WDEC_E4M3) -----------------------------------------
+    # -- the opt-in weight formats (include/speechllm.h SL_WDEC_*; their rules: _lib.WEIGHT_FORMATS and the library's own table) --------
     def w8_shapes(self):
         """(N, K) of the five decode products: qkv, o, gate/up, down (per layer) and lm_head"""
-        a = self.arch
-        H, D, nh, nkv, F_ = a.hidden_size, a.head_dim, a.num_attention_heads, a.num_key_value_heads, a.intermediate_size
-        return dict(qkv=((nh + 2 * nkv) * D, H), o=(H, nh * D), gu=(2 * F_, H), down=(H, F_), lm_head=(a.vocab_size, H))
+        return llama_product_shapes(self.arch)
 
-    def e4m3_supported(self) -> Optional[str]:
-        """None, or why this model cannot take e4m3 decode weights"""
-        if not L.is16(self.dtype):
-            return "fp8 decode weights need a bfloat16 or float16 model: float32 is the parity mode"
-        bad = {n: k for n, (_, k) in self.w8_shapes().items() if k % 64}
-        if bad:
-            return f"fp8 decode weights need every reduction length to be a multiple of 64, not {bad}"
-        return None
+    def format_supported(self, fmt: L.WeightFormat) -> Optional[str]:
+        """None, or why this model cannot take weight format `fmt`"""
+        return format_unsupported(fmt, self.arch, self.dtype)
 
-    def _build_decode_images(self, what: str, pack, reserved: int):
-        """The decode matrices in another format: pack() of the same folded, permuted, interleaved tensors build_decode_weights packs
-        (`_decode_sources`), and an sl_llama_model struct that differs from `struct` in the five *_dec pointers and `reserved` only.
-        -> (struct, its layer array, per-layer images, the lm_head image)"""
-        self.build_decode_weights()
-        if not self.decode_packed or not self.struct.dec_fused_norm:
-            raise L.SpeechLLMError(f"{what} decode weights need the packed, gain-folded decode copies (build_decode_weights with fuse_norm)")
-        a = self.arch
+    def format_built(self, code: int):
+        """what build_format kept for a format: (struct, its layer array, per-layer images, the lm_head image or None), or four Nones"""
+        return self.__dict__.setdefault("_formats", {}).get(code, (None, None, None, None))
+
+    def build_format(self, fmt: L.WeightFormat) -> None:
+        """A further copy of the layer matrices as `fmt` weight images, and a further sl_llama_model struct, built once and kept; `struct` and the
+        16-bit matrices stay (a batch above the format's row limit, and the option switched off again, run on them).
+        Decode-image formats (e4m3: one byte per element and one fp32 scale per output row, about half a copy of the weights more; MXFP4: one e2m1
+        nibble per element and one e8m0 scale byte per row and 32 columns, about a quarter): images of the same folded, permuted, interleaved
+        tensors build_decode_weights packs (`_decode_sources`), lm_head included; the struct differs from `struct` in the five *_dec pointers
+        and `reserved` only.
+        MX linears: images of the ROW-MAJOR layer matrices — wqkv, wo, the gate/up interleave, wdown: no gain fold, no q / k permutation; the
+        struct has those four pointers of every layer replaced by the images and the four *_dec pointers NULL.  Embedding, norms and both
+        lm_head pointers are `struct`'s."""
+        if self.format_built(fmt.code)[0] is not None:
+            return
+        why = self.format_supported(fmt)
+        if why:
+            raise L.SpeechLLMError(why)
+        from . import ops
+        pack = getattr(ops, fmt.pack)
+        if fmt.decode_images:
+            self.build_decode_weights()
+            if not self.decode_packed or not self.struct.dec_fused_norm:
+                raise L.SpeechLLMError(f"{fmt.spellings[0]} decode weights need the packed, gain-folded decode copies (build_decode_weights with fuse_norm)")
         m = L.LlamaModel()
         C.memmove(C.byref(m), C.byref(self.struct), C.sizeof(L.LlamaModel))
-        layers = (L.LlamaLayer * a.num_hidden_layers)()
+        layers = (L.LlamaLayer * self.arch.num_hidden_layers)()
         C.memmove(layers, self._layers, C.sizeof(layers))
         images: List[Dict[str, torch.Tensor]] = []
-        for li in range(a.num_hidden_layers):
-            imgs = {n: pack(t.contiguous()) for n, t in zip(("qkv", "o", "gu", "down"), self._decode_sources(li, True))}
+        for li, lay in enumerate(layers):
+            srcs = self._decode_sources(li, True) if fmt.decode_images else (self.layer_t[li][n] for n in ("wqkv", "wo", "wgu", "wdown"))
+            imgs = {n: pack(t.contiguous()) for n, t in zip(("qkv", "o", "gu", "down"), srcs)}
             images.append(imgs)
-            lay = layers[li]
-            lay.wqkv_dec, lay.wo_dec, lay.wgu_dec, lay.wdown_dec = (imgs[n].data_ptr() for n in ("qkv", "o", "gu", "down"))
-        lm_head = pack(self._decode_sources(-1, True).contiguous())
-        m.lm_head_dec = lm_head.data_ptr()
+            ptrs = [imgs[n].data_ptr() for n in ("qkv", "o", "gu", "down")]
+            if fmt.decode_images:
+                lay.wqkv_dec, lay.wo_dec, lay.wgu_dec, lay.wdown_dec = ptrs
+            else:
+                lay.wqkv, lay.wo, lay.wgu, lay.wdown = ptrs
+                lay.wqkv_dec = lay.wo_dec = lay.wgu_dec = lay.wdown_dec = None
+        lm_head = pack(self._decode_sources(-1, True).contiguous()) if fmt.decode_images else None
+        if lm_head is not None:
+            m.lm_head_dec = lm_head.data_ptr()
         m.layers = C.cast(layers, C.POINTER(L.LlamaLayer))
-        m.reserved = reserved
+        m.reserved = fmt.code
         torch.cuda.synchronize(self.device)
-        return m, layers, images, lm_head
+        self._formats[fmt.code] = (m, layers, images, lm_head)
 
-    def _dequantised_state_dict(self, images, lm_head, dq_image) -> Dict[str, torch.Tensor]:
-        """HF-keyed fp32 CPU state dict of the model a quantised decode step computes: the seven projections of every layer and
-        lm_head.weight are dq_image(image, N, K) in natural row order (q / k rows un-permuted, gate / up de-interleaved); the norm gains
-        folded into them are 1."""
+    def format_dequantised_state_dict(self, fmt: L.WeightFormat) -> Dict[str, torch.Tensor]:
+        """HF-keyed fp32 CPU state dict of the WEIGHTS a model in format `fmt` multiplies by, for tests and for scoring the quantised model
+        offline: the seven projections of every layer are the dequantised images (exact in fp32 for e2m1 x 2^e; e4m3: byte value x s[n],
+        formed in fp64, stored as fp32) in natural row order (gate / up de-interleaved).  Decode-image formats: q / k rows un-permuted,
+        lm_head.weight dequantised too, and the norm gains, which are folded into the images, 1.  MX linears: norms, embedding and lm_head
+        are the model's own; the activations' MXFP8 rounding is not part of a state dict: a reference applies it in front of these seven."""
+        _, _, images, lm_head = self.format_built(fmt.code)
+        if images is None:
+            raise L.SpeechLLMError(f"dequantised state dict: build the {fmt.images} weight images first ({fmt.label})")
+        from . import ops
         a = self.arch
         H, D, nh, nkv, F_ = a.hidden_size, a.head_dim, a.num_attention_heads, a.num_key_value_heads, a.intermediate_size
         shapes = self.w8_shapes()
-        dq = lambda img, name: dq_image(img, *shapes[name])
-        perm = self._rope_perm().cpu()
-        ones = torch.ones(H, dtype=torch.float32)
-        sd = {"model.embed_tokens.weight": self.embed.float().cpu(), "model.norm.weight": ones.clone(), "lm_head.weight": dq(lm_head, "lm_head")}
+        dq = lambda img, name: getattr(ops, fmt.dequantise)(img, *shapes[name]).float()
+        folded = fmt.decode_images
+        perm = self._rope_perm().cpu() if folded else None
+        gain = lambda t: torch.ones(H, dtype=torch.float32) if folded else t.float().cpu()
+        sd = {"model.embed_tokens.weight": self.embed.float().cpu(), "model.norm.weight": gain(self.final_norm),
+              "lm_head.weight": dq(lm_head, "lm_head") if folded else self.lm_head.float().cpu()}
         for li, imgs in enumerate(images):
             p = f"model.layers.{li}."
-            qkv = torch.empty(shapes["qkv"], dtype=torch.float32)
-            qkv[perm] = dq(imgs["qkv"], "qkv")
+            qkv = dq(imgs["qkv"], "qkv")
+            if perm is not None:
+                qkv = torch.empty_like(qkv).index_copy_(0, perm, qkv)
             sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.v_proj.weight"] = \
                 (t.contiguous() for t in qkv.split([nh * D, nkv * D, nkv * D], 0))
             sd[p + "self_attn.o_proj.weight"] = dq(imgs["o"], "o")
             gu = dq(imgs["gu"], "gu").view(F_ // 16, 2, 16, H)
             sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"] = gu[:, 0].reshape(F_, H).contiguous(), gu[:, 1].reshape(F_, H).contiguous()
             sd[p + "mlp.down_proj.weight"] = dq(imgs["down"], "down")
-            sd[p + "input_layernorm.weight"], sd[p + "post_attention_layernorm.weight"] = ones.clone(), ones.clone()
+            sd[p + "input_layernorm.weight"], sd[p + "post_attention_layernorm.weight"] = gain(self.layer_t[li]["norm1"]), gain(self.layer_t[li]["norm2"])
         return sd
 
-    def build_decode_weights_e4m3(self) -> None:
-        """Third copy of the decode matrices: e4m3 weight images (sl_pack_weight_e4m3: one byte per element, one fp32 scale per output row)
-        of the same folded, permuted, interleaved tensors build_decode_weights packs, and a second sl_llama_model struct
-        (`struct_e4m3`) that differs from `struct` in the five *_dec pointers and `reserved` = SL_WDEC_E4M3 only.  The 16-bit decode
-        copies stay for batches above sl_w8_max_rows(); the images cost about half a copy of the weights more."""
-        if getattr(self, "struct_e4m3", None) is not None:
-            return
-        why = self.e4m3_supported()
-        if why:
-            raise L.SpeechLLMError(why)
-        from . import ops
-        self.struct_e4m3, self._layers_e4m3, self.w8_images, self.w8_lm_head = self._build_decode_images("fp8", ops.pack_weight_e4m3, L.WDEC_E4M3)
-
-    def e4m3_dequantised_state_dict(self) -> Dict[str, torch.Tensor]:
-        """HF-keyed fp32 CPU state dict of the model the e4m3 decode step computes: the seven projections of every layer and
-        lm_head.weight are the dequantised images (byte value x s[n], formed in fp64, stored as fp32) in natural row order (q / k rows
-        un-permuted, gate / up de-interleaved); the norm gains folded into them are 1.  For tests and for scoring the quantised model
-        offline."""
-        if getattr(self, "struct_e4m3", None) is None:
-            raise L.SpeechLLMError("e4m3_dequantised_state_dict: call build_decode_weights_e4m3 first")
-        from . import ops
-
-        def dq(img: torch.Tensor, n: int, k: int) -> torch.Tensor:
-            b, s = ops.w8_image_parts(img.cpu(), n, k)
-            return (b.contiguous().view(torch.float8_e4m3fn).double() * s.double()[:, None])[:n].float()
-
-        return self._dequantised_state_dict(self.w8_images, self.w8_lm_head, dq)
-
-    # -- opt-in MXFP4 decode weights (include/speechllm.h: MXFP4 weight images, SL_WDEC_MXFP4) -------------------------------------
-    def mxfp4_supported(self) -> Optional[str]:
-        """None, or why this model cannot take MXFP4 decode weights"""
-        if not L.is16(self.dtype):
-            return "mxfp4 decode weights need a bfloat16 or float16 model: float32 is the parity mode"
-        bad = {n: k for n, (_, k) in self.w8_shapes().items() if k % 128}
-        if bad:
-            return f"mxfp4 decode weights need every reduction length to be a multiple of 128, not {bad}"
-        return None
-
-    def build_decode_weights_mxfp4(self) -> None:
-        """A further copy of the decode matrices: MXFP4 weight images (sl_pack_weight_mxfp4: one e2m1 nibble per element, one e8m0 scale
-        byte per row and 32 columns), and the struct `struct_mxfp4` with `reserved` = SL_WDEC_MXFP4.  The 16-bit decode copies stay for
-        batches above sl_w4_max_rows(); the images cost about a quarter copy of the weights more."""
-        if getattr(self, "struct_mxfp4", None) is not None:
-            return
-        why = self.mxfp4_supported()
-        if why:
-            raise L.SpeechLLMError(why)
-        from . import ops
-        self.struct_mxfp4, self._layers_mxfp4, self.w4_images, self.w4_lm_head = self._build_decode_images("mxfp4", ops.pack_weight_mxfp4, L.WDEC_MXFP4)
-
-    def mxfp4_dequantised_state_dict(self) -> Dict[str, torch.Tensor]:
-        """_dequantised_state_dict of the model the MXFP4 decode step computes (every value e2m1 x 2^e, exact in fp32).  For tests and for
-        scoring the quantised model offline: 4-bit weights are a different model."""
-        if getattr(self, "struct_mxfp4", None) is None:
-            raise L.SpeechLLMError("mxfp4_dequantised_state_dict: call build_decode_weights_mxfp4 first")
-        from . import ops
-        return self._dequantised_state_dict(self.w4_images, self.w4_lm_head, lambda img, n, k: ops.w4_dequantise(img, n, k).float())
-
-    # -- opt-in MX linears (include/speechllm.h: MX weight images, SL_WDEC_MX_LINEAR) -----------------------------------------------
-    def mx_supported(self) -> Optional[str]:
-        """None, or why this model cannot run its layer products as MXFP8 x MXFP4"""
-        if not L.is16(self.dtype):
-            return "linear_dtype='mx' needs a bfloat16 or float16 model: float32 is the parity mode"
-        bad = {n: k for n, (_, k) in self.w8_shapes().items() if n != "lm_head" and k % 128}
-        if bad:
-            return f"linear_dtype='mx' needs every reduction length to be a multiple of 128, not {bad}"
-        return None
-
-    def build_linear_weights_mx(self) -> None:
-        """MX weight images (ops.pack_weight_mx) of the ROW-MAJOR layer matrices — wqkv, wo, the gate/up interleave, wdown: no gain fold,
-        no q / k permutation — and the struct `struct_mx`: `struct` with those four pointers of every layer replaced by the images, the
-        four *_dec pointers NULL and `reserved` = SL_WDEC_MX_LINEAR.  Embedding, norms and both lm_head pointers are `struct`'s.  The
-        16-bit matrices stay (the option can be switched off again); the images cost about a quarter copy of the layer weights more."""
-        if getattr(self, "struct_mx", None) is not None:
-            return
-        why = self.mx_supported()
-        if why:
-            raise L.SpeechLLMError(why)
-        from . import ops
-        a = self.arch
-        m = L.LlamaModel()
-        C.memmove(C.byref(m), C.byref(self.struct), C.sizeof(L.LlamaModel))
-        layers = (L.LlamaLayer * a.num_hidden_layers)()
-        C.memmove(layers, self._layers, C.sizeof(layers))
-        images: List[Dict[str, torch.Tensor]] = []
-        for li in range(a.num_hidden_layers):
-            t = self.layer_t[li]
-            imgs = {n: ops.pack_weight_mx(t[src]) for n, src in (("qkv", "wqkv"), ("o", "wo"), ("gu", "wgu"), ("down", "wdown"))}
-            images.append(imgs)
-            lay = layers[li]
-            lay.wqkv, lay.wo, lay.wgu, lay.wdown = (imgs[n].data_ptr() for n in ("qkv", "o", "gu", "down"))
-            lay.wqkv_dec = lay.wo_dec = lay.wgu_dec = lay.wdown_dec = None
-        m.layers = C.cast(layers, C.POINTER(L.LlamaLayer))
-        m.reserved = L.WDEC_MX_LINEAR
-        torch.cuda.synchronize(self.device)
-        self.struct_mx, self._layers_mx, self.mx_images = m, layers, images
-
-    def mx_dequantised_state_dict(self) -> Dict[str, torch.Tensor]:
-        """HF-keyed fp32 CPU state dict of the WEIGHTS the MX linears multiply by: the seven projections of every layer are the dequantised
-        MX images (e2m1 x 2^e, exact in fp32) in natural row order (gate / up de-interleaved); norms, embedding and lm_head are the
-        model's own.  The activations' MXFP8 rounding is not part of a state dict: a reference applies it in front of these seven."""
-        if getattr(self, "struct_mx", None) is None:
-            raise L.SpeechLLMError("mx_dequantised_state_dict: call build_linear_weights_mx first")
-        from . import ops
-        a = self.arch
-        H, D, nh, nkv, F_ = a.hidden_size, a.head_dim, a.num_attention_heads, a.num_key_value_heads, a.intermediate_size
-        shapes = self.w8_shapes()
-        dq = lambda img, name: ops.mx_dequantise(img, *shapes[name]).float()
-        sd = {"model.embed_tokens.weight": self.embed.float().cpu(), "model.norm.weight": self.final_norm.float().cpu(), "lm_head.weight": self.lm_head.float().cpu()}
-        for li, imgs in enumerate(self.mx_images):
-            p = f"model.layers.{li}."
-            sd[p + "self_attn.q_proj.weight"], sd[p + "self_attn.k_proj.weight"], sd[p + "self_attn.v_proj.weight"] = \
-                (t.contiguous() for t in dq(imgs["qkv"], "qkv").split([nh * D, nkv * D, nkv * D], 0))
-            sd[p + "self_attn.o_proj.weight"] = dq(imgs["o"], "o")
-            gu = dq(imgs["gu"], "gu").view(F_ // 16, 2, 16, H)
-            sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"] = gu[:, 0].reshape(F_, H).contiguous(), gu[:, 1].reshape(F_, H).contiguous()
-            sd[p + "mlp.down_proj.weight"] = dq(imgs["down"], "down")
-            sd[p + "input_layernorm.weight"] = self.layer_t[li]["norm1"].float().cpu()
-            sd[p + "post_attention_layernorm.weight"] = self.layer_t[li]["norm2"].float().cpu()
-        return sd
+    # the formats' names of before the table: one-line delegations
+    e4m3_supported = lambda self: self.format_supported(L.WEIGHT_FORMATS[L.WDEC_E4M3])
+    mxfp4_supported = lambda self: self.format_supported(L.WEIGHT_FORMATS[L.WDEC_MXFP4])
+    mx_supported = lambda self: self.format_supported(L.WEIGHT_FORMATS[L.WDEC_MX_LINEAR])
+    build_decode_weights_e4m3 = lambda self: self.build_format(L.WEIGHT_FORMATS[L.WDEC_E4M3])
+    build_decode_weights_mxfp4 = lambda self: self.build_format(L.WEIGHT_FORMATS[L.WDEC_MXFP4])
+    build_linear_weights_mx = lambda self: self.build_format(L.WEIGHT_FORMATS[L.WDEC_MX_LINEAR])
+    e4m3_dequantised_state_dict = lambda self: self.format_dequantised_state_dict(L.WEIGHT_FORMATS[L.WDEC_E4M3])
+    mxfp4_dequantised_state_dict = lambda self: self.format_dequantised_state_dict(L.WEIGHT_FORMATS[L.WDEC_MXFP4])
+    mx_dequantised_state_dict = lambda self: self.format_dequantised_state_dict(L.WEIGHT_FORMATS[L.WDEC_MX_LINEAR])
+    struct_e4m3 = property(lambda self: self.format_built(L.WDEC_E4M3)[0])
+    struct_mxfp4 = property(lambda self: self.format_built(L.WDEC_MXFP4)[0])
+    struct_mx = property(lambda self: self.format_built(L.WDEC_MX_LINEAR)[0])
+    w8_images = property(lambda self: self.format_built(L.WDEC_E4M3)[2])
+    w4_images = property(lambda self: self.format_built(L.WDEC_MXFP4)[2])
+    mx_images = property(lambda self: self.format_built(L.WDEC_MX_LINEAR)[2])
+    w8_lm_head = property(lambda self: self.format_built(L.WDEC_E4M3)[3])
+    w4_lm_head = property(lambda self: self.format_built(L.WDEC_MXFP4)[3])
 
     def n_params(self) -> int:
         return sum(t.numel() for t in self._keep if t.dtype == self.dtype)
 
     def weight_bytes_per_token(self, fmt=None) -> int:
-        """Bytes of weights one decode step streams: every layer matrix + final norm + lm_head.  fmt = "fp8" / torch.float8_e4m3fn: the
-        e4m3 weight images instead (bytes and scales; the norm gains are folded in and not read); fmt = "mxfp4": the MXFP4 weight images
-        (4 bits per element + one scale byte per 32: 4.25 bits per weight)."""
+        """Bytes of weights one decode step streams: every layer matrix + final norm + lm_head.  fmt = a weight_dtype ("fp8" /
+        torch.float8_e4m3fn, "mxfp4"): its weight images instead, scales included (the norm gains are folded in and not read; MXFP4: 4 bits
+        per element + one scale byte per 32, 4.25 bits per weight)."""
         a = self.arch
-        if L.weight_format_code(fmt) == L.WDEC_E4M3:
-            sh = self.w8_shapes()
-            img = lambda n: ((sh[n][0] + 15) // 16 * 16) * (sh[n][1] + 4)
-            return a.num_hidden_layers * sum(img(n) for n in ("qkv", "o", "gu", "down")) + img("lm_head")
-        if L.weight_format_code(fmt) == L.WDEC_MXFP4:
-            sh = self.w8_shapes()
-            img = lambda n: ((sh[n][0] + 15) // 16 * 16) * (sh[n][1] // 2 + sh[n][1] // 32)
-            return a.num_hidden_layers * sum(img(n) for n in ("qkv", "o", "gu", "down")) + img("lm_head")
+        f = L.WEIGHT_FORMATS[L.weight_format_code(fmt)]
+        if f.image_bytes:
+            from . import ops
+            img = {n: getattr(ops, f.image_bytes)(*nk) for n, nk in self.w8_shapes().items()}
+            return a.num_hidden_layers * sum(img[n] for n in ("qkv", "o", "gu", "down")) + img["lm_head"]
         per_layer = (a.num_attention_heads + 2 * a.num_key_value_heads) * a.head_dim * a.hidden_size \
             + a.num_attention_heads * a.head_dim * a.hidden_size + 3 * a.intermediate_size * a.hidden_size + 2 * a.hidden_size
         total = per_layer * a.num_hidden_layers + a.hidden_size + a.vocab_size * a.hidden_size
         return total * (2 if L.is16(self.dtype) else 4)
+
+
+def llama_product_shapes(arch: LlamaArch):
+    """(N, K) of the five products of a decode step: qkv, o, gate/up, down (per layer) and lm_head"""
+    H, D, nh, nkv, F_ = arch.hidden_size, arch.head_dim, arch.num_attention_heads, arch.num_key_value_heads, arch.intermediate_size
+    return dict(qkv=((nh + 2 * nkv) * D, H), o=(H, nh * D), gu=(2 * F_, H), down=(H, F_), lm_head=(arch.vocab_size, H))
+
+
+def format_unsupported(fmt: L.WeightFormat, arch: LlamaArch, dtype: torch.dtype) -> Optional[str]:
+    """None, or why a model of this architecture and dtype cannot take weight format `fmt`: the one statement of the check, for the device
+    weights and for the option's setter (which runs before there are device weights)"""
+    if not L.is16(dtype):
+        return f"{fmt.label} needs a bfloat16 or float16 model: float32 is the parity mode and keeps its weights and products in float32"
+    kmul = fmt.k_multiple
+    bad = {n: k for n, (_, k) in llama_product_shapes(arch).items() if k % kmul and (fmt.decode_images or n != "lm_head")}
+    if bad:
+        return f"{fmt.label} needs every reduction length to be a multiple of {kmul}, not {bad}"
+    return None
 
 
 # ------------------------------------------------------------------------------------------------
