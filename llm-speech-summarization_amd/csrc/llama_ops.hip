@@ -493,7 +493,8 @@ extern "C" int sl_greedy_select_partial_sc(const float* amax_val, const int32_t*
 //   one token survives), then one draw from the renormalised survivors.  One block per row; thresholds by 4-pass radix
 //   selection over the order-preserving 32-bit image of the logits (by count for top-k, by probability mass for top-p), so no
 //   sort and no O(V) scratch; the draw is the inverse CDF in INDEX order at u = hash(seed, row, step) — reproducible, and the
-//   test restates it on the host.  Tokens of equal logit share their fate (all kept or all dropped).
+//   test restates it on the host.  Tokens of equal logit share their fate (all kept or all dropped).  NaN counts as -inf wherever the
+//   row is read; a row without a finite logit commits token 0 (tests/select_ref.py).
 // ----------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t ord_key(float x) {
   const uint32_t u = __float_as_uint(x);
@@ -511,7 +512,8 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
   __shared__ float s_above;
   __shared__ float part[1024];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* row = logits + (int64_t)b * V;
+  const float* rowp = logits + (int64_t)b * V;
+  auto row = [&](int i) { const float x = rowp[i]; return x != x ? -INFINITY : x; };   // NaN counts as -inf: no seat, no mass
   auto block_sum = [&](float v) {
     v = wave_sum(v);
     __syncthreads();
@@ -523,13 +525,21 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
   };
   // row maximum (numerical stability of the exponentials)
   float m = -INFINITY;
-  for (int i = tid; i < V; i += 1024) m = fmaxf(m, row[i]);
+  for (int i = tid; i < V; i += 1024) m = fmaxf(m, row(i));
   m = wave_max(m);
   if (lane == 0) redf[wave] = m;
   __syncthreads();
   m = redf[0];
   for (int w = 1; w < 16; ++w) m = fmaxf(m, redf[w]);
   __syncthreads();
+  if (m == -INFINITY) {   // no finite logit (m is the block's, so every thread leaves here): token 0 as greedy gives, log-probability -inf
+    if (tid == 0) {
+      choice[b] = 0;
+      const int step = gen_count[b];
+      if (logprob_out && step < max_new) logprob_out[(int64_t)b * max_new + step] = -INFINITY;
+    }
+    return;
+  }
   auto prob = [&](float x) { return __expf((x - m) * inv_temp); };
 
   // radix selection: MODE 0 = by count (k-th largest key), MODE 1 = by mass (first key, from the top, at which the mass of
@@ -543,7 +553,7 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
       for (int i = tid; i < 256; i += 1024) { hcnt[i] = 0; hmass_fx[i] = 0ull; }
       __syncthreads();
       for (int i = tid; i < V; i += 1024) {
-        const float x = row[i];
+        const float x = row(i);
         const uint32_t k = ord_key(x);
         if (k < floor_key || (k & hi_mask) != prefix) continue;
         const int bin = (k >> shift) & 255;
@@ -584,7 +594,7 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
   if (top_k > 0 && top_k < V) keep_key = radix_select(0, (float)top_k, 0u);
   if (top_p < 1.0f) {
     float z1 = 0.f;
-    for (int i = tid; i < V; i += 1024) { const float x = row[i]; if (ord_key(x) >= keep_key) z1 += prob(x); }
+    for (int i = tid; i < V; i += 1024) { const float x = row(i); if (ord_key(x) >= keep_key) z1 += prob(x); }
     z1 = block_sum(z1);
     const uint32_t kp = radix_select(1, top_p * z1, keep_key);
     keep_key = kp > keep_key ? kp : keep_key;
@@ -593,7 +603,7 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
   const int Cn = (V + 1023) / 1024;
   const int i0 = tid * Cn, i1 = (i0 + Cn) < V ? (i0 + Cn) : V;
   float loc = 0.f;
-  for (int i = i0; i < i1; ++i) { const float x = row[i]; if (ord_key(x) >= keep_key) loc += prob(x); }
+  for (int i = i0; i < i1; ++i) { const float x = row(i); if (ord_key(x) >= keep_key) loc += prob(x); }
   part[tid] = loc;
   __syncthreads();
   if (tid == 0) {
@@ -607,23 +617,25 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
     float run = 0.f;
     int t = 0;
     for (; t < 1023; ++t) { if (run + part[t] > target) break; run += part[t]; }
-    // walk the slice; the LAST surviving index seen is the fallback when rounding leaves target >= the total
+    // walk the slice; the LAST survivor of mass above zero seen is the fallback when rounding leaves target >= the total (a -inf token
+    // passes keep_key = 0 and must never be returned)
     int pick = -1, last = -1;
     const int j0 = t * Cn, j1 = (j0 + Cn) < V ? (j0 + Cn) : V;
     for (int i = j0; i < j1; ++i) {
-      const float x = row[i];
+      const float x = row(i);
       if (ord_key(x) < keep_key) continue;
-      last = i;
-      run += prob(x);
+      const float p = prob(x);
+      if (p > 0.f) last = i;
+      run += p;
       if (run > target) { pick = i; break; }
     }
     if (pick < 0) pick = last;
-    if (pick < 0) {   // empty slice (cannot happen with z > 0): fall back to the global argmax bookkeeping index 0
-      for (int i = 0; i < V; ++i) if (ord_key(row[i]) >= keep_key) { pick = i; break; }
+    if (pick < 0) {   // empty slice (cannot happen with z > 0): the first survivor of mass above zero
+      for (int i = 0; i < V; ++i) { const float x = row(i); if (ord_key(x) >= keep_key && prob(x) > 0.f) { pick = i; break; } }
     }
     choice[b] = pick < 0 ? 0 : pick;
     // token log-probabilities: the drawn token under the renormalised survivors, log(p / z) with the p and the z of the draw
-    if (logprob_out && (int)step < max_new) logprob_out[(int64_t)b * max_new + step] = logf(prob(row[pick < 0 ? 0 : pick]) / z);
+    if (logprob_out && (int)step < max_new) logprob_out[(int64_t)b * max_new + step] = logf(prob(row(pick < 0 ? 0 : pick)) / z);
   }
 }
 
