@@ -1192,6 +1192,35 @@ int sl_generate_cont(const sl_llama_model* m, const sl_kv_cache* kv, void* x, co
                      sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host, const int32_t* past_len_host, const int32_t* slot_host);
 
 /* ---------------------------------------------------------------------------------------------
+ * HF's four further logits warpers in the device sampler; additive to ABI 7, no struct above changes its size.
+ * They run behind temperature / top-k / top-p in HF's order: min_p, typical_p, epsilon_cutoff, eta_cutoff.  S is the survivor set
+ * entering a stage, p the softmax of the scores / T over S, H = -sum_S p ln p (natural log); equal scores always share their fate:
+ *   min_p           in [0, 1], 0 = off:   keep i iff p_i >= min_p * max_S p            (the maximum and its ties always stay)
+ *   typical_p       in (0, 1], 1 = off:   d_i = |-ln p_i - H|; drop i iff the mass of the tokens of S with a strictly smaller d is
+ *                                         >= typical_p  (HF's rule; a band in score: the row maximum itself may be dropped)
+ *   epsilon_cutoff  in [0, 1), 0 = off:   keep i iff p_i >= epsilon or x_i is the largest score in S
+ *   eta_cutoff      in [0, 1), 0 = off:   eta = min(epsilon, sqrt(epsilon) * exp(-H)); keep i iff p_i >= eta or x_i is the largest in S
+ * The draw (u = hash(seed, row, step), inverse CDF in index order, never a token of mass zero), the log-probability log(p / z) and the
+ * row without a finite logit (token 0, -inf) are sl_sample_select_sc's over the final survivors.  A value outside its range or NaN is
+ * SL_ERR_ARG before any launch, with the value in sl_last_error.  warp NULL, or every field at its off value, gives exactly the call
+ * without it: bit for bit and launch for launch, the same captured graphs.  No workspace grows: sl_generate_workspace_bytes_n /
+ * _cont / _sc sizes hold for sl_generate_w, and choice_ws is B int32 as before (the warped kernel keeps its state in LDS and registers).
+ *
+ * sl_sample_select_w: sl_sample_select_sc (logprob_out may be NULL: then sl_sample_select) + warp.
+ * sl_generate_w: ONE entry for the plain, scored, several-answers and continued forms — sl_generate_sc's arguments, then
+ * num_return_sequences (sl_generate_n; 1 = one answer), past_len_host / slot_host (sl_generate_cont; NULL = a fresh cache), then warp.
+ * Without opts->sample the warp values are checked and otherwise ignored, as temperature is. */
+typedef struct { float min_p, typical_p, epsilon_cutoff, eta_cutoff; } sl_warp_opts;
+int sl_sample_select_w(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                       const int32_t* eos_ids_host, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t* unfinished, int32_t* ctx_len,
+                       int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, int32_t* choice_ws,
+                       float* logprob_out, sl_stream stream, const sl_warp_opts* warp);
+int sl_generate_w(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                  const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
+                  sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host, int32_t num_return_sequences,
+                  const int32_t* past_len_host, const int32_t* slot_host, const sl_warp_opts* warp);
+
+/* ---------------------------------------------------------------------------------------------
  * Teacher-forced scoring: the log-probability of GIVEN tokens, batched; additive to ABI 7.
  * For a scored row with hidden state h and label y:  logprob = log_softmax(lm_head(final_norm(h)))[y] in fp32, NaN counted as -inf, one
  * fixed order of additions (no float atomics).  A label outside [0, vocab) (HF's -100) marks an IGNORED position: its logprob is 0.0f, it

@@ -208,6 +208,35 @@ class LogitsOpts(C.Structure):
     _fields_ = [("repetition_penalty", c_f32), ("no_repeat_ngram_size", c_i32), ("min_new_tokens", c_i32), ("reserved", c_i32)]
 
 
+class WarpOpts(C.Structure):
+    """sl_warp_opts: HF's min_p / typical_p / epsilon_cutoff / eta_cutoff warpers of a sampling call (0 / 1.0 / 0 / 0 = off)"""
+    _fields_ = [("min_p", c_f32), ("typical_p", c_f32), ("epsilon_cutoff", c_f32), ("eta_cutoff", c_f32)]
+
+
+WARP_OFF = dict(min_p=0.0, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0)
+
+
+def warp_opts(values):
+    """dict with any of WARP_OFF's keys (None = off), or None -> WarpOpts, or None when every option is off (a NULL pointer: the library
+    then runs exactly the call without them).  Ranges are the header's; a value outside raises before anything is launched."""
+    v = dict(WARP_OFF)
+    for k, x in (values or {}).items():
+        if k not in WARP_OFF:
+            raise SpeechLLMError(f"unknown warper option {k!r}: {sorted(WARP_OFF)}")
+        if x is not None:
+            v[k] = float(x)
+    if not 0.0 <= v["min_p"] <= 1.0:
+        raise SpeechLLMError(f"min_p {v['min_p']!r} outside [0, 1]")
+    if not 0.0 < v["typical_p"] <= 1.0:
+        raise SpeechLLMError(f"typical_p {v['typical_p']!r} outside (0, 1]")
+    for k in ("epsilon_cutoff", "eta_cutoff"):
+        if not 0.0 <= v[k] < 1.0:
+            raise SpeechLLMError(f"{k} {v[k]!r} outside [0, 1)")
+    if v == WARP_OFF:
+        return None
+    return WarpOpts(**v)
+
+
 class ScoreOpts(C.Structure):
     """sl_score_opts: lm_head rows per pass of sl_llama_score (0 = default) and the path switch (0 = rule, 1 = fp32 logits, 2 = fused)"""
     _fields_ = [("row_chunk", c_i32), ("force_path", c_i32), ("reserved", c_i32 * 6)]
@@ -402,6 +431,12 @@ _PROTOS = {
     "sl_generate_workspace_bytes_cont": (c_sz, [C.POINTER(LlamaModel), c_i64, c_i32, c_i32, C.POINTER(LogitsOpts), c_i32]),
     "sl_generate_cont": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(GenerateOpts), C.POINTER(c_i32),
                                  C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts), C.POINTER(c_f32), C.POINTER(c_i32), C.POINTER(c_i32)]),
+    # min_p / typical_p / epsilon_cutoff / eta_cutoff in the device sampler (additive to ABI 7)
+    "sl_sample_select_w": (c_i32, [c_vp, c_i32, c_i32, c_f32, c_i32, c_f32, C.c_uint64, C.POINTER(c_i32), c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp, c_i32, c_vp, c_vp, c_vp, C.POINTER(WarpOpts)]),
+    "sl_generate_w": (c_i32, [C.POINTER(LlamaModel), C.POINTER(KVCache), c_vp, C.POINTER(c_i32), c_i32, C.POINTER(GenerateOpts), C.POINTER(c_i32),
+                              C.POINTER(GenerateStats), c_vp, c_sz, c_vp, C.POINTER(LogitsOpts), C.POINTER(c_f32), c_i32, C.POINTER(c_i32), C.POINTER(c_i32),
+                              C.POINTER(WarpOpts)]),
     # teacher-forced scoring (additive to ABI 7)
     "sl_gemm_top1_lse_tgt": (c_i32, [C.POINTER(GemmArgs), C.POINTER(GemmEx), c_vp, c_vp, c_vp, c_vp]),
     "sl_score_finalize": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),

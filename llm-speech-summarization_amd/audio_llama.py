@@ -214,7 +214,8 @@ class AudioLlamaForCausalLM:
                                                  do_sample=False, temperature=1.0, top_k=50, top_p=1.0, hub_do_sample=None,
                                                  num_beams=1, length_penalty=1.0, early_stopping=False, num_return_sequences=1,
                                                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
-                                                 return_dict_in_generate=False, output_scores=False)
+                                                 return_dict_in_generate=False, output_scores=False,
+                                                 min_p=None, typical_p=1.0, epsilon_cutoff=0.0, eta_cutoff=0.0)
         self.sample_seed = 0
         self._sd = state_dict
         self.device = torch.device("cpu")
@@ -259,12 +260,22 @@ class AudioLlamaForCausalLM:
             g = obj.generation_config
             g.temperature, g.top_k, g.top_p = float(gc.get("temperature", 1.0)), int(gc.get("top_k", 50)), float(gc.get("top_p", 1.0))
             g.hub_do_sample = bool(gc.get("do_sample", False))
+            cls.apply_warper_config(g, gc)
             if gc.get("eos_token_id") is not None:
                 e = gc["eos_token_id"]
                 g.eos_token_id = list(e) if isinstance(e, (list, tuple)) else [e]
             if gc.get("pad_token_id") is not None:
                 g.pad_token_id = gc["pad_token_id"]
         return obj
+
+    @staticmethod
+    def apply_warper_config(g, values: dict) -> None:
+        """min_p / typical_p / epsilon_cutoff / eta_cutoff of a generation_config.json (or of the yaml's runtime section) -> `g`; a key
+        that is absent or null leaves the field as it is, a value outside its range raises (L.warp_opts)."""
+        found = {k: values[k] for k in L.WARP_OFF if values.get(k) is not None}
+        L.warp_opts(found)
+        for k, v in found.items():
+            setattr(g, k, float(v))
 
     def eval(self):
         return self
@@ -595,7 +606,9 @@ class AudioLlamaForCausalLM:
                  top_p: Optional[float] = None, seed: Optional[int] = None, num_beams: Optional[int] = None,
                  length_penalty: Optional[float] = None, early_stopping=None, num_return_sequences: Optional[int] = None,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, min_new_tokens: Optional[int] = None,
-                 return_dict_in_generate: Optional[bool] = None, output_scores: Optional[bool] = None, past_key_values: Optional[KVSession] = None, **unused):
+                 return_dict_in_generate: Optional[bool] = None, output_scores: Optional[bool] = None, past_key_values: Optional[KVSession] = None,
+                 min_p: Optional[float] = None, typical_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
+                 eta_cutoff: Optional[float] = None, **unused):
         """past_key_values=<KVSession> (llm.new_session(B)): the call runs in the session's cache and CONTINUES it — the prompt rows are the
         new rows only (the follow-up question), the earlier turns are the cache; see generate_packed(session=).  Not with num_beams > 1 or
         num_return_sequences > 1.
@@ -610,7 +623,10 @@ class AudioLlamaForCausalLM:
         log_softmax(the scores the selection saw)[chosen token] — HF's compute_transition_scores(normalize_logits=True) — 0.0 at and after
         a row's finish.  sequences_scores: `last_beam_scores` in beam mode, else the per-row sum of token_logprobs when scores are on.
         output_scores without return_dict_in_generate returns the tensor and sets `last_token_logprobs`.  Beam search with output_scores
-        raises: per-token scores along beam back-pointers are not built."""
+        raises: per-token scores along beam back-pointers are not built.
+        min_p / typical_p / epsilon_cutoff / eta_cutoff: HF's four further warpers behind temperature / top-k / top-p, in HF's order, in the
+        device sampler; None falls back to `generation_config` (None / 1.0 / 0.0 / 0.0 = off: the call is then exactly the
+        call without them).  A value outside its range raises; without do_sample they are ignored, as temperature is."""
         g = self.generation_config
         ret_dict = bool(getattr(g, "return_dict_in_generate", False) if return_dict_in_generate is None else return_dict_in_generate)
         want_scores = bool(getattr(g, "output_scores", False) if output_scores is None else output_scores)
@@ -653,7 +669,12 @@ class AudioLlamaForCausalLM:
             if seed is None:
                 seed, self.sample_seed = self.sample_seed, self.sample_seed + 1
             sample = dict(temperature=float(g.temperature if temperature is None else temperature), top_k=int(g.top_k if top_k is None else top_k),
-                          top_p=float(g.top_p if top_p is None else top_p), seed=int(seed))
+                          top_p=float(g.top_p if top_p is None else top_p), seed=int(seed),
+                          min_p=getattr(g, "min_p", None) if min_p is None else min_p,
+                          typical_p=getattr(g, "typical_p", None) if typical_p is None else typical_p,
+                          epsilon_cutoff=getattr(g, "epsilon_cutoff", None) if epsilon_cutoff is None else epsilon_cutoff,
+                          eta_cutoff=getattr(g, "eta_cutoff", None) if eta_cutoff is None else eta_cutoff)
+            L.warp_opts({k: sample[k] for k in L.WARP_OFF})      # a value out of range raises here, before any device work
         if not want_scores:
             ids, n_cols = self.generate_packed(x, lens, max_new_tokens, use_eos=use_eos, sample=sample, logits=logits, num_return=R, **skw)
             seqs = ids[:, :n_cols].to(torch.int64)
@@ -736,6 +757,8 @@ class AudioLlamaForCausalLM:
         scores=True: returns (ids, n_cols, logprobs), logprobs a float32 (B, max_new) host tensor of the chosen tokens' log-probabilities
         (sl_generate_sc; 0.0 at and after a row's finish); above 64 rows a greedy step keeps the fused lm_head top-1 and carries a third
         partial.  Not with beams.  False: exactly the call without them.
+        sample: dict(temperature, top_k, top_p, seed) and, optionally, min_p / typical_p / epsilon_cutoff / eta_cutoff (None or the off value
+        0 / 1.0 / 0 / 0: off) -> one draw per row and step (sl_generate_w when one of the four is on; a dict without them is the call it was).
         num_return = R > 1 (sampling only): R answers per prompt from ONE prefill (sl_generate_n) -> (B * R, max_new) ids / logprobs,
         prompt-major; row_limits then has B * R entries; the cache holds B prompt slots + B * R row slots.  The draws are those of a call
         on every prompt repeated R times.  `last_generate_stats` has prefill_seqs and attn_path ("copy" / "grouped").
@@ -799,6 +822,8 @@ class AudioLlamaForCausalLM:
         if sample is not None:
             o.sample, o.temperature, o.top_k, o.top_p = 1, float(sample["temperature"]), int(sample["top_k"]), float(sample["top_p"])
             o.seed = int(sample["seed"]) & 0xFFFFFFFFFFFFFFFF
+        # min_p / typical_p / epsilon_cutoff / eta_cutoff: None when every one is off, and the calls below are then the ones they were
+        wp = None if sample is None else L.warp_opts({k: sample.get(k) for k in L.WARP_OFF})
         st = L.GenerateStats()
         lp = self._logits_struct(logits, max_new_tokens)
         lp_ref = C.byref(lp) if lp is not None else None
@@ -811,8 +836,12 @@ class AudioLlamaForCausalLM:
             if nbytes == 0:
                 L.check(-1, "sl_generate_workspace_bytes_n")
             ws = self._workspace(nbytes)
-            L.check(lib.sl_generate_n(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, n_prompts, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
-                                      L.stream_ptr(), lp_ref, lps, R), "sl_generate_n")
+            if wp is not None:
+                L.check(lib.sl_generate_w(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, n_prompts, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+                                          L.stream_ptr(), lp_ref, lps, R, None, None, C.byref(wp)), "sl_generate_w")
+            else:
+                L.check(lib.sl_generate_n(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, n_prompts, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+                                          L.stream_ptr(), lp_ref, lps, R), "sl_generate_n")
             self._record_generate_stats(st, B, fmt_name, prefill_seqs=n_prompts, num_return_sequences=R,
                                         attn_path={1: "copy", 2: "grouped"}[int(lib.sl_generate_last_attn_path())])
             ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B, max_new_tokens)
@@ -823,8 +852,12 @@ class AudioLlamaForCausalLM:
             lps = (C.c_float * (B * max_new_tokens))() if scores else None
             past_c = (C.c_int32 * B)(*session.valid_len)
             ws = self._workspace(lib.sl_generate_workspace_bytes_cont(C.byref(struct), x.shape[0], B, max_new_tokens, lp_ref, int(bool(scores))))
-            L.check(lib.sl_generate_cont(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
-                                         L.stream_ptr(), lp_ref, lps, past_c, None), "sl_generate_cont")
+            if wp is not None:
+                L.check(lib.sl_generate_w(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+                                          L.stream_ptr(), lp_ref, lps, 1, past_c, None, C.byref(wp)), "sl_generate_w")
+            else:
+                L.check(lib.sl_generate_cont(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+                                             L.stream_ptr(), lp_ref, lps, past_c, None), "sl_generate_cont")
             ids = torch.frombuffer(out, dtype=torch.int32).clone().view(B, max_new_tokens)
             gen = self.generation_config
             eos = (list(gen.eos_token_id) if isinstance(gen.eos_token_id, (list, tuple)) else ([] if gen.eos_token_id is None else [gen.eos_token_id])) if use_eos else []
@@ -833,7 +866,12 @@ class AudioLlamaForCausalLM:
             if scores:
                 return ids, int(st.n_steps), torch.frombuffer(lps, dtype=torch.float32).clone().view(B, max_new_tokens)
             return ids, int(st.n_steps)
-        if scores:
+        if wp is not None:      # the workspace is the unwarped call's (speechllm.h)
+            lps = (C.c_float * (B * max_new_tokens))() if scores else None
+            ws = self._workspace(lib.sl_generate_workspace_bytes_sc(C.byref(struct), x.shape[0], B, max_new_tokens, lp_ref, int(bool(scores))))
+            L.check(lib.sl_generate_w(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),
+                                      L.stream_ptr(), lp_ref, lps, 1, None, None, C.byref(wp)), "sl_generate_w")
+        elif scores:
             lps = (C.c_float * (B * max_new_tokens))()
             ws = self._workspace(lib.sl_generate_workspace_bytes_sc(C.byref(struct), x.shape[0], B, max_new_tokens, lp_ref, 1))
             L.check(lib.sl_generate_sc(C.byref(struct), C.byref(kv), x.data_ptr(), cu_c, B, C.byref(o), out, C.byref(st), ws.data_ptr(), ws.numel(),

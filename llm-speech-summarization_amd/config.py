@@ -112,6 +112,25 @@ def runtime_logits(config):
     return out
 
 
+def runtime_warpers(config):
+    """The sampling warpers a config's `runtime` section names: optional `min_p`, `typical_p`, `epsilon_cutoff`, `eta_cutoff` -> the dict of
+    those present (empty in the shipped yamls), each a number in its range (min_p [0, 1], typical_p (0, 1], the cutoffs [0, 1)); they set
+    the llm's generation_config and act where a call samples."""
+    rt = config.get("runtime", {}) if hasattr(config, "get") else {}
+    rt = rt or {}
+    ranges = dict(min_p=lambda v: 0.0 <= v <= 1.0, typical_p=lambda v: 0.0 < v <= 1.0, epsilon_cutoff=lambda v: 0.0 <= v < 1.0,
+                  eta_cutoff=lambda v: 0.0 <= v < 1.0)
+    out = {}
+    for key, ok in ranges.items():
+        v = rt.get(key)
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(v):
+            raise ValueError(f"runtime.{key}: {v!r} is outside its range")
+        out[key] = float(v)
+    return out
+
+
 def runtime_beams(config):
     """The beam-search options a config's `runtime` section names: optional `num_beams` (default 1 = greedy), `length_penalty` (1.0) and
     `early_stopping` (false / true / "never") -> None for greedy, else the dict the `beams` keyword of generate_packed takes."""

@@ -674,6 +674,14 @@ int main() {
     memset(&go, 0, sizeof(go));
     go.max_new_tokens = 16;
     EXPECT_ARG_ERROR(sl_generate_sc(nullptr, nullptr, nullptr, nullptr, 1, &go, nullptr, nullptr, nullptr, 0, nullptr, nullptr, (float*)ws));
+    // min_p / typical_p / epsilon_cutoff / eta_cutoff: a value outside its range is refused before any launch, by both entries
+    const sl_warp_opts bad[] = {{-0.1f, 1.f, 0.f, 0.f}, {1.5f, 1.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 1.5f, 0.f, 0.f}, {0.f, 1.f, 1.f, 0.f},
+                                {0.f, 1.f, -0.1f, 0.f}, {0.f, 1.f, 0.f, 1.f}, {0.f, 1.f, 0.f, NAN}, {NAN, 1.f, 0.f, 0.f}};
+    for (const sl_warp_opts& w : bad) {
+      EXPECT_ARG_ERROR(sl_sample_select_w((const float*)ws, 4, 100, 1.f, 0, 1.f, 1, eos, 3, 0, 1, ctx, ctx, ctx, ctx, ctx, out_ids, 8, ctx, (float*)ws, nullptr, &w));
+      EXPECT_ARG_ERROR(sl_generate_w(nullptr, nullptr, nullptr, nullptr, 1, &go, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 1, nullptr, nullptr, &w));
+    }
+    EXPECT(sizeof(sl_warp_opts) == 16, "sl_warp_opts is four floats");
   }
   if (g_fail == 0) printf("argcheck ok\n");
   return g_fail == 0 ? 0 : 1;

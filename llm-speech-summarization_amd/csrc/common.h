@@ -592,4 +592,7 @@ int sl_greedy_select_impl(const float* logits, int32_t B, int32_t V, const SlRow
 int sl_greedy_select_partial_impl(const float* amax_val, const int32_t* amax_idx, const float* amax_sum, int32_t n_groups, int32_t B, const SlRowState& rs,
                                   hipStream_t st);
 int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed, int32_t* choice_ws,
-                          const int32_t* row_ids, const SlRowState& rs, hipStream_t st);
+                          const int32_t* row_ids, const SlRowState& rs, hipStream_t st, const sl_warp_opts* warp = nullptr);
+// the ranges of speechllm.h's sl_warp_opts (NULL passes); refused values land in sl_last_error
+int sl_warp_opts_check(const char* who, const sl_warp_opts* w);
+bool sl_warp_opts_on(const sl_warp_opts* w);      // some option is on (NULL: none)

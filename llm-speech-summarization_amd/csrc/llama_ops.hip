@@ -639,14 +639,219 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
   }
 }
 
+// ----------------------------------------------------------------------------------------------
+// The warped form: sample_rows_kernel with HF's four further warpers behind top-p, in HF's order — min_p, typical_p,
+// epsilon_cutoff, eta_cutoff.  With a = (x - m) / T the warped score relative to the row maximum, a survivor is a token with
+//   ord_key(x) >= keep_key   (top-k / top-p, as above)
+//   a >= a_lo                (min_p: ln min_p;  the cutoffs: min(ln(eta Z), largest a in S), so the largest score in S always stays)
+//   |a - c| <= d_hi          (typical_p: c = sum_S p a / Z is ln Z - H, so |a - c| IS |-ln p - H|; a band in score that may drop m)
+// d_hi comes from the by-mass radix selection above run on the inverted bits of |a - c| (a float >= 0 orders as its bits do): dropped iff
+// the mass of the strictly smaller distances is >= typical_p Z.  Every stage that needs Z, sum p a or the largest a of its S takes them in
+// ONE pass over the row (stage_stats); min_p takes none.  Masses stay relative to m: a survivor of a band that dropped m still holds at
+// least V^-2, far above what fp32 and the 2^-40 histogram lose.  The draw and the log-probability are sample_rows_kernel's.
+// ----------------------------------------------------------------------------------------------
+struct WarpArgs { float ln_min_p, typical_p, eps, eta; };    // ln_min_p = -inf, typical_p = 1, eps = eta = 0: off
+
+// bits of |a - c|, never contracted with the product that made a: the selection's histogram and the survivor predicate must see the SAME
+// distance for a token, or the token on the boundary could be binned on one side and tested on the other
+__device__ __forceinline__ uint32_t dist_bits(float a, float c) {
+#pragma clang fp contract(off)
+  return __float_as_uint(fabsf(a - c));
+}
+
+__global__ __launch_bounds__(1024) void sample_rows_warp_kernel(const float* __restrict__ logits, int V, float inv_temp, int top_k, float top_p, uint64_t seed,
+                                                                const int32_t* __restrict__ gen_count, int32_t* __restrict__ choice,
+                                                                const int32_t* __restrict__ row_ids, float* __restrict__ logprob_out, int max_new, WarpArgs wa) {
+  __shared__ float redf[3][16];
+  __shared__ int hcnt[256];
+  __shared__ unsigned long long hmass_fx[256];   // 2^-40 fixed point, as in sample_rows_kernel: the bin totals are the same on every run
+  __shared__ uint32_t s_prefix;
+  __shared__ float s_above;
+  __shared__ float part[1024];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* rowp = logits + (int64_t)b * V;
+  auto row = [&](int i) { const float x = rowp[i]; return x != x ? -INFINITY : x; };
+  float m = -INFINITY;
+  for (int i = tid; i < V; i += 1024) m = fmaxf(m, row(i));
+  m = wave_max(m);
+  if (lane == 0) redf[0][wave] = m;
+  __syncthreads();
+  m = redf[0][0];
+  for (int w = 1; w < 16; ++w) m = fmaxf(m, redf[0][w]);
+  __syncthreads();
+  if (m == -INFINITY) {
+    if (tid == 0) {
+      choice[b] = 0;
+      const int step = gen_count[b];
+      if (logprob_out && step < max_new) logprob_out[(int64_t)b * max_new + step] = -INFINITY;
+    }
+    return;
+  }
+  auto score = [&](float x) { return (x - m) * inv_temp; };
+  auto prob = [&](float x) { return __expf((x - m) * inv_temp); };
+
+  // the survivor predicate: what every later stage and the draw see
+  uint32_t keep_key = 0, d_hi = 0xFFFFFFFFu;
+  float a_lo = -INFINITY, c = 0.f;
+  auto alive = [&](float x) {
+    if (ord_key(x) < keep_key) return false;
+    const float a = score(x);
+    return a >= a_lo && dist_bits(a, c) <= d_hi;
+  };
+  auto score_key = [&](float x) { return ord_key(x); };
+  auto dist_key = [&](float x) { return ~dist_bits(score(x), c); };   // larger key = closer to the expected -ln p
+
+  // sample_rows_kernel's radix selection over key_of(x), among the tokens alive now
+  auto radix_select = [&](int mode, float limit, auto key_of) -> uint32_t {
+    uint32_t prefix = 0;
+    float above = 0.f;
+    for (int pass = 0; pass < 4; ++pass) {
+      const int shift = 24 - 8 * pass;
+      const uint32_t hi_mask = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
+      for (int i = tid; i < 256; i += 1024) { hcnt[i] = 0; hmass_fx[i] = 0ull; }
+      __syncthreads();
+      for (int i = tid; i < V; i += 1024) {
+        const float x = row(i);
+        if (!alive(x)) continue;
+        const uint32_t k = key_of(x);
+        if ((k & hi_mask) != prefix) continue;
+        const int bin = (k >> shift) & 255;
+        if (mode == 0) atomicAdd(&hcnt[bin], 1);
+        else atomicAdd(&hmass_fx[bin], (unsigned long long)(prob(x) * 1099511627776.0f));
+      }
+      __syncthreads();
+      if (tid == 0) {
+        float run = above;
+        int sel = -1;
+        for (int bin = 255; bin >= 0; --bin) {
+          const float w = mode == 0 ? (float)hcnt[bin] : (float)hmass_fx[bin] * (1.0f / 1099511627776.0f);
+          if (mode == 0 ? (hcnt[bin] > 0 && run + w >= limit) : (hmass_fx[bin] > 0ull && run + w >= limit)) { sel = bin; break; }
+          run += w;
+        }
+        if (sel < 0) {           // the limit is never reached: the smallest populated bin
+          for (int bin = 255; bin >= 0; --bin)
+            if (mode == 0 ? hcnt[bin] > 0 : hmass_fx[bin] > 0ull) sel = bin;
+          run = above;
+          for (int bin = 255; bin > sel; --bin) run += mode == 0 ? (float)hcnt[bin] : (float)hmass_fx[bin] * (1.0f / 1099511627776.0f);
+          if (sel < 0) sel = 0;
+        }
+        s_prefix = prefix | ((uint32_t)sel << shift);
+        s_above = run;
+      }
+      __syncthreads();
+      prefix = s_prefix;
+      above = s_above;
+      __syncthreads();
+    }
+    return prefix;
+  };
+
+  // one pass over the survivors: z = sum p, s1 = sum p a (a token of mass zero adds nothing to either), amax = the largest a
+  auto stage_stats = [&](float& z, float& s1, float& amax) {
+    float lz = 0.f, ls = 0.f, la = -INFINITY;
+    for (int i = tid; i < V; i += 1024) {
+      const float x = row(i);
+      if (!alive(x)) continue;
+      const float a = score(x), p = __expf(a);
+      la = fmaxf(la, a);
+      if (p > 0.f) { lz += p; ls += p * a; }
+    }
+    lz = wave_sum(lz); ls = wave_sum(ls); la = wave_max(la);
+    __syncthreads();
+    if (lane == 0) { redf[0][wave] = lz; redf[1][wave] = ls; redf[2][wave] = la; }
+    __syncthreads();
+    z = 0.f; s1 = 0.f; amax = -INFINITY;
+    for (int w = 0; w < 16; ++w) { z += redf[0][w]; s1 += redf[1][w]; amax = fmaxf(amax, redf[2][w]); }
+  };
+
+  float z, s1, amax;
+  if (top_k > 0 && top_k < V) keep_key = radix_select(0, (float)top_k, score_key);
+  if (top_p < 1.0f) {
+    stage_stats(z, s1, amax);
+    const uint32_t kp = radix_select(1, top_p * z, score_key);
+    keep_key = kp > keep_key ? kp : keep_key;
+  }
+  a_lo = wa.ln_min_p;                                  // the largest score of S is m here (a = 0 >= ln min_p): it and its ties stay
+  if (wa.typical_p < 1.0f) {
+    stage_stats(z, s1, amax);
+    c = s1 / z;
+    d_hi = ~radix_select(1, wa.typical_p * z, dist_key);
+  }
+  if (wa.eps > 0.f) {
+    stage_stats(z, s1, amax);
+    a_lo = fmaxf(a_lo, fminf(logf(wa.eps * z), amax));
+  }
+  if (wa.eta > 0.f) {
+    stage_stats(z, s1, amax);
+    const float lnz = logf(z), h = lnz - s1 / z, le = logf(wa.eta);
+    a_lo = fmaxf(a_lo, fminf(fminf(le, 0.5f * le - h) + lnz, amax));
+  }
+  // the draw: sample_rows_kernel's, over the survivors
+  const int Cn = (V + 1023) / 1024;
+  const int i0 = tid * Cn, i1 = (i0 + Cn) < V ? (i0 + Cn) : V;
+  float loc = 0.f;
+  for (int i = i0; i < i1; ++i) { const float x = row(i); if (alive(x)) loc += prob(x); }
+  part[tid] = loc;
+  __syncthreads();
+  if (tid == 0) {
+    float zt = 0.f;
+    for (int t = 0; t < 1024; ++t) zt += part[t];
+    const uint32_t step = (uint32_t)gen_count[b];
+    const uint32_t rid = row_ids ? (uint32_t)row_ids[b] : (uint32_t)b;
+    const uint32_t h = lowbias32(step ^ lowbias32(rid ^ (uint32_t)seed) ^ (uint32_t)(seed >> 32));
+    const float u = (float)(h >> 8) * (1.0f / 16777216.0f);
+    const float target = u * zt;
+    float run = 0.f;
+    int t = 0;
+    for (; t < 1023; ++t) { if (run + part[t] > target) break; run += part[t]; }
+    int pick = -1, last = -1;
+    const int j0 = t * Cn, j1 = (j0 + Cn) < V ? (j0 + Cn) : V;
+    for (int i = j0; i < j1; ++i) {
+      const float x = row(i);
+      if (!alive(x)) continue;
+      const float p = prob(x);
+      if (p > 0.f) last = i;
+      run += p;
+      if (run > target) { pick = i; break; }
+    }
+    if (pick < 0) pick = last;
+    if (pick < 0) {
+      for (int i = 0; i < V; ++i) { const float x = row(i); if (alive(x) && prob(x) > 0.f) { pick = i; break; } }
+    }
+    choice[b] = pick < 0 ? 0 : pick;
+    if (logprob_out && (int)step < max_new) logprob_out[(int64_t)b * max_new + step] = logf(prob(row(pick < 0 ? 0 : pick)) / zt);
+  }
+}
+
+// NULL or every option at its off value: no warped form
+bool sl_warp_opts_on(const sl_warp_opts* w) {
+  return w && (w->min_p != 0.f || w->typical_p != 1.0f || w->epsilon_cutoff != 0.f || w->eta_cutoff != 0.f);
+}
+// the `!(..)` forms refuse NaN
+int sl_warp_opts_check(const char* who, const sl_warp_opts* w) {
+  if (!w) return 0;
+  SL_CHECK_ARG(w->min_p >= 0.f && w->min_p <= 1.0f, "%s: min_p %f outside [0, 1]", who, (double)w->min_p);
+  SL_CHECK_ARG(w->typical_p > 0.f && w->typical_p <= 1.0f, "%s: typical_p %f outside (0, 1]", who, (double)w->typical_p);
+  SL_CHECK_ARG(w->epsilon_cutoff >= 0.f && w->epsilon_cutoff < 1.0f, "%s: epsilon_cutoff %f outside [0, 1)", who, (double)w->epsilon_cutoff);
+  SL_CHECK_ARG(w->eta_cutoff >= 0.f && w->eta_cutoff < 1.0f, "%s: eta_cutoff %f outside [0, 1)", who, (double)w->eta_cutoff);
+  return 0;
+}
+
 int sl_sample_select_impl(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed, int32_t* choice_ws,
-                          const int32_t* row_ids, const SlRowState& rs, hipStream_t st) {
+                          const int32_t* row_ids, const SlRowState& rs, hipStream_t st, const sl_warp_opts* warp) {
   SL_CHECK_ARG(logits && row_state_ok(rs) && choice_ws && B > 0 && V > 0, "sl_sample_select: bad arguments");
   SL_CHECK_ARG(temperature > 0.f && top_p > 0.f && top_p <= 1.0f && top_k >= 0, "sl_sample_select: need temperature > 0, 0 < top_p <= 1, top_k >= 0 (got %f, %f, %d)",
                (double)temperature, (double)top_p, top_k);
   SL_CHECK_ARG(rs.n_eos >= 0 && rs.n_eos <= 8, "sl_sample_select: at most 8 eos ids");
-  hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(1024), 0, st, logits, V, 1.0f / temperature, top_k, top_p, seed, rs.gen_count, choice_ws, row_ids,
-                     rs.logprob_out, rs.max_new);
+  SL_TRY(sl_warp_opts_check("sl_sample_select_w", warp));
+  if (sl_warp_opts_on(warp)) {
+    const WarpArgs wa{warp->min_p > 0.f ? logf(warp->min_p) : -INFINITY, warp->typical_p, warp->epsilon_cutoff, warp->eta_cutoff};
+    hipLaunchKernelGGL(sample_rows_warp_kernel, dim3(B), dim3(1024), 0, st, logits, V, 1.0f / temperature, top_k, top_p, seed, rs.gen_count, choice_ws,
+                       row_ids, rs.logprob_out, rs.max_new, wa);
+  } else {
+    hipLaunchKernelGGL(sample_rows_kernel, dim3(B), dim3(1024), 0, st, logits, V, 1.0f / temperature, top_k, top_p, seed, rs.gen_count, choice_ws, row_ids,
+                       rs.logprob_out, rs.max_new);
+  }
   SL_CHECK_LAUNCH("sample_rows");
   auto* kern = rs.logprob_out ? greedy_select_kernel<true> : greedy_select_kernel<false>;
   hipLaunchKernelGGL(kern, dim3(B), dim3(64), 0, st, logits, V, eos_list(rs), rs, (const int32_t*)choice_ws);
@@ -668,6 +873,14 @@ extern "C" int sl_sample_select_sc(const float* logits, int32_t B, int32_t V, fl
                                    float* logprob_out, sl_stream stream) {
   const SlRowState rs{unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, nullptr, logprob_out, eos_ids, n_eos, pad_id, use_eos, 1};
   return sl_sample_select_impl(logits, B, V, temperature, top_k, top_p, seed, choice_ws, nullptr, rs, (hipStream_t)stream);
+}
+
+extern "C" int sl_sample_select_w(const float* logits, int32_t B, int32_t V, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                                  const int32_t* eos_ids, int32_t n_eos, int32_t pad_id, int32_t use_eos, int32_t* unfinished, int32_t* ctx_len,
+                                  int32_t* gen_count, int32_t* finish_len, int32_t* next_ids, int32_t* out_ids, int32_t max_new, int32_t* choice_ws,
+                                  float* logprob_out, sl_stream stream, const sl_warp_opts* warp) {
+  const SlRowState rs{unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, max_new, nullptr, logprob_out, eos_ids, n_eos, pad_id, use_eos, 1};
+  return sl_sample_select_impl(logits, B, V, temperature, top_k, top_p, seed, choice_ws, nullptr, rs, (hipStream_t)stream, warp);
 }
 
 extern "C" int sl_greedy_select(const float* logits, int32_t B, int32_t V, const int32_t* eos_ids, int32_t n_eos, int32_t pad_id,

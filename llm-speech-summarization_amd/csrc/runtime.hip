@@ -1350,6 +1350,7 @@ struct DecodeGraphKey {
   int eos[8];
   int sample, top_k;
   float temperature, top_p;
+  float min_p, typical_p, epsilon_cutoff, eta_cutoff;   // the warped sampler (all 0 in a graph without it)
   uint64_t seed;
   int beam_k, beam_m, beam_es;     // beam search (0 in every other graph: a beam graph and a greedy graph never share a key)
   float beam_lp;
@@ -1471,7 +1472,7 @@ static int compact_rung(int n_live) {
   return (n_live + 63) / 64 * 64;
 }
 
-struct SampleOpts { float temperature; int top_k; float top_p; uint64_t seed; };
+struct SampleOpts { float temperature; int top_k; float top_p; uint64_t seed; sl_warp_opts warp; bool warped; };   // warped: some option of warp is on
 
 // the three timing events of a generate call, destroyed on every way out of it
 struct Events3 {
@@ -1528,6 +1529,7 @@ static int decode_graph_key(const GraphCtx& g, int B, DecodeGraphKey& key) {
   SL_HIP(hipGetDevice(&key.device));
   for (int i = 0; i < g.n_eos && i < 8; ++i) key.eos[i] = g.eos[i];
   if (g.smp) { key.sample = 1; key.temperature = g.smp->temperature; key.top_k = g.smp->top_k; key.top_p = g.smp->top_p; key.seed = g.smp->seed; }
+  if (g.smp && g.smp->warped) { key.min_p = g.smp->warp.min_p; key.typical_p = g.smp->warp.typical_p; key.epsilon_cutoff = g.smp->warp.epsilon_cutoff; key.eta_cutoff = g.smp->warp.eta_cutoff; }
   key.beam_k = g.beam_k; key.beam_m = g.beam_m; key.beam_es = g.beam_es; key.beam_lp = g.beam_lp;
   if (g.lp->on) { key.lp_penalty = g.lp->o.repetition_penalty; key.lp_ngram = g.lp->o.no_repeat_ngram_size; key.lp_min_new = g.lp->o.min_new_tokens; }
   key.scores = g.scores;
@@ -1702,8 +1704,9 @@ extern "C" size_t sl_generate_workspace_bytes_n(const sl_llama_model* m, int64_t
 static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
                          const sl_generate_opts* o, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
                          sl_stream stream, const sl_logits_opts* lp_opts = nullptr, float* out_lp_host = nullptr, int N = 1, const int32_t* past_host = nullptr,
-                         const int32_t* slot_host = nullptr) {
+                         const int32_t* slot_host = nullptr, const sl_warp_opts* warp = nullptr) {
   SL_CHECK_ARG(o != nullptr, "sl_generate: null options");
+  SL_TRY(sl_warp_opts_check("sl_generate_w", warp));      // a value out of range is refused first, and named
   // sl_generate_cont: the caller keeps the cache.  Refused before anything is launched: compaction (it moves live rows into the slots of finished
   // ones and destroys their K / V), several answers per prompt, and slots other than the identity (a decode row's slot is its row index)
   bool past_any = false;      // some sequence continues: the shared-prefix promise is then about the cache ([0, P) below every past)
@@ -1741,7 +1744,8 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
   const int B0 = nseq * N;         // decode rows: row s * N + j is answer j of prompt s
   SL_TRY(llama_wformat_check("sl_generate", m, B0, SL_ENTRY_DECODE));      // compaction only moves down the row ladder: a call that starts within the e4m3 range stays within it
   SL_CHECK_ARG(n_eos >= 0 && n_eos <= 8 && (n_eos == 0 || eos_ids_host != nullptr), "sl_generate: 0..8 eos ids");
-  SampleOpts smp_s{o->temperature, o->top_k, o->top_p, o->seed};
+  SampleOpts smp_s{o->temperature, o->top_k, o->top_p, o->seed, {0.f, 1.0f, 0.f, 0.f}, sl_warp_opts_on(warp)};
+  if (smp_s.warped) smp_s.warp = *warp;
   const SampleOpts* smp = o->sample ? &smp_s : nullptr;
   if (smp) SL_CHECK_ARG(smp->temperature > 0.f && smp->top_p > 0.f && smp->top_p <= 1.0f && smp->top_k >= 0, "sl_generate: sampling needs temperature > 0, 0 < top_p <= 1, top_k >= 0");
   hipStream_t st = (hipStream_t)stream;
@@ -1831,7 +1835,8 @@ static int generate_impl(const sl_llama_model* m, const sl_kv_cache* kv, void* x
       SL_TRY(sl_logits_process_impl(logits, B, m->vocab, rs.out_ids, nullptr, max_new_tokens, rs.gen_count, rs.unfinished, &lp.o, eos_ids_host, n_eos, 0,
                                     tab.d<float>(RT::LPS), s_));
     if (smp)
-      return sl_sample_select_impl(logits, B, m->vocab, smp->temperature, smp->top_k, smp->top_p, smp->seed, tab.d<int32_t>(RT::CHOICE), tab.d<int32_t>(RT::ROW), rs, s_);
+      return sl_sample_select_impl(logits, B, m->vocab, smp->temperature, smp->top_k, smp->top_p, smp->seed, tab.d<int32_t>(RT::CHOICE), tab.d<int32_t>(RT::ROW), rs, s_,
+                                   smp->warped ? &smp->warp : nullptr);
     return sl_greedy_select_impl(logits, B, m->vocab, rs, s_);
   };
   SL_TRY(select(B0, st));
@@ -1989,6 +1994,14 @@ extern "C" int sl_generate_n(const sl_llama_model* m, const sl_kv_cache* kv, voi
                              sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host, int32_t num_return_sequences) {
   return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream, lp, out_logprobs_host,
                        num_return_sequences);
+}
+
+extern "C" int sl_generate_w(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq,
+                             const sl_generate_opts* opts, int32_t* out_ids_host, sl_generate_stats* stats, void* workspace, size_t workspace_bytes,
+                             sl_stream stream, const sl_logits_opts* lp, float* out_logprobs_host, int32_t num_return_sequences,
+                             const int32_t* past_len_host, const int32_t* slot_host, const sl_warp_opts* warp) {
+  return generate_impl(m, kv, x, cu_seqlens_host, nseq, opts, out_ids_host, stats, workspace, workspace_bytes, stream, lp, out_logprobs_host,
+                       num_return_sequences, past_len_host, slot_host, warp);
 }
 
 static int generate_compat(const sl_llama_model* m, const sl_kv_cache* kv, void* x, const int32_t* cu_seqlens_host, int32_t nseq, sl_generate_opts& o,

@@ -81,7 +81,7 @@ class LLMSpeechTextInference():
             raise L.SpeechLLMError("linear_dtype differs from the layer-product format of the llm that was passed in: construct that llm with the same linear_dtype")
         self.llm = llm.eval().to(self.device)
         # runtime.num_beams / length_penalty / early_stopping of the config (absent in the shipped yamls: greedy) -> beam search
-        from .config import runtime_beams, runtime_logits, runtime_num_return
+        from .config import runtime_beams, runtime_logits, runtime_num_return, runtime_warpers
         self.beams = runtime_beams(self.config)
         # runtime.num_return_sequences (absent in the shipped yamls: 1) -> that many SAMPLED answers per utterance, prompt-major
         self.num_return_sequences = runtime_num_return(self.config)
@@ -89,6 +89,11 @@ class LLMSpeechTextInference():
             raise ValueError("runtime.num_return_sequences > 1 with runtime.num_beams > 1 (beam sampling) is not built")
         # runtime.repetition_penalty / no_repeat_ngram_size / min_new_tokens (absent in the shipped yamls: off) -> HF's logits processors
         self.logits = runtime_logits(self.config)
+        # runtime.min_p / typical_p / epsilon_cutoff / eta_cutoff (absent in the shipped yamls: off) -> the llm's generation_config: the sampler's
+        # further warpers wherever a call samples
+        warpers = runtime_warpers(self.config)
+        if warpers:
+            AudioLlamaForCausalLM.apply_warper_config(self.llm.generation_config, warpers)
 
     def __getattr__(self, name):
         # get_ctc_pool_ranges exists only with a segmenter: without one the class has no such attribute, as in the reference
@@ -254,7 +259,7 @@ class LLMSpeechTextInference():
         if num_return > 1:      # several answers are sampled ones: HF's warpers as llm.generate builds them
             g = self.llm.generation_config
             seed, self.llm.sample_seed = self.llm.sample_seed, self.llm.sample_seed + 1
-            sample = dict(temperature=float(g.temperature), top_k=int(g.top_k), top_p=float(g.top_p), seed=int(seed))
+            sample = dict(temperature=float(g.temperature), top_k=int(g.top_k), top_p=float(g.top_p), seed=int(seed), **self._warpers_for())
         if scores:
             ids, n_cols, lps = self.llm.generate_packed(x, lens, max_new_tokens, use_eos=True, shared_prefix=shared, beams=self.beams, logits=logits or None,
                                                         scores=True, sample=sample, num_return=num_return, **skw)
@@ -376,7 +381,17 @@ class LLMSpeechTextInference():
         return self.llm.score(prompts, self._response_ids(responses), return_top1=return_top1)
 
     # -- conversations: follow-up questions about the same recordings (an extension) -------------------------------------------------
-    def _sample_for(self, do_sample=None, temperature=None, top_k=None, top_p=None, seed=None):
+    def _warpers_for(self, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None):
+        """the generation_config's min_p / typical_p / epsilon_cutoff / eta_cutoff, each overridden by a keyword that is not None -> the
+        optional keys of generate_packed's `sample` dict (checked here: a value out of range raises before any device work)"""
+        g = self.llm.generation_config
+        given = dict(min_p=min_p, typical_p=typical_p, epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+        d = {k: (getattr(g, k, None) if v is None else v) for k, v in given.items()}
+        L.warp_opts(d)
+        return d
+
+    def _sample_for(self, do_sample=None, temperature=None, top_k=None, top_p=None, seed=None, min_p=None, typical_p=None, epsilon_cutoff=None,
+                    eta_cutoff=None):
         """HF's sampling keywords -> the `sample` dict of generate_packed (None: greedy), as llm.generate builds it"""
         g = self.llm.generation_config
         if not bool(g.do_sample if do_sample is None else do_sample):
@@ -384,14 +399,14 @@ class LLMSpeechTextInference():
         if seed is None:
             seed, self.llm.sample_seed = self.llm.sample_seed, self.llm.sample_seed + 1
         return dict(temperature=float(g.temperature if temperature is None else temperature), top_k=int(g.top_k if top_k is None else top_k),
-                    top_p=float(g.top_p if top_p is None else top_p), seed=int(seed))
+                    top_p=float(g.top_p if top_p is None else top_p), seed=int(seed), **self._warpers_for(min_p, typical_p, epsilon_cutoff, eta_cutoff))
 
     def start_conversation(self, audios, additional_text_prompts=None, max_new_tokens=256, repetition_penalty=None, no_repeat_ngram_size=None,
                            min_new_tokens=None, return_scores=False, ctc_pool_ranges=None, **sampling):
         """generate_audio_responses that KEEPS what it computed: -> (texts, conversation).  The utterances are answered in one batch whose K/V
         stays in a session of the llm (llm.new_session), and conversation.ask(texts) then answers a follow-up question per utterance for the
         cost of the new rows alone — no second pass over the audio prompt or the first answer.  One generate call's worth of utterances
-        (SL_MAX_DECODE_BATCH); greedy or sampled (do_sample / temperature / top_k / top_p / seed), never beams or several answers.
+        (SL_MAX_DECODE_BATCH); greedy or sampled (do_sample / temperature / top_k / top_p / seed / min_p / typical_p / epsilon_cutoff / eta_cutoff), never beams or several answers.
         return_scores: ((texts, scores), conversation)."""
         n = len(audios)
         texts = list(additional_text_prompts) if additional_text_prompts is not None else [""] * n

@@ -1000,6 +1000,20 @@ def sample_select_sc(logits, temperature, top_k, top_p, seed, eos_ids, pad_id, u
                                         L.ptr(out_ids), out_ids.shape[1], L.ptr(choice), L.ptr(logprobs), L.stream_ptr()), "sl_sample_select_sc")
 
 
+def sample_select_w(logits, temperature, top_k, top_p, seed, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids,
+                    logprobs=None, warp=None) -> None:
+    """sl_sample_select_w: sample_select_sc (logprobs None: sample_select) with HF's min_p / typical_p / epsilon_cutoff / eta_cutoff behind
+    top-p.  warp: an L.WarpOpts (passed as it is, so that the library's own range checks can be reached), a dict of the four names, or None."""
+    B, V = logits.shape
+    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
+    choice = torch.empty(B, dtype=torch.int32, device=logits.device)
+    w = warp if isinstance(warp, L.WarpOpts) else L.warp_opts(warp)
+    L.check(L.lib().sl_sample_select_w(L.ptr(logits), B, V, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, eos, len(eos_ids),
+                                       pad_id, int(use_eos), L.ptr(unfinished), L.ptr(ctx_len), L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids),
+                                       L.ptr(out_ids), out_ids.shape[1], L.ptr(choice), None if logprobs is None else L.ptr(logprobs), L.stream_ptr(),
+                                       None if w is None else C.byref(w)), "sl_sample_select_w")
+
+
 # ---- teacher-forced scoring (speechllm.h: sl_gemm_top1_lse_tgt, sl_score_*; DESIGN 3.11)
 def gemm_top1_lse_tgt(A: torch.Tensor, W: torch.Tensor, tgt_col: torch.Tensor, bias: Optional[torch.Tensor] = None, out=None, tgt_val=None):
     """gemm_top1_lse plus the wanted column's value per row: returns (val, idx, sum, tgt_val); tgt_val[m] = the logit at (m, tgt_col[m]),
