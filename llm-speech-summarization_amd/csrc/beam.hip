@@ -9,7 +9,7 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t beam_ord_key(float x) {      // order-preserving 32-bit image of a float (llama_ops.hip ord_key)
+__device__ __forceinline__ uint32_t beam_ord_key(float x) {      // order-preserving 32-bit image of a float (select.hip ord_key)
   const uint32_t u = __float_as_uint(x);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }

@@ -576,7 +576,7 @@ struct SlFamilyPin {
   ~SlFamilyPin() { sl_family_pin(prev); }
 };
 
-// Per-row generation state a select pass reads and advances (llama_ops.hip), all device arrays of B rows unless noted: the one argument
+// Per-row generation state a select pass reads and advances (select.hip), all device arrays of B rows unless noted: the one argument
 // of the three selects below, which the extern "C" entries and the generation loop (runtime.hip) fill.
 struct SlRowState {
   int32_t *unfinished, *ctx_len, *gen_count, *finish_len, *next_ids;

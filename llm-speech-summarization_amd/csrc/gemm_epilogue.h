@@ -12,7 +12,7 @@
 // Fused row-wise top-1 in place of the store (greedy decode: lm_head + argmax, hf:generation/utils.py:2911-2925 `torch.argmax(
 // next_token_scores)` over ref:model/audio_llama.py:67's logits).  The wave holds MT*16 rows x 64 columns; lane (r, q) has rows
 // 4q..4q+3 of column r of each 16-column fragment.  Per row: the best of the lane's four fragments, then across the 16 lanes of
-// the row group, always with (value, column) compared the way greedy_select_kernel does — the first maximum wins, NaN never wins.  One (value, column) pair per row and 64-column group
+// the row group, always with (value, column) compared the way greedy_select_kernel (select.hip) does — the first maximum wins, NaN never wins.  One (value, column) pair per row and 64-column group
 // goes out at [group][row]: 64 contiguous bytes per 16 rows, 1/64 of the logits the select pass would otherwise re-read.
 template <typename T, int MT, int NT>
 __device__ __forceinline__ void tile_argmax(const GemmP& p, f32x4 (&acc)[MT][NT], int row_base, int col_base, int q, int r, int wz) {

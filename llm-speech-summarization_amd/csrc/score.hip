@@ -5,7 +5,7 @@
 #include "common.h"
 
 // ----------------------------------------------------------------------------------------------
-// planes -> log-probability and top-1.  The layout of greedy_select_partial_kernel (llama_ops.hip): block = 32 rows x 32 group stripes,
+// planes -> log-probability and top-1.  The layout of greedy_select_partial_kernel (select.hip): block = 32 rows x 32 group stripes,
 // eight groups in flight per thread, the stripes meet in LDS in stripe order; compare rule: larger value, then lower column.
 //   m = max_g val_g, total = sum_g sum_g * expf(val_g - m) (a stripe's groups in index order, then the stripes in order),
 //   logprob = (tgt - m) - logf(total)

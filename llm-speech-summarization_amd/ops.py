@@ -286,12 +286,16 @@ def attn_decode(q, q_stride, k_cache, v_cache, ctx_len, n_heads, n_kv, D, max_ct
     return out
 
 
+def _select_state(eos_ids, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids):
+    """what every select entry takes besides its own arguments: (the EOS ids as a C array, the row-state arguments in the entries' order)"""
+    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
+    return eos, (L.ptr(unfinished), L.ptr(ctx_len), L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids), L.ptr(out_ids), out_ids.shape[1])
+
+
 def greedy_select(logits, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids) -> None:
     B, V = logits.shape
-    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
-    L.check(L.lib().sl_greedy_select(L.ptr(logits), B, V, eos, len(eos_ids), pad_id, int(use_eos), L.ptr(unfinished), L.ptr(ctx_len),
-                                     L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids), L.ptr(out_ids), out_ids.shape[1],
-                                     L.stream_ptr()), "sl_greedy_select")
+    eos, state = _select_state(eos_ids, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids)
+    L.check(L.lib().sl_greedy_select(L.ptr(logits), B, V, eos, len(eos_ids), pad_id, int(use_eos), *state, L.stream_ptr()), "sl_greedy_select")
 
 
 def gemm_top1(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None):
@@ -316,9 +320,8 @@ def gemm_top1(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = N
 
 def greedy_select_partial(val, idx, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, advance_ctx=True) -> None:
     ng, B = val.shape
-    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
-    L.check(L.lib().sl_greedy_select_partial(L.ptr(val), L.ptr(idx), ng, B, eos, len(eos_ids), pad_id, int(use_eos), int(advance_ctx), L.ptr(unfinished),
-                                             L.ptr(ctx_len), L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids), L.ptr(out_ids), out_ids.shape[1],
+    eos, state = _select_state(eos_ids, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids)
+    L.check(L.lib().sl_greedy_select_partial(L.ptr(val), L.ptr(idx), ng, B, eos, len(eos_ids), pad_id, int(use_eos), int(advance_ctx), *state,
                                              L.stream_ptr()), "sl_greedy_select_partial")
 
 
@@ -927,11 +930,10 @@ def kd_mse_rows(a, b, row_coef, row_slot, losses, loss_col, da=None):
 def sample_select(logits, temperature, top_k, top_p, seed, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids) -> None:
     """sl_sample_select: HF's temperature / top-k / top-p warpers + one reproducible draw per row, then greedy_select's bookkeeping."""
     B, V = logits.shape
-    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
     choice = torch.empty(B, dtype=torch.int32, device=logits.device)
+    eos, state = _select_state(eos_ids, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids)
     L.check(L.lib().sl_sample_select(L.ptr(logits), B, V, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, eos, len(eos_ids), pad_id,
-                                     int(use_eos), L.ptr(unfinished), L.ptr(ctx_len), L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids), L.ptr(out_ids),
-                                     out_ids.shape[1], L.ptr(choice), L.stream_ptr()), "sl_sample_select")
+                                     int(use_eos), *state, L.ptr(choice), L.stream_ptr()), "sl_sample_select")
 
 
 def sample_uniform(seed: int, row: int, step: int) -> float:
@@ -975,29 +977,26 @@ def gemm_top1_lse(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor]
 
 def greedy_select_sc(logits, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, logprobs) -> None:
     B, V = logits.shape
-    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
-    L.check(L.lib().sl_greedy_select_sc(L.ptr(logits), B, V, eos, len(eos_ids), pad_id, int(use_eos), L.ptr(unfinished), L.ptr(ctx_len),
-                                        L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids), L.ptr(out_ids), out_ids.shape[1], L.ptr(logprobs),
-                                        L.stream_ptr()), "sl_greedy_select_sc")
+    eos, state = _select_state(eos_ids, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids)
+    L.check(L.lib().sl_greedy_select_sc(L.ptr(logits), B, V, eos, len(eos_ids), pad_id, int(use_eos), *state, L.ptr(logprobs), L.stream_ptr()),
+            "sl_greedy_select_sc")
 
 
 def greedy_select_partial_sc(val, idx, ssum, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids, logprobs,
                              advance_ctx=True) -> None:
     ng, B = val.shape
-    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
+    eos, state = _select_state(eos_ids, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids)
     L.check(L.lib().sl_greedy_select_partial_sc(L.ptr(val), L.ptr(idx), L.ptr(ssum), ng, B, eos, len(eos_ids), pad_id, int(use_eos), int(advance_ctx),
-                                                L.ptr(unfinished), L.ptr(ctx_len), L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids), L.ptr(out_ids),
-                                                out_ids.shape[1], L.ptr(logprobs), L.stream_ptr()), "sl_greedy_select_partial_sc")
+                                                *state, L.ptr(logprobs), L.stream_ptr()), "sl_greedy_select_partial_sc")
 
 
 def sample_select_sc(logits, temperature, top_k, top_p, seed, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids,
                      logprobs) -> None:
     B, V = logits.shape
-    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
     choice = torch.empty(B, dtype=torch.int32, device=logits.device)
+    eos, state = _select_state(eos_ids, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids)
     L.check(L.lib().sl_sample_select_sc(L.ptr(logits), B, V, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, eos, len(eos_ids),
-                                        pad_id, int(use_eos), L.ptr(unfinished), L.ptr(ctx_len), L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids),
-                                        L.ptr(out_ids), out_ids.shape[1], L.ptr(choice), L.ptr(logprobs), L.stream_ptr()), "sl_sample_select_sc")
+                                        pad_id, int(use_eos), *state, L.ptr(choice), L.ptr(logprobs), L.stream_ptr()), "sl_sample_select_sc")
 
 
 def sample_select_w(logits, temperature, top_k, top_p, seed, eos_ids, pad_id, use_eos, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids,
@@ -1005,12 +1004,11 @@ def sample_select_w(logits, temperature, top_k, top_p, seed, eos_ids, pad_id, us
     """sl_sample_select_w: sample_select_sc (logprobs None: sample_select) with HF's min_p / typical_p / epsilon_cutoff / eta_cutoff behind
     top-p.  warp: an L.WarpOpts (passed as it is, so that the library's own range checks can be reached), a dict of the four names, or None."""
     B, V = logits.shape
-    eos = (C.c_int32 * max(1, len(eos_ids)))(*eos_ids)
     choice = torch.empty(B, dtype=torch.int32, device=logits.device)
     w = warp if isinstance(warp, L.WarpOpts) else L.warp_opts(warp)
+    eos, state = _select_state(eos_ids, unfinished, ctx_len, gen_count, finish_len, next_ids, out_ids)
     L.check(L.lib().sl_sample_select_w(L.ptr(logits), B, V, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, eos, len(eos_ids),
-                                       pad_id, int(use_eos), L.ptr(unfinished), L.ptr(ctx_len), L.ptr(gen_count), L.ptr(finish_len), L.ptr(next_ids),
-                                       L.ptr(out_ids), out_ids.shape[1], L.ptr(choice), None if logprobs is None else L.ptr(logprobs), L.stream_ptr(),
+                                       pad_id, int(use_eos), *state, L.ptr(choice), None if logprobs is None else L.ptr(logprobs), L.stream_ptr(),
                                        None if w is None else C.byref(w)), "sl_sample_select_w")
 
 

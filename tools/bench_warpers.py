@@ -2,8 +2,8 @@
 the same random weights and inputs (Llama-3.2-3B shapes, bf16, 137-token prompts), and the selection kernel alone.
 
 Measured at 1 024, 256 and 1 rows: ms per captured decode step and tok/s with sampling on (temperature 0.8, top_k 50, top_p 0.95: the
-unfused lm_head -> fp32 logits -> sample_rows_kernel) and, on top of that, min_p / typical_p / epsilon_cutoff / eta_cutoff one at a time and
-all four (sample_rows_warp_kernel); then the two selection kernels alone on Gaussian rows of the real vocabulary (us per launch).
+unfused lm_head -> fp32 logits -> sample_rows_kernel<false>) and, on top of that, min_p / typical_p / epsilon_cutoff / eta_cutoff one at a time and
+all four (sample_rows_kernel<true>); then the two instantiations alone on Gaussian rows of the real vocabulary (us per launch).
 
     python tools/bench_warpers.py [--reps 5] [--out profiles/warpers.txt]
 
